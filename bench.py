@@ -20,6 +20,8 @@ Contract: `python bench.py --gpus N --steps K --warmup W` (torchrun for N>1, one
 GPU); W untimed warm-up steps, exactly K timed steps between barrier+synchronize, MAX over
 ranks, rank 0 prints ONE JSON line.  Elements shard across ranks with no collective on the
 data path (every element is independent): weak scaling, n per GPU fixed.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Extra objects on the line:
   roofline      dominant kernel: algorithmic bytes per launch / mean launch time measured with
@@ -103,6 +105,30 @@ class StepData:
         self.shares = ctx.empty_matrix(m, n)
         self.y = ctx.empty(n)
         self.rec = None     # pre-marshalled recombination launch
+
+
+DUMP_SAMPLE = 1 << 18       # element positions written by --dump-outputs (26 MB in all)
+
+
+def dump_outputs(path, s):
+    """--dump-outputs: what one step hands its caller -- the shares (m, n) and the recombined y (n) -- at a fixed, seeded
+    sample of DUMP_SAMPLE element positions (every position when n is smaller), written as float64 next to index.npy.
+    float64 holds 53 of an element's 61 bits, so each array is also written exactly as <name>_u16.npy: its four 16-bit
+    digits, least significant first, as float32."""
+    n = s.y.n
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(20260925).choice(n, DUMP_SAMPLE, replace=False))
+    sel = torch.from_numpy(idx).to(s.y.t.device)
+    outs = {'y': s.y.t.index_select(0, sel), 'shares': s.shares.t[:, :n].index_select(1, sel)}
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'index.npy'), idx.astype(np.float64))
+    for name, x in outs.items():
+        v = x.cpu().numpy().view(np.uint64)
+        np.save(os.path.join(path, f'{name}.npy'), v.astype(np.float64))
+        digits = (v[..., None] >> np.arange(0, 64, 16, dtype=np.uint64)) & np.uint64(0xFFFF)
+        np.save(os.path.join(path, f'{name}_u16.npy'), digits.astype(np.float32))
 
 
 def time_launches(fn, sets, reps):
@@ -400,7 +426,7 @@ def cpu_baseline(n_full, t, m, lam, seed=20260925):
     """The reference's own CPU path on this host (kind "reference": mpyc's FiniteFieldArray.__mul__,
     thresha.np_random_split with live secrets.randbelow draws, thresha.np_recombine -- oracle/refbaseline.py -- on 1
     core and as one process per core over equal slices), when an mpyc checkout is importable (the staged copy
-    _refstage/ on the GPU box, /root/reference in the build container).  The C port of the same pass
+    oracle/_ref/ that build() makes, or the checkout itself).  The C port of the same pass
     (oracle/fforacle.c, OpenMP) is timed beside it on the full workload and reported as `port_value` -- a much harder
     baseline than the reference; it is `value` only when no reference checkout is present (kind "port").
     Checker/baseline only -- never the product."""
@@ -434,7 +460,7 @@ def cpu_baseline(n_full, t, m, lam, seed=20260925):
     host_cores = os.cpu_count() or cores
     out = {'value': round(res['allcores'], 1), 'unit': 'field-ops/s', 'cores': cores, 'host_cores': host_cores, 'kind': 'port',
            'sample': port_sample, 'value_1core': round(res['1core'], 1)}
-    ref_root = next((r_ for r_ in (os.path.join(ROOT, '_refstage'), '/root/reference') if os.path.isdir(os.path.join(r_, 'mpyc'))), None)
+    ref_root = next((r_ for r_ in (os.path.join(ROOT, 'oracle', '_ref'), '/root/reference') if os.path.isdir(os.path.join(r_, 'mpyc'))), None)
     r = None
     if ref_root is not None:
         procs = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
@@ -470,7 +496,7 @@ def api_leg(n_full, parties_on_gpus=False):
     """The path THROUGH the reference's public API: tests/api_program.py -- an ordinary MPyC
     program, `mpc.output(a * b)` on SecFld(2^61-1) arrays, i.e. Runtime.np_multiply -> _reshare -> output
     (runtime.py:1096-1141, 603-689, 513-600) -- run as party processes under mpyc_amd.install(), and on the unmodified
-    reference beside it (host cores).  Needs an importable mpyc (the staged copy _refstage/ on the GPU box).
+    reference beside it (host cores).  Needs an importable mpyc (the staged copy oracle/_ref/ made by build()).
 
     Per configuration: elements/s = n * multiplications / median wall time of one repetition at party 0 (inputs
     already shared; a repetition ends with the opened result on the device and a device synchronisation), and
@@ -478,10 +504,10 @@ def api_leg(n_full, parties_on_gpus=False):
     time of the timed repetitions.  m = 1 is the runtime's own overhead + the kernels; m = 3 adds the reference's
     pickle + asyncio TCP transport between three local party processes (out of scope for the engine, SURVEY 8e:
     "party networking stays on the host") which then dominates: see `note`."""
-    ref_root = next((r_ for r_ in (os.path.join(ROOT, '_refstage'), '/root/reference')
+    ref_root = next((r_ for r_ in (os.path.join(ROOT, 'oracle', '_ref'), '/root/reference')
                      if os.path.isdir(os.path.join(r_, 'mpyc'))), None)
     if ref_root is None:
-        return {'skipped': 'no importable mpyc checkout (stage one with tools/stage_reference.sh)'}
+        return {'skipped': 'no importable mpyc checkout (build() stages one into oracle/_ref/)'}
     import statistics
     import subprocess
     prog = os.path.join(ROOT, 'tests', 'api_program.py')
@@ -627,10 +653,10 @@ def list_path_leg():
     mpyc_amd.list_path_min secrets on) beside the reference's own functions in one process; parity on replayed draws
     (element by element, incl. the reference's un-reduced sums), then both timed with live randomness.  A host-bound
     row by nature: 10^4 Python integers in and out per call; it is here for coverage of the config, not for the roofline."""
-    ref_root = next((r_ for r_ in (os.path.join(ROOT, '_refstage'), '/root/reference')
+    ref_root = next((r_ for r_ in (os.path.join(ROOT, 'oracle', '_ref'), '/root/reference')
                      if os.path.isdir(os.path.join(r_, 'mpyc'))), None)
     if ref_root is None:
-        return {'skipped': 'no importable mpyc checkout (stage one with tools/stage_reference.sh)'}
+        return {'skipped': 'no importable mpyc checkout (build() stages one into oracle/_ref/)'}
     import subprocess
     env = dict(os.environ)
     env['PYTHONPATH'] = os.pathsep.join([os.path.join(ROOT, 'tests'), ROOT, ref_root])
@@ -882,7 +908,11 @@ def main():
                     help='N >= 3: also run three MPyC parties on three GPUs over the device-side wire (opt-in; never run on >1 GPU)')
     ap.add_argument('--layout', choices=('element', 'party-major'), default='element',
                     help="'party-major': only the configs[3] section (gate sharded + party-major exchange), more steps")
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -898,6 +928,8 @@ def main():
         # (`--n` is an ambiguous abbreviation for torch.distributed.run's own parser: it travels in the environment)
         fwd = ['--gpus', str(args.gpus), '--steps', str(args.steps), '--warmup', str(args.warmup), '--sets', str(args.sets),
                '--layout', args.layout, '--budget', str(args.budget)]
+        if args.dump_outputs:
+            fwd += ['--dump-outputs', args.dump_outputs]
         fwd += [f_ for f_, on in (('--no-cpu-baseline', args.no_cpu_baseline), ('--no-extras', args.no_extras),
                                   ('--no-api-leg', args.no_api_leg), ('--no-multi-gpu-leg', args.no_multi_gpu_leg),
                                   ('--parties-on-gpus', args.parties_on_gpus), ('--full', args.full)) if on]
@@ -991,6 +1023,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # before the unfused pass and the extras, which overwrite these buffers
+        dump_outputs(args.dump_outputs, sets[(args.warmup + args.steps - 1) % len(sets)])
 
     # the same work as three separate kernels (c materialised), for reference
     for i in range(min(args.warmup, 3)):

@@ -10,7 +10,7 @@ exactly as the runtime calls them for `a * b` on a SecFld array in the default 3
 
 -- on 1 core, and on `procs` cores as independent processes over equal slices (the reference is single-threaded;
 SURVEY 8d prescribes N processes on n/N slices).  `mpyc` must be importable (PYTHONPATH holds the reference
-checkout: /root/reference in the build container, the staged copy _refstage/ on the GPU box); only
+checkout, or the staged copy oracle/_ref/ that build() makes from it); only
 mpyc.finfields and mpyc.thresha are imported (mpyc.runtime parses sys.argv and starts a runtime).
 """
 import os

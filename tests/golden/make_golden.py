@@ -433,6 +433,26 @@ def npfunc_cases():
     print('wrote npfuncs.json', os.path.getsize(os.path.join(OUT, 'npfuncs.json')))
 
 
+def npring_cases():
+    """NumPy ring functions the reference serves through its GENERIC __array_function__ / __array_ufunc__ path
+    (finfields.py:728-819): what it returns for np.diff, ediff1d, cross, polyval / polymul / polyadd, square and a negative
+    slice step (tests/test_numpy_functions.py::test_expected_values_are_the_references).  Entries are large enough that
+    NumPy keeps object temporaries inside np.cross."""
+    p = P61
+    F = finfields.GF(p)
+    V = np.array([2**60 + 3, p - 1, 2**59 + 77, 2**60, 2**58 + 5, 2**57 + 6, 2**56 + 9], dtype=object)
+    W = np.array([p - 2, 2**58 + 4, 10**18, 2**57 + 1], dtype=object)
+    fv, fw = F.array(V), F.array(W)
+    L = lambda x: hxl(int(e) for e in np.asarray(x.value).reshape(-1))
+    out = {'modulus': hx(p), 'V': hxl(V), 'W': hxl(W),
+           'diff': L(np.diff(fv)), 'ediff1d': L(np.ediff1d(fv)), 'cross': L(np.cross(fv[:3], fw[:3])),
+           'polyval': L(np.polyval(fw, fv)), 'polymul': L(np.polymul(fv, fw)), 'polyadd': L(np.polyadd(fv, fw)),
+           'square': L(np.square(fv)), 'step_minus2': L(fv[::-2])}
+    with open(os.path.join(OUT, 'npring.json'), 'w') as fh:
+        json.dump(out, fh, separators=(',', ':'))
+    print('wrote npring.json', os.path.getsize(os.path.join(OUT, 'npring.json')))
+
+
 def wire_cases():
     """The reference's marshalled forms of share rows:
       * field.to_bytes / from_bytes (finfields.py:91-102): byte_length little-endian bytes per element, incl. the
@@ -511,7 +531,7 @@ def roots_cases():
     print('wrote roots.json', os.path.getsize(os.path.join(OUT, 'roots.json')))
 
 
-ALL = ('main', 'prss', 'matmul', 'linalg', 'npfuncs', 'sqrt', 'wire', 'roots')
+ALL = ('main', 'prss', 'matmul', 'linalg', 'npfuncs', 'npring', 'sqrt', 'wire', 'roots')
 
 def wide_cases():
     """Three-limb primes (129..192 bits: the default fields of SecInt(97..160), finfields.py:311-344): the same
@@ -559,6 +579,9 @@ if __name__ == '__main__':
     if 'npfuncs' in sys.argv[1:]:
         npfunc_cases()
         sys.exit(0)
+    if 'npring' in args:
+        npring_cases()
+        sys.exit(0)
     if 'linalg' in sys.argv[1:]:
         linalg_cases()
         sys.exit(0)
@@ -567,6 +590,7 @@ if __name__ == '__main__':
     matmul_cases()
     linalg_cases()
     npfunc_cases()
+    npring_cases()
     sqrt_cases()
     wire_cases()
     roots_cases()

@@ -8,7 +8,7 @@ share row np_random_split hands out, of every array np_recombine returns and of 
 must agree digest for digest, for one party (t = 0) and for three local parties over TCP (t = 1).
 
   * build container (`-m "not gpu"`): the mirror's host logic on tests/cpuctx.py, n = 3000;
-  * GPU box (`-m gpu`): the kernels, n = 10^6, against the staged reference copy (_refstage/, see
+  * GPU box (`-m gpu`): the kernels, n = 10^6, against the staged reference copy (oracle/_ref/, see
     tests/test_mpyc_dropin.py); skipped if no copy was staged.
 """
 import json
@@ -19,7 +19,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGE = os.path.join(ROOT, '_refstage')
+STAGE = os.path.join(ROOT, 'oracle', '_ref')
 PROG = os.path.join(ROOT, 'tests', 'api_program.py')
 
 
@@ -74,7 +74,7 @@ def test_api_path_chain_and_wide_prime_host_logic(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 @pytest.mark.parametrize('parties,t', [(1, 0), (3, 1)])
 def test_api_path_matches_reference_on_gpu_1e6(tmp_path, parties, t):
     """n = 10^6 SecFld(2^61-1) elements through mpc.input / a * b / mpc.output on the GPU box: every share row, every
@@ -87,7 +87,7 @@ def test_api_path_matches_reference_on_gpu_1e6(tmp_path, parties, t):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_api_path_matches_reference_on_gpu_at_the_north_star_size(tmp_path):
     """north_star: "bit-exact vs mpyc.thresha on 10^7-element SecFld arrays" -- through the API, against the reference
     itself run beside it: n = 10^7 over 2^61 - 1, one party (mpc.input / a * b / mpc.output = np_multiply + output,
@@ -100,7 +100,7 @@ def test_api_path_matches_reference_on_gpu_at_the_north_star_size(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_api_path_three_parties_at_the_north_star_size(tmp_path):
     """The same at n = 10^7 for three parties (t = 1: np_random_split by every party, np_recombine of 2t+1 rows,
     runtime.py:603-689) with the engine's parties exchanging rows over the device-side wire; the reference's three
@@ -113,7 +113,7 @@ def test_api_path_three_parties_at_the_north_star_size(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_api_path_chain_wide_prime_on_gpu(tmp_path):
     n = 100_000
     ref = run_program(STAGE, 'ref', n, 3, str(tmp_path), prime=2**128 - 173, chain=3, reps=1)
@@ -122,7 +122,7 @@ def test_api_path_chain_wide_prime_on_gpu(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_api_path_device_side_wire_on_gpu(tmp_path):
     """Three co-located parties with MPYC_AMD_IPC_WIRE=1: the pickled share rows carry an interprocess handle of the
     device buffer instead of the limb bytes (mpyc_amd/finfields.py, _array_from_ipc); what every party splits, receives,

@@ -6,6 +6,8 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -142,3 +144,83 @@ def test_bounded_subprocess_ends_the_whole_process_group(tmp_path):
     bench.LEG_BUDGET.update(deadline=None)
     a, b = bench.free_base_port(3), bench.free_base_port(3)
     assert a != b and 1024 < a < 65000
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and '--steps must be at least 1' in r.stderr
+
+
+def _dumped(path):
+    import numpy as np
+    return {f[:-len('.npy')]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_writes_a_seeded_exact_sample(tmp_path):
+    """bench.dump_outputs on host tensors: a fixed sample of the shares and of y, float32 / float64 only, under 64 MB,
+    the 16-bit digits give every element back exactly, and the same buffers give the same files."""
+    from types import SimpleNamespace
+    import numpy as np
+    import torch
+    n, m = bench.DUMP_SAMPLE + 1001, 3
+    g = torch.Generator().manual_seed(5)
+    shares = torch.randint(0, bench.P61, (m, n + 7), dtype=torch.int64, generator=g)     # rows padded like a DevMatrix
+    y = torch.randint(0, bench.P61, (n,), dtype=torch.int64, generator=g)
+    s = SimpleNamespace(y=SimpleNamespace(t=y, n=n), shares=SimpleNamespace(t=shares))
+    bench.dump_outputs(str(tmp_path / 'a'), s)
+    bench.dump_outputs(str(tmp_path / 'b'), s)
+    a, b = _dumped(tmp_path / 'a'), _dumped(tmp_path / 'b')
+    assert sorted(a) == ['index', 'shares', 'shares_u16', 'y', 'y_u16']
+    assert sum(os.path.getsize(tmp_path / 'a' / f'{k}.npy') for k in a) < 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    idx = a['index'].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and (np.diff(idx) > 0).all() and idx[-1] < n
+    weights = np.array([1 << 16 * i for i in range(4)], dtype=object)
+    for name, full in (('y', y.numpy()), ('shares', shares[:, :n].numpy())):
+        exact = (a[f'{name}_u16'].astype(np.int64).astype(object) * weights).sum(axis=-1)
+        assert (exact == full[..., idx].astype(object)).all(), name
+        assert np.array_equal(a[name], full[..., idx].astype(np.float64)), name
+
+
+def test_dump_outputs_keeps_every_position_of_a_small_run(tmp_path):
+    from types import SimpleNamespace
+    import torch
+    n = 1000
+    y = torch.arange(n, dtype=torch.int64) * 7919
+    shares = torch.stack([y + j for j in range(3)])
+    bench.dump_outputs(str(tmp_path), SimpleNamespace(y=SimpleNamespace(t=y, n=n), shares=SimpleNamespace(t=shares)))
+    d = _dumped(tmp_path)
+    assert d['index'].tolist() == list(range(n)) and d['y'].tolist() == (y.numpy() * 1.0).tolist()
+    assert d['shares'].shape == (3, n) and d['shares_u16'].shape == (3, n, 4)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_path(tmp_path):
+    """Two runs with the same arguments dump the same outputs; the dumped shares lie on a line (t = 1) and y is
+    their recombination at 0 from parties 1..3, i.e. the dump is what the last timed step computed."""
+    import subprocess
+    import numpy as np
+    runs = []
+    for tag in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-extras',
+                            '--no-cpu-baseline', '--no-api-leg', '--no-multi-gpu-leg', '--dump-outputs', str(tmp_path / tag)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, FFGPU_BENCH_N='100000'))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        assert json.loads(r.stdout.splitlines()[-1])['steps'] == 3
+        runs.append(_dumped(tmp_path / tag))
+    a, b = runs
+    assert sorted(a) == sorted(b) == ['index', 'shares', 'shares_u16', 'y', 'y_u16']
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert a['index'].tolist() == list(range(100000))
+    weights = np.array([1 << 16 * i for i in range(4)], dtype=object)
+    sh = (a['shares_u16'].astype(np.int64).astype(object) * weights).sum(axis=-1)
+    y = (a['y_u16'].astype(np.int64).astype(object) * weights).sum(axis=-1)
+    p = bench.P61
+    assert sh.shape == (3, 100000) and (sh < p).all() and (y < p).all()
+    assert ((sh[0] - 2 * sh[1] + sh[2]) % p == 0).all()
+    assert ((3 * sh[0] - 3 * sh[1] + sh[2] - y) % p == 0).all()
+    assert y.any()

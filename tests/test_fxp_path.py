@@ -24,7 +24,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGE = os.path.join(ROOT, '_refstage')
+STAGE = os.path.join(ROOT, 'oracle', '_ref')
 PROG = os.path.join(ROOT, 'tests', 'fxp_program.py')
 OUTLIER_SEED = 4      # FXP_SEED for which the reference itself (one party, n = 10^5) produces ONE short-mask outlier (found by
 #                       running the reference over seeds 1..10 in the build container: seeds 4 and 9 have one, the others none)
@@ -87,7 +87,7 @@ def test_fxp_product_production_prf_host_logic(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 @pytest.mark.parametrize('parties', [1, 3])
 def test_fxp_product_matches_reference_on_gpu_1e5(tmp_path, parties):
     n = 100_000
@@ -102,7 +102,7 @@ def test_fxp_product_matches_reference_on_gpu_1e5(tmp_path, parties):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_fxp_product_production_prf_on_gpu(tmp_path):
     """the same program with the device PRF at n = 10^6, one party and three: correct to fixed-point accuracy (apart from
     the reference's own short-mask outliers, counted separately)"""

@@ -13,6 +13,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# processes that may hold a GPU at once, this test process included (the GPU hosts are shared)
+MAX_GPU_PROCS = 6
 
 
 def _run_worker(backend, nproc, port):
@@ -54,8 +56,9 @@ def test_party_major_world_of_one_runs_on_kernels():
 @pytest.mark.gpu
 def test_party_major_under_rccl():
     import torch
-    out = _run_worker('nccl', torch.cuda.device_count(), 29541)
-    assert f'DIST_GPU_OK nccl {torch.cuda.device_count()}' in out
+    nproc = min(torch.cuda.device_count(), MAX_GPU_PROCS - 1)
+    out = _run_worker('nccl', nproc, 29541)
+    assert f'DIST_GPU_OK nccl {nproc}' in out
 
 
 @pytest.mark.gpu
@@ -80,21 +83,22 @@ def _bench_lines(args, env_extra, timeout=900):
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_control_flow_on_one_gpu():
-    """The command the driver runs for the scaling record, with the 8 ranks forced onto GPU 0 (gloo, since RCCL refuses
+def test_bench_four_ranks_control_flow_on_one_gpu():
+    """The command the driver runs for the scaling record, with 4 ranks forced onto GPU 0 (gloo, since RCCL refuses
     two ranks on one device): self-launch under torch.distributed.run, headline + roofline before the first collective
-    of the configs[3] section, the section itself on 8 ranks, one compact line that parses."""
-    line, detail = _bench_lines(['--gpus', '8', '--steps', '2', '--warmup', '1'],
+    of the configs[3] section, the section itself on 4 ranks, one compact line that parses.  Four ranks
+    and this process keep the processes holding the GPU within MAX_GPU_PROCS."""
+    line, detail = _bench_lines(['--gpus', '4', '--steps', '2', '--warmup', '1'],
                                 {'FFGPU_BENCH_DEVICE': '0', 'FFGPU_BENCH_LEG_TIMEOUT': '600'})
-    assert line['n_gpus'] == 8 and line['distributed']['world_size'] == 8 and line['distributed']['backend'] == 'gloo'
-    assert len(line['distributed']['ranks']) == 8 and line['distributed']['distinct_devices'] == 1
+    assert line['n_gpus'] == 4 and line['distributed']['world_size'] == 4 and line['distributed']['backend'] == 'gloo'
+    assert len(line['distributed']['ranks']) == 4 and line['distributed']['distinct_devices'] == 1
     assert all(r['pci_bus_id'] for r in line['distributed']['ranks'])
     assert line['config']['workload'].startswith('configs[1]') and line['config']['n_per_gpu'] == 10_000_000
     assert line['scaling'] == 'weak' and line['value'] > 0 and line['steps'] == 2
     assert line['roofline']['bound'] == 'hbm' and 0 < line['roofline']['frac'] < 1
     assert 'cpu_baseline' not in line                      # rank 0 at N = 1 only
     assert 'error' not in line['multi_gpu'], line['multi_gpu']
-    assert detail['multi_gpu']['config']['n_gpus'] == 8
+    assert detail['multi_gpu']['config']['n_gpus'] == 4
     for leg in ('gate_sharded', 'party_major_all_to_all', 'party_major_allgather'):
         assert line['multi_gpu'][leg]['ms_per_step'] > 0
     # every rank's parity checks of the section, all-reduced (MIN) into one flag

@@ -8,7 +8,7 @@ three and in a rotated x order, at x_r = 0 and x_rs = [0, 5] -- for raw-int shar
 (thresha.py:109; mirror == reference % p) and against oracle.recombine_unreduced, for field-element shares by value and type.
 
   * build container (`-m "not gpu"`): the mirror's host logic on tests/cpuctx.py against /root/reference;
-  * GPU box (`-m gpu`): the kernels, against the staged reference copy (_refstage/).
+  * GPU box (`-m gpu`): the kernels, against the staged reference copy (oracle/_ref/).
 Both must produce the same digests (same seed): the CPU twin's digests are pinned below.
 """
 import json
@@ -19,7 +19,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGE = os.path.join(ROOT, '_refstage')
+STAGE = os.path.join(ROOT, 'oracle', '_ref')
 PROG = os.path.join(ROOT, 'tests', 'list_path_program.py')
 
 # SHA-256 over the (m, n) share matrix / the opened secrets of the seeded run (LP_SEED=5, n=10^4, m=3, t=1, 2^61-1), as the
@@ -53,7 +53,7 @@ def test_configs0_list_path_1e4_host_logic():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_configs0_list_path_1e4_on_gpu():
     res = run(STAGE, 'gpu')
     check(res, 10_000)
@@ -61,7 +61,7 @@ def test_configs0_list_path_1e4_on_gpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(not os.path.isdir(os.path.join(STAGE, 'mpyc')), reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_list_path_other_settings_on_gpu():
     """the same comparison at m = 7, t = 3 over 2^64 - 189 (t draws per secret: the c[0] -> X^t convention matters) and
     over the two-limb prime 2^128 - 173"""

@@ -7,8 +7,8 @@ np_aes demo, unmodified, on top of it:
   * build container (reference in /root/reference, no GPU): `-m "not gpu"`, on the Python-integer context of
     tests/cpuctx.py -- checks the HOST logic of the substitution;
   * GPU box: `-m gpu`, on libffgpu's kernels.  The reference does not exist there unless a copy was staged
-    into the untracked scratch directory `_refstage/` (tools/stage_reference.sh, build container only; it is
-    git-ignored, never committed); without it these tests skip.
+    into oracle/_ref/ (build() does it where the reference checkout exists, oracle/Makefile `ref`; it is
+    git-ignored, never committed, and travels with the working tree); without it these tests skip.
 """
 import os
 import subprocess
@@ -17,7 +17,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGE = os.path.join(ROOT, '_refstage')
+STAGE = os.path.join(ROOT, 'oracle', '_ref')
 FIPS197 = '69c4e0d86a7b0430d8cdb78070b4c55a'        # docs/demos.rst:611, FIPS-197 appendix C.1
 
 
@@ -116,21 +116,21 @@ def test_np_aes_demo_under_install_host_logic():
 # GPU box (needs the staged reference copy)
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_reference_suite_under_install_on_gpu():
     out = _run_reference_tests(STAGE, False, REF_FILES, {'MPYC_AMD_LIST_MIN': '0', 'MPYC_AMD_LAZY_INTS_MIN': '0'})
     assert ' passed' in out and 'failed' not in out
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_np_aes_demo_under_install_on_gpu():
     _run_np_aes(STAGE, False, ['-1'])
     _run_np_aes(STAGE, False, ['-1', '-M3'])
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_reference_np_demos_under_install_on_gpu():
     """demos/np-run-all.sh of the reference, unmodified, with and without install(): identical printed results
     (tools/run_np_demos.sh; profiles/r02_np_demos.md)."""
@@ -184,7 +184,7 @@ def test_pickled_rows_keep_their_field_class_host_logic():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_pickled_rows_keep_their_field_class_on_gpu():
     env = _env(STAGE, False, os.path.join(ROOT, 'mpyc_amd', 'autoinstall'))
     r = subprocess.run([sys.executable, '-c', _SAME_P_CODE], capture_output=True, text=True, cwd='/tmp', env=env, timeout=300)
@@ -263,7 +263,7 @@ def test_np_reciprocal_reader_host_logic():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (_refstage/)')
+@pytest.mark.skipif(_ref_root(True) is None, reason='no staged reference copy (oracle/_ref/, made by build())')
 def test_np_reciprocal_reader_on_gpu():
     env = _env(STAGE, False, os.path.join(ROOT, 'mpyc_amd', 'autoinstall'))
     r = subprocess.run([sys.executable, '-c', _RECIPROCAL_CODE], capture_output=True, text=True, cwd='/tmp', env=env, timeout=600)

@@ -11,7 +11,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = next((r for r in ('/root/reference', os.path.join(ROOT, '_refstage')) if os.path.isdir(os.path.join(r, 'mpyc'))), None)
+REF = next((r for r in ('/root/reference', os.path.join(ROOT, 'oracle', '_ref')) if os.path.isdir(os.path.join(r, 'mpyc'))), None)
 PROG = os.path.join(ROOT, 'tests', 'prss_mode_program.py')
 
 

@@ -136,7 +136,7 @@ def test_foreign_prf_class_is_admitted_only_after_a_known_answer_check(monkeypat
         assert gth.register_shake_prf(cls) is False and cls not in gth.SHAKE_PRF_TYPES
     import os
     import sys
-    for root in (os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), '_refstage'), '/root/reference'):
+    for root in (os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle', '_ref'), '/root/reference'):
         if os.path.isdir(os.path.join(root, 'mpyc')):
             monkeypatch.syspath_prepend(root)
             sys.modules.pop('mpyc.thresha', None) if 'mpyc' not in sys.modules else None

@@ -9,7 +9,7 @@ repetitions only.  Every function's own time (tottime) is attributed to
     other       everything else (the program itself, import-time leftovers)
 -> one markdown table: wall ms per repetition, ms and share per group, GPU-busy ms beside it.
 
-    python tools/api_host_profile.py [out.md]          (GPU box; needs the staged reference copy _refstage/)
+    python tools/api_host_profile.py [out.md]          (GPU box; needs the staged reference copy oracle/_ref/)
 """
 import json
 import os
@@ -19,7 +19,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = next((r for r in (os.path.join(ROOT, '_refstage'), '/root/reference') if os.path.isdir(os.path.join(r, 'mpyc'))), None)
+REF = next((r for r in (os.path.join(ROOT, 'oracle', '_ref'), '/root/reference') if os.path.isdir(os.path.join(r, 'mpyc'))), None)
 PROG = os.path.join(ROOT, 'tests', 'api_program.py')
 
 
@@ -75,7 +75,7 @@ def profile(n, reps, tmp, parties=1):
 
 def main():
     if REF is None:
-        raise SystemExit('no importable mpyc checkout (stage one with tools/stage_reference.sh)')
+        raise SystemExit('no importable mpyc checkout (build() stages one into oracle/_ref/)')
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'gpurun_out', 'r05_api_host.md')
     rows = []
     with tempfile.TemporaryDirectory() as tmp:

@@ -2,7 +2,7 @@
 # The reference's own vectorised demos (demos/np-run-all.sh), unmodified, with and without mpyc_amd.install():
 # same printed results expected (offsets / seeds fixed so that the runs are comparable;
 # np_cnnmnist is left out: its weight files are not part of the checkout).  usage: run_np_demos.sh <mpyc checkout> [cpuctx]   (cpuctx: build container, no GPU)
-REF=${1:-_refstage}; MODE=${2:-gpu}
+REF=${1:-oracle/_ref}; MODE=${2:-gpu}
 R=$(cd "$(dirname "$0")/.." && pwd)
 REF=$(cd "$REF" && pwd)
 SITE=$R/mpyc_amd/autoinstall; EXTRA=""

@@ -1,13 +1,7 @@
 #!/bin/bash
-# Build container only: copy the parts of the reference checkout that the drop-in acceptance tests run
-# (tests/test_mpyc_dropin.py, -m gpu) into the UNTRACKED scratch directory _refstage/ (git-ignored, never
-# committed; gpurun ships it to the GPU box, where /root/reference does not exist).
+# Stage the reference checkout into oracle/_ref/ (git-ignored, never committed): the recipe build() runs too
+# (oracle/Makefile `ref`).  The drop-in acceptance tests (-m gpu) run the copy.   usage: stage_reference.sh [<mpyc checkout>]
 set -e
 cd "$(dirname "$0")/.."
-rm -rf _refstage && mkdir -p _refstage/demos
-cp -r /root/reference/mpyc _refstage/mpyc
-cp -r /root/reference/tests _refstage/tests
-cp /root/reference/demos/np_*.py /root/reference/demos/pseudoinverse.py /root/reference/demos/sha3.py _refstage/demos/
-cp -r /root/reference/demos/data _refstage/demos/data 2>/dev/null || true
-find _refstage -name __pycache__ -prune -exec rm -rf {} +
-du -sh _refstage
+make -C oracle ref ${1:+MPYC_REFERENCE="$1"}
+du -sh oracle/_ref
