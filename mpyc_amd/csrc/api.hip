@@ -32,31 +32,31 @@ const FieldOps* ffgpu_ops_gf2w32();
 const FieldOps* ffgpu_ops_gf2w64();
 const FieldOps* ffgpu_ops_gf2w128();
 int ffgpu_sbox_build_lut(const void* gf2p8_policy, const uint8_t* rows8, uint8_t b, uint8_t* lut256);
-int ffgpu_launch_sbox(const uint8_t* lut256, int device, const void* in, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_to_bits(int device, const void* in, const void* addend, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_mask_open(const void* policy, int device, const void* const* rows, const uint64_t* coef2, int nrows,
+int ffgpu_launch_sbox(const uint8_t* lut256, const ffgpu::LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st);
+int ffgpu_launch_gf8_to_bits(const ffgpu::LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st);
+int ffgpu_launch_gf8_mask_open(const void* policy, const ffgpu::LaunchCfg& lc, const void* const* rows, const uint64_t* coef2, int nrows,
                                const void* const* rbits, const uint64_t* mu2, int np, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_bits_affine_fold(const void* policy, int device, const uint64_t* m2, const uint64_t* bias2, const void* c,
+int ffgpu_launch_gf8_bits_affine_fold(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, const void* c,
                                       const void* rbits, size_t ybr, void* out, size_t ybo, size_t n, int nbatch,
                                       hipStream_t st);
-int ffgpu_launch_gf8_group8(const void* policy, int device, const uint64_t* m2, const uint64_t* bias2, int fold,
+int ffgpu_launch_gf8_group8(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
                             const void* in, void* out, size_t ngroups, hipStream_t st);
-int ffgpu_launch_copy(int device, const void* src, void* dst, size_t bytes, hipStream_t st);
-int ffgpu_launch_valu_probe(int device, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st);
+int ffgpu_launch_copy(const ffgpu::LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st);
+int ffgpu_launch_valu_probe(const ffgpu::LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st);
 int ffgpu_gf8_build_tables(const void* policy, void* tables_out);
 int ffgpu_gf2w_build_rtable(const void* policy, int limbs, void* rtable_out);
-int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, int device, const void* const* rows, const uint64_t* lam2,
+int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const ffgpu::LaunchCfg& lc, const void* const* rows, const uint64_t* lam2,
                                 int k, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_sbox_layer(const void* policy, int device, const void* x, size_t xs, const void* r, size_t rs, void* out,
+int ffgpu_launch_gf8_sbox_layer(const void* policy, const ffgpu::LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs, void* out,
                                 size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2, int t, int m,
                                 size_t n, hipStream_t st, const ffgpu::RngArgs* rng);
 void ffgpu_gf8_sbox_layer_tables(const void* policy, const void* mul_tables, const uint64_t* m2, const uint64_t* bias2,
                                  unsigned char* out);
-int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, int device, const void* a,
+int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const ffgpu::LaunchCfg& lc, const void* a,
                               const void* b, void* out, size_t n, hipStream_t st);
-size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, int device, const void* a, const void* b, void* out, size_t n,
+size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                                          hipStream_t st);
-int ffgpu_launch_gf8_mul_tab(const void* tables, int device, const void* a, const void* b, void* out, size_t n,
+int ffgpu_launch_gf8_mul_tab(const void* tables, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                              hipStream_t st);
 
 struct ffgpu_ctx {
@@ -67,7 +67,7 @@ struct ffgpu_ctx {
     int policy_kind;
     const FieldOps* ops;
     uint64_t rng_r[2];  // 2^W mod p for the keystream sampler
-    ffgpu::Tuning tune; // run-time switches, read from the environment when the context is created
+    ffgpu::LaunchCfg lc; // launch shape and run-time switches, filled when the context is created
     int gf8_tab_min;    // GF(2^n<=8): arrays of at least this many elements multiply through LDS tables
     alignas(16) unsigned char gf8_tables[1536];
     int gf2w_limbs;     // GF(2^n), 9 <= n <= 128: 1 or 2 limbs -> windowed multiplication kernel
@@ -133,28 +133,6 @@ static int launch_status(int rc) {
     if (rc == 2) return FFGPU_ENOTSUP;
     return FFGPU_EINVAL;
 }
-
-namespace ffgpu {
-LaunchCfg launch_cfg(int device) {
-    static std::mutex mu;
-    static LaunchCfg cache[64];
-    static bool have[64];
-    std::lock_guard<std::mutex> g(mu);
-    int d = (device >= 0 && device < 64) ? device : 0;
-    if (!have[d]) {
-        int cus = 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || cus <= 0)
-            cus = 256;
-        int bpc = 0;  // uncapped
-        const char* e = getenv("FFGPU_BLOCKS_PER_CU");
-        if (e && atoi(e) >= 0) bpc = atoi(e);
-        cache[d].num_cu = cus;
-        cache[d].blocks_per_cu = bpc;
-        have[d] = true;
-    }
-    return cache[d];
-}
-}  // namespace ffgpu
 
 struct DeviceGuard {
     int prev;
@@ -294,13 +272,19 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
     c->elem_bytes = pb.elem_bytes;
     c->policy_kind = pb.kind;
     rng_const(pb, c->rng_r);
-    {   // the library's switches: read here, once per context -- no call path looks at the environment
-        const char* e = getenv("FFGPU_MM_MFMA");
-        c->tune.mm_mfma = e ? (atoi(e) != 0) : 1;
+    {   // the launch shape and the library's switches: read here, once per context -- no call path looks at the
+        // environment or queries the device
+        int cus = 256;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+        c->lc.num_cu = cus;
+        const char* e = getenv("FFGPU_BLOCKS_PER_CU");
+        c->lc.blocks_per_cu = e && atoi(e) >= 0 ? atoi(e) : 0;     // 0: uncapped
+        e = getenv("FFGPU_MM_MFMA");
+        c->lc.mm_mfma = e ? (atoi(e) != 0) : 1;
         e = getenv("FFGPU_MM_MFMA_MIN");
-        c->tune.mm_mfma_min = e ? atof(e) : 8e7;
+        c->lc.mm_mfma_min = e ? atof(e) : 8e7;
         e = getenv("FFGPU_GF2W_BITSLICED");
-        c->tune.gf2w_bitsliced = e ? (atoi(e) != 0) : 1;
+        c->lc.gf2w_bitsliced = e ? (atoi(e) != 0) : 1;
     }
     c->gf2w_limbs = 0;
     if (pb.kind == POL_GF2W64 || pb.kind == POL_GF2W128) {
@@ -314,7 +298,7 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         } else {
             GF2W64 f;
             memcpy(&f, pb.bytes, sizeof(f));
-            in_regs = f.n <= 32 || (f.fast & 1) != 0;
+            in_regs = (f.fast & 1) != 0;
         }
         if (!in_regs) {
             c->gf2w_limbs = pb.kind == POL_GF2W128 ? 2 : 1;
@@ -529,7 +513,7 @@ static int do_ew2(ffgpu_ctx* ctx, int op, const void* a, const void* b, void* ou
     ARGCHK(a && b && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->ew2(ctx->policy, ctx->device, op, a, b, out, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->ew2(ctx->policy, ctx->lc, op, a, b, out, n, (hipStream_t)stream));
 }
 static int do_ew1(ffgpu_ctx* ctx, int op, const void* a, const uint64_t* s, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
@@ -537,7 +521,7 @@ static int do_ew1(ffgpu_ctx* ctx, int op, const void* a, const uint64_t* s, void
     ARGCHK(a && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->ew1(ctx->policy, ctx->device, op, a, s, out, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, op, a, s, out, n, (hipStream_t)stream));
 }
 
 int ffgpu_reduce(ffgpu_ctx* ctx, const void* raw, void* out, size_t n, void* stream) {
@@ -553,25 +537,25 @@ int ffgpu_mul(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n,
     if (ctx && ctx->gf8_tab_min && n >= (size_t)ctx->gf8_tab_min && a && b && out) {
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, ctx->device, a, b, out, n,
+        return launch_status(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, ctx->lc, a, b, out, n,
                                                       (hipStream_t)stream));
     }
     if (ctx && ctx->gf2w_limbs && n && a && b && out) {
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, ctx->device,
+        return launch_status(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, ctx->lc,
                                                        a, b, out, n, (hipStream_t)stream));
     }
-    if (ctx && ctx->policy_kind == POL_GF2W64 && ctx->tune.gf2w_bitsliced && a && b && out && n >= ((size_t)1 << 21)) {
+    if (ctx && ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && a && b && out && n >= ((size_t)1 << 21)) {
         // GF(2^64) with the default modulus: bit-sliced product for all whole pairs of elements, the element-wise kernel for
         // the odd last one -- both launches under ONE timer scope (ffgpu_last_kernel_ms reports the call, not its tail)
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        const size_t done = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, ctx->device, a, b, out, n, (hipStream_t)stream);
+        const size_t done = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, ctx->lc, a, b, out, n, (hipStream_t)stream);
         if (done && hipGetLastError() != hipSuccess) return FFGPU_EHIP;
         if (done == n) return FFGPU_OK;
         if (done)
-            return launch_status(ctx->ops->ew2(ctx->policy, ctx->device, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
+            return launch_status(ctx->ops->ew2(ctx->policy, ctx->lc, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
                                                (char*)out + 8 * done, n - done, (hipStream_t)stream));
     }
     return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
@@ -598,7 +582,7 @@ int ffgpu_muladd(ffgpu_ctx* ctx, const void* a, const void* b, const void* c, vo
     ARGCHK(a && b && c && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->muladd(ctx->policy, ctx->device, a, b, c, out, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->muladd(ctx->policy, ctx->lc, a, b, c, out, n, (hipStream_t)stream));
 }
 
 static int make_exp(const uint64_t* e, int limbs, ExpArgs* ex) {
@@ -686,11 +670,11 @@ int ffgpu_pow(ffgpu_ctx* ctx, const void* a, const uint64_t* host_exp, int exp_l
     if (ex.nbits == 0) {
         // a^0 = 1 (also for a = 0, as pow(0, 0, p) = 1): 0*a + 1
         uint64_t zero[3] = {0, 0, 0}, one[3] = {1, 0, 0};
-        rc = launch_status(ctx->ops->ew1(ctx->policy, ctx->device, OP_MUL, a, zero, out, n, (hipStream_t)stream));
+        rc = launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, OP_MUL, a, zero, out, n, (hipStream_t)stream));
         if (rc != FFGPU_OK) return rc;
-        return launch_status(ctx->ops->ew1(ctx->policy, ctx->device, OP_ADD, out, one, out, n, (hipStream_t)stream));
+        return launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, OP_ADD, out, one, out, n, (hipStream_t)stream));
     }
-    return launch_status(ctx->ops->pow(ctx->policy, ctx->device, a, &ex, out, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->pow(ctx->policy, ctx->lc, a, &ex, out, n, (hipStream_t)stream));
 }
 
 // three-limb primes: exponents derived from p by limb arithmetic
@@ -759,7 +743,7 @@ int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stre
     }
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->sqrt_cl(ctx->policy, ctx->device, a, &eleg, &elad, out, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->sqrt_cl(ctx->policy, ctx->lc, a, &eleg, &elad, out, n, (hipStream_t)stream));
 }
 
 int ffgpu_gauss(ffgpu_ctx* ctx, void* a, int n, int ncols, size_t batch, int mode, void* det_out,
@@ -774,7 +758,7 @@ int ffgpu_gauss(ffgpu_ctx* ctx, void* a, int n, int ncols, size_t batch, int mod
     ExpArgs ex;
     inverse_exponent(ctx, &ex);
     if (hipMemsetAsync(dev_singular, 0, batch * sizeof(int), (hipStream_t)stream) != hipSuccess) return FFGPU_EHIP;
-    return launch_status(ctx->ops->gauss(ctx->policy, ctx->device, a, n, ncols, batch, mode, &ex,
+    return launch_status(ctx->ops->gauss(ctx->policy, ctx->lc, a, n, ncols, batch, mode, &ex,
                                          mode ? det_out : nullptr, (int*)dev_singular, (hipStream_t)stream));
 }
 
@@ -787,7 +771,7 @@ int ffgpu_inv(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* dev_zero
         inverse_exponent(ctx, &ex3);
         DeviceGuard g3(ctx->device);
         LaunchTimer lt3(ctx, (hipStream_t)stream);
-        return launch_status(ctx->ops->inv(ctx->policy, ctx->device, a, &ex3, out, n, (int*)dev_zero_flag,
+        return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &ex3, out, n, (int*)dev_zero_flag,
                                            (hipStream_t)stream));
     }
     // exponent q - 2 (order of the multiplicative group minus one)
@@ -806,14 +790,14 @@ int ffgpu_inv(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* dev_zero
     if (ctx->kind == FFGPU_PRIME && q == 2) {   // GF(2): 1^-1 = 1
         ExpArgs one;
         one.e[0] = 1; one.e[1] = one.e[2] = 0; one.nbits = 1; one.post = 0;
-        return launch_status(ctx->ops->inv(ctx->policy, ctx->device, a, &one, out, n, (int*)dev_zero_flag,
+        return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &one, out, n, (int*)dev_zero_flag,
                                            (hipStream_t)stream));
     }
     ExpArgs ex;
     int rc = make_exp(el, 2, &ex);
     if (rc != FFGPU_OK) return rc;
     if (ex.nbits == 0) { ex.e[0] = 1; ex.nbits = 1; }        // GF(2^1): q - 2 = 0 -> x^-1 = x
-    return launch_status(ctx->ops->inv(ctx->policy, ctx->device, a, &ex, out, n, (int*)dev_zero_flag,
+    return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &ex, out, n, (int*)dev_zero_flag,
                                        (hipStream_t)stream));
 }
 
@@ -824,7 +808,7 @@ int ffgpu_beaver_combine(ffgpu_ctx* ctx, const void* z, const void* x, const voi
     ARGCHK(z && x && y && d && e && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->beaver(ctx->policy, ctx->device, z, x, y, d, e, out, add_de ? 1 : 0, n,
+    return launch_status(ctx->ops->beaver(ctx->policy, ctx->lc, z, x, y, d, e, out, add_de ? 1 : 0, n,
                                           (hipStream_t)stream));
 }
 
@@ -838,7 +822,7 @@ static int do_split(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, co
     ARGCHK((m == 1 || share_stride >= n) && (t <= 1 || coeff_stride >= n));
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->split(ctx->policy, ctx->device, a, fused ? b : nullptr, coeffs,
+    return launch_status(ctx->ops->split(ctx->policy, ctx->lc, a, fused ? b : nullptr, coeffs,
                                          coeff_stride, t, m, shares, share_stride, n, (hipStream_t)stream,
                                          nullptr));
 }
@@ -871,7 +855,7 @@ static int do_split_rng(ffgpu_ctx* ctx, const void* a, const void* b, bool fused
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     if (fused && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    return launch_status(ctx->ops->split(ctx->policy, ctx->device, a, fused ? b : nullptr, nullptr, 0, t, m,
+    return launch_status(ctx->ops->split(ctx->policy, ctx->lc, a, fused ? b : nullptr, nullptr, 0, t, m,
                                          shares, share_stride, n, (hipStream_t)stream, t > 0 ? &ra : nullptr));
 }
 int ffgpu_ctx_scalar_limbs(const ffgpu_ctx* ctx) { return (ctx && ctx->elem_bytes == 24) ? 3 : 2; }
@@ -906,7 +890,7 @@ int ffgpu_split_rng_state(ffgpu_ctx* ctx, const void* secrets, const void* mul_b
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     if (mul_by && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    int rc = ctx->ops->split(ctx->policy, ctx->device, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n,
+    int rc = ctx->ops->split(ctx->policy, ctx->lc, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n,
                              (hipStream_t)stream, t > 0 ? &ra : nullptr);
     if (rc) return launch_status(rc);
     return FFGPU_OK;       // the kernel's last workgroup advanced the nonce (rng_state_release)
@@ -962,7 +946,7 @@ int ffgpu_gate_rng_batch(ffgpu_ctx* ctx, const void* const* host_rows_a, const u
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     ra.aux = gf8_tables_on_device(ctx);
-    return launch_status(ctx->ops->gate(ctx->policy, ctx->device, host_rows_a, host_lambda_a, ka, host_rows_b,
+    return launch_status(ctx->ops->gate(ctx->policy, ctx->lc, host_rows_a, host_lambda_a, ka, host_rows_b,
                                         host_lambda_b, kb, t, m, shares, share_stride, n, (hipStream_t)stream, &ra,
                                         nbatch, batch_stride_a, batch_stride_b, batch_stride_out));
 }
@@ -987,7 +971,7 @@ int ffgpu_rng_coeffs(ffgpu_ctx* ctx, const uint8_t* host_key32, uint64_t nonce, 
     ARGCHK(coeffs && (t == 1 || coeff_stride >= n));
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->rng_coeffs(ctx->policy, ctx->device, coeffs, coeff_stride, t, n,
+    return launch_status(ctx->ops->rng_coeffs(ctx->policy, ctx->lc, coeffs, coeff_stride, t, n,
                                               (hipStream_t)stream, &ra));
 }
 int ffgpu_split_rng(ffgpu_ctx* ctx, const void* secrets, const uint8_t* host_key32, uint64_t nonce, int rounds,
@@ -1016,12 +1000,12 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
         const int limbs = ctx->policy_kind == POL_GF2W128 ? 2 : 1;
         int rc = 0;
         for (int r = 0; r < w && rc == 0; ++r)
-            rc = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, ctx->device, host_rows, host_lambda + 2 * (size_t)r * k,
+            rc = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, ctx->lc, host_rows, host_lambda + 2 * (size_t)r * k,
                                              k, (char*)out + (size_t)r * out_stride * ctx->elem_bytes, n,
                                              (hipStream_t)stream);
         if (rc != 2) return launch_status(rc);
     }
-    return launch_status(ctx->ops->recombine(ctx->policy, ctx->device, host_rows, host_lambda, k, w, out,
+    return launch_status(ctx->ops->recombine(ctx->policy, ctx->lc, host_rows, host_lambda, k, w, out,
                                              out_stride, n, (hipStream_t)stream));
 }
 
@@ -1040,7 +1024,7 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
         // split-K partial sums
         size_t want = 0;
         const size_t Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
-        if (ctx->kind == FFGPU_PRIME && M > 8 && N > 8 && K >= 64 && ctx->tune.mm_mfma && (double)M * N * K >= ctx->tune.mm_mfma_min) {
+        if (ctx->kind == FFGPU_PRIME && M > 8 && N > 8 && K >= 64 && ctx->lc.mm_mfma && (double)M * N * K >= ctx->lc.mm_mfma_min) {
             want = (size_t)(ctx->elem_bytes <= 8 ? 8 : 16) * (Mp + Np) * Kp + ((size_t)64 << 20);   // digit planes per operand + split-K slabs
             if (want > ((size_t)8 << 30)) want = 0;
         }
@@ -1077,8 +1061,8 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
             ws_bytes = slot->bytes;
         }
     }
-    return launch_status(ctx->ops->matmul(ctx->policy, ctx->device, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws,
-                                          ws_bytes, &ctx->tune, (hipStream_t)stream));
+    return launch_status(ctx->ops->matmul(ctx->policy, ctx->lc, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws,
+                                          ws_bytes, (hipStream_t)stream));
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
@@ -1092,7 +1076,7 @@ int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64
     if (ctx->kind == FFGPU_BINARY && ctx->elem_bytes == 1 && g == 8 && (((uintptr_t)in) & 7u) == 0) {
         // groups of 8 bytes: packed-byte kernel (misc.hip)
         if (r == 8 && (((uintptr_t)out) & 7u) == 0)
-            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->device, host_matrix, host_bias, 0, in, out,
+            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, host_matrix, host_bias, 0, in, out,
                                                          ngroups, (hipStream_t)stream));
         bool pow2 = (r == 1);
         for (int c = 0; pow2 && c < 8; ++c) pow2 = (host_matrix[2 * c] == (1ull << c));
@@ -1100,11 +1084,11 @@ int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64
             uint64_t eye[128];
             memset(eye, 0, sizeof(eye));
             for (int c = 0; c < 8; ++c) eye[2 * (c * 8 + c)] = 1;
-            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->device, eye, nullptr, 1, in, out, ngroups,
+            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, eye, nullptr, 1, in, out, ngroups,
                                                          (hipStream_t)stream));
         }
     }
-    return launch_status(ctx->ops->group_matvec(ctx->policy, ctx->device, host_matrix, host_bias, r, g, in, out,
+    return launch_status(ctx->ops->group_matvec(ctx->policy, ctx->lc, host_matrix, host_bias, r, g, in, out,
                                                 ngroups, (hipStream_t)stream));
 }
 
@@ -1117,7 +1101,7 @@ int ffgpu_gf256_bit_affine(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
     if ((((uintptr_t)in) & 7u) || (!from_bits && (((uintptr_t)out) & 7u))) return FFGPU_EINVAL;
     DeviceGuard gd(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->device, host_matrix, host_bias, from_bits ? 1 : 0, in,
+    return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, host_matrix, host_bias, from_bits ? 1 : 0, in,
                                                  out, n, (hipStream_t)stream));
 }
 
@@ -1130,7 +1114,7 @@ static int do_dot(ffgpu_ctx* ctx, const void* a, const void* b, void* out, void*
         return FFGPU_OK;
     }
     ARGCHK(a && workspace);
-    return launch_status(ctx->ops->dot(ctx->policy, ctx->device, a, b, out, workspace, n, (hipStream_t)stream));
+    return launch_status(ctx->ops->dot(ctx->policy, ctx->lc, a, b, out, workspace, n, (hipStream_t)stream));
 }
 int ffgpu_dot(ffgpu_ctx* ctx, const void* a, const void* b, void* out, void* workspace, size_t n, void* stream) {
     ARGCHK(n == 0 || b);
@@ -1151,7 +1135,7 @@ int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, 
     uint64_t r2[2] = {ctx->rng_r[0], ctx->rng_r[1]};
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->prss(ctx->policy, ctx->device, host_streams, ks, d, l, mask_bits, host_weights,
+    return launch_status(ctx->ops->prss(ctx->policy, ctx->lc, host_streams, ks, d, l, mask_bits, host_weights,
                                         r2, accumulate, out, n, (hipStream_t)stream));
 }
 
@@ -1165,7 +1149,7 @@ int ffgpu_prss_chacha(ffgpu_ctx* ctx, const uint8_t* host_keys, int ks, int d, i
     uint64_t r2[2] = {ctx->rng_r[0], ctx->rng_r[1]};
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->prss_chacha(ctx->policy, ctx->device, host_keys, ks, d, l, mask_bits, rounds, host_weights,
+    return launch_status(ctx->ops->prss_chacha(ctx->policy, ctx->lc, host_keys, ks, d, l, mask_bits, rounds, host_weights,
                                                r2, accumulate, out, n, (hipStream_t)stream));
 }
 int ffgpu_prss_chacha_layout(int l, int* tb, int* dpt) {
@@ -1181,7 +1165,7 @@ int ffgpu_gf256_to_bits(ffgpu_ctx* ctx, const void* in, const void* addend, void
     ARGCHK(in && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_to_bits(ctx->device, in, addend, out, n, (hipStream_t)stream));
+    return launch_status(ffgpu_launch_gf8_to_bits(ctx->lc, in, addend, out, n, (hipStream_t)stream));
 }
 
 int ffgpu_gf256_mask_open(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_coef, int nrows,
@@ -1196,7 +1180,7 @@ int ffgpu_gf256_mask_open(ffgpu_ctx* ctx, const void* const* host_rows, const ui
     for (int p = 0; p < np; ++p) ARGCHK(host_rbits[p]);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_mask_open(ctx->policy, ctx->device, host_rows, host_coef, nrows, host_rbits, host_mu,
+    return launch_status(ffgpu_launch_gf8_mask_open(ctx->policy, ctx->lc, host_rows, host_coef, nrows, host_rbits, host_mu,
                                                     np, out, n, (hipStream_t)stream));
 }
 
@@ -1211,7 +1195,7 @@ int ffgpu_gf256_bits_affine_fold(ffgpu_ctx* ctx, const uint64_t* host_matrix, co
     ARGCHK(nbatch == 1 || (rbits_batch_stride >= 8 * n && out_batch_stride >= n));
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_bits_affine_fold(ctx->policy, ctx->device, host_matrix, host_bias, c, rbits,
+    return launch_status(ffgpu_launch_gf8_bits_affine_fold(ctx->policy, ctx->lc, host_matrix, host_bias, c, rbits,
                                                            rbits_batch_stride, out, out_batch_stride, n, nbatch,
                                                            (hipStream_t)stream));
 }
@@ -1264,7 +1248,7 @@ int ffgpu_gf256_sbox_layer(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
         }
     }
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_sbox_layer(ctx->policy, ctx->device, x, x_stride, rbits, rbits_stride, out, out_stride,
+    return launch_status(ffgpu_launch_gf8_sbox_layer(ctx->policy, ctx->lc, x, x_stride, rbits, rbits_stride, out, out_stride,
                                                      ctx->sbl_tables_dev, host_lambda, host_mu, t, m, n, (hipStream_t)stream, &ra));
 }
 
@@ -1293,7 +1277,7 @@ int ffgpu_gf256_sbox(ffgpu_ctx* ctx, const void* in, const uint8_t* host_rows8, 
     }
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_sbox(lut, ctx->device, in, out, n, (hipStream_t)stream));
+    return launch_status(ffgpu_launch_sbox(lut, ctx->lc, in, out, n, (hipStream_t)stream));
 }
 
 }  // extern "C"
@@ -1346,19 +1330,19 @@ int ffgpu_copy(ffgpu_ctx* ctx, const void* src, void* dst, size_t bytes, void* s
     ARGCHK(src && dst);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_copy(ctx->device, src, dst, bytes, (hipStream_t)stream));
+    return launch_status(ffgpu_launch_copy(ctx->lc, src, dst, bytes, (hipStream_t)stream));
 }
 int ffgpu_valu_probe(ffgpu_ctx* ctx, int op, int iters, int waves_per_simd, void* scratch32, double* out3, void* stream) {
     ARGCHK(ctx && scratch32 && out3);
     ARGCHK(op >= 0 && op <= 13 && iters >= 1 && waves_per_simd >= 1 && waves_per_simd <= 8);
     DeviceGuard g(ctx->device);
-    return launch_status(ffgpu_launch_valu_probe(ctx->device, op, iters, waves_per_simd, scratch32, out3, (hipStream_t)stream));
+    return launch_status(ffgpu_launch_valu_probe(ctx->lc, op, iters, waves_per_simd, scratch32, out3, (hipStream_t)stream));
 }
 int ffgpu_time_copy(ffgpu_ctx* ctx, const void* src, void* dst, size_t bytes, int reps, void* stream,
                     float* ms) {
     ARGCHK(ctx && src && dst);
     return time_loop(ctx, reps, stream, ms, [&]() {
-        return launch_status(ffgpu_launch_copy(ctx->device, src, dst, bytes, (hipStream_t)stream));
+        return launch_status(ffgpu_launch_copy(ctx->lc, src, dst, bytes, (hipStream_t)stream));
     });
 }
 

@@ -1459,12 +1459,11 @@ FF_HD void ff_clmul128(uint64_t alo, uint64_t ahi, uint64_t blo, uint64_t bhi, u
 }
 
 // ---------------------------------------------------------------------------
-// GF2W64 / GF2W128: GF(2^n) for 33 <= n <= 64 (and 9..32 for callers that ask for 8-byte words) / 65 <= n <= 128.
+// GF2W64 / GF2W128: GF(2^n) for 33 <= n <= 64 / 65 <= n <= 128 (9 <= n <= 32: GF2W32 below).
 // mul: carry-less product (above) + reduction.  For moduli x^n + r(x) with a
 // short r (r < 2^28: every default MPyC irreducible, e.g. x^128+x^7+x^2+x+1) the
 // high part is folded down with one shift-xor per set bit of r (`fast`, nfold
-// passes); other moduli take the bit-serial loop.  n <= 32 reduces bit-serially
-// (at most 31 steps on a 64-bit product).
+// passes); other moduli take the bit-serial loop.
 // ---------------------------------------------------------------------------
 struct GF2W64 {
     typedef uint64_t elem;
@@ -1502,6 +1501,9 @@ struct GF2W64 {
         return c;
     }
     FF_HD uint64_t mul(uint64_t a, uint64_t b) const {
+        // (n <= 32 never reaches this type: build_binary_policy sends it to GF2W32.  The branch stays because it steers
+        // how the callers' loops are unrolled: without it k_group_matvec and the dense-modulus k_recombine<7> take 1.9-2.2x
+        // the time on GF(2^64) -- 441 / 407 VGPRs instead of 63 / 210)
         if (n <= 32) {
             uint64_t pr = ff_clmul32((uint32_t)a, (uint32_t)b);
             // sparse modulus (every default MPyC irreducible): a few fold passes, as for the wider fields (round 6: GF(2^32)

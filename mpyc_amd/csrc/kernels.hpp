@@ -162,10 +162,16 @@ __device__ __forceinline__ void stg(e96* p, const Pack<u128e>& x) {
 // per-wave LDS region (written 16 bytes per lane, read back as three 8-byte words at a 24-byte stride, or the other way
 // round: conflict-free either way); no barrier: a wave's LDS instructions execute in order, a wavefront-scope fence on
 // the LDS address space alone keeps the compiler from reordering them.
-// next iteration's arrays are not held up by anything else.  The launchers (launch.hpp, Launchers<F>::nvec_of) hand 24-byte fields
-// whole waves only (nvec a multiple of 64, the rest goes through the scalar tail) and require 16-byte aligned rows.
-// Loads come in two steps so that a kernel puts ALL its global loads in flight before the first LDS round trip:   auto ra = ldgw_issue<NT>(pa), rb = ldgw_issue<NT>(pb);
-//                                                  P x = ldgw_finish(ra), y = ldgw_finish(rb);
+// What guarantees whole waves: every launcher takes nvec from Launchers<F>::plan (launch.hpp), which hands 24-byte fields a
+// multiple of 64 (the rest goes through the scalar tail) and requires 16-byte aligned rows; with 64-lane waves and blocks
+// of whole waves (checked below) every wave of the streaming loop is then entirely in or entirely out.
+// Loads come in two steps so that a kernel puts ALL its global loads in flight before the first LDS round trip:
+//     auto ra = ldgw_issue<NT>(pa), rb = ldgw_issue<NT>(pb);
+//     P x = ldgw_finish(ra), y = ldgw_finish(rb);
+static_assert(BLOCK % 64 == 0, "ldgw / stgw: a workgroup is whole 64-lane waves");
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "ldgw / stgw assume 64-lane waves: build for a wave64-only (gfx9 / CDNA) target"
+#endif
 template <bool NT, class P>
 __device__ __forceinline__ auto ldgw_issue(const P* p) { return ldg<NT>(p); }
 template <class X>

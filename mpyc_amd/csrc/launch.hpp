@@ -5,15 +5,11 @@
 namespace ffgpu {
 
 // ---- launch plumbing -------------------------------------------------------
+// The library's launch shape and run-time switches (one table: INTEGRATION.md section 6).  Filled ONCE per context, when it
+// is created (ffgpu_ctx_create), and carried by it: no getenv and no device query on any call path.
 struct LaunchCfg {
-    int blocks_per_cu;  // 0 = uncapped grid: one 16-byte pack per thread (default, measured best)
-    int num_cu;
-};
-LaunchCfg launch_cfg(int device);
-
-// The library's run-time switches (one table: INTEGRATION.md section 6).  Read from the environment ONCE per context, when
-// it is created (ffgpu_ctx_create), and carried by it: no getenv on any call path.
-struct Tuning {
+    int num_cu;             // compute units of the context's device
+    int blocks_per_cu;      // FFGPU_BLOCKS_PER_CU: cap of the streaming grids; 0 = uncapped: one 16-byte pack per thread (default, measured best)
     int mm_mfma;            // FFGPU_MM_MFMA=0: dense products stay on the VALU kernel (cross-checks of the matrix-core path)
     double mm_mfma_min;     // FFGPU_MM_MFMA_MIN: smallest M*N*K that goes to the matrix cores (default 8e7)
     int gf2w_bitsliced;     // FFGPU_GF2W_BITSLICED=0: GF(2^64) products through the multiplier kernel only
@@ -31,44 +27,43 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // host-side table of launchers for one policy type; the context stores the
 // policy blob and a pointer to this table.
 struct FieldOps {
-    int (*ew2)(const void* F, int device, int op, const void* a, const void* b, void* o, size_t n,
+    int (*ew2)(const void* F, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                hipStream_t st);
-    int (*ew1)(const void* F, int device, int op, const void* a, const uint64_t* scalar2, void* o,
+    int (*ew1)(const void* F, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                size_t n, hipStream_t st);
-    int (*muladd)(const void* F, int device, const void* a, const void* b, const void* c, void* o,
+    int (*muladd)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
                   size_t n, hipStream_t st);
     // coef == nullptr && rng != nullptr: coefficients are drawn in-kernel from the keystream
-    int (*split)(const void* F, int device, const void* a, const void* b, const void* coef,
+    int (*split)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
                  size_t cstride, int t, int m, void* out, size_t ostride, size_t n, hipStream_t st,
                  const RngArgs* rng);
-    int (*rng_coeffs)(const void* F, int device, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
+    int (*rng_coeffs)(const void* F, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
                       const RngArgs* rng);
-    int (*recombine)(const void* F, int device, const void* const* rows, const uint64_t* lam2, int k,
+    int (*recombine)(const void* F, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                      int w, void* out, size_t ostride, size_t n, hipStream_t st);
-    int (*pow)(const void* F, int device, const void* a, const ExpArgs* ex, void* out, size_t n, hipStream_t st);
-    int (*inv)(const void* F, int device, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
+    int (*pow)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, hipStream_t st);
+    int (*inv)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
                hipStream_t st);
-    int (*matmul)(const void* F, int device, const void* A, size_t lda, const void* B, size_t ldb, void* C,
-                  size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, const Tuning* tune,
-                  hipStream_t st);
-    int (*dot)(const void* F, int device, const void* a, const void* b, void* out, void* workspace, size_t n,
+    int (*matmul)(const void* F, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
+                  size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t st);
+    int (*dot)(const void* F, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                hipStream_t st);
     // nbatch > 1: gridDim.y independent gates in one launch, operands / outputs of gate y at element offsets y*yA, y*yB, y*yO
-    int (*gate)(const void* F, int device, const void* const* rowsA, const uint64_t* lamA2, int kA,
+    int (*gate)(const void* F, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
                 const void* const* rowsB, const uint64_t* lamB2, int kB, int t, int m, void* out, size_t ostride,
                 size_t n, hipStream_t st, const RngArgs* rng, int nbatch, size_t yA, size_t yB, size_t yO);
-    int (*sqrt_cl)(const void* F, int device, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out, size_t n,
+    int (*sqrt_cl)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out, size_t n,
                    hipStream_t st);
-    int (*gauss)(const void* F, int device, void* A, int n, int ncols, size_t batch, int det_mode, const ExpArgs* ex,
+    int (*gauss)(const void* F, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode, const ExpArgs* ex,
                  void* det, int* sing, hipStream_t st);
-    int (*group_matvec)(const void* F, int device, const uint64_t* m2, const uint64_t* bias2, int r, int g,
+    int (*group_matvec)(const void* F, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
                         const void* in, void* out, size_t ngroups, hipStream_t st);
-    int (*beaver)(const void* F, int device, const void* z, const void* x, const void* y, const void* d, const void* e,
+    int (*beaver)(const void* F, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d, const void* e,
                   void* out, int add_de, size_t n, hipStream_t st);
-    int (*prss)(const void* F, int device, const void* const* streams, int ks, int d, int l, int mask_bits,
+    int (*prss)(const void* F, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
                 const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
     // keys40: ks x (32-byte ChaCha key + 8-byte nonce)
-    int (*prss_chacha)(const void* F, int device, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
+    int (*prss_chacha)(const void* F, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                        const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
 };
 
@@ -142,6 +137,34 @@ struct Launchers {
         if (sizeof(E) == 24) return n & ~(size_t)63;
         return n / EPV;
     }
+    // The streaming plan of a launch: nvec packs through the vector loop, one pack per thread up to the grid cap (one element
+    // per thread when the operands do not allow packs).  The one place where nvec_of and grid_for meet: every launcher takes
+    // its nvec from here, so 24-byte fields get whole waves whatever grid it then picks.
+    struct Plan {
+        size_t nvec;
+        unsigned grid;
+    };
+    static Plan plan(size_t n, bool vec, const LaunchCfg& lc) {
+        const size_t nvec = nvec_of(n, vec);
+        return {nvec, grid_for(nvec ? nvec : n, lc)};
+    }
+    // share generation with in-kernel coefficients (k_split RNG, the gate): the grouped loop serves up to 4 packs per thread
+    // (RngLayout::G) on half as many threads as packs, a slightly larger grid is harmless; below ~2.6e5 packs it cannot
+    // fill the chip and every thread takes one pack instead (ra.spread).  Small grids let the kernel's last workgroup
+    // advance the device-resident nonce (ra.release, gy gates per launch counted); otherwise rng_advance follows.
+    static Plan plan_rng(size_t n, bool vec, const LaunchCfg& lc, RngArgs& ra, unsigned gy = 1) {
+        Plan p = plan(n, vec, lc);
+        const bool spread = p.nvec > 0 && p.nvec < 262144;
+        ra.spread = spread ? 1 : 0;
+        if (p.nvec && !spread) p.grid = grid_for((n / EPV + 2) / 2, lc);
+        ra.release = !ra.no_advance && (size_t)p.grid * gy <= RNG_RELEASE_MAX_GRID;
+        return p;
+    }
+    // after an RNG launch: advance the device-resident nonce unless the kernel did (ra.release) or the caller will
+    static void rng_advance(const RngArgs& ra, hipStream_t st) {
+        if (ra.dev_key && !ra.release && !ra.no_advance)
+            hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, st, const_cast<RngKey*>(ra.dev_key), 1u);
+    }
     // (a member function, not a lambda inside `matmul`: clang does not emit the host stub of a kernel specialisation
     // that is only named inside a generic lambda's discarded-branch neighbourhood)
     template <bool BRAW>
@@ -163,21 +186,18 @@ struct Launchers {
 
     template <int OP>
     static void go_ew2(const F& f, const LaunchCfg& lc, const E* a, const E* b, E* o, size_t n, hipStream_t st) {
-        bool vec = al(a) && al(b) && al(o);
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
+        const Plan p = plan(n, al(a) && al(b) && al(o), lc);
         constexpr int OCC = EwOccupancy<F, OP>::waves;
         // (streamed loads and stores carry the non-temporal hint: +4-8 %, profiles/r01_tuning.md; the un-hinted instantiations
         // that rounds 1-5 kept behind FFGPU_NT=0 for A/B runs are gone)
         if constexpr (OCC > 0)
-            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(grid), dim3(BLOCK), 0, st, f, a, b, o, nvec, n);
+            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n);
         else
-            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(grid), dim3(BLOCK), 0, st, f, a, b, o, nvec, n);
+            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n);
     }
-    static int ew2(const void* Fp, int device, int op, const void* a, const void* b, void* o, size_t n,
+    static int ew2(const void* Fp, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         const E* A = (const E*)a;
         const E* B = (const E*)b;
         E* O = (E*)o;
@@ -193,15 +213,12 @@ struct Launchers {
 
     template <int OP>
     static void go_ew1(const F& f, const LaunchCfg& lc, const E* a, W s, E* o, size_t n, hipStream_t st) {
-        bool vec = al(a) && al(o);
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
-        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(grid), dim3(BLOCK), 0, st, f, a, s, o, nvec, n);
+        const Plan p = plan(n, al(a) && al(o), lc);
+        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n);
     }
-    static int ew1(const void* Fp, int device, int op, const void* a, const uint64_t* scalar2, void* o,
+    static int ew1(const void* Fp, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                    size_t n, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         W s = scalar2 ? word_at<F>(f, scalar2, 0) : word_from_limbs<F>(f, 0, 0);
         const E* A = (const E*)a;
         E* O = (E*)o;
@@ -218,74 +235,56 @@ struct Launchers {
         return 0;
     }
 
-    static int muladd(const void* Fp, int device, const void* a, const void* b, const void* c, void* o,
+    static int muladd(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
                       size_t n, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
-        bool vec = al(a) && al(b) && al(c) && al(o);
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
-        hipLaunchKernelGGL((k_muladd<F, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a,
-                           (const E*)b, (const E*)c, (E*)o, nvec, n);
+        const Plan p = plan(n, al(a) && al(b) && al(c) && al(o), lc);
+        hipLaunchKernelGGL((k_muladd<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a,
+                           (const E*)b, (const E*)c, (E*)o, p.nvec, n);
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
 
     template <int T, bool FUSE, bool RNG, bool REC = false>
-    static void go_split(const F& f, unsigned grid, bool nt, const E* a, const E* b, const E* coef,
-                         size_t cstride, int m, E* out, size_t ostride, size_t nvec, size_t n, hipStream_t st,
-                         const RngArgs& ra, const GateSrc<F>& gs, unsigned gy = 1) {
-        (void)nt;
-        hipLaunchKernelGGL((k_split<F, T, FUSE, true, RNG, REC>), dim3(grid, gy), dim3(BLOCK), 0, st, f, a, b,
-                           coef, cstride, m, out, ostride, nvec, n, ra, gs);
+    static void go_split(const F& f, const Plan& p, const E* a, const E* b, const E* coef, size_t cstride, int m, E* out,
+                         size_t ostride, size_t n, hipStream_t st, const RngArgs& ra, const GateSrc<F>& gs, unsigned gy = 1) {
+        hipLaunchKernelGGL((k_split<F, T, FUSE, true, RNG, REC>), dim3(p.grid, gy), dim3(BLOCK), 0, st, f, a, b,
+                           coef, cstride, m, out, ostride, p.nvec, n, ra, gs);
     }
     template <bool FUSE, bool RNG>
     static int split_t(const F& f, const LaunchCfg& lc, const E* a, const E* b, const E* coef, size_t cstride,
                        int t, int m, E* out, size_t ostride, size_t n, hipStream_t st, const RngArgs& ra_in) {
-        if (t > MAXT) {
-            RngArgs ra = ra_in;
-            unsigned grid = grid_for(n, lc);
-            ra.release = !ra.no_advance && grid <= RNG_RELEASE_MAX_GRID;
-            hipLaunchKernelGGL((k_split_any<F, FUSE, RNG>), dim3(grid), dim3(BLOCK), 0, st, f, a, b, coef, cstride,
-                               t, m, out, ostride, n, ra);
-            if (RNG && ra.dev_key && !ra.release && !ra.no_advance)
-                hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, st, const_cast<RngKey*>(ra.dev_key), 1u);
-            return 0;
-        }
-        bool vec = al(a) && (!FUSE || al(b)) && al(out) &&
-                   (stride_ok(ostride) || m <= 1) &&
-                   (RNG || t == 0 || (al(coef) && (stride_ok(cstride) || t <= 1)));
-        size_t nvec = nvec_of(n, vec);
-        // RNG kernels serve up to 4 packs per thread (RngLayout::G); a slightly larger grid is harmless.
-        // Below ~2.6e5 packs the grouped loop cannot fill the chip: one pack per thread instead (ra.spread).
         RngArgs ra = ra_in;
-        const bool spread = RNG && nvec > 0 && nvec < 262144;
-        ra.spread = spread ? 1 : 0;
-        unsigned grid = grid_for(nvec ? (RNG && !spread ? (n / EPV + 2) / 2 : nvec) : n, lc);
-        ra.release = !ra.no_advance && grid <= RNG_RELEASE_MAX_GRID;
-        const bool nt = true;
-        GateSrc<F> gs;
-        memset(&gs, 0, sizeof(gs));
-        switch (t) {
-            case 0: go_split<0, FUSE, false>(f, grid, nt, a, b, coef, cstride, m, out, ostride, nvec, n, st, ra, gs); break;
-            case 1: go_split<1, FUSE, RNG>(f, grid, nt, a, b, coef, cstride, m, out, ostride, nvec, n, st, ra, gs); break;
-            case 2: go_split<2, FUSE, RNG>(f, grid, nt, a, b, coef, cstride, m, out, ostride, nvec, n, st, ra, gs); break;
-            case 3: go_split<3, FUSE, RNG>(f, grid, nt, a, b, coef, cstride, m, out, ostride, nvec, n, st, ra, gs); break;
-            case 4: go_split<4, FUSE, RNG>(f, grid, nt, a, b, coef, cstride, m, out, ostride, nvec, n, st, ra, gs); break;
-            default: return 1;
+        if (t > MAXT) {
+            const Plan p = RNG ? plan_rng(n, false, lc, ra) : plan(n, false, lc);
+            hipLaunchKernelGGL((k_split_any<F, FUSE, RNG>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, coef, cstride,
+                               t, m, out, ostride, n, ra);
+        } else {
+            const bool vec = al(a) && (!FUSE || al(b)) && al(out) &&
+                             (stride_ok(ostride) || m <= 1) &&
+                             (RNG || t == 0 || (al(coef) && (stride_ok(cstride) || t <= 1)));
+            const Plan p = RNG ? plan_rng(n, vec, lc, ra) : plan(n, vec, lc);
+            GateSrc<F> gs;
+            memset(&gs, 0, sizeof(gs));
+            switch (t) {
+                case 0: go_split<0, FUSE, false>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
+                case 1: go_split<1, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
+                case 2: go_split<2, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
+                case 3: go_split<3, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
+                case 4: go_split<4, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
+                default: return 1;
+            }
         }
-        if (RNG && t > 0 && ra.dev_key && !ra.release && !ra.no_advance)
-            hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, st, const_cast<RngKey*>(ra.dev_key), 1u);
+        if (RNG && t > 0) rng_advance(ra, st);
         return 0;
     }
     // fused chain gate: both factors given as recombinations (GateSrc), product re-shared with the device CSPRNG
-    static int gate(const void* Fp, int device, const void* const* rowsA, const uint64_t* lamA2, int kA,
+    static int gate(const void* Fp, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
                     const void* const* rowsB, const uint64_t* lamB2, int kB, int t, int m, void* out, size_t ostride,
                     size_t n, hipStream_t st, const RngArgs* rng, int nbatch, size_t yA, size_t yB, size_t yO) {
         const F& f = *reinterpret_cast<const F*>(Fp);
         if (t < 1 || t > 3 || kA < 1 || kA > GATE_MAXK || kB < 0 || kB > GATE_MAXK || !rng) return 2;
         if (nbatch < 1 || nbatch > 255) return 2;
-        LaunchCfg lc = launch_cfg(device);
         GateSrc<F> gs;
         memset(&gs, 0, sizeof(gs));
         bool vec = al(out) && (stride_ok(ostride) || m <= 1);
@@ -311,29 +310,23 @@ struct Launchers {
         constexpr int SLG = scalar_limbs<F>();
         gs.plainA = kA == 1 && lamA2[0] == 1 && lamA2[1] == 0 && (SLG < 3 || lamA2[SLG - 1] == 0);
         gs.plainB = kB == 1 && lamB2[0] == 1 && lamB2[1] == 0 && (SLG < 3 || lamB2[SLG - 1] == 0);
-        size_t nvec = nvec_of(n, vec);
         RngArgs ra = *rng;
-        const bool spread = nvec > 0 && nvec < 262144;
-        ra.spread = spread ? 1 : 0;
-        unsigned grid = grid_for(nvec ? (!spread ? (n / EPV + 2) / 2 : nvec) : n, lc);
         const unsigned gy = (unsigned)nbatch;
-        ra.release = !ra.no_advance && (size_t)grid * gy <= RNG_RELEASE_MAX_GRID;
+        const Plan p = plan_rng(n, vec, lc, ra, gy);
         E* o = (E*)out;
         switch (t) {
-            case 1: go_split<1, true, true, true>(f, grid, true, nullptr, nullptr, nullptr, 0, m, o, ostride, nvec, n, st, ra, gs, gy); break;
-            case 2: go_split<2, true, true, true>(f, grid, true, nullptr, nullptr, nullptr, 0, m, o, ostride, nvec, n, st, ra, gs, gy); break;
-            default: go_split<3, true, true, true>(f, grid, true, nullptr, nullptr, nullptr, 0, m, o, ostride, nvec, n, st, ra, gs, gy); break;
+            case 1: go_split<1, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
+            case 2: go_split<2, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
+            default: go_split<3, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
         }
-        if (ra.dev_key && !ra.release && !ra.no_advance)
-            hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, st, const_cast<RngKey*>(ra.dev_key), 1u);
+        rng_advance(ra, st);
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int split(const void* Fp, int device, const void* a, const void* b, const void* coef,
+    static int split(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
                      size_t cstride, int t, int m, void* out, size_t ostride, size_t n, hipStream_t st,
                      const RngArgs* rng) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         RngArgs ra;
         memset(&ra, 0, sizeof(ra));
         int rc;
@@ -351,10 +344,9 @@ struct Launchers {
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int rng_coeffs(const void* Fp, int device, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
+    static int rng_coeffs(const void* Fp, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
                           const RngArgs* rng) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         E* C = (E*)coef;
         size_t npacks = (n + EPV - 1) / EPV;
         unsigned grid = grid_for(npacks, lc);
@@ -363,8 +355,7 @@ struct Launchers {
             FFGPU_CHECK_LAUNCH();
             return 0;
         }
-        bool vec = al(coef) && (stride_ok(cstride) || t <= 1);
-        size_t nvec = nvec_of(n, vec);
+        const size_t nvec = plan(n, al(coef) && (stride_ok(cstride) || t <= 1), lc).nvec;
         switch (t) {
             case 1: hipLaunchKernelGGL((k_rng_coeffs<F, 1>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
             case 2: hipLaunchKernelGGL((k_rng_coeffs<F, 2>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
@@ -390,15 +381,13 @@ struct Launchers {
                 ra.lam[r * K + j] = f.prep(word_at<F>(f, lam2, (size_t)r * K + j));
             }
         for (int i = w * K; i < MAXW * K; ++i) ra.lam[i] = ra.lam[0];
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
-        hipLaunchKernelGGL((k_recombine<F, K, true>), dim3(grid), dim3(BLOCK), 0, st, f, ra, w, out, ostride,
-                           nvec, n);
+        const Plan p = plan(n, vec, lc);
+        hipLaunchKernelGGL((k_recombine<F, K, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, ra, w, out, ostride,
+                           p.nvec, n);
     }
-    static int recombine(const void* Fp, int device, const void* const* rows, const uint64_t* lam2, int k,
+    static int recombine(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                          int w, void* out, size_t ostride, size_t n, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         E* O = (E*)out;
         if (k > MAXK) {
             if (k > MAXK_ANY) return 2;
@@ -440,23 +429,18 @@ struct Launchers {
         return 0;
     }
 
-    static int pow(const void* Fp, int device, const void* a, const ExpArgs* ex, void* out, size_t n,
+    static int pow(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
-        bool vec = al(a) && al(out);
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
-        hipLaunchKernelGGL((k_pow<F, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out, nvec, n);
+        const Plan p = plan(n, al(a) && al(out), lc);
+        hipLaunchKernelGGL((k_pow<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out, p.nvec, n);
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int inv(const void* Fp, int device, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
+    static int inv(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
-        bool vec = al(a) && al(out);
-        size_t nvec = nvec_of(n, vec);
+        const size_t nvec = plan(n, al(a) && al(out), lc).nvec;
         // packs per thread: ONE exponentiation (70 products for 2^61 - 1) is shared by G x CH packs, and the
         // G x CH x N prefix words stay in registers (two waves per SIMD at CH = 8..12 for one-word fields)
         if constexpr (F::EPW == 1 && sizeof(W) == 8) {
@@ -584,7 +568,7 @@ struct Launchers {
     }
     // one-word primes, 2..8 columns: column sums, one instantiation per N; two rows of A per workgroup up to 4 columns
     template <int NN>
-    static void go_matvec_col(const F& f, int device, const E* A, size_t lda, const E* B, size_t ldb, E* C, size_t ldc, int M,
+    static void go_matvec_col(const F& f, const LaunchCfg& lc, const E* A, size_t lda, const E* B, size_t ldb, E* C, size_t ldc, int M,
                               int K, hipStream_t st) {
         if constexpr (col_mac_ok<F>::value) {
             constexpr int R = NN <= 4 ? 2 : 1;
@@ -593,7 +577,7 @@ struct Launchers {
             // B contiguous and 16-byte aligned, rows of A aligned: sixteen lanes per row (a wave per row when 16 rows per
             // workgroup would leave CUs without one), the rows of B through LDS
             if (vec && ldb == (size_t)NN && al(B) && K >= 64) {
-                const int ncu = launch_cfg(device).num_cu;
+                const int ncu = lc.num_cu;
                 if ((M + 15) / 16 >= 2 * (ncu > 0 ? ncu : 256))
                     hipLaunchKernelGGL((k_matvec_sub_col<F, NN, 16>), dim3((unsigned)((M + 15) / 16)), dim3(BLOCK), 0, st, f, A, lda, B, C, ldc, M, K);
                 else
@@ -636,9 +620,8 @@ struct Launchers {
             hipLaunchKernelGGL((k_vecmat_partial_col<F, MM, C::UNR, C::MINB>), grid, dim3(BLOCK), 0, st, f, A, lda, B, ldb, part, K, N, kchunk);
         }
     }
-    static int matmul(const void* Fp, int device, const void* A, size_t lda, const void* B, size_t ldb, void* C,
-                      size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, const Tuning* tune,
-                      hipStream_t st) {
+    static int matmul(const void* Fp, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
+                      size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
         if constexpr (F::EPW == 1) {
             // (three-limb words: the eight-column kernel would spill, N in 5..8 takes the tiled product)
@@ -648,13 +631,13 @@ struct Launchers {
                 if constexpr (col_mac_ok<F>::value) {
                     if (N >= 2 && K > 32) {               // (short rows keep the one-thread-per-row kernel)
                         switch (N) {
-                            case 2: go_matvec_col<2>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 3: go_matvec_col<3>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 4: go_matvec_col<4>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 5: go_matvec_col<5>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 6: go_matvec_col<6>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 7: go_matvec_col<7>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            default: go_matvec_col<8>(f, device, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 2: go_matvec_col<2>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 3: go_matvec_col<3>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 4: go_matvec_col<4>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 5: go_matvec_col<5>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 6: go_matvec_col<6>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            case 7: go_matvec_col<7>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
+                            default: go_matvec_col<8>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
                         }
                         done = true;
                     }
@@ -673,7 +656,7 @@ struct Launchers {
                 int cpt = (int)Pack<W>::N, target = 1024;        // columns per thread, workgroups
                 if constexpr (col_mac_ok<F>::value) {
                     cpt = 1;
-                    const int ncu = launch_cfg(device).num_cu;
+                    const int ncu = lc.num_cu;
                     target = (ncu > 0 ? ncu : 256) * vecmat_col_per_cu(M);
                 }
                 const int cols_blocks = (N / cpt + BLOCK - 1) / BLOCK;
@@ -709,8 +692,8 @@ struct Launchers {
                 }
             }
         }
-        const bool use_mfma = !tune || tune->mm_mfma != 0;
-        const double mfma_min = tune ? tune->mm_mfma_min : 8e7;
+        const bool use_mfma = lc.mm_mfma != 0;
+        const double mfma_min = lc.mm_mfma_min;
         if constexpr (F::EPW == 1 && !F::BINARY && sizeof(W) <= 8) {
             // large dense products over primes of up to 64 bits: int8 matrix cores, 8 signed base-256 digits per operand
             // (k_limb_gemm_glds), 4 for 32-bit storage (k_limb_gemm_l4)
@@ -751,7 +734,7 @@ struct Launchers {
                         // ONE round of workgroups (a workgroup holds a CU: 512 registers per lane): tiles x slabs ~ CUs.
                         // Measured (round 4, 64 x 4096 x 4096): 256 workgroups 94 us, 384: 127, 512: 107, 768: 117, 1536: 121
                         // -- every extra slab repeats the epilogue and the pipeline fill.
-                        const int ncu = launch_cfg(device).num_cu;
+                        const int ncu = lc.num_cu;
                         const int target = ncu > 0 ? ncu : 256;
                         ks = (int)((target + tiles - 1) / tiles);
                         if (ks > Kp / 256) ks = Kp / 256;
@@ -870,12 +853,10 @@ struct Launchers {
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int dot(const void* Fp, int device, const void* a, const void* b, void* out, void* workspace, size_t n,
+    static int dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
-        bool vec = al(a) && (!b || al(b));
-        size_t nvec = nvec_of(n, vec);
+        const size_t nvec = plan(n, al(a) && (!b || al(b)), lc).nvec;
         size_t iters = nvec ? nvec : n;
         size_t want = (iters + (size_t)BLOCK * 8 - 1) / ((size_t)BLOCK * 8);     // >= 8 packs per thread
         unsigned grid = (unsigned)(want < 1 ? 1 : want > DOT_MAX_BLOCKS ? DOT_MAX_BLOCKS : want);
@@ -888,26 +869,23 @@ struct Launchers {
                                part, nvec, n);
         hipLaunchKernelGGL((k_dot_final<F>), dim3(1), dim3(BLOCK), 0, st, f, (const W*)part, (int)grid, (E*)out);
         FFGPU_CHECK_LAUNCH();
-        (void)lc;
         return 0;
     }
-    static int sqrt_cl(const void* Fp, int device, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out,
+    static int sqrt_cl(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out,
                        size_t n, hipStream_t st) {
         if constexpr (F::BINARY) {
             return 2;
         } else {
             const F& f = *reinterpret_cast<const F*>(Fp);
-            LaunchCfg lc = launch_cfg(device);
-            unsigned grid = grid_for(n, lc);
+                unsigned grid = grid_for(n, lc);
             hipLaunchKernelGGL((k_sqrt_cl<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *eleg, *elad, (E*)out, n);
             FFGPU_CHECK_LAUNCH();
             return 0;
         }
     }
-    static int gauss(const void* Fp, int device, void* A, int n, int ncols, size_t batch, int det_mode,
+    static int gauss(const void* Fp, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode,
                      const ExpArgs* ex, void* det, int* sing, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        (void)device;
         constexpr int TI = 4;
         constexpr size_t ZMAX = 32768;                    // grid.z limit: larger batches go in chunks
         for (size_t b0 = 0; b0 < batch; b0 += ZMAX) {
@@ -929,11 +907,10 @@ struct Launchers {
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int group_matvec(const void* Fp, int device, const uint64_t* m2, const uint64_t* bias2, int r, int g,
+    static int group_matvec(const void* Fp, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
                             const void* in, void* out, size_t ngroups, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
         if (r < 1 || g < 1 || r > GM_MAX || g > GM_MAX) return 2;
-        LaunchCfg lc = launch_cfg(device);
         GroupMatArgs<F> ga;
         memset(&ga, 0, sizeof(ga));
         for (int i = 0; i < r * g; ++i) ga.m[i] = f.prep(word_at<F>(f, m2, i));
@@ -964,23 +941,19 @@ struct Launchers {
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int beaver(const void* Fp, int device, const void* z, const void* x, const void* y, const void* d,
+    static int beaver(const void* Fp, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d,
                       const void* e, void* out, int add_de, size_t n, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
-        bool vec = al(z) && al(x) && al(y) && al(d) && al(e) && al(out);
-        size_t nvec = nvec_of(n, vec);
-        unsigned grid = grid_for(nvec ? nvec : n, lc);
-        hipLaunchKernelGGL((k_beaver<F, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)z, (const E*)x, (const E*)y,
-                           (const E*)d, (const E*)e, (E*)out, add_de, nvec, n);
+        const Plan p = plan(n, al(z) && al(x) && al(y) && al(d) && al(e) && al(out), lc);
+        hipLaunchKernelGGL((k_beaver<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)z, (const E*)x, (const E*)y,
+                           (const E*)d, (const E*)e, (E*)out, add_de, p.nvec, n);
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
-    static int prss(const void* Fp, int device, const void* const* streams, int ks, int d, int l, int mask_bits,
+    static int prss(const void* Fp, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
                     const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n,
                     hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
-        LaunchCfg lc = launch_cfg(device);
         if (ks < 1 || d < 1 || l < 1 || ks > PRSS_MAXS || ks * d > PRSS_MAXW) return 2;
         PrssArgs<F> pa;
         memset(&pa, 0, sizeof(pa));
@@ -996,7 +969,7 @@ struct Launchers {
         return 0;
     }
 
-    static int prss_chacha(const void* Fp, int device, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
+    static int prss_chacha(const void* Fp, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                            const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
         if (ks < 1 || d < 1 || l < 1 || l > 64 || ks > PRSS_CC_MAXS || ks * d > PRSS_CC_MAXW) return 2;

@@ -68,10 +68,9 @@ int ffgpu_sbox_build_lut(const void* policy, const uint8_t* rows8, uint8_t b, ui
     return 0;
 }
 
-int ffgpu_launch_sbox(const uint8_t* lut256, int device, const void* in, void* out, size_t n, hipStream_t st) {
+int ffgpu_launch_sbox(const uint8_t* lut256, const LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st) {
     SboxLut tab;
     memcpy(tab.v, lut256, 256);
-    LaunchCfg lc = launch_cfg(device);
     bool vec = aligned16(in) && aligned16(out);
     size_t nvec = vec ? n / 16 : 0;
     unsigned grid = grid_for(nvec ? nvec : n, lc);      // uncapped: the per-workgroup table copy is cheap (measured best)
@@ -110,8 +109,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_to_bits(const uint8_t* __restrict
     }
 }
 
-int ffgpu_launch_gf8_to_bits(int device, const void* in, const void* addend, void* out, size_t n, hipStream_t st) {
-    LaunchCfg lc = launch_cfg(device);
+int ffgpu_launch_gf8_to_bits(const LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st) {
     bool vec = (((uintptr_t)in) & 1u) == 0 && (((uintptr_t)out) & 15u) == 0 && (!addend || (((uintptr_t)addend) & 15u) == 0);
     size_t npair = vec ? n / 2 : 0;
     unsigned grid = grid_for(npair ? npair : n, lc);
@@ -250,12 +248,11 @@ static bool gf8_group8_args(const GF2P8& f, const uint64_t* m2, const uint64_t* 
     return general;
 }
 
-int ffgpu_launch_gf8_group8(const void* policy, int device, const uint64_t* m2, const uint64_t* bias2, int fold,
+int ffgpu_launch_gf8_group8(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
                             const void* in, void* out, size_t ngroups, hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
     Gf8Group8Args ga;
     const bool general = gf8_group8_args(f, m2, bias2, fold, ga);
-    LaunchCfg lc = launch_cfg(device);
     const bool vec = (((uintptr_t)in) & 15u) == 0 && (((uintptr_t)out) & (fold ? 1u : 15u)) == 0;
     const size_t npack = vec ? ngroups / 2 : 0;
     unsigned grid = grid_for(npack ? (npack + 1) / 2 : ngroups, lc);
@@ -456,7 +453,7 @@ static void gf8_byte_tables(const GF2P8& f, const uint64_t* m2, const uint64_t* 
 }
 
 // rows / rbits: host arrays of device pointers; coef2 / mu2: canonical 2-limb host scalars
-int ffgpu_launch_gf8_mask_open(const void* policy, int device, const void* const* rows, const uint64_t* coef2, int nrows,
+int ffgpu_launch_gf8_mask_open(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* coef2, int nrows,
                                const void* const* rbits, const uint64_t* mu2, int np, void* out, size_t n, hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
     if (nrows < 0 || nrows > GF8_MO_MAXROWS || np < 0 || np > GF8_MO_MAXP) return 2;
@@ -483,14 +480,13 @@ int ffgpu_launch_gf8_mask_open(const void* policy, int device, const void* const
         vec = vec && (((uintptr_t)rbits[p]) & 15u) == 0;
     }
     const size_t npair = vec ? n / 2 : 0;
-    LaunchCfg lc = launch_cfg(device);
     unsigned grid = grid_for(npair ? (npair + 1) / 2 : n, lc);
     hipLaunchKernelGGL(k_gf8_mask_open, dim3(grid), dim3(BLOCK), 0, st, f, tb, a, (uint8_t*)out, npair, n);
     FFGPU_CHECK_LAUNCH();
     return 0;
 }
 
-int ffgpu_launch_gf8_bits_affine_fold(const void* policy, int device, const uint64_t* m2, const uint64_t* bias2, const void* c,
+int ffgpu_launch_gf8_bits_affine_fold(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, const void* c,
                                       const void* rbits, size_t ybr, void* out, size_t ybo, size_t n, int nbatch,
                                       hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
@@ -499,7 +495,6 @@ int ffgpu_launch_gf8_bits_affine_fold(const void* policy, int device, const uint
     bool vec = (((uintptr_t)c) & 1u) == 0 && (((uintptr_t)rbits) & 15u) == 0 && (((uintptr_t)out) & 1u) == 0;
     if (nbatch > 1) vec = vec && (ybr % 16 == 0) && (ybo % 2 == 0);
     const size_t npair = vec ? n / 2 : 0;
-    LaunchCfg lc = launch_cfg(device);
     unsigned grid = grid_for(npair ? (npair + 1) / 2 : n, lc);
     hipLaunchKernelGGL(k_gf8_bits_affine_fold, dim3(grid, (unsigned)nbatch), dim3(BLOCK), 0, st, tb,
                        (const uint8_t*)c, (const uint8_t*)rbits, ybr, (uint8_t*)out, ybo, npair, n);
@@ -858,7 +853,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
 // tables_dev: SBL_TABLE_BYTES of device memory (the caller caches it per matrix); returns 2 when the shape is not
 // covered (rows not 4- / 16-byte aligned, m > 7 or t > 3): the caller composes the layer from the per-step kernels
 // then.  Any n: the n % 4 bytes after the last whole word of each row are handled by one thread with byte accesses.
-int ffgpu_launch_gf8_sbox_layer(const void* policy, int device, const void* x, size_t xs, const void* r, size_t rs, void* out,
+int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs, void* out,
                                 size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2, int t, int m,
                                 size_t n, hipStream_t st, const RngArgs* rng) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
@@ -882,7 +877,6 @@ int ffgpu_launch_gf8_sbox_layer(const void* policy, int device, const void* x, s
     // persistent above one round of resident workgroups (4 per CU at t = 1, m <= 4: 119-128 VGPRs; 3 for m >= 5; 2-3 per CU
     // for t >= 2): the threads of the t = 1 kernels then carry their keystream from step to step instead of discarding 15
     // of every 48 words
-    LaunchCfg lc = launch_cfg(device);
     const size_t resident = (size_t)(lc.num_cu > 0 ? lc.num_cu : 256) * (t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2));
     if (want > resident) want = resident;
     const unsigned grid = (unsigned)want;
@@ -985,7 +979,7 @@ void k_gf2w64_mul_bitsliced(const uint4* a, const uint4* b, uint4* o, size_t nsl
 
 // returns the number of leading elements it has multiplied (all of them but the last one of an odd n; 0 = not applicable):
 // the caller sends the rest through the element-wise kernel
-size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, int device, const void* a, const void* b, void* out, size_t n,
+size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                                          hipStream_t st) {
     const GF2W64& f = *reinterpret_cast<const GF2W64*>(policy);
     if (f.n != 64 || f.red != 0x1bull || n < ((size_t)1 << 21) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15)) return 0;
@@ -1077,10 +1071,9 @@ int ffgpu_gf8_build_tables(const void* policy, void* tables_out) {
     return 1;
 }
 
-int ffgpu_launch_gf8_mul_tab(const void* tables, int device, const void* a, const void* b, void* out, size_t n,
+int ffgpu_launch_gf8_mul_tab(const void* tables, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                              hipStream_t st) {
     const Gf8Tables& tb = *reinterpret_cast<const Gf8Tables*>(tables);
-    LaunchCfg lc = launch_cfg(device);
     bool vec = aligned16(a) && aligned16(b) && aligned16(out);
     size_t nvec = vec ? n / 16 : 0;
     unsigned grid = grid_for(nvec ? nvec : n, lc);      // uncapped: the per-workgroup table copy is cheap (measured best)
@@ -1260,10 +1253,9 @@ int ffgpu_gf2w_build_rtable(const void* policy, int limbs, void* rtable_out) {
     return 0;
 }
 
-int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, int device, const void* a,
+int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const LaunchCfg& lc, const void* a,
                               const void* b, void* out, size_t n, hipStream_t st) {
     const Gf2wRTable& rt = *reinterpret_cast<const Gf2wRTable*>(rtable);
-    LaunchCfg lc = launch_cfg(device);
     unsigned grid = grid_for(n, lc);
     // R[1] = x^n mod f = r(x): sparse path when it fits 28 bits (every default MPyC irreducible does)
     const bool sparse = rt.hi[1] == 0 && rt.lo[1] < (1ull << 28);
@@ -1477,11 +1469,10 @@ __global__ __launch_bounds__(REC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEEP 
 }
 
 template <int LIMBS, int KT, bool DEEP>
-static int launch_gf2w_rec(const void* policy, int device, const Gf2wRecArgs<LIMBS>& ra, void* out, size_t n, hipStream_t st) {
+static int launch_gf2w_rec(const void* policy, const LaunchCfg& lc, const Gf2wRecArgs<LIMBS>& ra, void* out, size_t n, hipStream_t st) {
     typedef Gf2wTraits<LIMBS> Tr;
     const typename Tr::F& f = *reinterpret_cast<const typename Tr::F*>(policy);
     const size_t lds = (size_t)KT * 16 * LIMBS * 16 * sizeof(typename Tr::L);
-    LaunchCfg lc = launch_cfg(device);
     size_t want = (n + REC_BLOCK - 1) / REC_BLOCK, cap;
     if (KT > 0) {
         // persistent grid: the table build (a few field multiplications per thread) is amortised over many elements
@@ -1508,7 +1499,7 @@ static int launch_gf2w_rec(const void* policy, int device, const Gf2wRecArgs<LIM
 }
 
 template <int LIMBS>
-static int dispatch_gf2w_rec(const void* policy, int device, const void* const* rows, const uint64_t* lam2, int k, void* out,
+static int dispatch_gf2w_rec(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k, void* out,
                              size_t n, hipStream_t st) {
     Gf2wRecArgs<LIMBS> ra;
     memset(&ra, 0, sizeof(ra));
@@ -1543,13 +1534,13 @@ static int dispatch_gf2w_rec(const void* policy, int device, const void* const* 
             for (int p = 0; p < ra.kp; ++p) r2.prow[p] = ra.prow[p];
             GF2W128 unused;                                                    // (the policy is read by the table build only)
             memset(&unused, 0, sizeof(unused));
-            return launch_gf2w_rec<2, 0, false>(&unused, device, r2, out, n / 2, st);
+            return launch_gf2w_rec<2, 0, false>(&unused, lc, r2, out, n / 2, st);
         }
     }
     // (DEEP = 16 look-ups per batch in flight for every table count > 0: the round-3 measurement; kt = 0 is a plain XOR)
 #define GF2W_REC_CASE(KK)                                                                         \
     case KK:                                                                                      \
-        return launch_gf2w_rec<LIMBS, KK, (KK > 0)>(policy, device, ra, out, n, st);
+        return launch_gf2w_rec<LIMBS, KK, (KK > 0)>(policy, lc, ra, out, n, st);
     switch (kt) {
         GF2W_REC_CASE(0) GF2W_REC_CASE(1) GF2W_REC_CASE(2) GF2W_REC_CASE(3) GF2W_REC_CASE(4) GF2W_REC_CASE(5)
         GF2W_REC_CASE(6) GF2W_REC_CASE(7) GF2W_REC_CASE(8) GF2W_REC_CASE(9)
@@ -1559,11 +1550,11 @@ static int dispatch_gf2w_rec(const void* policy, int device, const void* const* 
 }
 
 // k rows (1..9), one output row; limbs selects GF2W64 / GF2W128.  Returns 2 if the shape is not covered.
-int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, int device, const void* const* rows, const uint64_t* lam2,
+int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2,
                                 int k, void* out, size_t n, hipStream_t st) {
     if (k < 1 || k > REC_MAXK) return 2;
-    return limbs == 2 ? dispatch_gf2w_rec<2>(policy, device, rows, lam2, k, out, n, st)
-                      : dispatch_gf2w_rec<1>(policy, device, rows, lam2, k, out, n, st);
+    return limbs == 2 ? dispatch_gf2w_rec<2>(policy, lc, rows, lam2, k, out, n, st)
+                      : dispatch_gf2w_rec<1>(policy, lc, rows, lam2, k, out, n, st);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
@@ -1576,9 +1567,8 @@ __global__ __launch_bounds__(BLOCK) void k_copy16(const uint4* __restrict__ src,
     }
 }
 
-int ffgpu_launch_copy(int device, const void* src, void* dst, size_t bytes, hipStream_t st) {
+int ffgpu_launch_copy(const LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st) {
     if (!aligned16(src) || !aligned16(dst) || (bytes & 15)) return 1;
-    LaunchCfg lc = launch_cfg(device);
     size_t nvec = bytes / 16;
     unsigned grid = grid_for(nvec, lc);
     hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec);
@@ -1644,9 +1634,8 @@ __global__ __launch_bounds__(BLOCK) void k_valu_probe(uint32_t* __restrict__ sin
 }
 
 // out[0] = lane-operations per second, out[1] = shader clock in MHz, out[2] = shader cycles per wave instruction and SIMD
-int ffgpu_launch_valu_probe(int device, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st) {
+int ffgpu_launch_valu_probe(const LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st) {
     // SYNCHRONISES the stream (event + a blocking read-back of the cycle counts): a measurement aid, not capturable
-    LaunchCfg lc = launch_cfg(device);
     if (op < 0 || op > 13 || iters < 1 || waves_per_simd < 1 || waves_per_simd > 8) return 1;
     const unsigned grid = (unsigned)(lc.num_cu * waves_per_simd);           // 256 threads = 4 waves = one per SIMD
     uint32_t* sink = (uint32_t*)scratch32;

@@ -243,9 +243,7 @@ inline int build_binary_policy(PolicyBlob* c, const uint64_t* mod, int nlimbs) {
                 if (e < 0) e = 0;
                 ++folds;
             }
-            // n <= 32: a pass costs ~2 + 2 popcount(red) instructions, a long-division step ~5: fold only when it is the cheaper one
-            const bool pays = deg > 32 || folds * (2 + 2 * __builtin_popcountll(f.red)) < 5 * (deg - 1);
-            if (e == 0 && pays) f.fast = 1u | ((uint32_t)folds << 8);
+            if (e == 0) f.fast = 1u | ((uint32_t)folds << 8);
         }
         store_policy(c, f, POL_GF2W64, PB_RED_WIDE);
         return PB_OK;

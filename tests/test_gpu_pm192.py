@@ -173,12 +173,65 @@ def test_wave_contiguous_accesses_of_24_byte_elements(eng):
     tail for the ragged rest and for rows that are only 8-byte aligned.  Element-wise operations, fused multiply-add,
     share generation (supplied coefficients, fused product) and the Beaver combination around every wave boundary, on
     views at odd element offsets, in place, for a 2^k - c prime and a prime of no special shape."""
+    check_wave_boundaries(eng, 3 * 256 * 64 + 130)           # several workgroups, several waves each, a ragged end
+
+
+def test_wave_boundaries_under_a_capped_grid(coracle):
+    """The same checks, and share generation / recombination over 2^61 - 1, with FFGPU_BLOCKS_PER_CU=1: one workgroup
+    per CU, so every thread of the streaming loops takes several packs and the launchers' nvec (Launchers::plan) decides
+    which waves go through ldgw / stgw.  The switch is read when a context is created: a fresh child process gets it
+    (this process and the child: two processes on the GPU)."""
+    import os
+    import subprocess
+    import sys
+    tests = os.path.dirname(os.path.abspath(__file__))
+    child = ('import sys; sys.path[:0] = [%r, %r]\n'
+             'import torch\n'
+             'from mpyc_amd import engine\n'
+             'from oracle import coracle\n'
+             'import test_gpu_pm192 as t\n'
+             'ncu = torch.cuda.get_device_properties(0).multi_processor_count\n'
+             'per_pass = ncu * 256                                  # threads of the capped grid\n'
+             't.check_wave_boundaries(engine, 2 * per_pass + 3 * 64 + 130)\n'
+             't.check_p61_split_recombine(engine, coracle, 3 * per_pass * 2 + 37)\n'
+             'print("CAPPED_OK")\n') % (os.path.dirname(tests), tests)
+    env = dict(os.environ, FFGPU_BLOCKS_PER_CU='1')
+    r = subprocess.run([sys.executable, '-c', child], capture_output=True, text=True, timeout=900, env=env,
+                       cwd=os.path.dirname(tests))
+    assert r.returncode == 0 and 'CAPPED_OK' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def check_p61_split_recombine(eng, co, n):
+    """share generation (supplied coefficients, device CSPRNG with and without the fused product) and recombination
+    over 2^61 - 1 against the C oracle, n elements"""
+    p = 2**61 - 1
+    t, m = 3, 7
+    cf = co.CField(p)
+    ctx = eng.FieldContext(p, device=0)
+    rs = np.random.default_rng(61)
+    A, B = (rs.integers(0, p, n, dtype=np.uint64) for _ in range(2))
+    C = rs.integers(0, p, (t, n), dtype=np.uint64)
+    dA, dB = ctx.from_numpy(A), ctx.from_numpy(B)
+    sh = ctx.split(dA, ctx.matrix_from_numpy(C), t, m)
+    assert (sh.to_numpy() == cf.split(A, C, t, m)).all(), n
+    key, nonce = bytes(range(3, 35)), 77
+    Cr = co.rng_coeffs(cf, key, nonce, 20, t, n)
+    assert (ctx.split_rng(dA, t, m, key=key, nonce=nonce).to_numpy() == cf.split(A, Cr, t, m)).all(), n
+    prod = cf.ew(co.MUL, A, B)
+    fused = ctx.split_rng(dA, t, m, key=key, nonce=nonce, mul_by=dB)
+    assert (fused.to_numpy() == cf.split(prod, Cr, t, m)).all(), n
+    xs = [((2 + j) % m) + 1 for j in range(2 * t + 1)]
+    lam = po.recombination_vector(po.Field(p, False), xs, 0)
+    assert (ctx.recombine([sh.row(x - 1) for x in xs], lam).to_numpy() == A).all(), n
+    assert (ctx.recombine([fused.row(x - 1) for x in xs], lam).to_numpy() == prod).all(), n
+
+
+def check_wave_boundaries(eng, big):
     from mpyc_amd.finfields import find_prime_root, next_prime
     rng = random.Random(2406)
     for p in (find_prime_root(136)[0], next_prime(2**192 - 2**40)):
         F = po.Field(p, False)
         ctx = eng.FieldContext(p, device=0)
-        big = 3 * 256 * 64 + 130                                  # several workgroups, several waves each, a ragged end
         pool_a = [rng.randrange(p) for _ in range(big + 8)]
         pool_b = [rng.randrange(p) for _ in range(big + 8)]
         pool_a[:4] = [0, 1, p - 1, 2**128]

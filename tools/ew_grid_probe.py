@@ -1,4 +1,4 @@
-"""VALU-bound element-wise products under a capped grid (FFGPU_BLOCKS_PER_CU, read once per device): one pack per thread
+"""VALU-bound element-wise products under a capped grid (FFGPU_BLOCKS_PER_CU, read once per context): one pack per thread
 (uncapped, the streaming default) against a grid-stride loop over a few workgroups per CU.  n = 10^7."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
