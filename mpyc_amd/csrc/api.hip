@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "../../include/ffgpu.h"
+#include "handoff.hpp"
 #include "kernels.hpp"
 #include "policy_build.hpp"
 
@@ -87,6 +88,9 @@ struct ffgpu_ctx {
         int used;
     } scratch[8];
     std::mutex* scratch_mu;
+    // which outputs feed the next launch on their stream (handoff.hpp); guarded by handoff_mu
+    HandoffTracker handoff;
+    std::mutex* handoff_mu;
     void* gf8_tables_dev;   // device copy of gf8_tables (lazily, for the fused GF(2^n<=8) product)
     // tables of the fused S-box layer (ffgpu_gf256_sbox_layer) for the last affine map used with this context
     void* sbl_tables_dev;
@@ -246,6 +250,8 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
     ffgpu_ctx* c = (ffgpu_ctx*)calloc(1, sizeof(ffgpu_ctx));
     if (!c) return FFGPU_ENOMEM;
     c->scratch_mu = new std::mutex();
+    c->handoff_mu = new std::mutex();
+    c->handoff.reset();
     c->kind = kind;
     c->device = device;
     for (int i = 0; i < nlimbs; ++i) c->modulus[i] = modulus[i];
@@ -285,6 +291,9 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         c->lc.mm_mfma_min = e ? atof(e) : 8e7;
         e = getenv("FFGPU_GF2W_BITSLICED");
         c->lc.gf2w_bitsliced = e ? (atoi(e) != 0) : 1;
+        e = getenv("FFGPU_HANDOFF");
+        c->lc.handoff = e ? (atoi(e) != 0) : 1;
+        c->lc.keep_out = 0;
     }
     c->gf2w_limbs = 0;
     if (pb.kind == POL_GF2W64 || pb.kind == POL_GF2W128) {
@@ -338,6 +347,8 @@ int ffgpu_ctx_destroy(ffgpu_ctx* ctx) {
             if (sc.ptr) (void)hipFree(sc.ptr);
         delete ctx->scratch_mu;
         ctx->scratch_mu = nullptr;
+        delete ctx->handoff_mu;
+        ctx->handoff_mu = nullptr;
     }
     if (ctx && ctx->gf8_tables_dev) {
         DeviceGuard g(ctx->device);
@@ -507,13 +518,38 @@ int ffgpu_stream_sync(ffgpu_ctx* ctx, void* stream) {
         if (!(cond)) return FFGPU_EINVAL; \
     } while (0)
 
-static int do_ew2(ffgpu_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n, void* stream) {
+// The launch shape of one call: the context's, with keep_out set when the hand-off tracker predicts that the next launch on
+// the stream reads this call's outputs (handoff.hpp).  Every streaming call that reads or writes arrays goes through here
+// once, before its launches: what it reads settles the prediction for the call before it.
+static LaunchCfg handoff_lc(ffgpu_ctx* ctx, void* stream, int kind, const ByteRange* in, int nin, const ByteRange* out,
+                            int nout) {
+    LaunchCfg lc = ctx->lc;
+    if (lc.handoff) {
+        std::lock_guard<std::mutex> lk(*ctx->handoff_mu);
+        lc.keep_out = ctx->handoff.launch(stream, kind, in, nin, out, nout);
+    }
+    return lc;
+}
+// bytes of `rows` rows of n elements, `stride` elements apart
+static size_t rows_bytes(const ffgpu_ctx* ctx, size_t rows, size_t stride, size_t n) {
+    return ((rows > 0 ? rows - 1 : 0) * stride + n) * (size_t)ctx->elem_bytes;
+}
+
+static LaunchCfg ew2_lc(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n, void* stream) {
+    const size_t nb = rows_bytes(ctx, 1, 0, n);
+    const ByteRange in[2] = {byte_range(a, nb), byte_range(b, nb)}, o = byte_range(out, nb);
+    return handoff_lc(ctx, stream, HK_EW, in, 2, &o, 1);
+}
+// (lc: the call's launch shape when the caller has taken it already -- ffgpu_mul)
+static int do_ew2(ffgpu_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n, void* stream,
+                  const LaunchCfg* lc = nullptr) {
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && b && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->ew2(ctx->policy, ctx->lc, op, a, b, out, n, (hipStream_t)stream));
+    const LaunchCfg lc1 = lc ? *lc : ew2_lc(ctx, a, b, out, n, stream);
+    return launch_status(ctx->ops->ew2(ctx->policy, lc1, op, a, b, out, n, (hipStream_t)stream));
 }
 static int do_ew1(ffgpu_ctx* ctx, int op, const void* a, const uint64_t* s, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
@@ -521,7 +557,10 @@ static int do_ew1(ffgpu_ctx* ctx, int op, const void* a, const uint64_t* s, void
     ARGCHK(a && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, op, a, s, out, n, (hipStream_t)stream));
+    const size_t nb = rows_bytes(ctx, 1, 0, n);
+    const ByteRange in = byte_range(a, nb), o = byte_range(out, nb);
+    const LaunchCfg lc = handoff_lc(ctx, stream, HK_EW, &in, 1, &o, 1);
+    return launch_status(ctx->ops->ew1(ctx->policy, lc, op, a, s, out, n, (hipStream_t)stream));
 }
 
 int ffgpu_reduce(ffgpu_ctx* ctx, const void* raw, void* out, size_t n, void* stream) {
@@ -534,31 +573,34 @@ int ffgpu_sub(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n,
     return do_ew2(ctx, OP_SUB, a, b, out, n, stream);
 }
 int ffgpu_mul(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n, void* stream) {
-    if (ctx && ctx->gf8_tab_min && n >= (size_t)ctx->gf8_tab_min && a && b && out) {
+    if (!ctx || n == 0 || !a || !b || !out) return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
+    // (one hand-off step for the call, whichever kernels serve it; only the element-wise kernel takes keep_out)
+    const LaunchCfg lc = ew2_lc(ctx, a, b, out, n, stream);
+    if (ctx->gf8_tab_min && n >= (size_t)ctx->gf8_tab_min) {
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, ctx->lc, a, b, out, n,
+        return launch_status(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, lc, a, b, out, n,
                                                       (hipStream_t)stream));
     }
-    if (ctx && ctx->gf2w_limbs && n && a && b && out) {
+    if (ctx->gf2w_limbs) {
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, ctx->lc,
+        return launch_status(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, lc,
                                                        a, b, out, n, (hipStream_t)stream));
     }
-    if (ctx && ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && a && b && out && n >= ((size_t)1 << 21)) {
+    if (ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && n >= ((size_t)1 << 21)) {
         // GF(2^64) with the default modulus: bit-sliced product for all whole pairs of elements, the element-wise kernel for
         // the odd last one -- both launches under ONE timer scope (ffgpu_last_kernel_ms reports the call, not its tail)
         DeviceGuard g(ctx->device);
         LaunchTimer lt(ctx, (hipStream_t)stream);
-        const size_t done = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, ctx->lc, a, b, out, n, (hipStream_t)stream);
+        const size_t done = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, lc, a, b, out, n, (hipStream_t)stream);
         if (done && hipGetLastError() != hipSuccess) return FFGPU_EHIP;
         if (done == n) return FFGPU_OK;
         if (done)
-            return launch_status(ctx->ops->ew2(ctx->policy, ctx->lc, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
+            return launch_status(ctx->ops->ew2(ctx->policy, lc, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
                                                (char*)out + 8 * done, n - done, (hipStream_t)stream));
     }
-    return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
+    return do_ew2(ctx, OP_MUL, a, b, out, n, stream, &lc);
 }
 int ffgpu_neg(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stream) {
     return do_ew1(ctx, OP_NEG, a, nullptr, out, n, stream);
@@ -582,7 +624,10 @@ int ffgpu_muladd(ffgpu_ctx* ctx, const void* a, const void* b, const void* c, vo
     ARGCHK(a && b && c && out);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->muladd(ctx->policy, ctx->lc, a, b, c, out, n, (hipStream_t)stream));
+    const size_t nb = rows_bytes(ctx, 1, 0, n);
+    const ByteRange in[3] = {byte_range(a, nb), byte_range(b, nb), byte_range(c, nb)}, o = byte_range(out, nb);
+    const LaunchCfg lc = handoff_lc(ctx, stream, HK_EW, in, 3, &o, 1);
+    return launch_status(ctx->ops->muladd(ctx->policy, lc, a, b, c, out, n, (hipStream_t)stream));
 }
 
 static int make_exp(const uint64_t* e, int limbs, ExpArgs* ex) {
@@ -812,6 +857,17 @@ int ffgpu_beaver_combine(ffgpu_ctx* ctx, const void* z, const void* x, const voi
                                           (hipStream_t)stream));
 }
 
+static LaunchCfg split_lc(ffgpu_ctx* ctx, const void* a, const void* b, const void* coeffs, int t, size_t coeff_stride, int m,
+                          void* shares, size_t share_stride, size_t n, void* stream) {
+    ByteRange in[3];
+    int nin = 0;
+    in[nin++] = byte_range(a, rows_bytes(ctx, 1, 0, n));
+    if (b) in[nin++] = byte_range(b, rows_bytes(ctx, 1, 0, n));
+    if (coeffs) in[nin++] = byte_range(coeffs, rows_bytes(ctx, (size_t)t, coeff_stride, n));
+    const ByteRange o = byte_range(shares, rows_bytes(ctx, (size_t)m, share_stride, n));
+    return handoff_lc(ctx, stream, HK_SPLIT, in, nin, &o, 1);
+}
+
 static int do_split(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, const void* coeffs,
                     size_t coeff_stride, int t, int m, void* shares, size_t share_stride, size_t n,
                     void* stream) {
@@ -822,7 +878,9 @@ static int do_split(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, co
     ARGCHK((m == 1 || share_stride >= n) && (t <= 1 || coeff_stride >= n));
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->split(ctx->policy, ctx->lc, a, fused ? b : nullptr, coeffs,
+    const LaunchCfg lc = split_lc(ctx, a, fused ? b : nullptr, t > 0 ? coeffs : nullptr, t, coeff_stride, m, shares,
+                                  share_stride, n, stream);
+    return launch_status(ctx->ops->split(ctx->policy, lc, a, fused ? b : nullptr, coeffs,
                                          coeff_stride, t, m, shares, share_stride, n, (hipStream_t)stream,
                                          nullptr));
 }
@@ -855,7 +913,8 @@ static int do_split_rng(ffgpu_ctx* ctx, const void* a, const void* b, bool fused
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     if (fused && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    return launch_status(ctx->ops->split(ctx->policy, ctx->lc, a, fused ? b : nullptr, nullptr, 0, t, m,
+    const LaunchCfg lc = split_lc(ctx, a, fused ? b : nullptr, nullptr, 0, 0, m, shares, share_stride, n, stream);
+    return launch_status(ctx->ops->split(ctx->policy, lc, a, fused ? b : nullptr, nullptr, 0, t, m,
                                          shares, share_stride, n, (hipStream_t)stream, t > 0 ? &ra : nullptr));
 }
 int ffgpu_ctx_scalar_limbs(const ffgpu_ctx* ctx) { return (ctx && ctx->elem_bytes == 24) ? 3 : 2; }
@@ -890,7 +949,8 @@ int ffgpu_split_rng_state(ffgpu_ctx* ctx, const void* secrets, const void* mul_b
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     if (mul_by && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    int rc = ctx->ops->split(ctx->policy, ctx->lc, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n,
+    const LaunchCfg lc = split_lc(ctx, secrets, mul_by, nullptr, 0, 0, m, shares, share_stride, n, stream);
+    int rc = ctx->ops->split(ctx->policy, lc, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n,
                              (hipStream_t)stream, t > 0 ? &ra : nullptr);
     if (rc) return launch_status(rc);
     return FFGPU_OK;       // the kernel's last workgroup advanced the nonce (rng_state_release)
@@ -946,7 +1006,14 @@ int ffgpu_gate_rng_batch(ffgpu_ctx* ctx, const void* const* host_rows_a, const u
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     ra.aux = gf8_tables_on_device(ctx);
-    return launch_status(ctx->ops->gate(ctx->policy, ctx->lc, host_rows_a, host_lambda_a, ka, host_rows_b,
+    ByteRange in[14];
+    int nin = 0;
+    for (int j = 0; j < ka; ++j) in[nin++] = byte_range(host_rows_a[j], rows_bytes(ctx, (size_t)nbatch, batch_stride_a, n));
+    for (int j = 0; j < kb; ++j) in[nin++] = byte_range(host_rows_b[j], rows_bytes(ctx, (size_t)nbatch, batch_stride_b, n));
+    const size_t oelems = ((size_t)nbatch - 1) * batch_stride_out + ((size_t)m - 1) * share_stride + n;
+    const ByteRange o = byte_range(shares, oelems * (size_t)ctx->elem_bytes);
+    const LaunchCfg lc = handoff_lc(ctx, stream, HK_SPLIT, in, nin, &o, 1);
+    return launch_status(ctx->ops->gate(ctx->policy, lc, host_rows_a, host_lambda_a, ka, host_rows_b,
                                         host_lambda_b, kb, t, m, shares, share_stride, n, (hipStream_t)stream, &ra,
                                         nbatch, batch_stride_a, batch_stride_b, batch_stride_out));
 }
@@ -993,6 +1060,11 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
     for (int j = 0; j < k; ++j) ARGCHK(host_rows[j]);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
+    ByteRange in[MAXK_ANY];
+    const int nin = k < (int)MAXK_ANY ? k : (int)MAXK_ANY;     // (more rows than that: the launcher refuses them)
+    for (int j = 0; j < nin; ++j) in[j] = byte_range(host_rows[j], rows_bytes(ctx, 1, 0, n));
+    const ByteRange o = byte_range(out, rows_bytes(ctx, (size_t)w, out_stride, n));
+    const LaunchCfg lc = handoff_lc(ctx, stream, HK_REC, in, nin, &o, 1);
     // GF(2^n), 9 <= n <= 128 with a sparse modulus: shared nibble tables of the (uniform) Lagrange
     // coefficients in LDS instead of one full field multiplication per row and element
     if ((ctx->policy_kind == POL_GF2W64 || ctx->policy_kind == POL_GF2W128) && !ctx->gf2w_limbs && k <= 9 &&
@@ -1000,12 +1072,12 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
         const int limbs = ctx->policy_kind == POL_GF2W128 ? 2 : 1;
         int rc = 0;
         for (int r = 0; r < w && rc == 0; ++r)
-            rc = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, ctx->lc, host_rows, host_lambda + 2 * (size_t)r * k,
+            rc = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, lc, host_rows, host_lambda + 2 * (size_t)r * k,
                                              k, (char*)out + (size_t)r * out_stride * ctx->elem_bytes, n,
                                              (hipStream_t)stream);
         if (rc != 2) return launch_status(rc);
     }
-    return launch_status(ctx->ops->recombine(ctx->policy, ctx->lc, host_rows, host_lambda, k, w, out,
+    return launch_status(ctx->ops->recombine(ctx->policy, lc, host_rows, host_lambda, k, w, out,
                                              out_stride, n, (hipStream_t)stream));
 }
 
@@ -1330,7 +1402,9 @@ int ffgpu_copy(ffgpu_ctx* ctx, const void* src, void* dst, size_t bytes, void* s
     ARGCHK(src && dst);
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_copy(ctx->lc, src, dst, bytes, (hipStream_t)stream));
+    const ByteRange in = byte_range(src, bytes), o = byte_range(dst, bytes);
+    const LaunchCfg lc = handoff_lc(ctx, stream, HK_COPY, &in, 1, &o, 1);
+    return launch_status(ffgpu_launch_copy(lc, src, dst, bytes, (hipStream_t)stream));
 }
 int ffgpu_valu_probe(ffgpu_ctx* ctx, int op, int iters, int waves_per_simd, void* scratch32, double* out3, void* stream) {
     ARGCHK(ctx && scratch32 && out3);

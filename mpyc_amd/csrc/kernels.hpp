@@ -13,7 +13,9 @@
 //     different XCDs, block b -> XCD b%8) touch consecutive 4 KiB chunks, so
 //     every XCD's L2 and all HBM channels see the same uniform stream; there is
 //     no reuse to localise in an L2, hence no XCD remap;
-//   * streamed-once data carries the non-temporal hint (nt) on loads and stores;
+//   * streamed-once data carries the non-temporal hint (nt) on loads and stores -- except outputs that the next launch
+//     on the stream is predicted to read: those take the default policy and stay in the Infinity Cache for it
+//     (stg_k / stgw_k below, the prediction in handoff.hpp);
 //   * per-field constants (modulus, fold constant, Lagrange vector, party
 //     x-coordinates) are wave-uniform kernel arguments -> SGPRs, which beats
 //     staging them in LDS for fields this small.
@@ -256,6 +258,34 @@ __device__ __forceinline__ void stgw(u192e* p, const Pack<u192e>& x) {
     }
 }
 
+// Stores of outputs that the next launch on the stream reads back (Plan::keep, launch.hpp; handoff.hpp) take the default
+// cache policy, so the lines stay in the Infinity Cache for that launch; every other output streams past it (nt).  `keep`
+// is a kernel argument (a scalar branch): one kernel serves both policies.  The two empty asm statements (no instruction)
+// pin the default-policy store between two points that may touch *p: left alone, LLVM hoists or sinks two stores that differ
+// only in their cache hint into ONE store and drops the hint -- every output would then take the default policy, whatever
+// `keep` says.  (A bare memory clobber is not enough: the outputs are __restrict__, so it cannot reach them unless p is named.)
+#define FF_STORE_FENCE(p) asm volatile("" ::"v"(p) : "memory")
+template <bool NT, class P, class X>
+__device__ __forceinline__ void stg_k(P* p, const X& x, int keep) {
+    if (keep) {
+        FF_STORE_FENCE(p);
+        stg<false>(p, x);
+        FF_STORE_FENCE(p);
+    } else {
+        stg<NT>(p, x);
+    }
+}
+template <bool NT, class P, class X>
+__device__ __forceinline__ void stgw_k(P* p, const X& x, int keep) {
+    if (keep) {
+        FF_STORE_FENCE(p);
+        stgw<false>(p, x);
+        FF_STORE_FENCE(p);
+    } else {
+        stgw<NT>(p, x);
+    }
+}
+
 // element <-> word for the scalar tail (identity unless words pack elements)
 template <class F>
 __device__ __forceinline__ typename F::word ld_elem(const typename F::elem* p, size_t i) {
@@ -297,7 +327,7 @@ __device__ __forceinline__ typename F::word ew_apply(const F& f, typename F::wor
 // ---- out = a (op) b --------------------------------------------------------
 template <class F, int OP, bool NT>
 __device__ __forceinline__ void ew2_body(const F& f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ b,
-                                         typename F::elem* __restrict__ o, size_t nvec, size_t n) {
+                                         typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
@@ -313,7 +343,7 @@ __device__ __forceinline__ void ew2_body(const F& f, const typename F::elem* __r
         P r;
 #pragma unroll
         for (int q = 0; q < P::N; ++q) r.w[q] = ew_apply<F, OP>(f, x.w[q], y.w[q]);
-        stgw<NT>(ov + i, r);
+        stgw_k<NT>(ov + i, r, keep);
     }
     // scalar tail (n not a multiple of the pack size, or unaligned pointers: nvec == 0)
     const size_t done = nvec * (size_t)(P::N * F::EPW);
@@ -324,8 +354,8 @@ __device__ __forceinline__ void ew2_body(const F& f, const typename F::elem* __r
 template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew2(F f, const typename F::elem* __restrict__ a,
                                                 const typename F::elem* __restrict__ b,
-                                                typename F::elem* __restrict__ o, size_t nvec, size_t n) {
-    ew2_body<F, OP, NT>(f, a, b, o, nvec, n);
+                                                typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
+    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, keep);
 }
 // The same kernel held to WAVES waves per SIMD, for products that the VALU limits: left alone the compiler hoists all nine
 // 32 x 32 carry-less products of a GF(2^128) multiplication side by side (129 registers, three waves per SIMD); told to keep
@@ -334,8 +364,8 @@ __global__ __launch_bounds__(BLOCK) void k_ew2(F f, const typename F::elem* __re
 template <class F, int OP, bool NT, int WAVES>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 void k_ew2_occ(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ b,
-               typename F::elem* __restrict__ o, size_t nvec, size_t n) {
-    ew2_body<F, OP, NT>(f, a, b, o, nvec, n);
+               typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
+    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, keep);
 }
 template <class F, int OP> struct EwOccupancy { enum { waves = 0 }; };
 #ifndef FFGPU_GF2W128_OCC
@@ -347,7 +377,7 @@ template <> struct EwOccupancy<GF2W128, OP_MUL> { enum { waves = FFGPU_GF2W128_O
 template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew1(F f, const typename F::elem* __restrict__ a,
                                                 typename F::word s, typename F::elem* __restrict__ o,
-                                                size_t nvec, size_t n) {
+                                                size_t nvec, size_t n, int keep) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
@@ -359,7 +389,7 @@ __global__ __launch_bounds__(BLOCK) void k_ew1(F f, const typename F::elem* __re
         P r;
 #pragma unroll
         for (int q = 0; q < P::N; ++q) r.w[q] = ew_apply<F, OP>(f, x.w[q], s);
-        stgw<NT>(ov + i, r);
+        stgw_k<NT>(ov + i, r, keep);
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);
     for (size_t e = done + gid; e < n; e += gsz) {
@@ -372,7 +402,7 @@ template <class F, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_muladd(F f, const typename F::elem* __restrict__ a,
                                                    const typename F::elem* __restrict__ b,
                                                    const typename F::elem* __restrict__ c,
-                                                   typename F::elem* __restrict__ o, size_t nvec, size_t n) {
+                                                   typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
@@ -391,7 +421,7 @@ __global__ __launch_bounds__(BLOCK) void k_muladd(F f, const typename F::elem* _
         P r;
 #pragma unroll
         for (int q = 0; q < P::N; ++q) r.w[q] = f.muladd(x.w[q], y.w[q], z.w[q]);
-        stgw<NT>(ov + i, r);
+        stgw_k<NT>(ov + i, r, keep);
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);
     for (size_t e = done + gid; e < n; e += gsz) {
@@ -585,7 +615,7 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
                                                   const typename F::elem* __restrict__ b,
                                                   const typename F::elem* __restrict__ coef, size_t cstride,
                                                   int m, typename F::elem* __restrict__ out, size_t ostride,
-                                                  size_t nvec, size_t n, RngArgs ra, GateSrc<F> gs) {
+                                                  size_t nvec, size_t n, RngArgs ra, GateSrc<F> gs, int keep) {
     rng_load_state(ra);
     // batched launch: gate y = blockIdx.y reads its operand rows yA / yB elements further on and writes yO further on.
     // (The offsets are added where the rows are indexed: the row-pointer arrays stay read-only kernel arguments --
@@ -710,8 +740,8 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
             for (int party = 1; party <= m; ++party) {
 #pragma unroll
                 for (int q = 0; q < P::N; ++q) y.w[q] = share_diff_next<F, TT>(f, y.w[q], dd[q]);
-                if constexpr (WC) stgw<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y);
-                else stg<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y);
+                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
+                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
             }
         } else {
             // GF(2^n) (the points are field elements, not integers) and T = 0: Horner by the point
@@ -728,8 +758,8 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
                         y.w[q] = f.muladd_small(acc, (uint32_t)party, s.w[q]);
                     }
                 }
-                if constexpr (WC) stgw<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y);
-                else stg<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y);
+                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
+                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
             }
         }
     };
@@ -955,7 +985,7 @@ struct RecArgs {
 template <class F, int K, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_recombine(F f, RecArgs<F, K> ra, int w,
                                                       typename F::elem* __restrict__ out, size_t ostride,
-                                                      size_t nvec, size_t n) {
+                                                      size_t nvec, size_t n, int keep) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -989,7 +1019,7 @@ __global__ __launch_bounds__(BLOCK) void k_recombine(F f, RecArgs<F, K> ra, int 
                     y.w[q] = f.acc_reduce(s);
                 }
             }
-            stgw<NT>(reinterpret_cast<MP*>(out + (size_t)r * ostride) + i, y);
+            stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)r * ostride) + i, y, keep);
         }
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);

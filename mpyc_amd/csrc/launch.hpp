@@ -13,6 +13,9 @@ struct LaunchCfg {
     int mm_mfma;            // FFGPU_MM_MFMA=0: dense products stay on the VALU kernel (cross-checks of the matrix-core path)
     double mm_mfma_min;     // FFGPU_MM_MFMA_MIN: smallest M*N*K that goes to the matrix cores (default 8e7)
     int gf2w_bitsliced;     // FFGPU_GF2W_BITSLICED=0: GF(2^64) products through the multiplier kernel only
+    int handoff;            // FFGPU_HANDOFF=0: every streamed output non-temporal (no hand-off tracking, handoff.hpp)
+    int keep_out;           // PER LAUNCH, never set in the context's copy: this launch's outputs feed the next launch on its
+                            // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
 };
 
 inline unsigned grid_for(size_t iters, const LaunchCfg& lc) {
@@ -140,13 +143,15 @@ struct Launchers {
     // The streaming plan of a launch: nvec packs through the vector loop, one pack per thread up to the grid cap (one element
     // per thread when the operands do not allow packs).  The one place where nvec_of and grid_for meet: every launcher takes
     // its nvec from here, so 24-byte fields get whole waves whatever grid it then picks.
+    // keep: the vector loop stores its outputs with the default cache policy instead of nt (LaunchCfg::keep_out).
     struct Plan {
         size_t nvec;
         unsigned grid;
+        int keep;
     };
     static Plan plan(size_t n, bool vec, const LaunchCfg& lc) {
         const size_t nvec = nvec_of(n, vec);
-        return {nvec, grid_for(nvec ? nvec : n, lc)};
+        return {nvec, grid_for(nvec ? nvec : n, lc), lc.keep_out};
     }
     // share generation with in-kernel coefficients (k_split RNG, the gate): the grouped loop serves up to 4 packs per thread
     // (RngLayout::G) on half as many threads as packs, a slightly larger grid is harmless; below ~2.6e5 packs it cannot
@@ -191,9 +196,9 @@ struct Launchers {
         // (streamed loads and stores carry the non-temporal hint: +4-8 %, profiles/r01_tuning.md; the un-hinted instantiations
         // that rounds 1-5 kept behind FFGPU_NT=0 for A/B runs are gone)
         if constexpr (OCC > 0)
-            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n);
+            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.keep);
         else
-            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n);
+            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.keep);
     }
     static int ew2(const void* Fp, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                    hipStream_t st) {
@@ -214,7 +219,7 @@ struct Launchers {
     template <int OP>
     static void go_ew1(const F& f, const LaunchCfg& lc, const E* a, W s, E* o, size_t n, hipStream_t st) {
         const Plan p = plan(n, al(a) && al(o), lc);
-        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n);
+        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n, p.keep);
     }
     static int ew1(const void* Fp, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                    size_t n, hipStream_t st) {
@@ -240,7 +245,7 @@ struct Launchers {
         const F& f = *reinterpret_cast<const F*>(Fp);
         const Plan p = plan(n, al(a) && al(b) && al(c) && al(o), lc);
         hipLaunchKernelGGL((k_muladd<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a,
-                           (const E*)b, (const E*)c, (E*)o, p.nvec, n);
+                           (const E*)b, (const E*)c, (E*)o, p.nvec, n, p.keep);
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
@@ -249,7 +254,7 @@ struct Launchers {
     static void go_split(const F& f, const Plan& p, const E* a, const E* b, const E* coef, size_t cstride, int m, E* out,
                          size_t ostride, size_t n, hipStream_t st, const RngArgs& ra, const GateSrc<F>& gs, unsigned gy = 1) {
         hipLaunchKernelGGL((k_split<F, T, FUSE, true, RNG, REC>), dim3(p.grid, gy), dim3(BLOCK), 0, st, f, a, b,
-                           coef, cstride, m, out, ostride, p.nvec, n, ra, gs);
+                           coef, cstride, m, out, ostride, p.nvec, n, ra, gs, p.keep);
     }
     template <bool FUSE, bool RNG>
     static int split_t(const F& f, const LaunchCfg& lc, const E* a, const E* b, const E* coef, size_t cstride,
@@ -383,7 +388,7 @@ struct Launchers {
         for (int i = w * K; i < MAXW * K; ++i) ra.lam[i] = ra.lam[0];
         const Plan p = plan(n, vec, lc);
         hipLaunchKernelGGL((k_recombine<F, K, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, ra, w, out, ostride,
-                           p.nvec, n);
+                           p.nvec, n, p.keep);
     }
     static int recombine(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                          int w, void* out, size_t ostride, size_t n, hipStream_t st) {

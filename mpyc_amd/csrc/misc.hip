@@ -1558,12 +1558,12 @@ int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const LaunchCfg& 
 }
 
 __global__ __launch_bounds__(BLOCK) void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
-                                                   size_t nvec) {
+                                                   size_t nvec, int keep) {
     const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     const size_t gsz = (size_t)gridDim.x * BLOCK;
     for (size_t i = gid; i < nvec; i += gsz) {
         uint4 x = ldg<true>(src + i);
-        stg<true>(dst + i, x);
+        stg_k<true>(dst + i, x, keep);
     }
 }
 
@@ -1571,7 +1571,7 @@ int ffgpu_launch_copy(const LaunchCfg& lc, const void* src, void* dst, size_t by
     if (!aligned16(src) || !aligned16(dst) || (bytes & 15)) return 1;
     size_t nvec = bytes / 16;
     unsigned grid = grid_for(nvec, lc);
-    hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec);
+    hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec, lc.keep_out);
     FFGPU_CHECK_LAUNCH();
     return 0;
 }
