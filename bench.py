@@ -11,8 +11,7 @@ m=3, t=1:
 => 3n field-ops per step (one op = one element through one stage).  The first two stages run as
 ONE kernel (ffgpu_mul_split): the product is formed in registers and goes straight into share
 generation, exactly what mpyc_amd.finfields does for `a * b` followed by np_random_split (deferred
-product); c itself is never written to HBM.  The unfused three-kernel step is timed as well and
-reported as `unfused` (and each kernel separately under `kernels`).  Inputs are resident in
+product); c itself is never written to HBM.  Inputs are resident in
 HBM before the timed region; several independent buffer sets are rotated so that no launch
 finds its operands in the 256 MiB Infinity Cache.
 
@@ -22,8 +21,12 @@ ranks, rank 0 prints ONE JSON line.  Elements shard across ranks with no collect
 data path (every element is independent): weak scaling, n per GPU fixed.
 `--dump-outputs DIR` writes what the last timed step computed (dump_outputs); the inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
+Such a plain run does only that, and checks the last warm-up step against the oracle before the timed steps.
+`--full` adds everything else after them: the unfused three-kernel step (`unfused`), every kernel separately
+(`kernels`), other fields and configurations, the configs[3] / party-major section, the CPU baselines and the
+API-level legs; and a `# detail` line (also written to bench_detail.json) before the line.
 
-Extra objects on the line:
+Extra objects on the line (`--full`):
   roofline      dominant kernel: algorithmic bytes per launch / mean launch time measured with
                 events on the launch stream inside this run; peak = 8 TB/s HBM (spec).
   kernels       the same for every kernel of the step, plus configs[2] (P64, m=7, t=3) and the
@@ -342,11 +345,16 @@ def compact_line(out):
     return text
 
 
-def emit(out, detail_path=None):
-    """stdout protocol: `# detail {...}` (everything measured; not a bare JSON line), then the compact line LAST."""
+def emit(out, detail_path=None, detail=True):
+    """stdout protocol: `# detail {...}` (everything measured; not a bare JSON line), then the compact line LAST.
+    detail=False (a plain run): the compact line alone, and no file."""
     lap('rest')
     out['sections_s'] = dict(SECTIONS_S)
     out['wall_s'] = round(time.perf_counter() - T_PROCESS_START, 1)
+    if not detail:
+        sys.stdout.write(compact_line(out) + '\n')
+        sys.stdout.flush()
+        return
     paths = [detail_path] if detail_path else [os.path.join(ROOT, 'bench_detail.json'),
                                                 os.path.join(ROOT, 'gpurun_out', 'bench_detail.json')]
     written = []
@@ -525,7 +533,7 @@ def api_leg(n_full, parties_on_gpus=False):
         cmd = [sys.executable, prog, '--no-log'] + ([f'-M{parties}', '-B', str(free_base_port(parties))] if parties > 1 else [])
         t0 = time.perf_counter()
         if budget_left() < 3:
-            return {'skipped': 'time budget of the run spent (bench.py --full runs every leg)'}
+            return {'skipped': 'time budget of the run spent (bench.py --full --no-budget runs every leg)'}
         r = run_bounded(cmd, env, timeout)
         if r is None:
             return {'error': f'no result within {min(timeout, LEG_BUDGET["leg_timeout"]):.0f} s (process group ended)'}
@@ -592,7 +600,7 @@ def api_leg(n_full, parties_on_gpus=False):
               ([f'-M{parties}', '-B', str(free_base_port(parties))] if parties > 1 else [])
         t0 = time.perf_counter()
         if budget_left() < 3:
-            return {'skipped': 'time budget of the run spent (bench.py --full runs every leg)'}
+            return {'skipped': 'time budget of the run spent (bench.py --full --no-budget runs every leg)'}
         r = run_bounded(cmd, env, timeout)
         if r is None:
             return {'error': f'no result within {min(timeout, LEG_BUDGET["leg_timeout"]):.0f} s (process group ended)'}
@@ -895,24 +903,32 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--n', type=int, default=int(os.environ.get('FFGPU_BENCH_N', 10_000_000)), help='elements per GPU')
     ap.add_argument('--sets', type=int, default=4, help='rotating buffer sets')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-api-leg', action='store_true', help='skip the API-level section (party processes under install())')
-    ap.add_argument('--no-extras', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, every other section (unfused step, per-kernel rows and roofline, '
+                         'other fields and configurations, configs[3] section, CPU baselines, API-level legs) and the detail')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-api-leg', action='store_true',
+                    help='with --full: skip the API-level section (party processes under install())')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the per-kernel rows, the roofline and the other fields')
     ap.add_argument('--budget', type=float, default=float(os.environ.get('FFGPU_BENCH_BUDGET', '240')),
                     help='seconds the sections that run OTHER programs (reference baseline, API-level legs) may take together; '
                          'legs that no longer fit are reported as skipped (default 240; each leg also has a 60 s limit of its own)')
-    ap.add_argument('--full', action='store_true', help='no budget, 300 s per leg: the evidence passes')
-    ap.add_argument('--no-multi-gpu-leg', action='store_true', help='skip the configs[3] / party-major section')
+    ap.add_argument('--no-budget', action='store_true', help='with --full: no budget, 300 s per leg: the evidence passes')
+    ap.add_argument('--no-multi-gpu-leg', action='store_true', help='with --full: skip the configs[3] / party-major section')
     ap.add_argument('--parties-on-gpus', action='store_true',
                     default=os.environ.get('FFGPU_BENCH_PARTIES_ON_GPUS', '0') == '1',
-                    help='N >= 3: also run three MPyC parties on three GPUs over the device-side wire (opt-in; never run on >1 GPU)')
+                    help='with --full, N >= 3: also run three MPyC parties on three GPUs over the device-side wire (opt-in; '
+                         'never run on >1 GPU)')
     ap.add_argument('--layout', choices=('element', 'party-major'), default='element',
-                    help="'party-major': only the configs[3] section (gate sharded + party-major exchange), more steps")
+                    help="'party-major': only the configs[3] section (gate sharded + party-major exchange), more steps; "
+                         "implies --full")
     ap.add_argument('--dump-outputs', metavar='DIR',
                     help='after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.layout == 'party-major':
+        args.full = args.no_extras = args.no_cpu_baseline = True
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -932,7 +948,8 @@ def main():
             fwd += ['--dump-outputs', args.dump_outputs]
         fwd += [f_ for f_, on in (('--no-cpu-baseline', args.no_cpu_baseline), ('--no-extras', args.no_extras),
                                   ('--no-api-leg', args.no_api_leg), ('--no-multi-gpu-leg', args.no_multi_gpu_leg),
-                                  ('--parties-on-gpus', args.parties_on_gpus), ('--full', args.full)) if on]
+                                  ('--parties-on-gpus', args.parties_on_gpus), ('--full', args.full),
+                                  ('--no-budget', args.no_budget)) if on]
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + fwd
         raise SystemExit(subprocess.call(cmd, env=dict(os.environ, FFGPU_BENCH_N=str(args.n))))
@@ -1005,7 +1022,8 @@ def main():
 
     for i in range(args.warmup):
         step(i)
-    # parity guard inside the bench: recombining the fresh shares gives back a*b
+    # parity guard inside the bench: recombining the fresh shares gives back a*b.  A plain run keeps it too: it has always
+    # stood between the warm-up and the timed steps, and without it the headline reads 1-1.5 % faster (a moved yardstick)
     torch.cuda.synchronize()
     s0 = sets[(args.warmup - 1) % len(sets)] if args.warmup else None
     if s0 is not None:
@@ -1027,19 +1045,20 @@ def main():
         # before the unfused pass and the extras, which overwrite these buffers
         dump_outputs(args.dump_outputs, sets[(args.warmup + args.steps - 1) % len(sets)])
 
-    # the same work as three separate kernels (c materialised), for reference
-    for i in range(min(args.warmup, 3)):
-        step_unfused(i)
-    barrier()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        step_unfused(i)
-    barrier()
-    elapsed_unfused = time.perf_counter() - t1
-    if dist is not None:
-        tt = torch.tensor([elapsed_unfused], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed_unfused = float(tt.item())
+    if args.full:
+        # the same work as three separate kernels (c materialised), for reference
+        for i in range(min(args.warmup, 3)):
+            step_unfused(i)
+        barrier()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            step_unfused(i)
+        barrier()
+        elapsed_unfused = time.perf_counter() - t1
+        if dist is not None:
+            tt = torch.tensor([elapsed_unfused], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed_unfused = float(tt.item())
 
     devinfo = f'cuda:{local_rank} ({torch.cuda.get_device_name(local_rank)})'
     me = {'rank': rank, 'local_rank': local_rank, 'device': devinfo, 'pci_bus_id': ctx.pci_bus_id()}
@@ -1077,15 +1096,12 @@ def main():
         # two RCCL ranks on one GPU: the aggregate would count that GPU twice -- say so in the line and fail the run
         invalid.append('invalid: ranks share a device')
         out['scaling'] = invalid[0]
-    out['unfused'] = {'value': round(ops_total / elapsed_unfused, 1), 'unit': 'field-ops/s',
-                      'ms_per_step': round(elapsed_unfused / args.steps * 1e3, 5),
-                      'note': 'same step as three kernels (mul, split, recombine) with c written to HBM'}
+    if args.full:
+        out['unfused'] = {'value': round(ops_total / elapsed_unfused, 1), 'unit': 'field-ops/s',
+                          'ms_per_step': round(elapsed_unfused / args.steps * 1e3, 5),
+                          'note': 'same step as three kernels (mul, split, recombine) with c written to HBM'}
 
-    if args.layout == 'party-major':
-        args.no_extras = True
-        args.no_cpu_baseline = True
-
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         eb = 8
         reps = 10
         kern = {}
@@ -1684,10 +1700,10 @@ def main():
     def after_the_collectives():
         """Rank 0 alone, N = 1 only (the contract's `cpu_baseline` rule; at N > 1 the other ranks have left and the driver's
         N = 1 run already holds these sections): every measurement beyond the step's own kernels, the reference CPU path
-        and the API-level section.  A failure here never costs the headline line."""
-        if rank != 0 or world != 1:
+        and the API-level section (--full).  A failure here never costs the headline line."""
+        if rank != 0 or world != 1 or not args.full:
             return
-        if args.full:
+        if args.no_budget:
             LEG_BUDGET.update(deadline=None, leg_timeout=300.0)
         else:
             LEG_BUDGET.update(deadline=time.perf_counter() + args.budget, leg_timeout=60.0)
@@ -1728,7 +1744,7 @@ def main():
     # hangs), rank 0 still prints the line with everything measured above.
     def finish(code=None):
         if rank == 0:
-            emit(out)
+            emit(out, detail=args.full)
         if code is not None:
             sys.stdout.flush()
             os._exit(code)
@@ -1744,7 +1760,7 @@ def main():
             out.setdefault('multi_gpu', {'error': f'multi-GPU section did not finish within {limit:.0f} s (rank {rank})'})
             finish(0)
     threading.Thread(target=watchdog, daemon=True).start()
-    if not args.no_multi_gpu_leg:
+    if args.full and not args.no_multi_gpu_leg:
         full = args.layout == 'party-major'
         try:
             leg = multi_gpu_leg(dist, rank, world, local_rank, backend, n,
@@ -1770,7 +1786,7 @@ def main():
     # GPU -- three MPyC party processes under install() on GPUs 0, 1, 2 (MPYC_AMD_DEVICE=party), share rows crossing between
     # the GPUs as interprocess handles.  It has never run on more than one GPU, so it is not part of a default run; as
     # subprocesses with their own timeouts, after every collective is done; an error is reported in the object, never raised.
-    if rank == 0 and world >= 3 and args.parties_on_gpus and not args.no_api_leg:
+    if rank == 0 and world >= 3 and args.full and args.parties_on_gpus and not args.no_api_leg:
         torch.cuda.empty_cache()
         try:
             out['api_parties_on_gpus'] = api_leg(n, parties_on_gpus=True)

@@ -122,6 +122,16 @@ def test_emit_prints_detail_first_and_the_compact_line_last(tmp_path):
         assert json.load(fh)['api']['note'] == out['api']['note']
 
 
+def test_emit_of_a_plain_run_prints_the_compact_line_alone(tmp_path):
+    out = canned()
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.emit(out, detail_path=str(tmp_path / 'bench_detail.json'), detail=False)
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1 and json.loads(lines[0])['value'] == out['value'] and 'wall_s' in json.loads(lines[0])
+    assert not os.listdir(tmp_path)
+
+
 def test_bounded_subprocess_ends_the_whole_process_group(tmp_path):
     """bench.run_bounded: a leg that does not finish within its limit is ended TOGETHER with the processes it spawned (the
     party processes of `-M3`), reports None, and honours the run's budget; a finished leg returns its output."""
@@ -195,6 +205,28 @@ def test_dump_outputs_keeps_every_position_of_a_small_run(tmp_path):
     d = _dumped(tmp_path)
     assert d['index'].tolist() == list(range(n)) and d['y'].tolist() == (y.numpy() * 1.0).tolist()
     assert d['shares'].shape == (3, n) and d['shares_u16'].shape == (3, n, 4)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_alone():
+    """`bench.py --steps K --warmup W` without --full: one line with the headline, none of the sections --full adds,
+    and no detail file."""
+    import subprocess
+    detail = os.path.join(ROOT, 'bench_detail.json')
+    before = os.path.getmtime(detail) if os.path.exists(detail) else None
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1'], capture_output=True,
+                       text=True, timeout=600, cwd=ROOT, env=dict(os.environ, FFGPU_BENCH_N='100000'))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, [ln[:80] for ln in lines]
+    line = json.loads(lines[0])
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert line['unit'] == 'field-ops/s' and line['dtype'] == 'u64' and line['higher_is_better'] is True
+    assert line['metric'].startswith('field-ops/sec') and line['config']['n_per_gpu'] == 100000
+    for key in ('unfused', 'roofline', 'cpu_baseline', 'api', 'multi_gpu', 'configs0', 'configs2', 'valu_peak', 'hbm_fracs',
+                'detail_file'):
+        assert key not in line, key
+    assert (os.path.getmtime(detail) if os.path.exists(detail) else None) == before
 
 
 @pytest.mark.gpu

@@ -84,11 +84,11 @@ def _bench_lines(args, env_extra, timeout=900):
 
 @pytest.mark.gpu
 def test_bench_four_ranks_control_flow_on_one_gpu():
-    """The command the driver runs for the scaling record, with 4 ranks forced onto GPU 0 (gloo, since RCCL refuses
+    """The scaling command with --full, with 4 ranks forced onto GPU 0 (gloo, since RCCL refuses
     two ranks on one device): self-launch under torch.distributed.run, headline + roofline before the first collective
     of the configs[3] section, the section itself on 4 ranks, one compact line that parses.  Four ranks
     and this process keep the processes holding the GPU within MAX_GPU_PROCS."""
-    line, detail = _bench_lines(['--gpus', '4', '--steps', '2', '--warmup', '1'],
+    line, detail = _bench_lines(['--gpus', '4', '--steps', '2', '--warmup', '1', '--full'],
                                 {'FFGPU_BENCH_DEVICE': '0', 'FFGPU_BENCH_LEG_TIMEOUT': '600'})
     assert line['n_gpus'] == 4 and line['distributed']['world_size'] == 4 and line['distributed']['backend'] == 'gloo'
     assert len(line['distributed']['ranks']) == 4 and line['distributed']['distinct_devices'] == 1
@@ -137,7 +137,7 @@ def test_bench_refuses_two_rccl_ranks_on_one_device():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_has_every_required_object():
-    line, detail = _bench_lines(['--steps', '5', '--warmup', '2', '--no-api-leg'], {})
+    line, detail = _bench_lines(['--steps', '5', '--warmup', '2', '--full', '--no-api-leg'], {})
     assert line['n_gpus'] == 1 and line['dtype'] == 'u64' and line['unit'] == 'field-ops/s'
     for key in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'kernel', 'ms_per_launch', 'bytes_per_launch'):
         assert key in line['roofline'], key

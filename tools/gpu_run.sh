@@ -1,8 +1,8 @@
 #!/bin/bash
 # The ONE script for passes on the GPU box (replaces the per-round gpu_r0*.sh).  STAGES (any subset, in this order):
 #   newtests  pytest -m gpu on $NEWTESTS (files / node ids)          tests   the whole -m gpu suite
-#   bench     bench.py --steps 20 --warmup 5 (the driver's line)      prof    rocprofv3 --kernel-trace --stats of the bench
-#   benchfull the same with --full (every API-level leg, no budget)
+#   bench     bench.py --steps 20 --warmup 5 (the driver's line)      prof    rocprofv3 --kernel-trace --stats of bench --full
+#   benchfull the same with --full --no-budget (every section, every API-level leg, no budget)
 #   pmc       FETCH_SIZE / WRITE_SIZE passes of tools/pmc_probe.py    valu    SQ_INSTS_VALU pass of tools/valu_probe.py
 #   counters  SQ counter passes (waves, busy / wave cycles, VALU / LDS instructions and waits) of the GF(2^n) products and PRSS
 #   probe     bash -c "$PROBE" (timeout $PROBE_TIMEOUT, default 600)
@@ -28,12 +28,12 @@ if has bench; then
 fi
 if has benchfull; then
   SECONDS=0
-  (timeout 2400 python bench.py --steps 20 --warmup 5 --full) > $O/bench_full.log 2> $O/bench_full.err; echo "bench --full rc=$? wall=${SECONDS}s" | tee -a $O/bench_full.err
+  (timeout 2400 python bench.py --steps 20 --warmup 5 --full --no-budget) > $O/bench_full.log 2> $O/bench_full.err; echo "bench --full rc=$? wall=${SECONDS}s" | tee -a $O/bench_full.err
   cp bench_detail.json $O/bench_detail_full.json 2>/dev/null
   tail -n 1 $O/bench_full.log | cut -c1-600
 fi
 if has prof; then
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -o $T -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-api-leg) > $O/rocprof_$T.log 2>&1
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -o $T -- python $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-api-leg) > $O/rocprof_$T.log 2>&1
   echo "rocprof rc=$?"
 fi
 if has pmc; then

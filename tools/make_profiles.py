@@ -55,7 +55,7 @@ if 'pmc' in what and os.path.isdir(f'{G}/pmc_{tag}_FETCH_SIZE'):
 if 'stats' in what and os.path.exists(f'{G}/prof_{tag}/{tag}_kernel_stats.csv'):
     rows = list(csv.DictReader(open(f'{G}/prof_{tag}/{tag}_kernel_stats.csv')))
     with open(f'profiles/{tag}_kernel_stats.md', 'w') as fh:
-        fh.write(f'# {tag} -- `rocprofv3 --kernel-trace --stats` of `python bench.py --steps 20 --warmup 3 --no-cpu-baseline` (MI355X)\n\n')
+        fh.write(f'# {tag} -- `rocprofv3 --kernel-trace --stats` of `python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-api-leg` (MI355X)\n\n')
         fh.write(f'Raw file: profiles/{tag}_kernel_stats.csv (rocprofv3 `*_kernel_stats.csv`). Library kernels only below; the rest are '
                  'torch RNG/fill kernels that create the synthetic inputs outside the timed region.\n')
         fh.write('Template arguments of k_split: <field policy, T, fused local product, non-temporal, '
