@@ -281,6 +281,17 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
 int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
                  size_t M, size_t K, size_t N, void* stream);
 
+/* ---- convolution ---------------------------------------------------------------- */
+/* out[k] = sum_j a[k - j] * v[j] over the field, 0 <= k < na + nv - 1: the FULL convolution of two arrays
+ * (np.convolve modes 'same' and 'valid' are slices of it, taken by the caller).  The operand order does not
+ * matter: the shorter one becomes the tap vector.  One kernel, output-stationary tiles with the window of `a`
+ * and the taps staged in LDS and the field's lazily reduced multiply-accumulate; it reads a and v, writes out
+ * and uses no scratch memory, so memory is linear in na + nv.  na == 0, nv == 0 or an `out` that overlaps an
+ * operand: FFGPU_EINVAL.
+ * replaces: finfields.py:796-801 (np.convolve on the object arrays, then `%`), the local convolution of
+ * runtime.py:2580-2627 np_convolve (np.convolve(a, b) at :2627).                                 */
+int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size_t nv, void* out, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

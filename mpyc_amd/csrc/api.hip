@@ -293,6 +293,8 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         c->lc.gf2w_bitsliced = e ? (atoi(e) != 0) : 1;
         e = getenv("FFGPU_HANDOFF");
         c->lc.handoff = e ? (atoi(e) != 0) : 1;
+        e = getenv("FFGPU_CONV_WIDE_PER_CU");
+        c->lc.conv_wide_per_cu = e && atoi(e) >= 0 ? atoi(e) : 2;
         c->lc.keep_out = 0;
     }
     c->gf2w_limbs = 0;
@@ -1135,6 +1137,21 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
     }
     return launch_status(ctx->ops->matmul(ctx->policy, ctx->lc, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws,
                                           ws_bytes, (hipStream_t)stream));
+}
+
+int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size_t nv, void* out, void* stream) {
+    ARGCHK(ctx && a && v && out && na >= 1 && nv >= 1);
+    ARGCHK(na < ((size_t)1 << 40) && nv < ((size_t)1 << 40));
+    if (na < nv) {                                   // the shorter operand is the tap vector
+        std::swap(a, v);
+        std::swap(na, nv);
+    }
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, (na + nv - 1) * eb);
+    ARGCHK(!overlaps(o, byte_range(a, na * eb)) && !overlaps(o, byte_range(v, nv * eb)));   // tiles read while others write
+    DeviceGuard g(ctx->device);
+    LaunchTimer lt(ctx, (hipStream_t)stream);
+    return launch_status(ctx->ops->convolve(ctx->policy, ctx->lc, a, na, v, nv, out, (hipStream_t)stream));
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,

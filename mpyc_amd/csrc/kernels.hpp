@@ -2215,4 +2215,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 }  // namespace ffgpu
 
 #include "matmul.hpp"   // dense, skinny and matrix-core products
+#include "convolve.hpp" // full convolution of two arrays
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -13,6 +13,8 @@ struct LaunchCfg {
     int mm_mfma;            // FFGPU_MM_MFMA=0: dense products stay on the VALU kernel (cross-checks of the matrix-core path)
     double mm_mfma_min;     // FFGPU_MM_MFMA_MIN: smallest M*N*K that goes to the matrix cores (default 8e7)
     int gf2w_bitsliced;     // FFGPU_GF2W_BITSLICED=0: GF(2^64) products through the multiplier kernel only
+    int conv_wide_per_cu;   // FFGPU_CONV_WIDE_PER_CU: 128-output tiles per compute unit from which ffgpu_convolve takes its wide shape
+                            // (default 2; 0: always wide, a huge value: always narrow -- tests drive both shapes at small sizes)
     int handoff;            // FFGPU_HANDOFF=0: every streamed output non-temporal (no hand-off tracking, handoff.hpp)
     int keep_out;           // PER LAUNCH, never set in the context's copy: this launch's outputs feed the next launch on its
                             // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
@@ -68,6 +70,9 @@ struct FieldOps {
     // keys40: ks x (32-byte ChaCha key + 8-byte nonce)
     int (*prss_chacha)(const void* F, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                        const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
+    // full convolution, na >= nv >= 1, out: na + nv - 1 elements
+    int (*convolve)(const void* F, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
+                    hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -858,6 +863,23 @@ struct Launchers {
         FFGPU_CHECK_LAUNCH();
         return 0;
     }
+    // Shape by output count (convolve_geom.hpp): wide tiles once they give every compute unit lc.conv_wide_per_cu of them,
+    // narrow ones below that, so that few outputs with many taps still fill the chip.  Neither needs scratch.
+    template <class S>
+    static int go_convolve(const F& f, const E* a, size_t na, const E* v, size_t nv, E* out, hipStream_t st) {
+        const size_t tiles = conv_tiles(na + nv - 1, S::TO);
+        if (tiles > 0x7fffffffu) return 1;
+        hipLaunchKernelGGL((k_convolve<F, S>), dim3((unsigned)tiles), dim3(BLOCK), 0, st, f, a, na, v, nv, out);
+        FFGPU_CHECK_LAUNCH();
+        return 0;
+    }
+    static int convolve(const void* Fp, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
+                        hipStream_t st) {
+        const F& f = *reinterpret_cast<const F*>(Fp);
+        if (conv_use_wide(na + nv - 1, lc.num_cu, lc.conv_wide_per_cu))
+            return go_convolve<ConvWide>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
+        return go_convolve<ConvNarrow>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
+    }
     static int dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
@@ -997,7 +1019,7 @@ struct Launchers {
     }
 
     static const FieldOps* table() {
-        static const FieldOps ops = {&ew2, &ew1, &muladd, &split, &rng_coeffs, &recombine, &pow, &inv, &matmul, &dot, &gate, &sqrt_cl, &gauss, &group_matvec, &beaver, &prss, &prss_chacha};
+        static const FieldOps ops = {&ew2, &ew1, &muladd, &split, &rng_coeffs, &recombine, &pow, &inv, &matmul, &dot, &gate, &sqrt_cl, &gauss, &group_matvec, &beaver, &prss, &prss_chacha, &convolve};
         return &ops;
     }
 };

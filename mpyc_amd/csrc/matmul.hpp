@@ -40,6 +40,12 @@ template <class F>
 struct MatmulDigits<F, true> {
     enum { NL = F::LAZY_NL };
 };
+// terms an unreduced accumulator takes between reductions: F::acc has headroom for 2^8 products, a digit column for
+// FF_D28_MAX_TERMS (fields.hpp).  k_matmul and k_convolve (convolve.hpp) flush on this bound.
+template <class F>
+struct AccFlush {
+    enum { TERMS = HasLazyAcc<F>::value ? (int)FF_D28_MAX_TERMS : 192 };
+};
 template <class F, int TM, int TN>
 __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* __restrict__ A, size_t lda,
                                                    const typename F::elem* __restrict__ B, size_t ldb,
@@ -58,7 +64,7 @@ __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* _
     // column sums (fields.hpp LazyDot), reduced every 32 terms -- ~100 instructions per term with the 128-bit limb arithmetic
     constexpr bool LZ = HasLazyAcc<F>::value;
     constexpr int NL = MatmulDigits<F, LZ>::NL;
-    constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = LZ ? (int)FF_D28_MAX_TERMS : 192;
+    constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = AccFlush<F>::TERMS;
     static_assert(FLUSH % BK == 0, "the flush test follows whole k-steps");
     using Acc = typename std::conditional<LZ, typename LazyAccOf<F>::type, typename F::acc>::type;
     __shared__ W As[LZ ? 1 : BK][LZ ? 1 : BM + 1];

@@ -612,6 +612,21 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_matmul(self._h, A.ptr, K, B.ptr, N, out.ptr, N, M, K, N, self._stream()), 'matmul')
         return out
 
+    def convolve(self, a: DevArray, v: DevArray, out: Optional[DevArray] = None) -> DevArray:
+        """Full convolution out[k] = sum_j a[k - j] * v[j], len(a) + len(v) - 1 elements, in one kernel with memory linear
+        in the operands (finfields.py:796-801; the local part of runtime.np_convolve, runtime.py:2627).  The operand
+        order does not matter; modes 'same' / 'valid' are slices the caller takes."""
+        if a.n == 0 or v.n == 0:
+            raise ValueError('convolve: non-empty arrays required')
+        n = a.n + v.n - 1
+        self._same(a.n, a, what='convolve operand')
+        self._same(v.n, v, what='convolve operand')
+        if out is not None:
+            self._same(n, out, what='convolve output')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_convolve(self._h, a.ptr, a.n, v.ptr, v.n, out.ptr, self._stream()), 'convolve')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

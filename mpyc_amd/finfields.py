@@ -2607,18 +2607,12 @@ def _np_array_equiv(a1, a2):
         return False
 
 
-def _np_convolve(a, v, mode='full'):
-    """np.convolve over the field (runtime.np_convolve's local part, runtime.py:2580): Toeplitz gather of
-    the longer operand (index 0 = zero element) times the shorter one through the product kernel."""
-    cls = type(a) if isinstance(a, FieldArray) else type(v)
-    a = a if isinstance(a, FieldArray) else cls(a)
-    v = v if isinstance(v, FieldArray) else cls(v)
-    if a.ndim != 1 or v.ndim != 1 or a.size == 0 or v.size == 0:
-        raise ValueError('convolve: 1-D non-empty arrays required')
-    if a.size < v.size:
-        a, v = v, a
+def _convolve_toeplitz(cls, a, v):
+    """Full convolution composed from existing operations: Toeplitz gather of the longer operand a (index 0 = zero
+    element) times the shorter one through the product kernel.  Memory is O(len(a) * len(v)); the route of a context
+    that cannot run the convolution kernel."""
     na, nv = a.size, v.size
-    ctx, eb = a.ctx, a.ctx.elem_bytes
+    ctx = a.ctx
     lb = ctx.limbs
     flat = a._dev.t.reshape(-1, lb) if lb else a._dev.t.reshape(-1)
     dev = flat.device
@@ -2627,7 +2621,25 @@ def _np_convolve(a, v, mode='full'):
     zero = torch.zeros((1, lb) if lb else (1,), dtype=flat.dtype, device=dev)
     t = torch.cat([zero, flat]).index_select(0, idx.reshape(-1))
     T = cls._wrap(DevArray(ctx, t, idx.numel()), tuple(idx.shape))
-    full = T @ v
+    return T @ v
+
+
+def _np_convolve(a, v, mode='full'):
+    """np.convolve over the field (runtime.np_convolve's local part, runtime.py:2580): the convolution kernel
+    (FieldContext.convolve) computes the full result, the modes are slices of it."""
+    cls = type(a) if isinstance(a, FieldArray) else type(v)
+    a = a if isinstance(a, FieldArray) else cls(a)
+    v = v if isinstance(v, FieldArray) else cls(v)
+    if a.ndim != 1 or v.ndim != 1 or a.size == 0 or v.size == 0:
+        raise ValueError('convolve: 1-D non-empty arrays required')
+    if a.size < v.size:
+        a, v = v, a
+    na, nv = a.size, v.size
+    ctx = a.ctx
+    if getattr(ctx, '_h', None) is not None:     # a context with a library handle runs the kernel
+        full = cls._wrap(ctx.convolve(a._dev, v._dev), (na + nv - 1,))
+    else:                                        # (the Python-integer stand-in of the CPU tests has none)
+        full = _convolve_toeplitz(cls, a, v)
     if mode == 'full':
         return full
     if mode == 'same':
