@@ -292,6 +292,35 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
  * runtime.py:2580-2627 np_convolve (np.convolve(a, b) at :2627).                                 */
 int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size_t nv, void* out, void* stream);
 
+/* ---- prefix scans and reductions along one axis ------------------------------------ */
+/* The array is contiguous row-major (outer, k, inner): element (o, j, i) at (o*k + j)*inner + i.  That covers every axis
+ * of every contiguous array without a transposed copy.  op: FFGPU_SCAN_ADD (field addition) or FFGPU_SCAN_MUL (field
+ * multiplication); both are exact and associative, so the result does not depend on the order of evaluation.
+ *
+ * ffgpu_scan: out(o, j, i) = a(o, 0, i) op ... op a(o, j, i), the inclusive scan along j.  with_initial != 0: out has
+ * k + 1 entries along the axis, the identity (0 / 1) first (np.cumulative_sum(include_initial=True)).  out == a (in
+ * place) is allowed when with_initial == 0; any other overlap of out with a: FFGPU_EINVAL.
+ * ffgpu_axis_reduce: out(o, i) = a(o, 0, i) op ... op a(o, k-1, i), outer*inner elements; out must not overlap a.
+ * Two geometries (csrc/scan_geom.hpp): a column walk (one thread per column pack, running value in registers, one
+ * launch, every element read once) when outer*inner fills the device, and row tiles otherwise (a workgroup scans a
+ * tile; lines of several tiles take reduce-then-scan: tile aggregates, one scan of the aggregates, a second pass with the
+ * carries -- three launches whatever k, and no workgroup ever waits for another).
+ * workspace: ffgpu_scan_workspace_bytes(ctx, outer, k, inner) bytes of device memory, 16-byte aligned (tile aggregates
+ * only: with the default tile one element per 4096 input elements, 2048 above 8-byte elements -- the query follows
+ * FFGPU_SCAN_TILE_THREADS, which tests lower; may be NULL when the query returns 0).  A smaller one: FFGPU_EINVAL.
+ * k == 0, outer*inner == 0, sizes whose product overflows size_t, or more tiles than a grid holds: FFGPU_EINVAL (the
+ * query returns 0 for them); nothing is launched.
+ * replaces: finfields.py:801, 807 (np.cumsum / np.cumprod on the object arrays, then `%`), finfields.py:1332-1349
+ * (FiniteFieldArray.sum / .prod along an axis), runtime.py:3476-3506 np_sum with an axis, runtime.py:3510-3549
+ * np_cumsum / np_cumulative_sum, the cumsum of runtime.py:3668 np_sgn.                                    */
+#define FFGPU_SCAN_ADD 0
+#define FFGPU_SCAN_MUL 1
+int ffgpu_scan(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t outer, size_t k, size_t inner, int with_initial,
+               void* workspace, size_t workspace_bytes, void* stream);
+int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t ffgpu_scan_workspace_bytes(ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

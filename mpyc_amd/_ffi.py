@@ -76,6 +76,9 @@ _SIGS = {
     'ffgpu_recombine': [_vp, ctypes.POINTER(_vp), _u64p, _int, _int, _vp, _sz, _sz, _vp],
     'ffgpu_matmul': [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp],
     'ffgpu_convolve': [_vp, _vp, _sz, _vp, _sz, _vp, _vp],
+    'ffgpu_scan': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _int, _vp, _sz, _vp],
+    'ffgpu_axis_reduce': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp],
+    'ffgpu_scan_workspace_bytes': [_vp, _sz, _sz, _sz],
     'ffgpu_sqrt_cl': [_vp, _vp, _vp, _sz, _vp],
     'ffgpu_gauss': [_vp, _vp, _int, _int, _sz, _int, _vp, _vp, _vp],
     'ffgpu_group_matvec': [_vp, _u64p, _u64p, _int, _int, _vp, _vp, _sz, _vp],
@@ -110,7 +113,7 @@ _SIGS = {
     'ffgpu_ipc_close': [_vp, _vp],
 }
 _RESTYPES = {'ffgpu_strerror': ctypes.c_char_p, 'ffgpu_last_hip_error': ctypes.c_char_p,
-             'ffgpu_rng_state_bytes': ctypes.c_size_t, 'ffgpu_shake128_close': None}
+             'ffgpu_rng_state_bytes': ctypes.c_size_t, 'ffgpu_scan_workspace_bytes': ctypes.c_size_t, 'ffgpu_shake128_close': None}
 
 EXPORTED = tuple(_SIGS)
 

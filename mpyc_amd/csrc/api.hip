@@ -295,6 +295,10 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         c->lc.handoff = e ? (atoi(e) != 0) : 1;
         e = getenv("FFGPU_CONV_WIDE_PER_CU");
         c->lc.conv_wide_per_cu = e && atoi(e) >= 0 ? atoi(e) : 2;
+        e = getenv("FFGPU_SCAN_GEOM");
+        c->lc.scan_geom = e && atoi(e) >= 0 && atoi(e) <= 2 ? atoi(e) : 0;
+        e = getenv("FFGPU_SCAN_TILE_THREADS");
+        c->lc.scan_tile_threads = e && atoi(e) >= 1 && atoi(e) <= 256 ? atoi(e) : 256;
         c->lc.keep_out = 0;
     }
     c->gf2w_limbs = 0;
@@ -1152,6 +1156,58 @@ int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size
     DeviceGuard g(ctx->device);
     LaunchTimer lt(ctx, (hipStream_t)stream);
     return launch_status(ctx->ops->convolve(ctx->policy, ctx->lc, a, na, v, nv, out, (hipStream_t)stream));
+}
+
+// the plan of a scan call, whichever alignment its pointers turn out to have: the larger workspace of the two
+static size_t scan_ws_elems(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner) {
+    size_t need = 0;
+    for (int aligned = 0; aligned < 2; ++aligned) {
+        const ScanPlan p = scan_plan(outer, k, inner, (size_t)ctx->elem_bytes, aligned != 0, ctx->lc.num_cu, ctx->lc.scan_geom,
+                                     ctx->lc.scan_tile_threads, 1);
+        if (!p.ok) return 0;
+        if (p.ws_elems > need) need = p.ws_elems;
+    }
+    return need;
+}
+size_t ffgpu_scan_workspace_bytes(ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner) {
+    if (!ctx) return 0;
+    return scan_ws_elems(ctx, outer, k, inner) * (size_t)ctx->elem_bytes;
+}
+static int do_scan(ffgpu_ctx* ctx, bool reduce, int op, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                   int with_initial, void* workspace, size_t workspace_bytes, void* stream) {
+    ARGCHK(ctx && a && out && (op == FFGPU_SCAN_ADD || op == FFGPU_SCAN_MUL));
+    ARGCHK(k >= 1 && outer >= 1 && inner >= 1);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const uintptr_t amask = eb == 12 ? 3u : 15u;     // what the launcher asks of a pointer for 16-byte packs
+    const bool aligned = (((uintptr_t)a | (uintptr_t)out) & amask) == 0;
+    const ScanPlan p = scan_plan(outer, k, inner, eb, aligned, ctx->lc.num_cu, ctx->lc.scan_geom, ctx->lc.scan_tile_threads,
+                                 with_initial ? 1 : 0);
+    ARGCHK(p.ok);                                    // overflowing products, more tiles than a grid
+    const size_t nin = p.lines * k, nout = reduce ? p.lines : p.lines * (k + (with_initial ? 1 : 0));
+    const ByteRange in = byte_range(a, nin * eb), o = byte_range(out, nout * eb);
+    // in place is safe (a thread or a workgroup reads its own elements before it writes them); any other overlap is not
+    ARGCHK((!reduce && !with_initial && a == out) || !overlaps(o, in));
+    ARGCHK(!workspace || ((uintptr_t)workspace & 15u) == 0);
+    if (workspace && workspace_bytes) {
+        const ByteRange w = byte_range(workspace, workspace_bytes);
+        ARGCHK(!overlaps(w, in) && !overlaps(w, o));
+    }
+    DeviceGuard g(ctx->device);
+    LaunchTimer lt(ctx, (hipStream_t)stream);
+    const int rc = reduce ? ctx->ops->axis_reduce(ctx->policy, ctx->lc, op, a, out, outer, k, inner, workspace, workspace_bytes,
+                                                  (hipStream_t)stream)
+                          : ctx->ops->scan(ctx->policy, ctx->lc, op, a, out, outer, k, inner, with_initial, workspace,
+                                           workspace_bytes, (hipStream_t)stream);
+    if (rc == 4 || rc == 5) return FFGPU_EINVAL;
+    return launch_status(rc);
+}
+int ffgpu_scan(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t outer, size_t k, size_t inner, int with_initial,
+               void* workspace, size_t workspace_bytes, void* stream) {
+    return do_scan(ctx, false, op, a, out, outer, k, inner, with_initial, workspace, workspace_bytes, stream);
+}
+int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t outer, size_t k, size_t inner, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return do_scan(ctx, true, op, a, out, outer, k, inner, 0, workspace, workspace_bytes, stream);
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,

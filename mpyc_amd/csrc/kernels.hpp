@@ -2216,4 +2216,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 
 #include "matmul.hpp"   // dense, skinny and matrix-core products
 #include "convolve.hpp" // full convolution of two arrays
+#include "scan.hpp"     // prefix scans and reductions along one axis
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -15,6 +15,10 @@ struct LaunchCfg {
     int gf2w_bitsliced;     // FFGPU_GF2W_BITSLICED=0: GF(2^64) products through the multiplier kernel only
     int conv_wide_per_cu;   // FFGPU_CONV_WIDE_PER_CU: 128-output tiles per compute unit from which ffgpu_convolve takes its wide shape
                             // (default 2; 0: always wide, a huge value: always narrow -- tests drive both shapes at small sizes)
+    int scan_geom;          // FFGPU_SCAN_GEOM: 0 = ffgpu_scan / ffgpu_axis_reduce choose their geometry (scan_geom.hpp), 1 = always the
+                            // column walk, 2 = always row tiles (tests drive both at small sizes; never changes a result)
+    int scan_tile_threads;  // FFGPU_SCAN_TILE_THREADS: threads of a row-tile workgroup that hold elements (default: all 256; tests
+                            // lower it so that small arrays span many tiles)
     int handoff;            // FFGPU_HANDOFF=0: every streamed output non-temporal (no hand-off tracking, handoff.hpp)
     int keep_out;           // PER LAUNCH, never set in the context's copy: this launch's outputs feed the next launch on its
                             // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
@@ -73,6 +77,12 @@ struct FieldOps {
     // full convolution, na >= nv >= 1, out: na + nv - 1 elements
     int (*convolve)(const void* F, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
                     hipStream_t st);
+    // inclusive scan / reduction along k of a contiguous (outer, k, inner) array with field addition (mul = 0) or
+    // multiplication; workspace: scan_plan().ws_elems elements.  4: the plan refuses the sizes, 5: workspace too small
+    int (*scan)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                int with_initial, void* workspace, size_t workspace_bytes, hipStream_t st);
+    int (*axis_reduce)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
+                       size_t inner, void* workspace, size_t workspace_bytes, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -880,6 +890,62 @@ struct Launchers {
             return go_convolve<ConvWide>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
         return go_convolve<ConvNarrow>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
     }
+    // Scans and axis reductions (scan.hpp).  The column walk follows the streaming plan of the other launchers: one column
+    // (pack) per thread up to the grid cap, packs only where every pointer allows them (al).  24-byte elements move per
+    // lane (three dwordx2) in both geometries: consecutive j of a column are a whole row apart, so the wave-contiguous
+    // ldgw / stgw contract would hold only for rows of whole waves, and the per-lane form serves every shape.
+    template <bool MUL, bool RED, bool UNIT>
+    static void go_scan_rows(const F& f, const ScanPlan& p, const E* a, E* out, size_t k, size_t inner, int wi, E* ws,
+                             hipStream_t st, unsigned blocks, unsigned lines) {
+        if constexpr (RED) {
+            hipLaunchKernelGGL((k_scan_tile_reduce<F, MUL, UNIT>), dim3(blocks), dim3(BLOCK), 0, st, f, a, p.ntiles > 1 ? ws : out,
+                               k, inner, p.ntiles, p.tt);
+            if (p.ntiles > 1)
+                hipLaunchKernelGGL((k_scan_tile_carry<F, MUL, true>), dim3(lines), dim3(BLOCK), 0, st, f, ws, out, p.ntiles);
+        } else {
+            if (p.ntiles > 1) {
+                hipLaunchKernelGGL((k_scan_tile_reduce<F, MUL, UNIT>), dim3(blocks), dim3(BLOCK), 0, st, f, a, ws, k, inner,
+                                   p.ntiles, p.tt);
+                hipLaunchKernelGGL((k_scan_tile_carry<F, MUL, false>), dim3(lines), dim3(BLOCK), 0, st, f, ws, (E*)nullptr,
+                                   p.ntiles);
+            }
+            hipLaunchKernelGGL((k_scan_tile<F, MUL, UNIT>), dim3(blocks), dim3(BLOCK), 0, st, f, a, out,
+                               p.ntiles > 1 ? (const E*)ws : (const E*)nullptr, k, inner, p.ntiles, p.tt, wi);
+        }
+    }
+    template <bool MUL, bool RED>
+    static int go_scan(const F& f, const LaunchCfg& lc, const E* a, E* out, size_t outer, size_t k, size_t inner, int wi,
+                       E* ws, size_t ws_bytes, hipStream_t st) {
+        static_assert((int)EPV == (int)(sizeof(E) <= 8 ? 16 / sizeof(E) : 1), "scan_epv mirrors the pack size");
+        const ScanPlan p = scan_plan(outer, k, inner, sizeof(E), al(a) && al(out), lc.num_cu, lc.scan_geom,
+                                     lc.scan_tile_threads, wi);
+        if (!p.ok) return 4;
+        if (p.geom == SCAN_COLS) {
+            hipLaunchKernelGGL((k_scan_cols<F, MUL, RED>), dim3(grid_for(p.units, lc)), dim3(BLOCK), 0, st, f, a, out, k, inner,
+                               p.per, p.units, p.vec, wi);
+            FFGPU_CHECK_LAUNCH();
+            return 0;
+        }
+        const unsigned blocks = (unsigned)(p.lines * p.ntiles), lines = (unsigned)p.lines;
+        if (p.ntiles > 1 && (!ws || ws_bytes / sizeof(E) < p.ws_elems)) return 5;
+        if (inner == 1) go_scan_rows<MUL, RED, true>(f, p, a, out, k, inner, wi, ws, st, blocks, lines);
+        else go_scan_rows<MUL, RED, false>(f, p, a, out, k, inner, wi, ws, st, blocks, lines);
+        FFGPU_CHECK_LAUNCH();
+        return 0;
+    }
+    static int scan(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                    int with_initial, void* workspace, size_t workspace_bytes, hipStream_t st) {
+        const F& f = *reinterpret_cast<const F*>(Fp);
+        const int wi = with_initial ? 1 : 0;
+        if (mul) return go_scan<true, false>(f, lc, (const E*)a, (E*)out, outer, k, inner, wi, (E*)workspace, workspace_bytes, st);
+        return go_scan<false, false>(f, lc, (const E*)a, (E*)out, outer, k, inner, wi, (E*)workspace, workspace_bytes, st);
+    }
+    static int axis_reduce(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
+                           size_t inner, void* workspace, size_t workspace_bytes, hipStream_t st) {
+        const F& f = *reinterpret_cast<const F*>(Fp);
+        if (mul) return go_scan<true, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
+        return go_scan<false, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
+    }
     static int dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = *reinterpret_cast<const F*>(Fp);
@@ -1019,7 +1085,7 @@ struct Launchers {
     }
 
     static const FieldOps* table() {
-        static const FieldOps ops = {&ew2, &ew1, &muladd, &split, &rng_coeffs, &recombine, &pow, &inv, &matmul, &dot, &gate, &sqrt_cl, &gauss, &group_matvec, &beaver, &prss, &prss_chacha, &convolve};
+        static const FieldOps ops = {&ew2, &ew1, &muladd, &split, &rng_coeffs, &recombine, &pow, &inv, &matmul, &dot, &gate, &sqrt_cl, &gauss, &group_matvec, &beaver, &prss, &prss_chacha, &convolve, &scan, &axis_reduce};
         return &ops;
     }
 };

@@ -627,6 +627,54 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_convolve(self._h, a.ptr, a.n, v.ptr, v.n, out.ptr, self._stream()), 'convolve')
         return out
 
+    def _scan_workspace(self, outer: int, k: int, inner: int):
+        """tile-aggregate workspace of scan / axis_reduce: one per stream, grown on demand (with the default tile one
+        element per 4096 input elements, 2048 above 8-byte elements); (pointer, bytes)"""
+        need = int(self._L.ffgpu_scan_workspace_bytes(self._h, outer, k, inner))
+        if need == 0:
+            return None, 0
+        wss = self.__dict__.setdefault('_scan_ws', {})
+        key = self._stream()
+        ws = wss.get(key)
+        if ws is None or ws.numel() < need:
+            ws = wss[key] = torch.empty(need, dtype=torch.uint8, device=self.torch_device)
+        return ws.data_ptr(), ws.numel()
+
+    def _scan_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, nout: int, out: Optional[DevArray],
+                   in_place_ok: bool):
+        if outer < 1 or k < 1 or inner < 1:
+            raise ValueError(f'{what}: outer, k and inner must be at least 1')
+        self._same(outer * k * inner, a, what=f'{what} operand')
+        if out is not None:
+            self._same(nout, out, what=f'{what} output')
+            eb = self.elem_bytes
+            if not (in_place_ok and out.ptr == a.ptr):    # tiles / columns are written while others are still read
+                if out.ptr < a.ptr + a.n * eb and a.ptr < out.ptr + out.n * eb:
+                    raise ValueError(f'{what}: the output overlaps the operand')
+        return out or self.empty(nout)
+
+    def scan(self, a: DevArray, outer: int, k: int, inner: int, mul: bool = False, with_initial: bool = False,
+             out: Optional[DevArray] = None) -> DevArray:
+        """Inclusive prefix sums (mul: products) along k of the contiguous (outer, k, inner) array `a` (np.cumsum / np.cumprod
+        on field arrays, finfields.py:801, 807; runtime.np_cumsum, runtime.py:3510-3549).  with_initial: k + 1 entries along
+        the axis, the identity first.  out may be `a` itself when with_initial is False."""
+        kk = k + (1 if with_initial else 0)
+        out = self._scan_args('scan', a, outer, k, inner, outer * kk * inner, out, not with_initial)
+        ws, wsb = self._scan_workspace(outer, k, inner)
+        _ffi.check(self._L.ffgpu_scan(self._h, 1 if mul else 0, a.ptr, out.ptr, outer, k, inner, 1 if with_initial else 0,
+                                      ws, wsb, self._stream()), 'scan')
+        return out
+
+    def axis_reduce(self, a: DevArray, outer: int, k: int, inner: int, mul: bool = False,
+                    out: Optional[DevArray] = None) -> DevArray:
+        """Sums (mul: products) along k of the contiguous (outer, k, inner) array `a`: outer * inner elements
+        (FiniteFieldArray.sum / .prod along an axis, finfields.py:1332-1349)."""
+        out = self._scan_args('axis_reduce', a, outer, k, inner, outer * inner, out, False)
+        ws, wsb = self._scan_workspace(outer, k, inner)
+        _ffi.check(self._L.ffgpu_axis_reduce(self._h, 1 if mul else 0, a.ptr, out.ptr, outer, k, inner, ws, wsb,
+                                             self._stream()), 'axis_reduce')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

@@ -1960,6 +1960,20 @@ class FieldArray:
         # elements: k <= 16 -> one thread per row (ffgpu_group_matvec with a row of ones); many rows -> matrix x
         # ones(k) (the HBM-bound matvec kernels); few long rows -> one two-stage reduction (ffgpu_sum) per row
         axis = axis if axis >= 0 else axis + self.ndim
+        if getattr(self.ctx, '_h', None) is not None and self.size:
+            # the reduction kernels (FieldContext.axis_reduce) on the array as it lies in memory for k > 16.  Measured against
+            # every branch of the composed route below (profiles/r09_scan.md): fewer than 64 rows (a Python loop over them)
+            # 1.4 to 4 times faster; many rows with inner > 1 (a permuted copy, then matrix x ones(k)) 6 to 74 times; many
+            # rows along the last axis (matrix x ones(k) with no copy: (10^5, 100), (10^4, 1000), (1000, 10^4)) 1.6 to
+            # 190 times.  k <= 16 keeps group_matvec, which is as fast or faster there
+            outer, k, inner = _axis_geometry(self._shape, axis)
+            if k > 16:
+                return type(self)._wrap(self.ctx.axis_reduce(self._dev, outer, k, inner), self._shape[:axis] + self._shape[axis + 1:])
+        return self._sum_axis_composed(axis)
+
+    def _sum_axis_composed(self, axis):
+        """sum along one axis (0 <= axis < ndim, ndim > 1) composed from existing operations: a permuted copy that moves the
+        axis last, then a product with a row of ones (or, for few long rows, one ffgpu_sum per row)"""
         if axis == self.ndim - 1:
             moved = self
         else:
@@ -1987,12 +2001,52 @@ class FieldArray:
                 ov[r:r + 1].copy_(ctx.sum(DevArray(ctx, lv[r].reshape(-1, ctx.limbs) if ctx.limbs else lv[r], k)).t)
         return cls._wrap(out, moved.shape[:-1])
 
-    def prod(self, axis=None, **kw):
-        """Product of all elements / along one axis (finfields.py:1339-1349): log2(k) halving passes of the
-        element-wise product kernel."""
+    def prod(self, axis=None, keepdims=False, initial=None, **kw):
+        """Product of all elements / along one axis (finfields.py:1339-1349): one reduction of the scan kernel family
+        (FieldContext.axis_reduce) on the array as it lies in memory."""
         cls, ctx = type(self), self.ctx
-        if kw.get('initial') is not None or kw.get('keepdims'):
-            raise NotImplementedError('prod: initial / keepdims')
+        if kw.get('where') is not None or kw.get('out') is not None:
+            raise NotImplementedError('prod: where / out')
+        if initial is not None:
+            r = self.prod(axis=axis, keepdims=keepdims)
+            return r * initial
+        if keepdims:
+            r = self.prod(axis=axis)
+            if axis is None or self.ndim <= 1:
+                return cls([r]).reshape((1,) * self.ndim)
+            axis = axis if axis >= 0 else axis + self.ndim
+            return r.reshape(self._shape[:axis] + (1,) + self._shape[axis + 1:])
+        if getattr(ctx, '_h', None) is None:              # (the Python-integer stand-in of the CPU tests has no kernels)
+            return self._prod_halving(axis)
+        if axis is not None and self.ndim > 1:
+            axis = axis if axis >= 0 else axis + self.ndim
+            outer, k, inner = _axis_geometry(self._shape, axis)
+            if ctx.binary and ctx.elem_bytes == 8 and ((inner > 1 and self.size >= 1 << 22)
+                                                       or (inner == 1 and outer >= 64 and 256 < k < 4096)):
+                # GF(2^64): the halving passes run the bit-sliced product kernel, which beats the in-register products of
+                # the column walk down many columns (the kernels at 0.72 to 0.93 of its speed from 2^22 elements, the
+                # smallest size measured, to 6.5 * 10^7) and of row tiles that a line does not fill ((10^4, 1000): 0.62;
+                # the neighbours (10^5, 100) and (1000, 10^4) go to the kernels, 2.0 and 1.4 times faster; the bounds
+                # between them are not measured), profiles/r09_scan.md
+                return self._prod_halving(axis)
+            if ctx.binary and ctx.elem_bytes == 1 and inner > 1 and outer * inner < 1 << 18 and self.size >= 1 << 22:
+                # GF(2^8) down few columns (fewer than 2^14 packs of 16: a thin column walk) of a large array: the halving
+                # passes are level or ahead ((64, 65536): the kernels at 0.96 of their speed; the one shape measured)
+                return self._prod_halving(axis)
+            rest = self._shape[:axis] + self._shape[axis + 1:]
+            if k == 0:
+                return cls(np.ones(rest, dtype=object))
+            if outer * inner == 0:
+                return cls(np.zeros(rest, dtype=object))
+            return cls._wrap(ctx.axis_reduce(self._dev, outer, k, inner, mul=True), rest)
+        if self.size == 0:
+            return cls.field(1)
+        return cls.field(_fops(cls.field).box(ctx.axis_reduce(self._dev, 1, self.size, 1, mul=True).to_ints()[0]))
+
+    def _prod_halving(self, axis=None):
+        """prod composed from existing operations: log2(k) halving passes of the element-wise product kernel after a
+        permuted copy (the route of a context that cannot run the reduction kernels)."""
+        cls, ctx = type(self), self.ctx
         if axis is not None and self.ndim > 1:
             axis = axis if axis >= 0 else axis + self.ndim
             perm = [axis] + [d for d in range(self.ndim) if d != axis]        # reduced axis FIRST: halves are contiguous
@@ -2850,14 +2904,37 @@ def _np_trim_zeros(filt, trim='fb', **kw):
     return filt[lo:hi]
 
 
+def _axis_geometry(shape, axis):
+    """(outer, k, inner) of a contiguous row-major array scanned or reduced along `axis`: element (o, j, i) at
+    (o * k + j) * inner + i -- every axis of every contiguous array, no transposed copy"""
+    return _prod(shape[:axis]), shape[axis], _prod(shape[axis + 1:])
+
+
 def _np_scan(a, axis, mul: bool, include_initial=False):
-    """np.cumsum / np.cumprod along one axis: Hillis-Steele scan, ceil(log2 k) passes of the add / mul kernel."""
+    """np.cumsum / np.cumprod along one axis (finfields.py:801, 807; runtime.np_cumsum, runtime.py:3510-3549): the scan
+    kernels (FieldContext.scan) on the array as it lies in memory, every element read and written once (three times for
+    lines longer than a tile)."""
     if axis is None:
         a, axis = a.reshape(-1), 0
     axis = axis if axis >= 0 else axis + a.ndim
+    ctx = a.ctx
+    if getattr(ctx, '_h', None) is not None and a.ndim >= 1:     # a context with a library handle runs the kernels
+        shape = tuple(a.shape)
+        outer, k, inner = _axis_geometry(shape, axis)
+        if k and outer * inner:
+            oshape = shape[:axis] + (k + (1 if include_initial else 0),) + shape[axis + 1:]
+            return a._wrap(ctx.scan(a._dev, outer, k, inner, mul=mul, with_initial=include_initial), oshape)
     if include_initial:                                   # np.cumulative_sum/prod: leading 0 / 1 along the axis
         init = type(a)(np.full(a.shape[:axis] + (1,) + a.shape[axis + 1:], 1 if mul else 0, dtype=object))
-        return _np_concatenate([init, _np_scan(a, axis, mul)], axis)
+        return _np_concatenate([init, _scan_hillis_steele(a, axis, mul)], axis)
+    return _scan_hillis_steele(a, axis, mul)
+
+
+def _scan_hillis_steele(a, axis, mul: bool):
+    """Scan along one axis composed from existing operations: Hillis-Steele, ceil(log2 k) passes of the add / mul kernel,
+    each on a clone of the whole array, after a transposed copy when the axis is not the first.  The route of a context
+    that cannot run the scan kernels (the Python-integer stand-in of the CPU tests), of empty arrays, and the yardstick
+    the kernels are measured against."""
     perm = [axis] + [d for d in range(a.ndim) if d != axis]
     inv = [perm.index(d) for d in range(a.ndim)]
     moved = a.transpose(*perm) if a.ndim > 1 else a.copy()
