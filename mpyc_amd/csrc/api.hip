@@ -7,7 +7,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <limits.h>
 #include <mutex>
+#include <new>
 
 #include "../../include/ffgpu.h"
 #include "handoff.hpp"
@@ -32,92 +34,6 @@ const FieldOps* ffgpu_ops_gf2p8();
 const FieldOps* ffgpu_ops_gf2w32();
 const FieldOps* ffgpu_ops_gf2w64();
 const FieldOps* ffgpu_ops_gf2w128();
-int ffgpu_sbox_build_lut(const void* gf2p8_policy, const uint8_t* rows8, uint8_t b, uint8_t* lut256);
-int ffgpu_launch_sbox(const uint8_t* lut256, const ffgpu::LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_to_bits(const ffgpu::LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_mask_open(const void* policy, const ffgpu::LaunchCfg& lc, const void* const* rows, const uint64_t* coef2, int nrows,
-                               const void* const* rbits, const uint64_t* mu2, int np, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_bits_affine_fold(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, const void* c,
-                                      const void* rbits, size_t ybr, void* out, size_t ybo, size_t n, int nbatch,
-                                      hipStream_t st);
-int ffgpu_launch_gf8_group8(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
-                            const void* in, void* out, size_t ngroups, hipStream_t st);
-int ffgpu_launch_copy(const ffgpu::LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st);
-int ffgpu_launch_valu_probe(const ffgpu::LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st);
-int ffgpu_gf8_build_tables(const void* policy, void* tables_out);
-int ffgpu_gf2w_build_rtable(const void* policy, int limbs, void* rtable_out);
-int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const ffgpu::LaunchCfg& lc, const void* const* rows, const uint64_t* lam2,
-                                int k, void* out, size_t n, hipStream_t st);
-int ffgpu_launch_gf8_sbox_layer(const void* policy, const ffgpu::LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs, void* out,
-                                size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2, int t, int m,
-                                size_t n, hipStream_t st, const ffgpu::RngArgs* rng);
-void ffgpu_gf8_sbox_layer_tables(const void* policy, const void* mul_tables, const uint64_t* m2, const uint64_t* bias2,
-                                 unsigned char* out);
-int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const ffgpu::LaunchCfg& lc, const void* a,
-                              const void* b, void* out, size_t n, hipStream_t st);
-size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
-                                         hipStream_t st);
-int ffgpu_launch_gf8_mul_tab(const void* tables, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
-                             hipStream_t st);
-
-struct ffgpu_ctx {
-    int kind;
-    int reduction;
-    int device;
-    int elem_bytes;
-    int policy_kind;
-    const FieldOps* ops;
-    uint64_t rng_r[2];  // 2^W mod p for the keystream sampler
-    ffgpu::LaunchCfg lc; // launch shape and run-time switches, filled when the context is created
-    int gf8_tab_min;    // GF(2^n<=8): arrays of at least this many elements multiply through LDS tables
-    alignas(16) unsigned char gf8_tables[1536];
-    int gf2w_limbs;     // GF(2^n), 9 <= n <= 128: 1 or 2 limbs -> windowed multiplication kernel
-    alignas(16) unsigned char gf2w_rtable[256];
-    // last S-box table built for this context (depends only on rows8, b)
-    uint8_t sbox_key[9];
-    int sbox_valid;
-    uint8_t sbox_lut[256];
-    alignas(16) unsigned char policy[128];
-    uint64_t modulus[3];
-    // grow-only device scratch of ffgpu_matmul (digit planes, split-K slabs), ONE BUFFER PER STREAM: launches on
-    // different streams never share scratch, and a buffer is only freed after its own stream has drained
-    struct Scratch {
-        hipStream_t stream;
-        void* ptr;
-        size_t bytes;
-        int used;
-    } scratch[8];
-    std::mutex* scratch_mu;
-    // which outputs feed the next launch on their stream (handoff.hpp); guarded by handoff_mu
-    HandoffTracker handoff;
-    std::mutex* handoff_mu;
-    void* gf8_tables_dev;   // device copy of gf8_tables (lazily, for the fused GF(2^n<=8) product)
-    // tables of the fused S-box layer (ffgpu_gf256_sbox_layer) for the last affine map used with this context
-    void* sbl_tables_dev;
-    unsigned char sbl_key[72];
-    int sbl_valid;
-    // opt-in timing of the most recent compute call (ffgpu_ctx_set_timing / ffgpu_last_kernel_ms)
-    int timing, timed;
-    hipEvent_t ev0, ev1;
-    // timing mode 2 (ffgpu_busy_ms): one event pair per compute call, harvested into acc_ms
-    enum { ACC_MAX = 256 };
-    hipEvent_t acc_ev[2 * ACC_MAX];
-    int acc_made, acc_n;
-    double acc_ms;
-    unsigned long long acc_calls;
-};
-
-// sum the elapsed time of the recorded event pairs of accumulate mode into acc_ms (waits for the last one)
-static void acc_harvest(ffgpu_ctx* c) {
-    if (c->acc_n == 0) return;
-    (void)hipEventSynchronize(c->acc_ev[2 * (c->acc_n - 1) + 1]);
-    for (int i = 0; i < c->acc_n; ++i) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->acc_ev[2 * i], c->acc_ev[2 * i + 1]) == hipSuccess) c->acc_ms += ms;
-    }
-    c->acc_calls += (unsigned long long)c->acc_n;
-    c->acc_n = 0;
-}
 
 static thread_local char g_hip_err[256] = "";
 
@@ -131,11 +47,15 @@ static int hip_fail(hipError_t e, const char* what) {
         if (e_ != hipSuccess) return hip_fail(e_, #call); \
     } while (0)
 
-static int launch_status(int rc) {
-    if (rc == 0) return FFGPU_OK;
-    if (rc & 0x10000) return hip_fail((hipError_t)(rc & 0xffff), "kernel launch");
-    if (rc == 2) return FFGPU_ENOTSUP;
-    return FFGPU_EINVAL;
+// what a launcher reported -> the status of the entry point (and the text of ffgpu_last_hip_error)
+static int status_of(const LaunchStatus& s) {
+    switch (s.code) {
+        case L_OK: return FFGPU_OK;
+        case L_NOT_SUPPORTED:
+        case L_DECLINED: return FFGPU_ENOTSUP;      // (declined: only where no other route is left)
+        case L_HIP_ERROR: return hip_fail(s.hip, "kernel launch");
+        default: return FFGPU_EINVAL;               // bad argument, plan refused, workspace too small
+    }
 }
 
 struct DeviceGuard {
@@ -150,6 +70,123 @@ struct DeviceGuard {
         if (switched) (void)hipSetDevice(prev);
     }
 };
+
+// grow-only device scratch of ffgpu_matmul (digit planes, split-K slabs), ONE BUFFER PER STREAM: launches on
+// different streams never share scratch, and a buffer is only freed after its own stream has drained
+struct ScratchSlots {
+    struct Slot {
+        hipStream_t stream = nullptr;
+        void* ptr = nullptr;
+        size_t bytes = 0;
+        int used = 0;
+    } slots[8];
+    std::mutex mu;
+    // the buffer of `st`, at least `want` bytes unless the device has none to give (*ptr may then be smaller or null: the
+    // VALU kernels need no scratch)
+    int get(hipStream_t st, size_t want, void** ptr, size_t* bytes) {
+        std::lock_guard<std::mutex> lk(mu);
+        Slot* slot = nullptr;
+        for (auto& sc : slots)
+            if (sc.used && sc.stream == st) slot = &sc;
+        if (!slot) {
+            for (auto& sc : slots)
+                if (!sc.used && !slot) slot = &sc;
+            if (!slot) {                                     // more streams than slots: recycle the smallest buffer
+                slot = &slots[0];
+                for (auto& sc : slots)
+                    if (sc.bytes < slot->bytes) slot = &sc;
+                HIPCHK(hipStreamSynchronize(slot->stream));
+                if (slot->ptr) (void)hipFree(slot->ptr);
+                slot->ptr = nullptr;
+                slot->bytes = 0;
+            }
+            slot->used = 1;
+            slot->stream = st;
+        }
+        if (slot->bytes < want) {
+            HIPCHK(hipStreamSynchronize(st));                // queued work may still read the old buffer
+            if (slot->ptr) (void)hipFree(slot->ptr);
+            slot->ptr = nullptr;
+            slot->bytes = 0;
+            if (hipMalloc(&slot->ptr, want) == hipSuccess) slot->bytes = want;
+            else (void)hipGetLastError();                    // no scratch: the VALU kernels need none
+        }
+        *ptr = slot->ptr;
+        *bytes = slot->bytes;
+        return FFGPU_OK;
+    }
+    void release() {                                         // (the context's destructor, under its device guard)
+        for (auto& sc : slots)
+            if (sc.ptr) (void)hipFree(sc.ptr);
+    }
+};
+
+// Every member starts at zero (several are read before they are first written).
+struct ffgpu_ctx {
+    int kind = 0;
+    int reduction = 0;
+    int device = 0;
+    int elem_bytes = 0;
+    int policy_kind = 0;
+    const FieldOps* ops = nullptr;
+    uint64_t rng_r[2] = {};  // 2^W mod p for the keystream sampler
+    ffgpu::LaunchCfg lc = {}; // launch shape and run-time switches, filled when the context is created
+    int gf8_tab_min = 0;    // GF(2^n<=8): arrays of at least this many elements multiply through LDS tables
+    alignas(16) unsigned char gf8_tables[1536] = {};
+    int gf2w_limbs = 0;     // GF(2^n), 9 <= n <= 128: 1 or 2 limbs -> windowed multiplication kernel
+    alignas(16) unsigned char gf2w_rtable[256] = {};
+    // last S-box table built for this context (depends only on rows8, b); guarded by sbox_mu
+    uint8_t sbox_key[9] = {};
+    int sbox_valid = 0;
+    uint8_t sbox_lut[256] = {};
+    std::mutex sbox_mu;
+    alignas(16) unsigned char policy[128] = {};
+    uint64_t modulus[3] = {};
+    ScratchSlots scratch;
+    // which outputs feed the next launch on their stream (handoff.hpp); guarded by handoff_mu
+    HandoffTracker handoff = {};
+    std::mutex handoff_mu;
+    void* gf8_tables_dev = nullptr;   // device copy of gf8_tables (lazily, for the fused GF(2^n<=8) product); guarded by gf8_mu
+    std::mutex gf8_mu;
+    // tables of the fused S-box layer (ffgpu_gf256_sbox_layer) for the last affine map used with this context; guarded by sbl_mu
+    void* sbl_tables_dev = nullptr;
+    unsigned char sbl_key[72] = {};
+    int sbl_valid = 0;
+    std::mutex sbl_mu;
+    // opt-in timing of the most recent compute call (ffgpu_ctx_set_timing / ffgpu_last_kernel_ms)
+    int timing = 0, timed = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // timing mode 2 (ffgpu_busy_ms): one event pair per compute call, harvested into acc_ms
+    enum { ACC_MAX = 256 };
+    hipEvent_t acc_ev[2 * ACC_MAX] = {};
+    int acc_made = 0, acc_n = 0;
+    double acc_ms = 0.0;
+    unsigned long long acc_calls = 0;
+
+    ~ffgpu_ctx() {
+        DeviceGuard g(device);
+        scratch.release();
+        if (gf8_tables_dev) (void)hipFree(gf8_tables_dev);
+        if (sbl_tables_dev) (void)hipFree(sbl_tables_dev);
+        for (int i = 0; i < 2 * acc_made; ++i) (void)hipEventDestroy(acc_ev[i]);
+        if (ev0) {
+            (void)hipEventDestroy(ev0);
+            (void)hipEventDestroy(ev1);
+        }
+    }
+};
+
+// sum the elapsed time of the recorded event pairs of accumulate mode into acc_ms (waits for the last one)
+static void acc_harvest(ffgpu_ctx* c) {
+    if (c->acc_n == 0) return;
+    (void)hipEventSynchronize(c->acc_ev[2 * (c->acc_n - 1) + 1]);
+    for (int i = 0; i < c->acc_n; ++i) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->acc_ev[2 * i], c->acc_ev[2 * i + 1]) == hipSuccess) c->acc_ms += ms;
+    }
+    c->acc_calls += (unsigned long long)c->acc_n;
+    c->acc_n = 0;
+}
 
 // brackets the launches of one API call with two events when the context has timing switched on
 struct LaunchTimer {
@@ -181,6 +218,26 @@ struct LaunchTimer {
         } else {
             (void)hipEventRecord(c->ev1, st);
             c->timed = 1;
+        }
+    }
+};
+
+// The scope of one compute call, opened once its arguments have been checked: the context's device is current, the
+// call's launches are timed when timing is on, `st` is its stream and `lc` its launch shape.  A tracked call (one whose
+// arrays take part in the hand-off, handoff.hpp) names its kind and byte ranges: lc.keep_out is then set when the
+// tracker predicts that the next launch on the stream reads this call's output, and what the call reads settles the
+// prediction for the call before it.
+struct CallScope {
+    DeviceGuard dev;
+    LaunchTimer timer;
+    hipStream_t st;
+    LaunchCfg lc;
+    CallScope(ffgpu_ctx* ctx, void* stream)
+        : dev(ctx->device), timer(ctx, (hipStream_t)stream), st((hipStream_t)stream), lc(ctx->lc) {}
+    CallScope(ffgpu_ctx* ctx, void* stream, int kind, const ByteRange* in, int nin, const ByteRange& out) : CallScope(ctx, stream) {
+        if (lc.handoff) {
+            std::lock_guard<std::mutex> lk(ctx->handoff_mu);
+            lc.keep_out = ctx->handoff.launch(stream, kind, in, nin, &out, 1);
         }
     }
 };
@@ -245,16 +302,28 @@ int ffgpu_device_pci_bus_id(int device, char* buf, int len) {
     return FFGPU_OK;
 }
 
+// The library's switches (INTEGRATION.md section 6 lists the same names): an integer outside [lowest, highest] counts as
+// not set.  The on/off switches take any integer, 0 is off.
+struct Switch {
+    const char* name;
+    int LaunchCfg::*field;
+    double LaunchCfg::*real;      // the one switch that is not an integer
+    double def;
+    int lowest, highest;
+};
+static const Switch SWITCHES[] = {
+    {"FFGPU_BLOCKS_PER_CU", &LaunchCfg::blocks_per_cu, nullptr, 0, 0, INT_MAX},     // 0: uncapped
+    {"FFGPU_MM_MFMA", &LaunchCfg::mm_mfma, nullptr, 1, INT_MIN, INT_MAX},
+    {"FFGPU_MM_MFMA_MIN", nullptr, &LaunchCfg::mm_mfma_min, 8e7, 0, 0},
+    {"FFGPU_GF2W_BITSLICED", &LaunchCfg::gf2w_bitsliced, nullptr, 1, INT_MIN, INT_MAX},
+    {"FFGPU_HANDOFF", &LaunchCfg::handoff, nullptr, 1, INT_MIN, INT_MAX},
+    {"FFGPU_CONV_WIDE_PER_CU", &LaunchCfg::conv_wide_per_cu, nullptr, 2, 0, INT_MAX},
+    {"FFGPU_SCAN_GEOM", &LaunchCfg::scan_geom, nullptr, 0, 0, 2},
+    {"FFGPU_SCAN_TILE_THREADS", &LaunchCfg::scan_tile_threads, nullptr, 256, 1, 256},
+};
+
 int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, ffgpu_ctx** out) {
     if (!modulus || !out || nlimbs < 1 || nlimbs > 3 || device < 0) return FFGPU_EINVAL;
-    ffgpu_ctx* c = (ffgpu_ctx*)calloc(1, sizeof(ffgpu_ctx));
-    if (!c) return FFGPU_ENOMEM;
-    c->scratch_mu = new std::mutex();
-    c->handoff_mu = new std::mutex();
-    c->handoff.reset();
-    c->kind = kind;
-    c->device = device;
-    for (int i = 0; i < nlimbs; ++i) c->modulus[i] = modulus[i];
     PolicyBlob pb;
     memset(&pb, 0, sizeof(pb));
     int rc;
@@ -265,14 +334,14 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
     } else {
         rc = FFGPU_EINVAL;
     }
-    if (rc == FFGPU_OK) {
-        c->ops = ops_for(pb.kind);
-        if (!c->ops) rc = FFGPU_ENOTSUP;
-    }
-    if (rc != FFGPU_OK) {
-        free(c);
-        return rc;
-    }
+    if (rc != FFGPU_OK) return rc;
+    if (!ops_for(pb.kind)) return FFGPU_ENOTSUP;
+    ffgpu_ctx* c = new (std::nothrow) ffgpu_ctx();
+    if (!c) return FFGPU_ENOMEM;
+    c->ops = ops_for(pb.kind);
+    c->kind = kind;
+    c->device = device;
+    for (int i = 0; i < nlimbs; ++i) c->modulus[i] = modulus[i];
     memcpy(c->policy, pb.bytes, sizeof(c->policy));
     c->reduction = pb.reduction;
     c->elem_bytes = pb.elem_bytes;
@@ -283,25 +352,16 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         int cus = 256;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
         c->lc.num_cu = cus;
-        const char* e = getenv("FFGPU_BLOCKS_PER_CU");
-        c->lc.blocks_per_cu = e && atoi(e) >= 0 ? atoi(e) : 0;     // 0: uncapped
-        e = getenv("FFGPU_MM_MFMA");
-        c->lc.mm_mfma = e ? (atoi(e) != 0) : 1;
-        e = getenv("FFGPU_MM_MFMA_MIN");
-        c->lc.mm_mfma_min = e ? atof(e) : 8e7;
-        e = getenv("FFGPU_GF2W_BITSLICED");
-        c->lc.gf2w_bitsliced = e ? (atoi(e) != 0) : 1;
-        e = getenv("FFGPU_HANDOFF");
-        c->lc.handoff = e ? (atoi(e) != 0) : 1;
-        e = getenv("FFGPU_CONV_WIDE_PER_CU");
-        c->lc.conv_wide_per_cu = e && atoi(e) >= 0 ? atoi(e) : 2;
-        e = getenv("FFGPU_SCAN_GEOM");
-        c->lc.scan_geom = e && atoi(e) >= 0 && atoi(e) <= 2 ? atoi(e) : 0;
-        e = getenv("FFGPU_SCAN_TILE_THREADS");
-        c->lc.scan_tile_threads = e && atoi(e) >= 1 && atoi(e) <= 256 ? atoi(e) : 256;
-        c->lc.keep_out = 0;
+        for (const Switch& sw : SWITCHES) {
+            const char* e = getenv(sw.name);
+            if (sw.real) {
+                c->lc.*sw.real = e ? atof(e) : sw.def;
+                continue;
+            }
+            const int v = e ? atoi(e) : (int)sw.def;
+            c->lc.*sw.field = v >= sw.lowest && v <= sw.highest ? v : (int)sw.def;
+        }
     }
-    c->gf2w_limbs = 0;
     if (pb.kind == POL_GF2W64 || pb.kind == POL_GF2W128) {
         // sparse moduli (all MPyC defaults) multiply in registers through the integer multiplier
         // (fields.hpp ff_clmul*); dense moduli use the 4-bit window kernel with LDS tables
@@ -320,8 +380,7 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
             ffgpu_gf2w_build_rtable(c->policy, c->gf2w_limbs, c->gf2w_rtable);
         }
     }
-    c->gf8_tab_min = 0;
-    if (pb.kind == POL_GF2P8 && ffgpu_gf8_build_tables(c->policy, c->gf8_tables) == 0) {
+    if (pb.kind == POL_GF2P8 && ffgpu_gf8_build_tables(c->policy, c->gf8_tables)) {
         c->gf8_tab_min = 1 << 18;   // below this the shift-xor kernel has lower latency
     }
     *out = c;
@@ -331,9 +390,8 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
 // device copy of the GF(2^n<=8) log/antilog tables for the fused share-generation kernel (made on first use:
 // contexts can be created and classified on machines without a GPU)
 static const void* gf8_tables_on_device(ffgpu_ctx* ctx) {
-    static std::mutex mu;
     if (!ctx->gf8_tab_min) return nullptr;                 // not a GF(2^n<=8) context with tables
-    std::lock_guard<std::mutex> g(mu);
+    std::lock_guard<std::mutex> g(ctx->gf8_mu);
     if (!ctx->gf8_tables_dev) {
         void* d = nullptr;
         if (hipMalloc(&d, sizeof(ctx->gf8_tables)) != hipSuccess) return nullptr;
@@ -347,33 +405,7 @@ static const void* gf8_tables_on_device(ffgpu_ctx* ctx) {
 }
 
 int ffgpu_ctx_destroy(ffgpu_ctx* ctx) {
-    if (ctx) {
-        DeviceGuard g(ctx->device);
-        for (auto& sc : ctx->scratch)
-            if (sc.ptr) (void)hipFree(sc.ptr);
-        delete ctx->scratch_mu;
-        ctx->scratch_mu = nullptr;
-        delete ctx->handoff_mu;
-        ctx->handoff_mu = nullptr;
-    }
-    if (ctx && ctx->gf8_tables_dev) {
-        DeviceGuard g(ctx->device);
-        (void)hipFree(ctx->gf8_tables_dev);
-    }
-    if (ctx && ctx->sbl_tables_dev) {
-        DeviceGuard g(ctx->device);
-        (void)hipFree(ctx->sbl_tables_dev);
-    }
-    if (ctx && ctx->acc_made) {
-        DeviceGuard g(ctx->device);
-        for (int i = 0; i < 2 * ctx->acc_made; ++i) (void)hipEventDestroy(ctx->acc_ev[i]);
-    }
-    if (ctx && ctx->ev0) {
-        DeviceGuard g(ctx->device);
-        (void)hipEventDestroy(ctx->ev0);
-        (void)hipEventDestroy(ctx->ev1);
-    }
-    free(ctx);
+    delete ctx;
     return FFGPU_OK;
 }
 int ffgpu_ctx_set_timing(ffgpu_ctx* ctx, int enable) {
@@ -524,49 +556,28 @@ int ffgpu_stream_sync(ffgpu_ctx* ctx, void* stream) {
         if (!(cond)) return FFGPU_EINVAL; \
     } while (0)
 
-// The launch shape of one call: the context's, with keep_out set when the hand-off tracker predicts that the next launch on
-// the stream reads this call's outputs (handoff.hpp).  Every streaming call that reads or writes arrays goes through here
-// once, before its launches: what it reads settles the prediction for the call before it.
-static LaunchCfg handoff_lc(ffgpu_ctx* ctx, void* stream, int kind, const ByteRange* in, int nin, const ByteRange* out,
-                            int nout) {
-    LaunchCfg lc = ctx->lc;
-    if (lc.handoff) {
-        std::lock_guard<std::mutex> lk(*ctx->handoff_mu);
-        lc.keep_out = ctx->handoff.launch(stream, kind, in, nin, out, nout);
-    }
-    return lc;
-}
 // bytes of `rows` rows of n elements, `stride` elements apart
 static size_t rows_bytes(const ffgpu_ctx* ctx, size_t rows, size_t stride, size_t n) {
     return ((rows > 0 ? rows - 1 : 0) * stride + n) * (size_t)ctx->elem_bytes;
 }
 
-static LaunchCfg ew2_lc(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n, void* stream) {
-    const size_t nb = rows_bytes(ctx, 1, 0, n);
-    const ByteRange in[2] = {byte_range(a, nb), byte_range(b, nb)}, o = byte_range(out, nb);
-    return handoff_lc(ctx, stream, HK_EW, in, 2, &o, 1);
-}
-// (lc: the call's launch shape when the caller has taken it already -- ffgpu_mul)
-static int do_ew2(ffgpu_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n, void* stream,
-                  const LaunchCfg* lc = nullptr) {
+static int do_ew2(ffgpu_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && b && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    const LaunchCfg lc1 = lc ? *lc : ew2_lc(ctx, a, b, out, n, stream);
-    return launch_status(ctx->ops->ew2(ctx->policy, lc1, op, a, b, out, n, (hipStream_t)stream));
+    const size_t nb = rows_bytes(ctx, 1, 0, n);
+    const ByteRange in[2] = {byte_range(a, nb), byte_range(b, nb)};
+    CallScope cs(ctx, stream, HK_EW, in, 2, byte_range(out, nb));
+    return status_of(ctx->ops->ew2(ctx->policy, cs.lc, op, a, b, out, n, cs.st));
 }
 static int do_ew1(ffgpu_ctx* ctx, int op, const void* a, const uint64_t* s, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
     const size_t nb = rows_bytes(ctx, 1, 0, n);
-    const ByteRange in = byte_range(a, nb), o = byte_range(out, nb);
-    const LaunchCfg lc = handoff_lc(ctx, stream, HK_EW, &in, 1, &o, 1);
-    return launch_status(ctx->ops->ew1(ctx->policy, lc, op, a, s, out, n, (hipStream_t)stream));
+    const ByteRange in = byte_range(a, nb);
+    CallScope cs(ctx, stream, HK_EW, &in, 1, byte_range(out, nb));
+    return status_of(ctx->ops->ew1(ctx->policy, cs.lc, op, a, s, out, n, cs.st));
 }
 
 int ffgpu_reduce(ffgpu_ctx* ctx, const void* raw, void* out, size_t n, void* stream) {
@@ -579,34 +590,25 @@ int ffgpu_sub(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n,
     return do_ew2(ctx, OP_SUB, a, b, out, n, stream);
 }
 int ffgpu_mul(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n, void* stream) {
-    if (!ctx || n == 0 || !a || !b || !out) return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
-    // (one hand-off step for the call, whichever kernels serve it; only the element-wise kernel takes keep_out)
-    const LaunchCfg lc = ew2_lc(ctx, a, b, out, n, stream);
-    if (ctx->gf8_tab_min && n >= (size_t)ctx->gf8_tab_min) {
-        DeviceGuard g(ctx->device);
-        LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, lc, a, b, out, n,
-                                                      (hipStream_t)stream));
-    }
-    if (ctx->gf2w_limbs) {
-        DeviceGuard g(ctx->device);
-        LaunchTimer lt(ctx, (hipStream_t)stream);
-        return launch_status(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, lc,
-                                                       a, b, out, n, (hipStream_t)stream));
-    }
-    if (ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && n >= ((size_t)1 << 21)) {
-        // GF(2^64) with the default modulus: bit-sliced product for all whole pairs of elements, the element-wise kernel for
-        // the odd last one -- both launches under ONE timer scope (ffgpu_last_kernel_ms reports the call, not its tail)
-        DeviceGuard g(ctx->device);
-        LaunchTimer lt(ctx, (hipStream_t)stream);
-        const size_t done = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, lc, a, b, out, n, (hipStream_t)stream);
-        if (done && hipGetLastError() != hipSuccess) return FFGPU_EHIP;
-        if (done == n) return FFGPU_OK;
-        if (done)
-            return launch_status(ctx->ops->ew2(ctx->policy, lc, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
-                                               (char*)out + 8 * done, n - done, (hipStream_t)stream));
-    }
-    return do_ew2(ctx, OP_MUL, a, b, out, n, stream, &lc);
+    const bool tables = ctx && ctx->gf8_tab_min && n >= (size_t)ctx->gf8_tab_min;
+    const bool bitsliced = ctx && ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && n >= ((size_t)1 << 21);
+    if (!ctx || n == 0 || !a || !b || !out || !(tables || ctx->gf2w_limbs || bitsliced)) return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
+    // one scope and one hand-off step for the call, whichever kernels serve it (only the element-wise kernel takes
+    // keep_out; ffgpu_last_kernel_ms reports the call, not its tail)
+    const size_t nb = rows_bytes(ctx, 1, 0, n);
+    const ByteRange in[2] = {byte_range(a, nb), byte_range(b, nb)};
+    CallScope cs(ctx, stream, HK_EW, in, 2, byte_range(out, nb));
+    if (tables) return status_of(ffgpu_launch_gf8_mul_tab(ctx->gf8_tables, cs.lc, a, b, out, n, cs.st));
+    if (ctx->gf2w_limbs)
+        return status_of(ffgpu_launch_gf2w_mul_win(ctx->policy, ctx->gf2w_limbs, ctx->gf2w_rtable, cs.lc, a, b, out, n, cs.st));
+    // GF(2^64) with the default modulus: bit-sliced product for all whole pairs of elements, the element-wise kernel for
+    // the odd last one (and for everything when the launcher declines: another modulus, unaligned arrays)
+    size_t done = 0;
+    const LaunchStatus ls = ffgpu_launch_gf2w64_mul_bitsliced(ctx->policy, cs.lc, a, b, out, n, cs.st, &done);
+    if (ls.code != L_DECLINED && !ls.ok()) return status_of(ls);
+    if (done == n) return FFGPU_OK;
+    return status_of(ctx->ops->ew2(ctx->policy, cs.lc, OP_MUL, (const char*)a + 8 * done, (const char*)b + 8 * done,
+                                   (char*)out + 8 * done, n - done, cs.st));
 }
 int ffgpu_neg(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stream) {
     return do_ew1(ctx, OP_NEG, a, nullptr, out, n, stream);
@@ -628,12 +630,10 @@ int ffgpu_muladd(ffgpu_ctx* ctx, const void* a, const void* b, const void* c, vo
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && b && c && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
     const size_t nb = rows_bytes(ctx, 1, 0, n);
-    const ByteRange in[3] = {byte_range(a, nb), byte_range(b, nb), byte_range(c, nb)}, o = byte_range(out, nb);
-    const LaunchCfg lc = handoff_lc(ctx, stream, HK_EW, in, 3, &o, 1);
-    return launch_status(ctx->ops->muladd(ctx->policy, lc, a, b, c, out, n, (hipStream_t)stream));
+    const ByteRange in[3] = {byte_range(a, nb), byte_range(b, nb), byte_range(c, nb)};
+    CallScope cs(ctx, stream, HK_EW, in, 3, byte_range(out, nb));
+    return status_of(ctx->ops->muladd(ctx->policy, cs.lc, a, b, c, out, n, cs.st));
 }
 
 static int make_exp(const uint64_t* e, int limbs, ExpArgs* ex) {
@@ -716,16 +716,15 @@ int ffgpu_pow(ffgpu_ctx* ctx, const void* a, const uint64_t* host_exp, int exp_l
     exp_try_cube_form(&ex);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    CallScope cs(ctx, stream);
     if (ex.nbits == 0) {
         // a^0 = 1 (also for a = 0, as pow(0, 0, p) = 1): 0*a + 1
         uint64_t zero[3] = {0, 0, 0}, one[3] = {1, 0, 0};
-        rc = launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, OP_MUL, a, zero, out, n, (hipStream_t)stream));
+        rc = status_of(ctx->ops->ew1(ctx->policy, cs.lc, OP_MUL, a, zero, out, n, cs.st));
         if (rc != FFGPU_OK) return rc;
-        return launch_status(ctx->ops->ew1(ctx->policy, ctx->lc, OP_ADD, out, one, out, n, (hipStream_t)stream));
+        return status_of(ctx->ops->ew1(ctx->policy, cs.lc, OP_ADD, out, one, out, n, cs.st));
     }
-    return launch_status(ctx->ops->pow(ctx->policy, ctx->lc, a, &ex, out, n, (hipStream_t)stream));
+    return status_of(ctx->ops->pow(ctx->policy, cs.lc, a, &ex, out, n, cs.st));
 }
 
 // three-limb primes: exponents derived from p by limb arithmetic
@@ -742,7 +741,8 @@ static void shr1_3(uint64_t x[3]) {
 }
 static bool three_limb_prime(const ffgpu_ctx* ctx) { return ctx->kind == FFGPU_PRIME && ctx->modulus[2] != 0; }
 
-// exponent q - 2 for x^-1 = x^(q-2); false for the two-element fields, where x^-1 = x
+// exponent q - 2 (order of the multiplicative group minus one) for x^-1 = x^(q-2); false for the two-element fields
+// GF(2) and GF(2^1), where q - 2 = 0 and x^-1 = x: exponent 1
 static bool inverse_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
     if (three_limb_prime(ctx)) {
         uint64_t e3[3];
@@ -756,7 +756,7 @@ static bool inverse_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
     } else {
         int deg = ctx->modulus[2] ? 128 : (ctx->modulus[1] ? 64 + (63 - __builtin_clzll(ctx->modulus[1]))
                                                            : 63 - __builtin_clzll(ctx->modulus[0]));
-        q = deg == 128 ? (ff_u128)0 : ((ff_u128)1 << deg);
+        q = deg == 128 ? (ff_u128)0 : ((ff_u128)1 << deg);   // 2^128 wraps to 0; q-2 below is still right
     }
     ff_u128 e = q - 2;
     uint64_t el[2] = {ff_lo(e), ff_hi(e)};
@@ -792,9 +792,8 @@ int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stre
         make_exp(l1, 2, &eleg);
         make_exp(l2, 2, &elad);
     }
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->sqrt_cl(ctx->policy, ctx->lc, a, &eleg, &elad, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->sqrt_cl(ctx->policy, cs.lc, a, &eleg, &elad, out, n, cs.st));
 }
 
 int ffgpu_gauss(ffgpu_ctx* ctx, void* a, int n, int ncols, size_t batch, int mode, void* det_out,
@@ -804,52 +803,22 @@ int ffgpu_gauss(ffgpu_ctx* ctx, void* a, int n, int ncols, size_t batch, int mod
     ARGCHK(dev_singular && (mode == 0 || det_out));
     if (n == 0) return FFGPU_OK;
     ARGCHK(a);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    CallScope cs(ctx, stream);
     ExpArgs ex;
     inverse_exponent(ctx, &ex);
-    if (hipMemsetAsync(dev_singular, 0, batch * sizeof(int), (hipStream_t)stream) != hipSuccess) return FFGPU_EHIP;
-    return launch_status(ctx->ops->gauss(ctx->policy, ctx->lc, a, n, ncols, batch, mode, &ex,
-                                         mode ? det_out : nullptr, (int*)dev_singular, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(dev_singular, 0, batch * sizeof(int), cs.st));
+    return status_of(ctx->ops->gauss(ctx->policy, cs.lc, a, n, ncols, batch, mode, &ex,
+                                     mode ? det_out : nullptr, (int*)dev_singular, cs.st));
 }
 
 int ffgpu_inv(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* dev_zero_flag, void* stream) {
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && out);
-    if (three_limb_prime(ctx)) {
-        ExpArgs ex3;
-        inverse_exponent(ctx, &ex3);
-        DeviceGuard g3(ctx->device);
-        LaunchTimer lt3(ctx, (hipStream_t)stream);
-        return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &ex3, out, n, (int*)dev_zero_flag,
-                                           (hipStream_t)stream));
-    }
-    // exponent q - 2 (order of the multiplicative group minus one)
-    ff_u128 q;
-    if (ctx->kind == FFGPU_PRIME) {
-        q = ff_make128(ctx->modulus[1], ctx->modulus[0]);
-    } else {
-        int deg = ctx->modulus[2] ? 128 : (ctx->modulus[1] ? 64 + (63 - __builtin_clzll(ctx->modulus[1]))
-                                                           : 63 - __builtin_clzll(ctx->modulus[0]));
-        q = deg == 128 ? (ff_u128)0 : ((ff_u128)1 << deg);   // 2^128 wraps to 0; q-2 below is still right
-    }
-    ff_u128 e = q - 2;
-    uint64_t el[2] = {ff_lo(e), ff_hi(e)};
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    if (ctx->kind == FFGPU_PRIME && q == 2) {   // GF(2): 1^-1 = 1
-        ExpArgs one;
-        one.e[0] = 1; one.e[1] = one.e[2] = 0; one.nbits = 1; one.post = 0;
-        return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &one, out, n, (int*)dev_zero_flag,
-                                           (hipStream_t)stream));
-    }
     ExpArgs ex;
-    int rc = make_exp(el, 2, &ex);
-    if (rc != FFGPU_OK) return rc;
-    if (ex.nbits == 0) { ex.e[0] = 1; ex.nbits = 1; }        // GF(2^1): q - 2 = 0 -> x^-1 = x
-    return launch_status(ctx->ops->inv(ctx->policy, ctx->lc, a, &ex, out, n, (int*)dev_zero_flag,
-                                       (hipStream_t)stream));
+    inverse_exponent(ctx, &ex);
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->inv(ctx->policy, cs.lc, a, &ex, out, n, (int*)dev_zero_flag, cs.st));
 }
 
 int ffgpu_beaver_combine(ffgpu_ctx* ctx, const void* z, const void* x, const void* y, const void* d, const void* e,
@@ -857,21 +826,19 @@ int ffgpu_beaver_combine(ffgpu_ctx* ctx, const void* z, const void* x, const voi
     ARGCHK(ctx);
     if (n == 0) return FFGPU_OK;
     ARGCHK(z && x && y && d && e && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->beaver(ctx->policy, ctx->lc, z, x, y, d, e, out, add_de ? 1 : 0, n,
-                                          (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->beaver(ctx->policy, cs.lc, z, x, y, d, e, out, add_de ? 1 : 0, n,
+                                      cs.st));
 }
 
-static LaunchCfg split_lc(ffgpu_ctx* ctx, const void* a, const void* b, const void* coeffs, int t, size_t coeff_stride, int m,
-                          void* shares, size_t share_stride, size_t n, void* stream) {
-    ByteRange in[3];
+// what a share-generation call reads: a, then b and t rows of coefficients where present; returns how many ranges
+static int split_inputs(const ffgpu_ctx* ctx, const void* a, const void* b, const void* coeffs, int t, size_t coeff_stride, size_t n,
+                        ByteRange in[3]) {
     int nin = 0;
     in[nin++] = byte_range(a, rows_bytes(ctx, 1, 0, n));
     if (b) in[nin++] = byte_range(b, rows_bytes(ctx, 1, 0, n));
     if (coeffs) in[nin++] = byte_range(coeffs, rows_bytes(ctx, (size_t)t, coeff_stride, n));
-    const ByteRange o = byte_range(shares, rows_bytes(ctx, (size_t)m, share_stride, n));
-    return handoff_lc(ctx, stream, HK_SPLIT, in, nin, &o, 1);
+    return nin;
 }
 
 static int do_split(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, const void* coeffs,
@@ -882,13 +849,12 @@ static int do_split(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, co
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && shares && (!fused || b) && (t == 0 || coeffs));
     ARGCHK((m == 1 || share_stride >= n) && (t <= 1 || coeff_stride >= n));
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    const LaunchCfg lc = split_lc(ctx, a, fused ? b : nullptr, t > 0 ? coeffs : nullptr, t, coeff_stride, m, shares,
-                                  share_stride, n, stream);
-    return launch_status(ctx->ops->split(ctx->policy, lc, a, fused ? b : nullptr, coeffs,
-                                         coeff_stride, t, m, shares, share_stride, n, (hipStream_t)stream,
-                                         nullptr));
+    ByteRange in[3];
+    const int nin = split_inputs(ctx, a, fused ? b : nullptr, t > 0 ? coeffs : nullptr, t, coeff_stride, n, in);
+    CallScope cs(ctx, stream, HK_SPLIT, in, nin, byte_range(shares, rows_bytes(ctx, (size_t)m, share_stride, n)));
+    return status_of(ctx->ops->split(ctx->policy, cs.lc, a, fused ? b : nullptr, coeffs,
+                                     coeff_stride, t, m, shares, share_stride, n, cs.st,
+                                     nullptr));
 }
 
 static int make_rng(const ffgpu_ctx* ctx, const uint8_t* key32, uint64_t nonce, int rounds, RngArgs* ra) {
@@ -905,6 +871,22 @@ static int make_rng(const ffgpu_ctx* ctx, const uint8_t* key32, uint64_t nonce, 
     return FFGPU_OK;
 }
 
+// the generator of a call whose key and nonce live on the device (ffgpu_rng_state_init); sampler: fill in the constant of
+// the keystream sampler (the S-box layer draws bytes and leaves it zero)
+static RngArgs make_dev_rng(const ffgpu_ctx* ctx, void* dev_state, uint64_t nonce_off, int defer_advance, bool sampler) {
+    RngArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.rk.rounds = 20;
+    if (sampler) {
+        ra.r0 = ctx->rng_r[0];
+        ra.r1 = ctx->rng_r[1];
+    }
+    ra.dev_key = (const RngKey*)dev_state;
+    ra.nonce_off = (uint32_t)nonce_off;
+    ra.no_advance = defer_advance ? 1 : 0;
+    return ra;
+}
+
 static int do_split_rng(ffgpu_ctx* ctx, const void* a, const void* b, bool fused, const uint8_t* key32,
                         uint64_t nonce, int rounds, int t, int m, void* shares, size_t share_stride, size_t n,
                         void* stream) {
@@ -916,12 +898,12 @@ static int do_split_rng(ffgpu_ctx* ctx, const void* a, const void* b, bool fused
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && shares && (!fused || b));
     ARGCHK(m == 1 || share_stride >= n);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    ByteRange in[3];
+    const int nin = split_inputs(ctx, a, fused ? b : nullptr, nullptr, 0, 0, n, in);
+    CallScope cs(ctx, stream, HK_SPLIT, in, nin, byte_range(shares, rows_bytes(ctx, (size_t)m, share_stride, n)));
     if (fused && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    const LaunchCfg lc = split_lc(ctx, a, fused ? b : nullptr, nullptr, 0, 0, m, shares, share_stride, n, stream);
-    return launch_status(ctx->ops->split(ctx->policy, lc, a, fused ? b : nullptr, nullptr, 0, t, m,
-                                         shares, share_stride, n, (hipStream_t)stream, t > 0 ? &ra : nullptr));
+    return status_of(ctx->ops->split(ctx->policy, cs.lc, a, fused ? b : nullptr, nullptr, 0, t, m,
+                                     shares, share_stride, n, cs.st, t > 0 ? &ra : nullptr));
 }
 int ffgpu_ctx_scalar_limbs(const ffgpu_ctx* ctx) { return (ctx && ctx->elem_bytes == 24) ? 3 : 2; }
 
@@ -933,10 +915,9 @@ int ffgpu_rng_state_init(ffgpu_ctx* ctx, void* dev_state, const uint8_t* host_ke
     RngArgs ra;
     int rc = make_rng(ctx, host_key32, nonce, rounds, &ra);
     if (rc != FFGPU_OK) return rc;
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    HIPCHK(hipMemcpyAsync(dev_state, &ra.rk, sizeof(RngKey), hipMemcpyHostToDevice, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));     // the source is on this stack frame
+    CallScope cs(ctx, stream);
+    HIPCHK(hipMemcpyAsync(dev_state, &ra.rk, sizeof(RngKey), hipMemcpyHostToDevice, cs.st));
+    HIPCHK(hipStreamSynchronize(cs.st));     // the source is on this stack frame
     return FFGPU_OK;
 }
 
@@ -946,20 +927,14 @@ int ffgpu_split_rng_state(ffgpu_ctx* ctx, const void* secrets, const void* mul_b
     ARGCHK(m >= 1 && t >= 0 && t < m);
     if (n == 0) return FFGPU_OK;
     ARGCHK(secrets && shares && (m == 1 || share_stride >= n));
-    RngArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.rk.rounds = 20;
-    ra.r0 = ctx->rng_r[0];
-    ra.r1 = ctx->rng_r[1];
-    ra.dev_key = (const RngKey*)dev_state;
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    RngArgs ra = make_dev_rng(ctx, dev_state, 0, 0, true);
+    ByteRange in[3];
+    const int nin = split_inputs(ctx, secrets, mul_by, nullptr, 0, 0, n, in);
+    CallScope cs(ctx, stream, HK_SPLIT, in, nin, byte_range(shares, rows_bytes(ctx, (size_t)m, share_stride, n)));
     if (mul_by && t > 0) ra.aux = gf8_tables_on_device(ctx);
-    const LaunchCfg lc = split_lc(ctx, secrets, mul_by, nullptr, 0, 0, m, shares, share_stride, n, stream);
-    int rc = ctx->ops->split(ctx->policy, lc, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n,
-                             (hipStream_t)stream, t > 0 ? &ra : nullptr);
-    if (rc) return launch_status(rc);
-    return FFGPU_OK;       // the kernel's last workgroup advanced the nonce (rng_state_release)
+    // (the kernel's last workgroup advances the nonce, or rng_advance after it: launch.hpp, plan_rng)
+    return status_of(ctx->ops->split(ctx->policy, cs.lc, secrets, mul_by, nullptr, 0, t, m, shares, share_stride, n, cs.st,
+                                     t > 0 ? &ra : nullptr));
 }
 
 int ffgpu_gate_rng(ffgpu_ctx* ctx, const void* const* host_rows_a, const uint64_t* host_lambda_a, int ka,
@@ -975,7 +950,7 @@ int ffgpu_rng_state_advance(ffgpu_ctx* ctx, void* dev_state, uint32_t by, void* 
     if (by == 0) return FFGPU_OK;
     DeviceGuard g(ctx->device);
     hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, (hipStream_t)stream, (RngKey*)dev_state, by);
-    return hipGetLastError() == hipSuccess ? FFGPU_OK : FFGPU_EHIP;
+    return status_of(launched());
 }
 
 int ffgpu_gate_rng_batch(ffgpu_ctx* ctx, const void* const* host_rows_a, const uint64_t* host_lambda_a, int ka,
@@ -994,13 +969,7 @@ int ffgpu_gate_rng_batch(ffgpu_ctx* ctx, const void* const* host_rows_a, const u
     ARGCHK(host_rows_a && host_lambda_a && (kb == 0 || (host_rows_b && host_lambda_b)));
     RngArgs ra;
     if (dev_state) {
-        memset(&ra, 0, sizeof(ra));
-        ra.rk.rounds = 20;
-        ra.r0 = ctx->rng_r[0];
-        ra.r1 = ctx->rng_r[1];
-        ra.dev_key = (const RngKey*)dev_state;
-        ra.nonce_off = (uint32_t)nonce;
-        ra.no_advance = defer_advance ? 1 : 0;
+        ra = make_dev_rng(ctx, dev_state, nonce, defer_advance, true);
     } else {
         int rc = make_rng(ctx, host_key32, nonce, rounds, &ra);
         if (rc != FFGPU_OK) return rc;
@@ -1009,19 +978,16 @@ int ffgpu_gate_rng_batch(ffgpu_ctx* ctx, const void* const* host_rows_a, const u
     ARGCHK(shares && (m == 1 || share_stride >= n));
     for (int j = 0; j < ka; ++j) ARGCHK(host_rows_a[j]);
     for (int j = 0; j < kb; ++j) ARGCHK(host_rows_b[j]);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    ra.aux = gf8_tables_on_device(ctx);
     ByteRange in[14];
     int nin = 0;
     for (int j = 0; j < ka; ++j) in[nin++] = byte_range(host_rows_a[j], rows_bytes(ctx, (size_t)nbatch, batch_stride_a, n));
     for (int j = 0; j < kb; ++j) in[nin++] = byte_range(host_rows_b[j], rows_bytes(ctx, (size_t)nbatch, batch_stride_b, n));
     const size_t oelems = ((size_t)nbatch - 1) * batch_stride_out + ((size_t)m - 1) * share_stride + n;
-    const ByteRange o = byte_range(shares, oelems * (size_t)ctx->elem_bytes);
-    const LaunchCfg lc = handoff_lc(ctx, stream, HK_SPLIT, in, nin, &o, 1);
-    return launch_status(ctx->ops->gate(ctx->policy, lc, host_rows_a, host_lambda_a, ka, host_rows_b,
-                                        host_lambda_b, kb, t, m, shares, share_stride, n, (hipStream_t)stream, &ra,
-                                        nbatch, batch_stride_a, batch_stride_b, batch_stride_out));
+    CallScope cs(ctx, stream, HK_SPLIT, in, nin, byte_range(shares, oelems * (size_t)ctx->elem_bytes));
+    ra.aux = gf8_tables_on_device(ctx);
+    return status_of(ctx->ops->gate(ctx->policy, cs.lc, host_rows_a, host_lambda_a, ka, host_rows_b,
+                                    host_lambda_b, kb, t, m, shares, share_stride, n, cs.st, &ra,
+                                    nbatch, batch_stride_a, batch_stride_b, batch_stride_out));
 }
 
 int ffgpu_split(ffgpu_ctx* ctx, const void* secrets, const void* coeffs, size_t coeff_stride, int t, int m,
@@ -1042,10 +1008,9 @@ int ffgpu_rng_coeffs(ffgpu_ctx* ctx, const uint8_t* host_key32, uint64_t nonce, 
     if (rc != FFGPU_OK) return rc;
     if (n == 0) return FFGPU_OK;
     ARGCHK(coeffs && (t == 1 || coeff_stride >= n));
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->rng_coeffs(ctx->policy, ctx->lc, coeffs, coeff_stride, t, n,
-                                              (hipStream_t)stream, &ra));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->rng_coeffs(ctx->policy, cs.lc, coeffs, coeff_stride, t, n,
+                                          cs.st, &ra));
 }
 int ffgpu_split_rng(ffgpu_ctx* ctx, const void* secrets, const uint8_t* host_key32, uint64_t nonce, int rounds,
                     int t, int m, void* shares, size_t share_stride, size_t n, void* stream) {
@@ -1064,27 +1029,23 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
     if (n == 0) return FFGPU_OK;
     ARGCHK(host_rows && host_lambda && out && (w == 1 || out_stride >= n));
     for (int j = 0; j < k; ++j) ARGCHK(host_rows[j]);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
     ByteRange in[MAXK_ANY];
     const int nin = k < (int)MAXK_ANY ? k : (int)MAXK_ANY;     // (more rows than that: the launcher refuses them)
     for (int j = 0; j < nin; ++j) in[j] = byte_range(host_rows[j], rows_bytes(ctx, 1, 0, n));
-    const ByteRange o = byte_range(out, rows_bytes(ctx, (size_t)w, out_stride, n));
-    const LaunchCfg lc = handoff_lc(ctx, stream, HK_REC, in, nin, &o, 1);
+    CallScope cs(ctx, stream, HK_REC, in, nin, byte_range(out, rows_bytes(ctx, (size_t)w, out_stride, n)));
     // GF(2^n), 9 <= n <= 128 with a sparse modulus: shared nibble tables of the (uniform) Lagrange
     // coefficients in LDS instead of one full field multiplication per row and element
     if ((ctx->policy_kind == POL_GF2W64 || ctx->policy_kind == POL_GF2W128) && !ctx->gf2w_limbs && k <= 9 &&
         n >= 65536) {
         const int limbs = ctx->policy_kind == POL_GF2W128 ? 2 : 1;
-        int rc = 0;
-        for (int r = 0; r < w && rc == 0; ++r)
-            rc = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, lc, host_rows, host_lambda + 2 * (size_t)r * k,
-                                             k, (char*)out + (size_t)r * out_stride * ctx->elem_bytes, n,
-                                             (hipStream_t)stream);
-        if (rc != 2) return launch_status(rc);
+        LaunchStatus ls;
+        for (int r = 0; r < w && ls.ok(); ++r)
+            ls = ffgpu_launch_gf2w_recombine(ctx->policy, limbs, cs.lc, host_rows, host_lambda + 2 * (size_t)r * k,
+                                             k, (char*)out + (size_t)r * out_stride * ctx->elem_bytes, n, cs.st);
+        if (ls.code != L_DECLINED) return status_of(ls);      // declined: the generic kernel below
     }
-    return launch_status(ctx->ops->recombine(ctx->policy, lc, host_rows, host_lambda, k, w, out,
-                                             out_stride, n, (hipStream_t)stream));
+    return status_of(ctx->ops->recombine(ctx->policy, cs.lc, host_rows, host_lambda, k, w, out,
+                                         out_stride, n, cs.st));
 }
 
 int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
@@ -1093,54 +1054,22 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
     if (M == 0 || N == 0) return FFGPU_OK;
     ARGCHK(C && ldc >= N && M < (1u << 30) && N < (1u << 30) && K < (1u << 30));
     ARGCHK(K == 0 || (A && B && lda >= K && ldb >= N));
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    CallScope cs(ctx, stream);
+    // scratch: int8 digit planes for the matrix-core product plus 64 MiB of split-K slabs (up to 8 GiB), else 64 MiB of
+    // split-K partial sums.  (Asked for in whole 8 / 16 planes per operand: more than the 4 and 12 digits of 4- and
+    // 12-byte elements need, and the split-K plans of the launcher see the size.)
+    size_t want = 0;
+    if (ctx->kind == FFGPU_PRIME) want = mfma_plane_bytes(cs.lc, ctx->elem_bytes <= 8 ? 8 : 16, M, K, N);
+    if (want) want += (size_t)64 << 20;
+    if (want > ((size_t)8 << 30)) want = 0;
+    if (!want && K >= 64 && ((M + 31) / 32) * ((N + 31) / 32) < 2048) want = (size_t)64 << 20;
     void* ws = nullptr;
     size_t ws_bytes = 0;
-    {
-        // scratch: int8 limb planes for the matrix-core product (10 x (M + N) x K bytes, up to 8 GiB), else 64 MiB of
-        // split-K partial sums
-        size_t want = 0;
-        const size_t Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
-        if (ctx->kind == FFGPU_PRIME && M > 8 && N > 8 && K >= 64 && ctx->lc.mm_mfma && (double)M * N * K >= ctx->lc.mm_mfma_min) {
-            want = (size_t)(ctx->elem_bytes <= 8 ? 8 : 16) * (Mp + Np) * Kp + ((size_t)64 << 20);   // digit planes per operand + split-K slabs
-            if (want > ((size_t)8 << 30)) want = 0;
-        }
-        if (!want && K >= 64 && ((M + 31) / 32) * ((N + 31) / 32) < 2048) want = (size_t)64 << 20;
-        if (want) {
-            std::lock_guard<std::mutex> lk(*ctx->scratch_mu);
-            ffgpu_ctx::Scratch* slot = nullptr;
-            for (auto& sc : ctx->scratch)
-                if (sc.used && sc.stream == (hipStream_t)stream) slot = &sc;
-            if (!slot) {
-                for (auto& sc : ctx->scratch)
-                    if (!sc.used && !slot) slot = &sc;
-                if (!slot) {                                     // more streams than slots: recycle the smallest buffer
-                    slot = &ctx->scratch[0];
-                    for (auto& sc : ctx->scratch)
-                        if (sc.bytes < slot->bytes) slot = &sc;
-                    HIPCHK(hipStreamSynchronize(slot->stream));
-                    if (slot->ptr) (void)hipFree(slot->ptr);
-                    slot->ptr = nullptr;
-                    slot->bytes = 0;
-                }
-                slot->used = 1;
-                slot->stream = (hipStream_t)stream;
-            }
-            if (slot->bytes < want) {
-                HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // queued work may still read the old buffer
-                if (slot->ptr) (void)hipFree(slot->ptr);
-                slot->ptr = nullptr;
-                slot->bytes = 0;
-                if (hipMalloc(&slot->ptr, want) == hipSuccess) slot->bytes = want;
-                else (void)hipGetLastError();                     // no scratch: the VALU kernels need none
-            }
-            ws = slot->ptr;
-            ws_bytes = slot->bytes;
-        }
+    if (want) {
+        const int rc = ctx->scratch.get(cs.st, want, &ws, &ws_bytes);
+        if (rc != FFGPU_OK) return rc;
     }
-    return launch_status(ctx->ops->matmul(ctx->policy, ctx->lc, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws,
-                                          ws_bytes, (hipStream_t)stream));
+    return status_of(ctx->ops->matmul(ctx->policy, cs.lc, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws, ws_bytes, cs.st));
 }
 
 int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size_t nv, void* out, void* stream) {
@@ -1153,9 +1082,8 @@ int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, (na + nv - 1) * eb);
     ARGCHK(!overlaps(o, byte_range(a, na * eb)) && !overlaps(o, byte_range(v, nv * eb)));   // tiles read while others write
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->convolve(ctx->policy, ctx->lc, a, na, v, nv, out, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->convolve(ctx->policy, cs.lc, a, na, v, nv, out, cs.st));
 }
 
 // the plan of a scan call, whichever alignment its pointers turn out to have: the larger workspace of the two
@@ -1192,14 +1120,10 @@ static int do_scan(ffgpu_ctx* ctx, bool reduce, int op, const void* a, void* out
         const ByteRange w = byte_range(workspace, workspace_bytes);
         ARGCHK(!overlaps(w, in) && !overlaps(w, o));
     }
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    const int rc = reduce ? ctx->ops->axis_reduce(ctx->policy, ctx->lc, op, a, out, outer, k, inner, workspace, workspace_bytes,
-                                                  (hipStream_t)stream)
-                          : ctx->ops->scan(ctx->policy, ctx->lc, op, a, out, outer, k, inner, with_initial, workspace,
-                                           workspace_bytes, (hipStream_t)stream);
-    if (rc == 4 || rc == 5) return FFGPU_EINVAL;
-    return launch_status(rc);
+    CallScope cs(ctx, stream);
+    return status_of(reduce ? ctx->ops->axis_reduce(ctx->policy, cs.lc, op, a, out, outer, k, inner, workspace, workspace_bytes, cs.st)
+                            : ctx->ops->scan(ctx->policy, cs.lc, op, a, out, outer, k, inner, with_initial, workspace,
+                                             workspace_bytes, cs.st));
 }
 int ffgpu_scan(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t outer, size_t k, size_t inner, int with_initial,
                void* workspace, size_t workspace_bytes, void* stream) {
@@ -1216,25 +1140,24 @@ int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64
     if (r > 16 || g > 16) return FFGPU_ENOTSUP;
     if (ngroups == 0) return FFGPU_OK;
     ARGCHK(in && out);
-    DeviceGuard gd(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    CallScope cs(ctx, stream);
     if (ctx->kind == FFGPU_BINARY && ctx->elem_bytes == 1 && g == 8 && (((uintptr_t)in) & 7u) == 0) {
         // groups of 8 bytes: packed-byte kernel (misc.hip)
         if (r == 8 && (((uintptr_t)out) & 7u) == 0)
-            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, host_matrix, host_bias, 0, in, out,
-                                                         ngroups, (hipStream_t)stream));
+            return status_of(ffgpu_launch_gf8_group8(ctx->policy, cs.lc, host_matrix, host_bias, 0, in, out,
+                                                     ngroups, cs.st));
         bool pow2 = (r == 1);
         for (int c = 0; pow2 && c < 8; ++c) pow2 = (host_matrix[2 * c] == (1ull << c));
         if (pow2 && (!host_bias || (host_bias[0] & 0xffu) == 0)) {   // np_from_bits: identity, then fold by 2^r
             uint64_t eye[128];
             memset(eye, 0, sizeof(eye));
             for (int c = 0; c < 8; ++c) eye[2 * (c * 8 + c)] = 1;
-            return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, eye, nullptr, 1, in, out, ngroups,
-                                                         (hipStream_t)stream));
+            return status_of(ffgpu_launch_gf8_group8(ctx->policy, cs.lc, eye, nullptr, 1, in, out, ngroups,
+                                                     cs.st));
         }
     }
-    return launch_status(ctx->ops->group_matvec(ctx->policy, ctx->lc, host_matrix, host_bias, r, g, in, out,
-                                                ngroups, (hipStream_t)stream));
+    return status_of(ctx->ops->group_matvec(ctx->policy, cs.lc, host_matrix, host_bias, r, g, in, out,
+                                            ngroups, cs.st));
 }
 
 int ffgpu_gf256_bit_affine(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int from_bits,
@@ -1244,22 +1167,20 @@ int ffgpu_gf256_bit_affine(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
     if (n == 0) return FFGPU_OK;
     ARGCHK(in && out);
     if ((((uintptr_t)in) & 7u) || (!from_bits && (((uintptr_t)out) & 7u))) return FFGPU_EINVAL;
-    DeviceGuard gd(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_group8(ctx->policy, ctx->lc, host_matrix, host_bias, from_bits ? 1 : 0, in,
-                                                 out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_gf8_group8(ctx->policy, cs.lc, host_matrix, host_bias, from_bits ? 1 : 0, in,
+                                             out, n, cs.st));
 }
 
 static int do_dot(ffgpu_ctx* ctx, const void* a, const void* b, void* out, void* workspace, size_t n, void* stream) {
     ARGCHK(ctx && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
+    CallScope cs(ctx, stream);
     if (n == 0) {   // empty sum = 0
-        HIPCHK(hipMemsetAsync(out, 0, (size_t)ctx->elem_bytes, (hipStream_t)stream));
+        HIPCHK(hipMemsetAsync(out, 0, (size_t)ctx->elem_bytes, cs.st));
         return FFGPU_OK;
     }
     ARGCHK(a && workspace);
-    return launch_status(ctx->ops->dot(ctx->policy, ctx->lc, a, b, out, workspace, n, (hipStream_t)stream));
+    return status_of(ctx->ops->dot(ctx->policy, cs.lc, a, b, out, workspace, n, cs.st));
 }
 int ffgpu_dot(ffgpu_ctx* ctx, const void* a, const void* b, void* out, void* workspace, size_t n, void* stream) {
     ARGCHK(n == 0 || b);
@@ -1278,10 +1199,9 @@ int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, 
     for (int s = 0; s < ks; ++s) ARGCHK(host_streams[s]);
     // limb radix constant for the wide reduction: 2^(8*elem_bytes) mod p (prime policies)
     uint64_t r2[2] = {ctx->rng_r[0], ctx->rng_r[1]};
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->prss(ctx->policy, ctx->lc, host_streams, ks, d, l, mask_bits, host_weights,
-                                        r2, accumulate, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->prss(ctx->policy, cs.lc, host_streams, ks, d, l, mask_bits, host_weights,
+                                    r2, accumulate, out, n, cs.st));
 }
 
 int ffgpu_prss_chacha(ffgpu_ctx* ctx, const uint8_t* host_keys, int ks, int d, int l, int mask_bits, int rounds,
@@ -1292,10 +1212,9 @@ int ffgpu_prss_chacha(ffgpu_ctx* ctx, const uint8_t* host_keys, int ks, int d, i
     if (n == 0) return FFGPU_OK;
     ARGCHK(host_keys && host_weights && out);
     uint64_t r2[2] = {ctx->rng_r[0], ctx->rng_r[1]};
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ctx->ops->prss_chacha(ctx->policy, ctx->lc, host_keys, ks, d, l, mask_bits, rounds, host_weights,
-                                               r2, accumulate, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->prss_chacha(ctx->policy, cs.lc, host_keys, ks, d, l, mask_bits, rounds, host_weights,
+                                           r2, accumulate, out, n, cs.st));
 }
 int ffgpu_prss_chacha_layout(int l, int* tb, int* dpt) {
     ARGCHK(l >= 1 && l <= 64 && tb && dpt);
@@ -1308,9 +1227,8 @@ int ffgpu_gf256_to_bits(ffgpu_ctx* ctx, const void* in, const void* addend, void
     if (ctx->kind != FFGPU_BINARY || ctx->elem_bytes != 1) return FFGPU_ENOTSUP;
     if (n == 0) return FFGPU_OK;
     ARGCHK(in && out);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_to_bits(ctx->lc, in, addend, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_gf8_to_bits(cs.lc, in, addend, out, n, cs.st));
 }
 
 int ffgpu_gf256_mask_open(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_coef, int nrows,
@@ -1323,10 +1241,9 @@ int ffgpu_gf256_mask_open(ffgpu_ctx* ctx, const void* const* host_rows, const ui
     ARGCHK(out && (nrows == 0 || (host_rows && host_coef)) && (np == 0 || (host_rbits && host_mu)));
     for (int r = 0; r < nrows; ++r) ARGCHK(host_rows[r]);
     for (int p = 0; p < np; ++p) ARGCHK(host_rbits[p]);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_mask_open(ctx->policy, ctx->lc, host_rows, host_coef, nrows, host_rbits, host_mu,
-                                                    np, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_gf8_mask_open(ctx->policy, cs.lc, host_rows, host_coef, nrows, host_rbits, host_mu,
+                                                np, out, n, cs.st));
 }
 
 int ffgpu_gf256_bits_affine_fold(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, const void* c,
@@ -1338,12 +1255,41 @@ int ffgpu_gf256_bits_affine_fold(ffgpu_ctx* ctx, const uint64_t* host_matrix, co
     if (n == 0) return FFGPU_OK;
     ARGCHK(c && rbits && out);
     ARGCHK(nbatch == 1 || (rbits_batch_stride >= 8 * n && out_batch_stride >= n));
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_bits_affine_fold(ctx->policy, ctx->lc, host_matrix, host_bias, c, rbits,
-                                                           rbits_batch_stride, out, out_batch_stride, n, nbatch,
-                                                           (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_gf8_bits_affine_fold(ctx->policy, cs.lc, host_matrix, host_bias, c, rbits,
+                                                       rbits_batch_stride, out, out_batch_stride, n, nbatch,
+                                                       cs.st));
 }
+
+}  // extern "C"
+
+// tables of the fused S-box layer: log / antilog of the field, np_from_bits, affine fold -- cached on the device per
+// (matrix, bias).  The caller holds the context's device.
+static int sbox_layer_tables_on_device(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias) {
+    unsigned char key[72];
+    for (int i = 0; i < 64; ++i) key[i] = (unsigned char)(host_matrix[2 * i] & 0xffu);
+    for (int i = 0; i < 8; ++i) key[64 + i] = host_bias ? (unsigned char)(host_bias[2 * i] & 0xffu) : 0;
+    std::lock_guard<std::mutex> lk(ctx->sbl_mu);
+    if (!ctx->sbl_tables_dev) {
+        void* d = nullptr;
+        if (hipMalloc(&d, 1536 + 2304 + 2304) != hipSuccess) return FFGPU_ENOMEM;
+        ctx->sbl_tables_dev = d;
+        ctx->sbl_valid = 0;
+    }
+    if (!ctx->sbl_valid || memcmp(key, ctx->sbl_key, sizeof(key)) != 0) {
+        unsigned char host_tables[1536 + 2304 + 2304];
+        ffgpu_gf8_sbox_layer_tables(ctx->policy, ctx->gf8_tables, host_matrix, host_bias, host_tables);
+        // a DIFFERENT affine map than the cached one: launches that still read the old tables (on any stream) finish first
+        if (ctx->sbl_valid) HIPCHK(hipDeviceSynchronize());
+        // (synchronous copy: not inside a stream capture -- engine.CapturedLaunches warms the call up first)
+        HIPCHK(hipMemcpy(ctx->sbl_tables_dev, host_tables, sizeof(host_tables), hipMemcpyHostToDevice));
+        memcpy(ctx->sbl_key, key, sizeof(key));
+        ctx->sbl_valid = 1;
+    }
+    return FFGPU_OK;
+}
+
+extern "C" {
 
 int ffgpu_gf256_sbox_layer(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, const uint64_t* host_lambda,
                            const uint64_t* host_mu, int t, int m, const void* x, size_t x_stride, const void* rbits,
@@ -1356,45 +1302,21 @@ int ffgpu_gf256_sbox_layer(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
     ARGCHK(!dev_state || nonce <= 0xffffffffull);
     RngArgs ra;
     if (dev_state) {
-        memset(&ra, 0, sizeof(ra));
-        ra.rk.rounds = 20;
-        ra.dev_key = (const RngKey*)dev_state;
-        ra.nonce_off = (uint32_t)nonce;
-        ra.no_advance = defer_advance ? 1 : 0;
+        ra = make_dev_rng(ctx, dev_state, nonce, defer_advance, false);
     } else {
         int rc = make_rng(ctx, host_key32, nonce, rounds, &ra);
         if (rc != FFGPU_OK) return rc;
     }
     if (n == 0) return FFGPU_OK;
     ARGCHK(x && rbits && out && x_stride >= n && out_stride >= n && rbits_stride >= 8 * n);
-    DeviceGuard g(ctx->device);
-    // tables: log / antilog of the field, np_from_bits, affine fold -- cached on the device per (matrix, bias)
-    unsigned char key[72];
-    for (int i = 0; i < 64; ++i) key[i] = (unsigned char)(host_matrix[2 * i] & 0xffu);
-    for (int i = 0; i < 8; ++i) key[64 + i] = host_bias ? (unsigned char)(host_bias[2 * i] & 0xffu) : 0;
-    {
-        static std::mutex mu_;
-        std::lock_guard<std::mutex> lk(mu_);
-        if (!ctx->sbl_tables_dev) {
-            void* d = nullptr;
-            if (hipMalloc(&d, 1536 + 2304 + 2304) != hipSuccess) return FFGPU_ENOMEM;
-            ctx->sbl_tables_dev = d;
-            ctx->sbl_valid = 0;
-        }
-        if (!ctx->sbl_valid || memcmp(key, ctx->sbl_key, sizeof(key)) != 0) {
-            unsigned char host_tables[1536 + 2304 + 2304];
-            ffgpu_gf8_sbox_layer_tables(ctx->policy, ctx->gf8_tables, host_matrix, host_bias, host_tables);
-            // a DIFFERENT affine map than the cached one: launches that still read the old tables (on any stream) finish first
-            if (ctx->sbl_valid) HIPCHK(hipDeviceSynchronize());
-            // (synchronous copy: not inside a stream capture -- engine.CapturedLaunches warms the call up first)
-            HIPCHK(hipMemcpy(ctx->sbl_tables_dev, host_tables, sizeof(host_tables), hipMemcpyHostToDevice));
-            memcpy(ctx->sbl_key, key, sizeof(key));
-            ctx->sbl_valid = 1;
-        }
+    {   // (the tables go up before the scope opens: an upload is not part of the call's timed launches)
+        DeviceGuard g(ctx->device);
+        const int rc = sbox_layer_tables_on_device(ctx, host_matrix, host_bias);
+        if (rc != FFGPU_OK) return rc;
     }
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_gf8_sbox_layer(ctx->policy, ctx->lc, x, x_stride, rbits, rbits_stride, out, out_stride,
-                                                     ctx->sbl_tables_dev, host_lambda, host_mu, t, m, n, (hipStream_t)stream, &ra));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_gf8_sbox_layer(ctx->policy, cs.lc, x, x_stride, rbits, rbits_stride, out, out_stride,
+                                                 ctx->sbl_tables_dev, host_lambda, host_mu, t, m, n, cs.st, &ra));
 }
 
 int ffgpu_gf256_sbox(ffgpu_ctx* ctx, const void* in, const uint8_t* host_rows8, uint8_t b, void* out,
@@ -1408,8 +1330,7 @@ int ffgpu_gf256_sbox(ffgpu_ctx* ctx, const void* in, const uint8_t* host_rows8, 
     ARGCHK(in && out);
     uint8_t lut[256];
     {
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
+        std::lock_guard<std::mutex> lk(ctx->sbox_mu);
         uint8_t key[9];
         memcpy(key, host_rows8, 8);
         key[8] = b;
@@ -1420,9 +1341,8 @@ int ffgpu_gf256_sbox(ffgpu_ctx* ctx, const void* in, const uint8_t* host_rows8, 
         }
         memcpy(lut, ctx->sbox_lut, 256);
     }
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    return launch_status(ffgpu_launch_sbox(lut, ctx->lc, in, out, n, (hipStream_t)stream));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_sbox(lut, cs.lc, in, out, n, cs.st));
 }
 
 }  // extern "C"
@@ -1473,23 +1393,21 @@ int ffgpu_copy(ffgpu_ctx* ctx, const void* src, void* dst, size_t bytes, void* s
     ARGCHK(ctx);
     if (bytes == 0) return FFGPU_OK;
     ARGCHK(src && dst);
-    DeviceGuard g(ctx->device);
-    LaunchTimer lt(ctx, (hipStream_t)stream);
-    const ByteRange in = byte_range(src, bytes), o = byte_range(dst, bytes);
-    const LaunchCfg lc = handoff_lc(ctx, stream, HK_COPY, &in, 1, &o, 1);
-    return launch_status(ffgpu_launch_copy(lc, src, dst, bytes, (hipStream_t)stream));
+    const ByteRange in = byte_range(src, bytes);
+    CallScope cs(ctx, stream, HK_COPY, &in, 1, byte_range(dst, bytes));
+    return status_of(ffgpu_launch_copy(cs.lc, src, dst, bytes, cs.st));
 }
 int ffgpu_valu_probe(ffgpu_ctx* ctx, int op, int iters, int waves_per_simd, void* scratch32, double* out3, void* stream) {
     ARGCHK(ctx && scratch32 && out3);
     ARGCHK(op >= 0 && op <= 13 && iters >= 1 && waves_per_simd >= 1 && waves_per_simd <= 8);
     DeviceGuard g(ctx->device);
-    return launch_status(ffgpu_launch_valu_probe(ctx->lc, op, iters, waves_per_simd, scratch32, out3, (hipStream_t)stream));
+    return status_of(ffgpu_launch_valu_probe(ctx->lc, op, iters, waves_per_simd, scratch32, out3, (hipStream_t)stream));
 }
 int ffgpu_time_copy(ffgpu_ctx* ctx, const void* src, void* dst, size_t bytes, int reps, void* stream,
                     float* ms) {
     ARGCHK(ctx && src && dst);
     return time_loop(ctx, reps, stream, ms, [&]() {
-        return launch_status(ffgpu_launch_copy(ctx->lc, src, dst, bytes, (hipStream_t)stream));
+        return status_of(ffgpu_launch_copy(ctx->lc, src, dst, bytes, (hipStream_t)stream));
     });
 }
 

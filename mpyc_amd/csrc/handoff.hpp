@@ -10,7 +10,7 @@
 //   * the next launch on that stream tells whether it reads any of them: that settles, for the producer's kind, whether
 //     the next producer of that kind keeps its outputs (default stores) or streams them (nt);
 //   * outputs larger than the cache never keep: the producer would evict its own first rows before anyone reads them.
-// The tracked calls (api.hip handoff_lc): element-wise operations, share generation (supplied coefficients, device RNG, the
+// The tracked calls (api.hip, the tracked form of CallScope): element-wise operations, share generation (supplied coefficients, device RNG, the
 // chain gate), recombination, device copy.  Launches of other calls are not seen: a split, a pow, then a recombination of the
 // shares counts as a hand-off from the split.
 // Host bookkeeping only: no synchronisation, no allocation, no device call.  A wrong guess costs speed, never a result --

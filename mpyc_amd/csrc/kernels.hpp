@@ -32,7 +32,7 @@
 namespace ffgpu {
 
 enum { BLOCK = 256 };
-enum EwOp { OP_ADD = 0, OP_SUB = 1, OP_MUL = 2, OP_RSUB = 3, OP_NEG = 4, OP_REDUCE = 5, OP_COPY = 6 };
+enum EwOp { OP_ADD = 0, OP_SUB = 1, OP_MUL = 2, OP_RSUB = 3, OP_NEG = 4, OP_REDUCE = 5 };
 
 enum { MAXK = 9, MAXW = 8, MAXK_ANY = 64, MAXT = 4 };
 

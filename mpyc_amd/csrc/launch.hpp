@@ -24,6 +24,33 @@ struct LaunchCfg {
                             // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
 };
 
+// What a launcher reports.  One value per meaning; api.hip maps them to FFGPU_* in one place (status_of).
+enum LaunchCode {
+    L_OK = 0,
+    L_BAD_ARG,         // an argument the entry point should have refused
+    L_NOT_SUPPORTED,   // sizes outside what the kernels are built for
+    L_DECLINED,        // this route does not serve the call: the caller takes another one (never leaves the library)
+    L_PLAN_REFUSED,    // scan_plan() refuses the sizes
+    L_WS_TOO_SMALL,    // the caller's workspace is smaller than the plan needs
+    L_HIP_ERROR        // a launch failed: `hip` says how
+};
+struct LaunchStatus {
+    LaunchCode code;
+    hipError_t hip;
+    LaunchStatus(LaunchCode c = L_OK, hipError_t e = hipSuccess) : code(c), hip(e) {}
+    bool ok() const { return code == L_OK; }
+};
+// the status of the launches enqueued so far by this call
+inline LaunchStatus launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LaunchStatus() : LaunchStatus(L_HIP_ERROR, e);
+}
+#define FFGPU_CHECK_LAUNCH()                      \
+    do {                                          \
+        const LaunchStatus s__ = launched();      \
+        if (!s__.ok()) return s__;                \
+    } while (0)
+
 inline unsigned grid_for(size_t iters, const LaunchCfg& lc) {
     size_t want = (iters + BLOCK - 1) / BLOCK;
     size_t cap = lc.blocks_per_cu > 0 ? (size_t)lc.blocks_per_cu * (size_t)lc.num_cu : (size_t)0x7fffffff;
@@ -36,52 +63,52 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 // host-side table of launchers for one policy type; the context stores the
 // policy blob and a pointer to this table.
 struct FieldOps {
-    int (*ew2)(const void* F, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
+    LaunchStatus (*ew2)(const void* F, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                hipStream_t st);
-    int (*ew1)(const void* F, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
+    LaunchStatus (*ew1)(const void* F, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                size_t n, hipStream_t st);
-    int (*muladd)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
+    LaunchStatus (*muladd)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
                   size_t n, hipStream_t st);
     // coef == nullptr && rng != nullptr: coefficients are drawn in-kernel from the keystream
-    int (*split)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
+    LaunchStatus (*split)(const void* F, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
                  size_t cstride, int t, int m, void* out, size_t ostride, size_t n, hipStream_t st,
                  const RngArgs* rng);
-    int (*rng_coeffs)(const void* F, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
+    LaunchStatus (*rng_coeffs)(const void* F, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
                       const RngArgs* rng);
-    int (*recombine)(const void* F, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
+    LaunchStatus (*recombine)(const void* F, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                      int w, void* out, size_t ostride, size_t n, hipStream_t st);
-    int (*pow)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, hipStream_t st);
-    int (*inv)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
+    LaunchStatus (*pow)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*inv)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
                hipStream_t st);
-    int (*matmul)(const void* F, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
+    LaunchStatus (*matmul)(const void* F, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
                   size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t st);
-    int (*dot)(const void* F, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
+    LaunchStatus (*dot)(const void* F, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                hipStream_t st);
     // nbatch > 1: gridDim.y independent gates in one launch, operands / outputs of gate y at element offsets y*yA, y*yB, y*yO
-    int (*gate)(const void* F, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
+    LaunchStatus (*gate)(const void* F, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
                 const void* const* rowsB, const uint64_t* lamB2, int kB, int t, int m, void* out, size_t ostride,
                 size_t n, hipStream_t st, const RngArgs* rng, int nbatch, size_t yA, size_t yB, size_t yO);
-    int (*sqrt_cl)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out, size_t n,
+    LaunchStatus (*sqrt_cl)(const void* F, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out, size_t n,
                    hipStream_t st);
-    int (*gauss)(const void* F, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode, const ExpArgs* ex,
+    LaunchStatus (*gauss)(const void* F, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode, const ExpArgs* ex,
                  void* det, int* sing, hipStream_t st);
-    int (*group_matvec)(const void* F, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
+    LaunchStatus (*group_matvec)(const void* F, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
                         const void* in, void* out, size_t ngroups, hipStream_t st);
-    int (*beaver)(const void* F, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d, const void* e,
+    LaunchStatus (*beaver)(const void* F, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d, const void* e,
                   void* out, int add_de, size_t n, hipStream_t st);
-    int (*prss)(const void* F, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
+    LaunchStatus (*prss)(const void* F, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
                 const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
     // keys40: ks x (32-byte ChaCha key + 8-byte nonce)
-    int (*prss_chacha)(const void* F, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
+    LaunchStatus (*prss_chacha)(const void* F, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                        const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
     // full convolution, na >= nv >= 1, out: na + nv - 1 elements
-    int (*convolve)(const void* F, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
+    LaunchStatus (*convolve)(const void* F, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
                     hipStream_t st);
     // inclusive scan / reduction along k of a contiguous (outer, k, inner) array with field addition (mul = 0) or
-    // multiplication; workspace: scan_plan().ws_elems elements.  4: the plan refuses the sizes, 5: workspace too small
-    int (*scan)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
+    // multiplication; workspace: scan_plan().ws_elems elements (L_PLAN_REFUSED, L_WS_TOO_SMALL)
+    LaunchStatus (*scan)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
                 int with_initial, void* workspace, size_t workspace_bytes, hipStream_t st);
-    int (*axis_reduce)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
+    LaunchStatus (*axis_reduce)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
                        size_t inner, void* workspace, size_t workspace_bytes, hipStream_t st);
 };
 
@@ -129,16 +156,28 @@ inline typename F::word word_at(const F& f, const uint64_t* base, size_t idx) {
     }
 }
 
-template <class F>
-inline typename F::word prep_const(const F& f, typename F::word c) {
-    return f.prep(c);
+// Run-time integer -> template parameter: calls fn(std::integral_constant<int, V>()) for the V of the list that equals v;
+// false when none does.  Only the listed values are instantiated.  (Kernels are launched from named member functions
+// that fn calls, see the note at launch_glds.)
+template <int LO, int... I>
+constexpr auto int_range_(std::integer_sequence<int, I...>) { return std::integer_sequence<int, LO + I...>(); }
+template <int LO, int HI>
+using IntRange = decltype(int_range_<LO>(std::make_integer_sequence<int, HI - LO + 1>()));
+template <int... V, class Fn>
+inline bool dispatch_int(std::integer_sequence<int, V...>, int v, Fn&& fn) {
+    return ((v == V ? (fn(std::integral_constant<int, V>()), true) : false) || ...);
 }
 
-#define FFGPU_CHECK_LAUNCH()                      \
-    do {                                          \
-        hipError_t e__ = hipGetLastError();       \
-        if (e__ != hipSuccess) return (int)e__ | 0x10000; \
-    } while (0)
+// Does an M x K x N product over a prime field go to the matrix cores, and with how many bytes of digit planes
+// (`digits` int8 planes per operand, padded to whole tiles)?  0: it stays on the vector ALUs.  The one copy of this
+// decision: ffgpu_matmul sizes the scratch with it, Launchers::matmul takes the route with it.
+// (from 9 rows / columns on: the tiles are padded to 64 -- a batch of 9..63 rows against 4096 x 4096 takes the 88 us of
+// 64 rows instead of 670-690 us on the vector ALUs)
+inline size_t mfma_plane_bytes(const LaunchCfg& lc, size_t digits, size_t M, size_t K, size_t N) {
+    if (!lc.mm_mfma || M <= SKINNY_MAX || N <= SKINNY_MAX || K < 64 || (double)M * N * K < lc.mm_mfma_min) return 0;
+    const size_t Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
+    return digits * (Mp + Np) * Kp;
+}
 
 template <class F>
 struct Launchers {
@@ -202,6 +241,8 @@ struct Launchers {
                                kslice, zs, Braw, ldb, pmod);
         }
     }
+    // the policy blob of the context (FieldOps entries take it untyped)
+    static const F& policy(const void* Fp) { return *reinterpret_cast<const F*>(Fp); }
     static bool stride_ok(size_t stride) { return (stride * sizeof(E)) % PACK_ALIGN == 0; }
 
     template <int OP>
@@ -215,20 +256,15 @@ struct Launchers {
         else
             hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.keep);
     }
-    static int ew2(const void* Fp, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
+    static LaunchStatus ew2(const void* Fp, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                    hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const E* A = (const E*)a;
         const E* B = (const E*)b;
         E* O = (E*)o;
-        switch (op) {
-            case OP_ADD: go_ew2<OP_ADD>(f, lc, A, B, O, n, st); break;
-            case OP_SUB: go_ew2<OP_SUB>(f, lc, A, B, O, n, st); break;
-            case OP_MUL: go_ew2<OP_MUL>(f, lc, A, B, O, n, st); break;
-            default: return 1;
-        }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        const bool known = dispatch_int(std::integer_sequence<int, OP_ADD, OP_SUB, OP_MUL>(), op,
+                                        [&](auto o_) { go_ew2<decltype(o_)::value>(f, lc, A, B, O, n, st); });
+        return known ? launched() : LaunchStatus(L_BAD_ARG);
     }
 
     template <int OP>
@@ -236,33 +272,24 @@ struct Launchers {
         const Plan p = plan(n, al(a) && al(o), lc);
         hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n, p.keep);
     }
-    static int ew1(const void* Fp, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
+    static LaunchStatus ew1(const void* Fp, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                    size_t n, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         W s = scalar2 ? word_at<F>(f, scalar2, 0) : word_from_limbs<F>(f, 0, 0);
         const E* A = (const E*)a;
         E* O = (E*)o;
-        switch (op) {
-            case OP_ADD: go_ew1<OP_ADD>(f, lc, A, s, O, n, st); break;
-            case OP_RSUB: go_ew1<OP_RSUB>(f, lc, A, s, O, n, st); break;
-            case OP_MUL: go_ew1<OP_MUL>(f, lc, A, s, O, n, st); break;
-            case OP_NEG: go_ew1<OP_NEG>(f, lc, A, s, O, n, st); break;
-            case OP_REDUCE: go_ew1<OP_REDUCE>(f, lc, A, s, O, n, st); break;
-            case OP_COPY: go_ew1<OP_COPY>(f, lc, A, s, O, n, st); break;
-            default: return 1;
-        }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        const bool known = dispatch_int(std::integer_sequence<int, OP_ADD, OP_RSUB, OP_MUL, OP_NEG, OP_REDUCE>(), op,
+                                        [&](auto o_) { go_ew1<decltype(o_)::value>(f, lc, A, s, O, n, st); });
+        return known ? launched() : LaunchStatus(L_BAD_ARG);
     }
 
-    static int muladd(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
+    static LaunchStatus muladd(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* c, void* o,
                       size_t n, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const Plan p = plan(n, al(a) && al(b) && al(c) && al(o), lc);
         hipLaunchKernelGGL((k_muladd<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a,
                            (const E*)b, (const E*)c, (E*)o, p.nvec, n, p.keep);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
 
     template <int T, bool FUSE, bool RNG, bool REC = false>
@@ -272,7 +299,7 @@ struct Launchers {
                            coef, cstride, m, out, ostride, p.nvec, n, ra, gs, p.keep);
     }
     template <bool FUSE, bool RNG>
-    static int split_t(const F& f, const LaunchCfg& lc, const E* a, const E* b, const E* coef, size_t cstride,
+    static LaunchStatus split_t(const F& f, const LaunchCfg& lc, const E* a, const E* b, const E* coef, size_t cstride,
                        int t, int m, E* out, size_t ostride, size_t n, hipStream_t st, const RngArgs& ra_in) {
         RngArgs ra = ra_in;
         if (t > MAXT) {
@@ -286,25 +313,22 @@ struct Launchers {
             const Plan p = RNG ? plan_rng(n, vec, lc, ra) : plan(n, vec, lc);
             GateSrc<F> gs;
             memset(&gs, 0, sizeof(gs));
-            switch (t) {
-                case 0: go_split<0, FUSE, false>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
-                case 1: go_split<1, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
-                case 2: go_split<2, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
-                case 3: go_split<3, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
-                case 4: go_split<4, FUSE, RNG>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs); break;
-                default: return 1;
-            }
+            const bool known = dispatch_int(IntRange<0, MAXT>(), t, [&](auto t_) {     // (t = 0 draws nothing: one kernel for both)
+                constexpr int T = decltype(t_)::value;
+                go_split<T, FUSE, (T > 0 && RNG)>(f, p, a, b, coef, cstride, m, out, ostride, n, st, ra, gs);
+            });
+            if (!known) return L_BAD_ARG;
         }
         if (RNG && t > 0) rng_advance(ra, st);
-        return 0;
+        return L_OK;
     }
     // fused chain gate: both factors given as recombinations (GateSrc), product re-shared with the device CSPRNG
-    static int gate(const void* Fp, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
+    static LaunchStatus gate(const void* Fp, const LaunchCfg& lc, const void* const* rowsA, const uint64_t* lamA2, int kA,
                     const void* const* rowsB, const uint64_t* lamB2, int kB, int t, int m, void* out, size_t ostride,
                     size_t n, hipStream_t st, const RngArgs* rng, int nbatch, size_t yA, size_t yB, size_t yO) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
-        if (t < 1 || t > 3 || kA < 1 || kA > GATE_MAXK || kB < 0 || kB > GATE_MAXK || !rng) return 2;
-        if (nbatch < 1 || nbatch > 255) return 2;
+        const F& f = policy(Fp);
+        if (t < 1 || t > 3 || kA < 1 || kA > GATE_MAXK || kB < 0 || kB > GATE_MAXK || !rng) return L_NOT_SUPPORTED;
+        if (nbatch < 1 || nbatch > 255) return L_NOT_SUPPORTED;
         GateSrc<F> gs;
         memset(&gs, 0, sizeof(gs));
         bool vec = al(out) && (stride_ok(ostride) || m <= 1);
@@ -334,22 +358,19 @@ struct Launchers {
         const unsigned gy = (unsigned)nbatch;
         const Plan p = plan_rng(n, vec, lc, ra, gy);
         E* o = (E*)out;
-        switch (t) {
-            case 1: go_split<1, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
-            case 2: go_split<2, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
-            default: go_split<3, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy); break;
-        }
+        dispatch_int(IntRange<1, 3>(), t, [&](auto t_) {
+            go_split<decltype(t_)::value, true, true, true>(f, p, nullptr, nullptr, nullptr, 0, m, o, ostride, n, st, ra, gs, gy);
+        });
         rng_advance(ra, st);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int split(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
+    static LaunchStatus split(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, const void* coef,
                      size_t cstride, int t, int m, void* out, size_t ostride, size_t n, hipStream_t st,
                      const RngArgs* rng) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         RngArgs ra;
         memset(&ra, 0, sizeof(ra));
-        int rc;
+        LaunchStatus rc;
         if (rng) {
             ra = *rng;
             rc = b ? split_t<true, true>(f, lc, (const E*)a, (const E*)b, nullptr, 0, t, m, (E*)out, ostride, n, st, ra)
@@ -360,31 +381,23 @@ struct Launchers {
                    : split_t<false, false>(f, lc, (const E*)a, nullptr, (const E*)coef, cstride, t, m, (E*)out,
                                            ostride, n, st, ra);
         }
-        if (rc) return rc;
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return rc.ok() ? launched() : rc;
     }
-    static int rng_coeffs(const void* Fp, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
+    static LaunchStatus rng_coeffs(const void* Fp, const LaunchCfg& lc, void* coef, size_t cstride, int t, size_t n, hipStream_t st,
                           const RngArgs* rng) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         E* C = (E*)coef;
         size_t npacks = (n + EPV - 1) / EPV;
         unsigned grid = grid_for(npacks, lc);
         if (t > MAXT) {
             hipLaunchKernelGGL((k_rng_coeffs_any<F>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, t, n, *rng);
-            FFGPU_CHECK_LAUNCH();
-            return 0;
+            return launched();
         }
         const size_t nvec = plan(n, al(coef) && (stride_ok(cstride) || t <= 1), lc).nvec;
-        switch (t) {
-            case 1: hipLaunchKernelGGL((k_rng_coeffs<F, 1>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
-            case 2: hipLaunchKernelGGL((k_rng_coeffs<F, 2>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
-            case 3: hipLaunchKernelGGL((k_rng_coeffs<F, 3>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
-            case 4: hipLaunchKernelGGL((k_rng_coeffs<F, 4>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng); break;
-            default: return 1;
-        }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        const bool known = dispatch_int(IntRange<1, MAXT>(), t, [&](auto t_) {
+            hipLaunchKernelGGL((k_rng_coeffs<F, decltype(t_)::value>), dim3(grid), dim3(BLOCK), 0, st, f, C, cstride, nvec, n, *rng);
+        });
+        return known ? launched() : LaunchStatus(L_BAD_ARG);
     }
 
     template <int K>
@@ -405,12 +418,12 @@ struct Launchers {
         hipLaunchKernelGGL((k_recombine<F, K, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, ra, w, out, ostride,
                            p.nvec, n, p.keep);
     }
-    static int recombine(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
+    static LaunchStatus recombine(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                          int w, void* out, size_t ostride, size_t n, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         E* O = (E*)out;
         if (k > MAXK) {
-            if (k > MAXK_ANY) return 2;
+            if (k > MAXK_ANY) return L_NOT_SUPPORTED;
             for (int r = 0; r < w; ++r) {
                 RecArgsAny<F> ra;
                 for (int j = 0; j < k; ++j) {
@@ -425,41 +438,28 @@ struct Launchers {
                 hipLaunchKernelGGL((k_recombine_any<F>), dim3(grid), dim3(BLOCK), 0, st, f, ra, k,
                                    O + (size_t)r * ostride, n);
             }
-            FFGPU_CHECK_LAUNCH();
-            return 0;
+            return launched();
         }
         for (int r0 = 0; r0 < w; r0 += MAXW) {
             int wc = (w - r0) < MAXW ? (w - r0) : MAXW;
             const uint64_t* l = lam2 + scalar_limbs<F>() * (size_t)r0 * k;
             E* o = O + (size_t)r0 * ostride;
-            switch (k) {
-                case 1: go_rec<1>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 2: go_rec<2>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 3: go_rec<3>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 4: go_rec<4>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 5: go_rec<5>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 6: go_rec<6>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 7: go_rec<7>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 8: go_rec<8>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                case 9: go_rec<9>(f, lc, rows, l, wc, o, ostride, n, st); break;
-                default: return 1;
-            }
+            if (!dispatch_int(IntRange<1, MAXK>(), k, [&](auto k_) { go_rec<decltype(k_)::value>(f, lc, rows, l, wc, o, ostride, n, st); }))
+                return L_BAD_ARG;
         }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
 
-    static int pow(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n,
+    static LaunchStatus pow(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n,
                    hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const Plan p = plan(n, al(a) && al(out), lc);
         hipLaunchKernelGGL((k_pow<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out, p.nvec, n);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int inv(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
+    static LaunchStatus inv(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t n, int* flag,
                    hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const size_t nvec = plan(n, al(a) && al(out), lc).nvec;
         // packs per thread: ONE exponentiation (70 products for 2^61 - 1) is shared by G x CH packs, and the
         // G x CH x N prefix words stay in registers (two waves per SIMD at CH = 8..12 for one-word fields)
@@ -497,32 +497,31 @@ struct Launchers {
             if constexpr (HasDigitChain<F>::value) {
                 // multi-limb 2^k - c primes: the whole batch in digits (k_inv_digits), NL = ceil(k / 28) registers per value
                 if (nvec >= 4096) {
-                    int rc = launch_inv_digits_from<F::CHAIN_MIN_NL>(f, lc, a, ex, out, nvec, n, flag, st);
-                    if (rc >= 0) return rc;
+                    const LaunchStatus rc = launch_inv_digits_from<F::CHAIN_MIN_NL>(f, lc, a, ex, out, nvec, n, flag, st);
+                    if (rc.code != L_DECLINED) return rc;
                 }
             }
             constexpr int CH = F::EPW > 1 ? 2 : 8;          // packed bytes: 8 words per batch (zero mask)
             return launch_inv<CH, 1>(f, lc, a, ex, out, nvec, n, flag, st);
         }
     }
-    // -1: the modulus has no digit form at this NL (DigitChain::setup: c too large) -> the word kernel
+    // L_DECLINED: the modulus has no digit form at this NL (DigitChain::setup: c too large) -> the word kernel
     template <int NL>
-    static int launch_inv_digits_from(const F& f, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t nvec,
+    static LaunchStatus launch_inv_digits_from(const F& f, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t nvec,
                                       size_t n, int* flag, hipStream_t st) {
         if constexpr (!HasDigitChain<F>::value) {
-            return -1;
+            return L_DECLINED;
         } else if constexpr (NL > F::CHAIN_MAX_NL) {
-            return -1;
+            return L_DECLINED;
         } else {
             if (f.k > 28u * NL) return launch_inv_digits_from<NL + 1>(f, lc, a, ex, out, nvec, n, flag, st);
             DigitChain<NL> dc;
-            if (!f.template chain_setup<NL>(dc)) return -1;
+            if (!f.template chain_setup<NL>(dc)) return L_DECLINED;
             constexpr int CH = NL <= 3 ? 32 : NL == 4 ? 24 : NL <= 6 ? 16 : 12;      // ~96 registers of prefix products
             unsigned grid = grid_for((nvec + CH - 1) / CH, lc);
             hipLaunchKernelGGL((k_inv_digits<F, NL, CH, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out, nvec, n,
                                flag);
-            FFGPU_CHECK_LAUNCH();
-            return 0;
+            return launched();
         }
     }
     // square-and-multiply after the leading run costs popcount(tail) products, the window table 8 up front and one per
@@ -537,7 +536,7 @@ struct Launchers {
         return ones <= 6;
     }
     template <int CH, int G, int WIN, int WAVES, bool LEAN, int WIN1 = 0>
-    static int launch_inv_fast(const F& f, const void* a, const ExpArgs* ex, void* out, size_t nvec, size_t n, int* flag,
+    static LaunchStatus launch_inv_fast(const F& f, const void* a, const ExpArgs* ex, void* out, size_t nvec, size_t n, int* flag,
                                hipStream_t st) {
         if constexpr (F::EPW == 1 && sizeof(W) == 8) {
             const size_t per_block = (size_t)BLOCK * CH * G;
@@ -546,19 +545,17 @@ struct Launchers {
             const unsigned grid = (unsigned)nfull + (unsigned)((rest + BLOCK - 1) / BLOCK) + ((rest == 0 && n > nvec * EPV) ? 1u : 0u);
             hipLaunchKernelGGL((k_inv_fast<F, CH, G, WIN, WAVES, LEAN, WIN1>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out,
                                nvec, n, (unsigned)nfull, flag);
-            FFGPU_CHECK_LAUNCH();
         }
-        return 0;
+        return launched();
     }
     template <int CH, int G>
-    static int launch_inv(const F& f, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t nvec, size_t n,
+    static LaunchStatus launch_inv(const F& f, const LaunchCfg& lc, const void* a, const ExpArgs* ex, void* out, size_t nvec, size_t n,
                           int* flag, hipStream_t st) {
         size_t iters = nvec ? (nvec + CH * G - 1) / (CH * G) : n;
         unsigned grid = grid_for(iters, lc);
         hipLaunchKernelGGL((k_inv_batch<F, CH, G, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *ex, (E*)out,
                            nvec, n, flag);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
 
     // skinny shapes (one output dimension <= 8): HBM-bound kernels that read the big operand once
@@ -597,8 +594,7 @@ struct Launchers {
             // B contiguous and 16-byte aligned, rows of A aligned: sixteen lanes per row (a wave per row when 16 rows per
             // workgroup would leave CUs without one), the rows of B through LDS
             if (vec && ldb == (size_t)NN && al(B) && K >= 64) {
-                const int ncu = lc.num_cu;
-                if ((M + 15) / 16 >= 2 * (ncu > 0 ? ncu : 256))
+                if ((M + 15) / 16 >= 2 * lc.num_cu)
                     hipLaunchKernelGGL((k_matvec_sub_col<F, NN, 16>), dim3((unsigned)((M + 15) / 16)), dim3(BLOCK), 0, st, f, A, lda, B, C, ldc, M, K);
                 else
                     hipLaunchKernelGGL((k_matvec_sub_col<F, NN, 64>), dim3((unsigned)((M + 3) / 4)), dim3(BLOCK), 0, st, f, A, lda, B, C, ldc, M, K);
@@ -640,252 +636,244 @@ struct Launchers {
             hipLaunchKernelGGL((k_vecmat_partial_col<F, MM, C::UNR, C::MINB>), grid, dim3(BLOCK), 0, st, f, A, lda, B, ldb, part, K, N, kchunk);
         }
     }
-    static int matmul(const void* Fp, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
-                      size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+    // ---- dense products: five routes, tried in this order; each says whether it took the product -----------------
+    struct Mat {
+        const E* A; size_t lda;
+        const E* B; size_t ldb;
+        E* C; size_t ldc;
+        int M, K, N;
+        void* ws; size_t ws_bytes;      // scratch of the call (api.hip, ScratchSlots), may be absent
+        hipStream_t st;
+    };
+    // at most 8 columns (4 for three-limb words: the eight-column kernel would spill, N in 5..8 takes the tiled product)
+    static bool mm_skinny_n(const F& f, const LaunchCfg& lc, const Mat& m) {
         if constexpr (F::EPW == 1) {
-            // (three-limb words: the eight-column kernel would spill, N in 5..8 takes the tiled product)
-            if (N <= (sizeof(W) > 16 ? 4 : SKINNY_MAX) && M >= 64 && K >= 1) {
-                const E* a = (const E*)A; const E* b = (const E*)B; E* c = (E*)C;
-                bool done = false;
-                if constexpr (col_mac_ok<F>::value) {
-                    if (N >= 2 && K > 32) {               // (short rows keep the one-thread-per-row kernel)
-                        switch (N) {
-                            case 2: go_matvec_col<2>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 3: go_matvec_col<3>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 4: go_matvec_col<4>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 5: go_matvec_col<5>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 6: go_matvec_col<6>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            case 7: go_matvec_col<7>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                            default: go_matvec_col<8>(f, lc, a, lda, b, ldb, c, ldc, M, K, st); break;
-                        }
-                        done = true;
-                    }
-                }
-                if (done) {}
-                else if (N == 1) go_matvec<1>(f, a, lda, b, ldb, c, ldc, M, K, N, st);
-                else if (N == 2) go_matvec<2>(f, a, lda, b, ldb, c, ldc, M, K, N, st);
-                else if (N <= 4) go_matvec<4>(f, a, lda, b, ldb, c, ldc, M, K, N, st);
-                else go_matvec<8>(f, a, lda, b, ldb, c, ldc, M, K, N, st);
-                FFGPU_CHECK_LAUNCH();
-                return 0;
-            }
-            if (M <= SKINNY_MAX && N >= 64 && K >= 1 && workspace) {
-                // split K so that one round of workgroups fills the chip; each chunk at least 8 rows.  One-word primes: one
-                // column per thread, as many workgroups as are resident at once (registers of the column sums)
-                int cpt = (int)Pack<W>::N, target = 1024;        // columns per thread, workgroups
-                if constexpr (col_mac_ok<F>::value) {
-                    cpt = 1;
-                    const int ncu = lc.num_cu;
-                    target = (ncu > 0 ? ncu : 256) * vecmat_col_per_cu(M);
-                }
-                const int cols_blocks = (N / cpt + BLOCK - 1) / BLOCK;
-                int ks = (target + cols_blocks - 1) / cols_blocks;
-                if (ks > (K + 7) / 8) ks = (K + 7) / 8;
-                if (ks < 1) ks = 1;
-                while (ks > 1 && (size_t)ks * M * N * sizeof(W) > workspace_bytes) ks /= 2;
-                if ((size_t)ks * M * N * sizeof(W) <= workspace_bytes) {
-                    const int kchunk = (K + ks - 1) / ks;
-                    ks = (K + kchunk - 1) / kchunk;
-                    W* part = (W*)workspace;
-                    const E* a = (const E*)A; const E* b = (const E*)B;
-                    if constexpr (col_mac_ok<F>::value) {
-                        switch (M) {
-                            case 1: go_vecmat_col<1>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 2: go_vecmat_col<2>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 3: go_vecmat_col<3>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 4: go_vecmat_col<4>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 5: go_vecmat_col<5>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 6: go_vecmat_col<6>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            case 7: go_vecmat_col<7>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                            default: go_vecmat_col<8>(f, a, lda, b, ldb, part, K, N, ks, kchunk, st); break;
-                        }
-                    } else if (M == 1) go_vecmat<1>(f, a, lda, b, ldb, part, M, K, N, ks, kchunk, st);
-                    else if (M == 2) go_vecmat<2>(f, a, lda, b, ldb, part, M, K, N, ks, kchunk, st);
-                    else if (M <= 4) go_vecmat<4>(f, a, lda, b, ldb, part, M, K, N, ks, kchunk, st);
-                    else go_vecmat<8>(f, a, lda, b, ldb, part, M, K, N, ks, kchunk, st);
-                    constexpr int CO = BLOCK / VECMAT_FINAL_G;
-                    hipLaunchKernelGGL((k_vecmat_final<F>), dim3((unsigned)(((size_t)M * N + CO - 1) / CO)), dim3(BLOCK), 0,
-                                       st, f, (const W*)part, ks, M, N, (E*)C, ldc);
-                    FFGPU_CHECK_LAUNCH();
-                    return 0;
+            if (m.N > (sizeof(W) > 16 ? 4 : SKINNY_MAX) || m.M < 64 || m.K < 1) return false;
+            if constexpr (col_mac_ok<F>::value) {
+                if (m.N >= 2 && m.K > 32) {               // (short rows keep the one-thread-per-row kernel)
+                    dispatch_int(IntRange<2, SKINNY_MAX>(), m.N, [&](auto n_) {
+                        go_matvec_col<decltype(n_)::value>(f, lc, m.A, m.lda, m.B, m.ldb, m.C, m.ldc, m.M, m.K, m.st);
+                    });
+                    return true;
                 }
             }
+            if (m.N == 1) go_matvec<1>(f, m.A, m.lda, m.B, m.ldb, m.C, m.ldc, m.M, m.K, m.N, m.st);
+            else if (m.N == 2) go_matvec<2>(f, m.A, m.lda, m.B, m.ldb, m.C, m.ldc, m.M, m.K, m.N, m.st);
+            else if (m.N <= 4) go_matvec<4>(f, m.A, m.lda, m.B, m.ldb, m.C, m.ldc, m.M, m.K, m.N, m.st);
+            else go_matvec<8>(f, m.A, m.lda, m.B, m.ldb, m.C, m.ldc, m.M, m.K, m.N, m.st);
+            return true;
         }
-        const bool use_mfma = lc.mm_mfma != 0;
-        const double mfma_min = lc.mm_mfma_min;
+        return false;
+    }
+    // at most 8 rows: partial sums over chunks of K in the scratch, then k_vecmat_final
+    static bool mm_skinny_m(const F& f, const LaunchCfg& lc, const Mat& m) {
+        if constexpr (F::EPW == 1) {
+            const int M = m.M, K = m.K, N = m.N;
+            if (M > SKINNY_MAX || N < 64 || K < 1 || !m.ws) return false;
+            // split K so that one round of workgroups fills the chip; each chunk at least 8 rows.  One-word primes: one
+            // column per thread, as many workgroups as are resident at once (registers of the column sums)
+            int cpt = (int)Pack<W>::N, target = 1024;        // columns per thread, workgroups
+            if constexpr (col_mac_ok<F>::value) {
+                cpt = 1;
+                target = lc.num_cu * vecmat_col_per_cu(M);
+            }
+            const int cols_blocks = (N / cpt + BLOCK - 1) / BLOCK;
+            int ks = (target + cols_blocks - 1) / cols_blocks;
+            if (ks > (K + 7) / 8) ks = (K + 7) / 8;
+            if (ks < 1) ks = 1;
+            while (ks > 1 && (size_t)ks * M * N * sizeof(W) > m.ws_bytes) ks /= 2;
+            if ((size_t)ks * M * N * sizeof(W) > m.ws_bytes) return false;
+            const int kchunk = (K + ks - 1) / ks;
+            ks = (K + kchunk - 1) / kchunk;
+            W* part = (W*)m.ws;
+            if constexpr (col_mac_ok<F>::value) {
+                dispatch_int(IntRange<1, SKINNY_MAX>(), M, [&](auto m_) {
+                    go_vecmat_col<decltype(m_)::value>(f, m.A, m.lda, m.B, m.ldb, part, K, N, ks, kchunk, m.st);
+                });
+            } else if (M == 1) go_vecmat<1>(f, m.A, m.lda, m.B, m.ldb, part, M, K, N, ks, kchunk, m.st);
+            else if (M == 2) go_vecmat<2>(f, m.A, m.lda, m.B, m.ldb, part, M, K, N, ks, kchunk, m.st);
+            else if (M <= 4) go_vecmat<4>(f, m.A, m.lda, m.B, m.ldb, part, M, K, N, ks, kchunk, m.st);
+            else go_vecmat<8>(f, m.A, m.lda, m.B, m.ldb, part, M, K, N, ks, kchunk, m.st);
+            constexpr int CO = BLOCK / VECMAT_FINAL_G;
+            hipLaunchKernelGGL((k_vecmat_final<F>), dim3((unsigned)(((size_t)M * N + CO - 1) / CO)), dim3(BLOCK), 0,
+                               m.st, f, (const W*)part, ks, M, N, m.C, m.ldc);
+            return true;
+        }
+        return false;
+    }
+    // large dense products over primes of up to 64 bits: int8 matrix cores, 8 signed base-256 digits per operand
+    // (k_limb_gemm_glds), 4 for 32-bit storage (k_limb_gemm_l4)
+    static bool mm_mfma(const F& f, const LaunchCfg& lc, const Mat& m) {
         if constexpr (F::EPW == 1 && !F::BINARY && sizeof(W) <= 8) {
-            // large dense products over primes of up to 64 bits: int8 matrix cores, 8 signed base-256 digits per operand
-            // (k_limb_gemm_glds), 4 for 32-bit storage (k_limb_gemm_l4)
+            const int M = m.M, K = m.K, N = m.N;
             const int L = sizeof(W) == 4 ? 4 : 8;
             const uint64_t pmod = (uint64_t)f.p;
             const int Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
-            const size_t need = (size_t)L * ((size_t)Mp + Np) * Kp;
-            // (from 9 rows / columns on: the tiles are padded to 64 -- a batch of 9..63 rows against 4096 x 4096 takes the 88 us of
-            // 64 rows instead of 670-690 us on the vector ALUs)
-            if (use_mfma && M > SKINNY_MAX && N > SKINNY_MAX && K >= 64 && (double)M * N * K >= mfma_min && workspace && need <= workspace_bytes) {
-                int8_t* Ap = (int8_t*)workspace;
-                int8_t* Bp = Ap + (size_t)L * Mp * Kp;
-                const unsigned ga = (unsigned)(((size_t)Mp * Kp + BLOCK - 1) / BLOCK);
-                dim3 gb(Np / 32, Kp / 32), gg(Np / 64, Mp / 64);
-                auto go = [&](auto lc_) {
-                    constexpr int LL = decltype(lc_)::value;
-                    hipLaunchKernelGGL((k_limb_split_a<F, LL>), dim3(ga), dim3(BLOCK), 0, st, (const E*)A, lda, pmod, Ap, M, K, Mp, Kp);
-                    // up to 128 rows of 64-bit elements: the product kernel converts B itself (BRAW), no digit planes of B --
-                    // for whole tiles and 16-byte aligned rows of B; ragged shapes go through the planes
-                    constexpr bool CAN_RAW = LL == 8 && sizeof(E) == 8;
-                    const bool braw = CAN_RAW && gg.y <= 2 && K % 32 == 0 && N % 64 == 0 && ldb % 2 == 0 && (((uintptr_t)B) & 15) == 0;
-                    if (!braw)
-                        hipLaunchKernelGGL((k_limb_split_bt<F, LL>), gb, dim3(BLOCK), 0, st, (const E*)B, ldb, pmod, Bp, K, N, Np, Kp);
-                    auto product = [&](dim3 grid, E* out, size_t out_ld, int kb, int ke, int acc_, int kslice, size_t zs) {
-                        if constexpr (CAN_RAW) {
-                            if (braw) launch_glds<true>(f, grid, st, Ap, (const int8_t*)nullptr, out, out_ld, M, N, Kp, kb, ke, acc_, kslice, zs, (const E*)B, ldb, pmod);
-                            else launch_glds<false>(f, grid, st, Ap, Bp, out, out_ld, M, N, Kp, kb, ke, acc_, kslice, zs, (const E*)nullptr, (size_t)0, (uint64_t)0);
-                        } else {
-                            hipLaunchKernelGGL((k_limb_gemm_l4<F>), grid, dim3(BLOCK), 0, st, f, (const int8_t*)Ap, (const int8_t*)Bp, out,
-                                               out_ld, M, N, Kp, kb, ke, acc_, kslice, zs);
-                        }
-                    };
-                    // few output tiles (a batch of 64..256 rows against a big matrix): split K over blockIdx.z into
-                    // slabs behind the planes, summed by k_splitk_sum
-                    const size_t tiles = (size_t)gg.x * gg.y;
-                    int ks = 1;
-                    if (tiles <= 128 && Kp >= 512) {
-                        // ONE round of workgroups (a workgroup holds a CU: 512 registers per lane): tiles x slabs ~ CUs.
-                        // Measured (round 4, 64 x 4096 x 4096): 256 workgroups 94 us, 384: 127, 512: 107, 768: 117, 1536: 121
-                        // -- every extra slab repeats the epilogue and the pipeline fill.
-                        const int ncu = lc.num_cu;
-                        const int target = ncu > 0 ? ncu : 256;
-                        ks = (int)((target + tiles - 1) / tiles);
-                        if (ks > Kp / 256) ks = Kp / 256;
-                        while (ks > 1 && need + 256 + (size_t)ks * M * N * sizeof(E) > workspace_bytes) --ks;
-                    }
-                    if (ks > 1 && Kp <= LIMB_KCHUNK) {
-                        const int kslice = ((Kp + ks - 1) / ks + 31) / 32 * 32;
-                        ks = (Kp + kslice - 1) / kslice;
-                        E* slabs = (E*)((char*)workspace + ((need + 255) / 256) * 256);
-                        dim3 g3(gg.x, gg.y, ks);
-                        product(g3, slabs, (size_t)N, 0, Kp, 0, kslice, (size_t)M * N);
-                        hipLaunchKernelGGL((k_splitk_sum<F>), dim3((unsigned)(((size_t)M * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, f,
-                                           (const E*)slabs, ks, M, N, (E*)C, ldc);
-                        return;
-                    }
-                    for (int kb = 0; kb < Kp; kb += LIMB_KCHUNK) {
-                        const int ke = kb + LIMB_KCHUNK < Kp ? kb + LIMB_KCHUNK : Kp;
-                        product(gg, (E*)C, ldc, kb, ke, kb > 0 ? 1 : 0, 0, (size_t)0);
+            const size_t need = mfma_plane_bytes(lc, L, M, K, N);
+            if (!need || !m.ws || need > m.ws_bytes) return false;
+            int8_t* Ap = (int8_t*)m.ws;
+            int8_t* Bp = Ap + (size_t)L * Mp * Kp;
+            const unsigned ga = (unsigned)(((size_t)Mp * Kp + BLOCK - 1) / BLOCK);
+            dim3 gb(Np / 32, Kp / 32), gg(Np / 64, Mp / 64);
+            auto go = [&](auto lc_) {
+                constexpr int LL = decltype(lc_)::value;
+                hipLaunchKernelGGL((k_limb_split_a<F, LL>), dim3(ga), dim3(BLOCK), 0, m.st, m.A, m.lda, pmod, Ap, M, K, Mp, Kp);
+                // up to 128 rows of 64-bit elements: the product kernel converts B itself (BRAW), no digit planes of B --
+                // for whole tiles and 16-byte aligned rows of B; ragged shapes go through the planes
+                constexpr bool CAN_RAW = LL == 8 && sizeof(E) == 8;
+                const bool braw = CAN_RAW && gg.y <= 2 && K % 32 == 0 && N % 64 == 0 && m.ldb % 2 == 0 && (((uintptr_t)m.B) & 15) == 0;
+                if (!braw)
+                    hipLaunchKernelGGL((k_limb_split_bt<F, LL>), gb, dim3(BLOCK), 0, m.st, m.B, m.ldb, pmod, Bp, K, N, Np, Kp);
+                auto product = [&](dim3 grid, E* out, size_t out_ld, int kb, int ke, int acc_, int kslice, size_t zs) {
+                    if constexpr (CAN_RAW) {
+                        if (braw) launch_glds<true>(f, grid, m.st, Ap, (const int8_t*)nullptr, out, out_ld, M, N, Kp, kb, ke, acc_, kslice, zs, m.B, m.ldb, pmod);
+                        else launch_glds<false>(f, grid, m.st, Ap, Bp, out, out_ld, M, N, Kp, kb, ke, acc_, kslice, zs, (const E*)nullptr, (size_t)0, (uint64_t)0);
+                    } else {
+                        hipLaunchKernelGGL((k_limb_gemm_l4<F>), grid, dim3(BLOCK), 0, m.st, f, (const int8_t*)Ap, (const int8_t*)Bp, out,
+                                           out_ld, M, N, Kp, kb, ke, acc_, kslice, zs);
                     }
                 };
-                if (L == 4) go(std::integral_constant<int, 4>());
-                else go(std::integral_constant<int, 8>());
-                FFGPU_CHECK_LAUNCH();
-                return 0;
-            }
+                // few output tiles (a batch of 64..256 rows against a big matrix): split K over blockIdx.z into
+                // slabs behind the planes, summed by k_splitk_sum
+                const size_t tiles = (size_t)gg.x * gg.y;
+                int ks = 1;
+                if (tiles <= 128 && Kp >= 512) {
+                    // ONE round of workgroups (a workgroup holds a CU: 512 registers per lane): tiles x slabs ~ CUs.
+                    // Measured (round 4, 64 x 4096 x 4096): 256 workgroups 94 us, 384: 127, 512: 107, 768: 117, 1536: 121
+                    // -- every extra slab repeats the epilogue and the pipeline fill.
+                    ks = (int)((lc.num_cu + tiles - 1) / tiles);
+                    if (ks > Kp / 256) ks = Kp / 256;
+                    while (ks > 1 && need + 256 + (size_t)ks * M * N * sizeof(E) > m.ws_bytes) --ks;
+                }
+                if (ks > 1 && Kp <= LIMB_KCHUNK) {
+                    const int kslice = ((Kp + ks - 1) / ks + 31) / 32 * 32;
+                    ks = (Kp + kslice - 1) / kslice;
+                    E* slabs = (E*)((char*)m.ws + ((need + 255) / 256) * 256);
+                    dim3 g3(gg.x, gg.y, ks);
+                    product(g3, slabs, (size_t)N, 0, Kp, 0, kslice, (size_t)M * N);
+                    hipLaunchKernelGGL((k_splitk_sum<F>), dim3((unsigned)(((size_t)M * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, m.st, f,
+                                       (const E*)slabs, ks, M, N, m.C, m.ldc);
+                    return;
+                }
+                for (int kb = 0; kb < Kp; kb += LIMB_KCHUNK) {
+                    const int ke = kb + LIMB_KCHUNK < Kp ? kb + LIMB_KCHUNK : Kp;
+                    product(gg, m.C, m.ldc, kb, ke, kb > 0 ? 1 : 0, 0, (size_t)0);
+                }
+            };
+            if (L == 4) go(std::integral_constant<int, 4>());
+            else go(std::integral_constant<int, 8>());
+            return true;
         }
+        return false;
+    }
+    // primes of 65..128 bits: the matrix-core product in passes over the diagonals (k_limb_gemm_wide)
+    static bool mm_mfma_wide(const F& f, const LaunchCfg& lc, const Mat& m) {
         if constexpr (F::EPW == 1 && !F::BINARY && sizeof(W) == 16) {
-            // primes of 65..128 bits: the matrix-core product in passes over the diagonals (k_limb_gemm_wide)
+            const int M = m.M, K = m.K, N = m.N;
             constexpr int LW = sizeof(E) == 12 ? 12 : 16;
             const int Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
-            const size_t need = (size_t)LW * ((size_t)Mp + Np) * Kp;
-            if (use_mfma && M > SKINNY_MAX && N > SKINNY_MAX && K >= 64 && (double)M * N * K >= mfma_min && workspace &&
-                need <= workspace_bytes) {
-                int8_t* Ap = (int8_t*)workspace;
-                int8_t* Bp = Ap + (size_t)LW * Mp * Kp;
-                const unsigned ga = (unsigned)(((size_t)Mp * Kp + BLOCK - 1) / BLOCK);
-                dim3 gb(Np / 32, Kp / 32), gg(Np / 64, Mp / 64);
-                hipLaunchKernelGGL((k_limb_split_a_wide<F, LW>), dim3(ga), dim3(BLOCK), 0, st, (const E*)A, lda, f.p_lo, f.p_hi, Ap, M,
-                                   K, Mp, Kp);
-                hipLaunchKernelGGL((k_limb_split_bt_wide<F, LW>), gb, dim3(BLOCK), 0, st, (const E*)B, ldb, f.p_lo, f.p_hi, Bp, K, N,
-                                   Np, Kp);
-                // 256^D0 mod p by repeated doubling of the canonical 1 (host, canonical arithmetic of the policy)
-                auto pow256 = [&](int d0) {
-                    W v;
-                    v.lo = 1;
-                    v.hi = 0;
-                    for (int i = 0; i < 8 * d0; ++i) v = f.add(v, v);
-                    return v;
+            const size_t need = mfma_plane_bytes(lc, LW, M, K, N);
+            if (!need || !m.ws || need > m.ws_bytes) return false;
+            int8_t* Ap = (int8_t*)m.ws;
+            int8_t* Bp = Ap + (size_t)LW * Mp * Kp;
+            const unsigned ga = (unsigned)(((size_t)Mp * Kp + BLOCK - 1) / BLOCK);
+            dim3 gb(Np / 32, Kp / 32), gg(Np / 64, Mp / 64);
+            hipLaunchKernelGGL((k_limb_split_a_wide<F, LW>), dim3(ga), dim3(BLOCK), 0, m.st, m.A, m.lda, f.p_lo, f.p_hi, Ap, M,
+                               K, Mp, Kp);
+            hipLaunchKernelGGL((k_limb_split_bt_wide<F, LW>), gb, dim3(BLOCK), 0, m.st, m.B, m.ldb, f.p_lo, f.p_hi, Bp, K, N,
+                               Np, Kp);
+            // 256^D0 mod p by repeated doubling of the canonical 1 (host, canonical arithmetic of the policy)
+            auto pow256 = [&](int d0) {
+                W v;
+                v.lo = 1;
+                v.hi = 0;
+                for (int i = 0; i < 8 * d0; ++i) v = f.add(v, v);
+                return v;
+            };
+            bool first = true;
+            for (int kb = 0; kb < Kp; kb += LIMB_KCHUNK_WIDE) {
+                const int ke = kb + LIMB_KCHUNK_WIDE < Kp ? kb + LIMB_KCHUNK_WIDE : Kp;
+                auto pass = [&](auto d0_, auto ndp_) {
+                    constexpr int D0 = decltype(d0_)::value, NDP = decltype(ndp_)::value;
+                    hipLaunchKernelGGL((k_limb_gemm_wide<F, LW, D0, NDP>), gg, dim3(BLOCK), 0, m.st, f, (const int8_t*)Ap,
+                                       (const int8_t*)Bp, m.C, m.ldc, M, N, Mp, Np, Kp, kb, ke, first ? 0 : 1, pow256(D0));
+                    first = false;
                 };
-                bool first = true;
-                for (int kb = 0; kb < Kp; kb += LIMB_KCHUNK_WIDE) {
-                    const int ke = kb + LIMB_KCHUNK_WIDE < Kp ? kb + LIMB_KCHUNK_WIDE : Kp;
-                    auto pass = [&](auto d0_, auto ndp_) {
-                        constexpr int D0 = decltype(d0_)::value, NDP = decltype(ndp_)::value;
-                        hipLaunchKernelGGL((k_limb_gemm_wide<F, LW, D0, NDP>), gg, dim3(BLOCK), 0, st, f, (const int8_t*)Ap,
-                                           (const int8_t*)Bp, (E*)C, ldc, M, N, Mp, Np, Kp, kb, ke, first ? 0 : 1, pow256(D0));
-                        first = false;
-                    };
-                    if constexpr (LW == 12) {            // 23 diagonals: 12 + 11
-                        pass(std::integral_constant<int, 0>(), std::integral_constant<int, 12>());
-                        pass(std::integral_constant<int, 12>(), std::integral_constant<int, 11>());
-                    } else {                              // 31 diagonals: 11 + 10 + 10
-                        pass(std::integral_constant<int, 0>(), std::integral_constant<int, 11>());
-                        pass(std::integral_constant<int, 11>(), std::integral_constant<int, 10>());
-                        pass(std::integral_constant<int, 21>(), std::integral_constant<int, 10>());
-                    }
+                if constexpr (LW == 12) {            // 23 diagonals: 12 + 11
+                    pass(std::integral_constant<int, 0>(), std::integral_constant<int, 12>());
+                    pass(std::integral_constant<int, 12>(), std::integral_constant<int, 11>());
+                } else {                              // 31 diagonals: 11 + 10 + 10
+                    pass(std::integral_constant<int, 0>(), std::integral_constant<int, 11>());
+                    pass(std::integral_constant<int, 11>(), std::integral_constant<int, 10>());
+                    pass(std::integral_constant<int, 21>(), std::integral_constant<int, 10>());
                 }
-                FFGPU_CHECK_LAUNCH();
-                return 0;
             }
+            return true;
         }
+        return false;
+    }
+    // every other product: tiles on the vector ALUs
+    static void mm_valu(const F& f, const Mat& m) {
+        const int M = m.M, K = m.K, N = m.N;
         if constexpr (F::EPW > 1) {
             dim3 grid((N + 31) / 32, (M + 31) / 32);
-            hipLaunchKernelGGL((k_matmul_bytes<F>), grid, dim3(BLOCK), 0, st, f, (const uint8_t*)A, lda,
-                               (const uint8_t*)B, ldb, (uint8_t*)C, ldc, M, K, N);
+            hipLaunchKernelGGL((k_matmul_bytes<F>), grid, dim3(BLOCK), 0, m.st, f, (const uint8_t*)m.A, m.lda,
+                               (const uint8_t*)m.B, m.ldb, (uint8_t*)m.C, m.ldc, M, K, N);
         } else {
             // 4 x 2 outputs per thread: measured best (1.93 T MAC/s at 4096^3 over GF(2^61-1))
             // small outputs (a 64 x 64 product is two 64 x 32 tiles): 32 x 32 tiles give four times as many workgroups
             const bool small_out = ((M + 63) / 64) * ((N + 31) / 32) < 64;
-            const int tcode = (sizeof(W) >= 16 || small_out) ? 22 : 42;   // two- and three-limb words: 2x2 keeps two waves per SIMD
-            const int bm = tcode == 42 ? 64 : 32;
+            const bool t42 = !(sizeof(W) >= 16 || small_out);   // two- and three-limb words: 2x2 keeps two waves per SIMD
+            const int bm = t42 ? 64 : 32;
             const int bn = 32;
             dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm);
             // too few output tiles to fill 256 CUs: split K over blockIdx.z into slabs of the workspace
             int ks = 1, kchunk = 0;
             const size_t tiles = (size_t)grid.x * grid.y;
-            E* out = (E*)C;
-            size_t out_ld = ldc, zstride = 0;
-            if (tiles < 512 && K >= 64 && workspace) {
+            E* out = m.C;
+            size_t out_ld = m.ldc, zstride = 0;
+            if (tiles < 512 && K >= 64 && m.ws) {
                 ks = (int)((1024 + tiles - 1) / tiles);
                 if (ks > K / 32) ks = K / 32;
-                while (ks > 1 && (size_t)ks * M * N * sizeof(E) > workspace_bytes) ks /= 2;
+                while (ks > 1 && (size_t)ks * M * N * sizeof(E) > m.ws_bytes) ks /= 2;
                 if (ks > 1) {
                     kchunk = ((K + ks - 1) / ks + 15) / 16 * 16;
                     ks = (K + kchunk - 1) / kchunk;
                     grid.z = ks;
-                    out = (E*)workspace;
+                    out = (E*)m.ws;
                     out_ld = N;
                     zstride = (size_t)M * N;
                 }
             }
             if (ks <= 1) kchunk = 0;
-            const E* a = (const E*)A; const E* b = (const E*)B;
-            if (tcode == 42)
-                hipLaunchKernelGGL((k_matmul<F, 4, 2>), grid, dim3(BLOCK), 0, st, f, a, lda, b, ldb, out, out_ld, M, K, N, kchunk, zstride);
-            else if (tcode == 22)
-                hipLaunchKernelGGL((k_matmul<F, 2, 2>), grid, dim3(BLOCK), 0, st, f, a, lda, b, ldb, out, out_ld, M, K, N, kchunk, zstride);
-            else if (tcode == 84)
-                hipLaunchKernelGGL((k_matmul<F, 8, 4>), grid, dim3(BLOCK), 0, st, f, a, lda, b, ldb, out, out_ld, M, K, N, kchunk, zstride);
+            if (t42)
+                hipLaunchKernelGGL((k_matmul<F, 4, 2>), grid, dim3(BLOCK), 0, m.st, f, m.A, m.lda, m.B, m.ldb, out, out_ld, M, K, N, kchunk, zstride);
             else
-                hipLaunchKernelGGL((k_matmul<F, 4, 4>), grid, dim3(BLOCK), 0, st, f, a, lda, b, ldb, out, out_ld, M, K, N, kchunk, zstride);
+                hipLaunchKernelGGL((k_matmul<F, 2, 2>), grid, dim3(BLOCK), 0, m.st, f, m.A, m.lda, m.B, m.ldb, out, out_ld, M, K, N, kchunk, zstride);
             if (ks > 1)
-                hipLaunchKernelGGL((k_splitk_sum<F>), dim3((unsigned)(((size_t)M * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, f,
-                                   (const E*)workspace, ks, M, N, (E*)C, ldc);
+                hipLaunchKernelGGL((k_splitk_sum<F>), dim3((unsigned)(((size_t)M * N + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, m.st, f,
+                                   (const E*)m.ws, ks, M, N, m.C, m.ldc);
         }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+    }
+    static LaunchStatus matmul(const void* Fp, const LaunchCfg& lc, const void* A, size_t lda, const void* B, size_t ldb, void* C,
+                               size_t ldc, int M, int K, int N, void* workspace, size_t workspace_bytes, hipStream_t st) {
+        const F& f = policy(Fp);
+        const Mat m = {(const E*)A, lda, (const E*)B, ldb, (E*)C, ldc, M, K, N, workspace, workspace_bytes, st};
+        if (!mm_skinny_n(f, lc, m) && !mm_skinny_m(f, lc, m) && !mm_mfma(f, lc, m) && !mm_mfma_wide(f, lc, m)) mm_valu(f, m);
+        return launched();
     }
     // Shape by output count (convolve_geom.hpp): wide tiles once they give every compute unit lc.conv_wide_per_cu of them,
     // narrow ones below that, so that few outputs with many taps still fill the chip.  Neither needs scratch.
     template <class S>
-    static int go_convolve(const F& f, const E* a, size_t na, const E* v, size_t nv, E* out, hipStream_t st) {
+    static LaunchStatus go_convolve(const F& f, const E* a, size_t na, const E* v, size_t nv, E* out, hipStream_t st) {
         const size_t tiles = conv_tiles(na + nv - 1, S::TO);
-        if (tiles > 0x7fffffffu) return 1;
+        if (tiles > 0x7fffffffu) return L_BAD_ARG;
         hipLaunchKernelGGL((k_convolve<F, S>), dim3((unsigned)tiles), dim3(BLOCK), 0, st, f, a, na, v, nv, out);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int convolve(const void* Fp, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
+    static LaunchStatus convolve(const void* Fp, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
                         hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         if (conv_use_wide(na + nv - 1, lc.num_cu, lc.conv_wide_per_cu))
             return go_convolve<ConvWide>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
         return go_convolve<ConvNarrow>(f, (const E*)a, na, (const E*)v, nv, (E*)out, st);
@@ -914,41 +902,39 @@ struct Launchers {
         }
     }
     template <bool MUL, bool RED>
-    static int go_scan(const F& f, const LaunchCfg& lc, const E* a, E* out, size_t outer, size_t k, size_t inner, int wi,
+    static LaunchStatus go_scan(const F& f, const LaunchCfg& lc, const E* a, E* out, size_t outer, size_t k, size_t inner, int wi,
                        E* ws, size_t ws_bytes, hipStream_t st) {
         static_assert((int)EPV == (int)(sizeof(E) <= 8 ? 16 / sizeof(E) : 1), "scan_epv mirrors the pack size");
         const ScanPlan p = scan_plan(outer, k, inner, sizeof(E), al(a) && al(out), lc.num_cu, lc.scan_geom,
                                      lc.scan_tile_threads, wi);
-        if (!p.ok) return 4;
+        if (!p.ok) return L_PLAN_REFUSED;
         if (p.geom == SCAN_COLS) {
             hipLaunchKernelGGL((k_scan_cols<F, MUL, RED>), dim3(grid_for(p.units, lc)), dim3(BLOCK), 0, st, f, a, out, k, inner,
                                p.per, p.units, p.vec, wi);
-            FFGPU_CHECK_LAUNCH();
-            return 0;
+            return launched();
         }
         const unsigned blocks = (unsigned)(p.lines * p.ntiles), lines = (unsigned)p.lines;
-        if (p.ntiles > 1 && (!ws || ws_bytes / sizeof(E) < p.ws_elems)) return 5;
+        if (p.ntiles > 1 && (!ws || ws_bytes / sizeof(E) < p.ws_elems)) return L_WS_TOO_SMALL;
         if (inner == 1) go_scan_rows<MUL, RED, true>(f, p, a, out, k, inner, wi, ws, st, blocks, lines);
         else go_scan_rows<MUL, RED, false>(f, p, a, out, k, inner, wi, ws, st, blocks, lines);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int scan(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
+    static LaunchStatus scan(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k, size_t inner,
                     int with_initial, void* workspace, size_t workspace_bytes, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const int wi = with_initial ? 1 : 0;
         if (mul) return go_scan<true, false>(f, lc, (const E*)a, (E*)out, outer, k, inner, wi, (E*)workspace, workspace_bytes, st);
         return go_scan<false, false>(f, lc, (const E*)a, (E*)out, outer, k, inner, wi, (E*)workspace, workspace_bytes, st);
     }
-    static int axis_reduce(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
+    static LaunchStatus axis_reduce(const void* Fp, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
                            size_t inner, void* workspace, size_t workspace_bytes, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         if (mul) return go_scan<true, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
         return go_scan<false, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
     }
-    static int dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
+    static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const size_t nvec = plan(n, al(a) && (!b || al(b)), lc).nvec;
         size_t iters = nvec ? nvec : n;
         size_t want = (iters + (size_t)BLOCK * 8 - 1) / ((size_t)BLOCK * 8);     // >= 8 packs per thread
@@ -961,24 +947,22 @@ struct Launchers {
             hipLaunchKernelGGL((k_dot_partial<F, false>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)a,
                                part, nvec, n);
         hipLaunchKernelGGL((k_dot_final<F>), dim3(1), dim3(BLOCK), 0, st, f, (const W*)part, (int)grid, (E*)out);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int sqrt_cl(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out,
+    static LaunchStatus sqrt_cl(const void* Fp, const LaunchCfg& lc, const void* a, const ExpArgs* eleg, const ExpArgs* elad, void* out,
                        size_t n, hipStream_t st) {
         if constexpr (F::BINARY) {
-            return 2;
+            return L_NOT_SUPPORTED;
         } else {
-            const F& f = *reinterpret_cast<const F*>(Fp);
+            const F& f = policy(Fp);
                 unsigned grid = grid_for(n, lc);
             hipLaunchKernelGGL((k_sqrt_cl<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, *eleg, *elad, (E*)out, n);
-            FFGPU_CHECK_LAUNCH();
-            return 0;
+            return launched();
         }
     }
-    static int gauss(const void* Fp, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode,
+    static LaunchStatus gauss(const void* Fp, const LaunchCfg& lc, void* A, int n, int ncols, size_t batch, int det_mode,
                      const ExpArgs* ex, void* det, int* sing, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         constexpr int TI = 4;
         constexpr size_t ZMAX = 32768;                    // grid.z limit: larger batches go in chunks
         for (size_t b0 = 0; b0 < batch; b0 += ZMAX) {
@@ -997,13 +981,12 @@ struct Launchers {
                 }
             }
         }
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int group_matvec(const void* Fp, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
+    static LaunchStatus group_matvec(const void* Fp, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int r, int g,
                             const void* in, void* out, size_t ngroups, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
-        if (r < 1 || g < 1 || r > GM_MAX || g > GM_MAX) return 2;
+        const F& f = policy(Fp);
+        if (r < 1 || g < 1 || r > GM_MAX || g > GM_MAX) return L_NOT_SUPPORTED;
         GroupMatArgs<F> ga;
         memset(&ga, 0, sizeof(ga));
         for (int i = 0; i < r * g; ++i) ga.m[i] = f.prep(word_at<F>(f, m2, i));
@@ -1020,34 +1003,30 @@ struct Launchers {
             if (g == 8 && r == 8 && al8 && (((uintptr_t)out) & 7u) == 0) {
                 hipLaunchKernelGGL((k_group8_bytes<F, 8>), dim3(grid), dim3(BLOCK), 0, st, f, ga, (const uint8_t*)in,
                                    (uint8_t*)out, ngroups);
-                FFGPU_CHECK_LAUNCH();
-                return 0;
+                return launched();
             }
             if (g == 8 && r == 1 && al8) {
                 hipLaunchKernelGGL((k_group8_bytes<F, 1>), dim3(grid), dim3(BLOCK), 0, st, f, ga, (const uint8_t*)in,
                                    (uint8_t*)out, ngroups);
-                FFGPU_CHECK_LAUNCH();
-                return 0;
+                return launched();
             }
         }
         hipLaunchKernelGGL((k_group_matvec<F>), dim3(grid), dim3(BLOCK), 0, st, f, ga, (const E*)in, (E*)out, ngroups);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int beaver(const void* Fp, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d,
+    static LaunchStatus beaver(const void* Fp, const LaunchCfg& lc, const void* z, const void* x, const void* y, const void* d,
                       const void* e, void* out, int add_de, size_t n, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
+        const F& f = policy(Fp);
         const Plan p = plan(n, al(z) && al(x) && al(y) && al(d) && al(e) && al(out), lc);
         hipLaunchKernelGGL((k_beaver<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)z, (const E*)x, (const E*)y,
                            (const E*)d, (const E*)e, (E*)out, add_de, p.nvec, n);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
-    static int prss(const void* Fp, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
+    static LaunchStatus prss(const void* Fp, const LaunchCfg& lc, const void* const* streams, int ks, int d, int l, int mask_bits,
                     const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n,
                     hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
-        if (ks < 1 || d < 1 || l < 1 || ks > PRSS_MAXS || ks * d > PRSS_MAXW) return 2;
+        const F& f = policy(Fp);
+        if (ks < 1 || d < 1 || l < 1 || ks > PRSS_MAXS || ks * d > PRSS_MAXW) return L_NOT_SUPPORTED;
         PrssArgs<F> pa;
         memset(&pa, 0, sizeof(pa));
         for (int s = 0; s < ks; ++s) pa.streams[s] = (const uint8_t*)streams[s];
@@ -1058,14 +1037,13 @@ struct Launchers {
         pa.ks = ks; pa.d = d; pa.l = l; pa.mask_bits = mask_bits; pa.accumulate = accumulate;
         unsigned grid = grid_for(n, lc);
         hipLaunchKernelGGL((k_prss<F>), dim3(grid), dim3(BLOCK), 0, st, f, pa, (E*)out, n);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
 
-    static int prss_chacha(const void* Fp, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
+    static LaunchStatus prss_chacha(const void* Fp, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                            const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st) {
-        const F& f = *reinterpret_cast<const F*>(Fp);
-        if (ks < 1 || d < 1 || l < 1 || l > 64 || ks > PRSS_CC_MAXS || ks * d > PRSS_CC_MAXW) return 2;
+        const F& f = policy(Fp);
+        if (ks < 1 || d < 1 || l < 1 || l > 64 || ks > PRSS_CC_MAXS || ks * d > PRSS_CC_MAXW) return L_NOT_SUPPORTED;
         PrssCcArgs<F> pa;
         memset(&pa, 0, sizeof(pa));
         for (int s = 0; s < ks; ++s) {
@@ -1080,14 +1058,49 @@ struct Launchers {
         const size_t tiles = (n + (size_t)pa.dpt - 1) / (size_t)pa.dpt;
         const unsigned grid = (unsigned)((tiles + BLOCK - 1) / BLOCK);
         hipLaunchKernelGGL((k_prss_chacha<F>), dim3(grid), dim3(BLOCK), 0, st, f, pa, (E*)out, n);
-        FFGPU_CHECK_LAUNCH();
-        return 0;
+        return launched();
     }
 
     static const FieldOps* table() {
-        static const FieldOps ops = {&ew2, &ew1, &muladd, &split, &rng_coeffs, &recombine, &pow, &inv, &matmul, &dot, &gate, &sqrt_cl, &gauss, &group_matvec, &beaver, &prss, &prss_chacha, &convolve, &scan, &axis_reduce};
+        static const FieldOps ops = {
+            .ew2 = &ew2, .ew1 = &ew1, .muladd = &muladd, .split = &split, .rng_coeffs = &rng_coeffs,
+            .recombine = &recombine, .pow = &pow, .inv = &inv, .matmul = &matmul, .dot = &dot,
+            .gate = &gate, .sqrt_cl = &sqrt_cl, .gauss = &gauss, .group_matvec = &group_matvec, .beaver = &beaver,
+            .prss = &prss, .prss_chacha = &prss_chacha, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce};
         return &ops;
     }
 };
 
 }  // namespace ffgpu
+
+// ---- misc.hip: kernels outside the per-policy tables (GF(2^8) S-box steps, GF(2^n) table products, copy, probes) ----
+// Declared here, once, for misc.hip and api.hip.
+int ffgpu_sbox_build_lut(const void* gf2p8_policy, const uint8_t* rows8, uint8_t b, uint8_t* lut256);
+bool ffgpu_gf8_build_tables(const void* policy, void* tables_out);     // false: no generator found, no tables
+int ffgpu_gf2w_build_rtable(const void* policy, int limbs, void* rtable_out);
+void ffgpu_gf8_sbox_layer_tables(const void* policy, const void* mul_tables, const uint64_t* m2, const uint64_t* bias2,
+                                 unsigned char* out);
+ffgpu::LaunchStatus ffgpu_launch_sbox(const uint8_t* lut256, const ffgpu::LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf8_to_bits(const ffgpu::LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf8_mask_open(const void* policy, const ffgpu::LaunchCfg& lc, const void* const* rows, const uint64_t* coef2,
+                                               int nrows, const void* const* rbits, const uint64_t* mu2, int np, void* out, size_t n,
+                                               hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf8_bits_affine_fold(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2,
+                                                      const void* c, const void* rbits, size_t ybr, void* out, size_t ybo, size_t n,
+                                                      int nbatch, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf8_group8(const void* policy, const ffgpu::LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
+                                            const void* in, void* out, size_t ngroups, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf8_sbox_layer(const void* policy, const ffgpu::LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs,
+                                                void* out, size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2,
+                                                int t, int m, size_t n, hipStream_t st, const ffgpu::RngArgs* rng);
+ffgpu::LaunchStatus ffgpu_launch_gf8_mul_tab(const void* tables, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
+                                             hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const ffgpu::LaunchCfg& lc, const void* a,
+                                              const void* b, void* out, size_t n, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out,
+                                                      size_t n, hipStream_t st, size_t* done);
+ffgpu::LaunchStatus ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const ffgpu::LaunchCfg& lc, const void* const* rows,
+                                                const uint64_t* lam2, int k, void* out, size_t n, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_copy(const ffgpu::LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_valu_probe(const ffgpu::LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out,
+                                            hipStream_t st);

@@ -68,15 +68,14 @@ int ffgpu_sbox_build_lut(const void* policy, const uint8_t* rows8, uint8_t b, ui
     return 0;
 }
 
-int ffgpu_launch_sbox(const uint8_t* lut256, const LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st) {
+LaunchStatus ffgpu_launch_sbox(const uint8_t* lut256, const LaunchCfg& lc, const void* in, void* out, size_t n, hipStream_t st) {
     SboxLut tab;
     memcpy(tab.v, lut256, 256);
     bool vec = aligned16(in) && aligned16(out);
     size_t nvec = vec ? n / 16 : 0;
     unsigned grid = grid_for(nvec ? nvec : n, lc);      // uncapped: the per-workgroup table copy is cheap (measured best)
     hipLaunchKernelGGL(k_sbox, dim3(grid), dim3(BLOCK), 0, st, tab, (const uint8_t*)in, (uint8_t*)out, nvec, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- GF(2^8): public byte -> its 8 bits as field elements, optionally added to bit shares ----------
@@ -109,14 +108,13 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_to_bits(const uint8_t* __restrict
     }
 }
 
-int ffgpu_launch_gf8_to_bits(const LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st) {
+LaunchStatus ffgpu_launch_gf8_to_bits(const LaunchCfg& lc, const void* in, const void* addend, void* out, size_t n, hipStream_t st) {
     bool vec = (((uintptr_t)in) & 1u) == 0 && (((uintptr_t)out) & 15u) == 0 && (!addend || (((uintptr_t)addend) & 15u) == 0);
     size_t npair = vec ? n / 2 : 0;
     unsigned grid = grid_for(npair ? npair : n, lc);
     hipLaunchKernelGGL(k_gf8_to_bits, dim3(grid), dim3(BLOCK), 0, st, (const uint8_t*)in, (const uint8_t*)addend,
                        (uint8_t*)out, npair, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- GF(2^n<=8): a public 8x8 matrix over every group of 8 bytes, on packed bytes ---------------------
@@ -248,7 +246,7 @@ static bool gf8_group8_args(const GF2P8& f, const uint64_t* m2, const uint64_t* 
     return general;
 }
 
-int ffgpu_launch_gf8_group8(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
+LaunchStatus ffgpu_launch_gf8_group8(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, int fold,
                             const void* in, void* out, size_t ngroups, hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
     Gf8Group8Args ga;
@@ -262,8 +260,7 @@ int ffgpu_launch_gf8_group8(const void* policy, const LaunchCfg& lc, const uint6
     else if (fold) hipLaunchKernelGGL((k_gf8_group8<true, false>), dim3(grid), dim3(BLOCK), 0, st, f, ga, iv, ov, npack, ngroups);
     else if (general) hipLaunchKernelGGL((k_gf8_group8<false, true>), dim3(grid), dim3(BLOCK), 0, st, f, ga, iv, ov, npack, ngroups);
     else hipLaunchKernelGGL((k_gf8_group8<false, false>), dim3(grid), dim3(BLOCK), 0, st, f, ga, iv, ov, npack, ngroups);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- GF(2^8) secure bit decomposition, fused (runtime.py:4411-4423 + demos/np_aes.py:40-42) --------------
@@ -453,10 +450,10 @@ static void gf8_byte_tables(const GF2P8& f, const uint64_t* m2, const uint64_t* 
 }
 
 // rows / rbits: host arrays of device pointers; coef2 / mu2: canonical 2-limb host scalars
-int ffgpu_launch_gf8_mask_open(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* coef2, int nrows,
+LaunchStatus ffgpu_launch_gf8_mask_open(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* coef2, int nrows,
                                const void* const* rbits, const uint64_t* mu2, int np, void* out, size_t n, hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
-    if (nrows < 0 || nrows > GF8_MO_MAXROWS || np < 0 || np > GF8_MO_MAXP) return 2;
+    if (nrows < 0 || nrows > GF8_MO_MAXROWS || np < 0 || np > GF8_MO_MAXP) return L_NOT_SUPPORTED;
     static thread_local Gf8ByteTables tb;
     static thread_local uint32_t tb_for[3] = {~0u, 0, 0};
     if (tb_for[0] != f.n || tb_for[1] != f.red) {                  // sum_b 2^b x_b: depends on the field only
@@ -482,11 +479,10 @@ int ffgpu_launch_gf8_mask_open(const void* policy, const LaunchCfg& lc, const vo
     const size_t npair = vec ? n / 2 : 0;
     unsigned grid = grid_for(npair ? (npair + 1) / 2 : n, lc);
     hipLaunchKernelGGL(k_gf8_mask_open, dim3(grid), dim3(BLOCK), 0, st, f, tb, a, (uint8_t*)out, npair, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
-int ffgpu_launch_gf8_bits_affine_fold(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, const void* c,
+LaunchStatus ffgpu_launch_gf8_bits_affine_fold(const void* policy, const LaunchCfg& lc, const uint64_t* m2, const uint64_t* bias2, const void* c,
                                       const void* rbits, size_t ybr, void* out, size_t ybo, size_t n, int nbatch,
                                       hipStream_t st) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
@@ -498,8 +494,7 @@ int ffgpu_launch_gf8_bits_affine_fold(const void* policy, const LaunchCfg& lc, c
     unsigned grid = grid_for(npair ? (npair + 1) / 2 : n, lc);
     hipLaunchKernelGGL(k_gf8_bits_affine_fold, dim3(grid, (unsigned)nbatch), dim3(BLOCK), 0, st, tb,
                        (const uint8_t*)c, (const uint8_t*)rbits, ybr, (uint8_t*)out, ybo, npair, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- GF(2^8): the WHOLE secure S-box layer of all parties in one kernel (demos/np_aes.py:37-43) ------------------
@@ -853,11 +848,11 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
 // tables_dev: SBL_TABLE_BYTES of device memory (the caller caches it per matrix); returns 2 when the shape is not
 // covered (rows not 4- / 16-byte aligned, m > 7 or t > 3): the caller composes the layer from the per-step kernels
 // then.  Any n: the n % 4 bytes after the last whole word of each row are handled by one thread with byte accesses.
-int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs, void* out,
+LaunchStatus ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs, void* out,
                                 size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2, int t, int m,
                                 size_t n, hipStream_t st, const RngArgs* rng) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
-    if (f.n != 8 || (((uintptr_t)x | (uintptr_t)out | xs | os) & 3) || (((uintptr_t)r | rs) & 15)) return 2;
+    if (f.n != 8 || (((uintptr_t)x | (uintptr_t)out | xs | os) & 3) || (((uintptr_t)r | rs) & 15)) return L_NOT_SUPPORTED;
     Gf8SboxLayerArgs a;
     memset(&a, 0, sizeof(a));
     a.x = (const uint8_t*)x; a.r = (const uint8_t*)r; a.out = (uint8_t*)out;
@@ -877,7 +872,7 @@ int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const v
     // persistent above one round of resident workgroups (4 per CU at t = 1, m <= 4: 119-128 VGPRs; 3 for m >= 5; 2-3 per CU
     // for t >= 2): the threads of the t = 1 kernels then carry their keystream from step to step instead of discarding 15
     // of every 48 words
-    const size_t resident = (size_t)(lc.num_cu > 0 ? lc.num_cu : 256) * (t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2));
+    const size_t resident = (size_t)lc.num_cu * (t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2));
     if (want > resident) want = resident;
     const unsigned grid = (unsigned)want;
     {   // the keystream's counter ranges never meet: threads stream blocks [g * bpt, (g + 1) * bpt) (or step i its blocks
@@ -885,7 +880,7 @@ int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const v
         // re-draws elsewhere in the library from 2^63 -- refuse shapes that would leave their range (n > ~10^17 bytes)
         const uint64_t gsz = (uint64_t)grid * BLOCK;
         const uint64_t steps = (nthreads_full + gsz - 1) / gsz;
-        if (gsz * (2 * steps + 2) >= (1ull << 61) || gsz * (steps / 16 + 1) >= (1ull << 61) || nthreads_full * 16ull >= (1ull << 61)) return 2;
+        if (gsz * (2 * steps + 2) >= (1ull << 61) || gsz * (steps / 16 + 1) >= (1ull << 61) || nthreads_full * 16ull >= (1ull << 61)) return L_NOT_SUPPORTED;
     }
     // (measured and NOT kept, round 4: letting up to 1024 workgroups advance the state themselves with a ticket drawn at
     // workgroup START -- the returning atomic sits in front of the wave's first loads in the in-order vmcnt queue, and 977
@@ -898,7 +893,7 @@ int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const v
         FFGPU_CHECK_LAUNCH();                                                                                         \
         if (ra.dev_key && !ra.release && !ra.no_advance)                                                              \
             hipLaunchKernelGGL((k_rng_advance<0>), dim3(1), dim3(1), 0, st, const_cast<RngKey*>(ra.dev_key), 1u);     \
-        return 0;                                                                                                     \
+        return L_OK;                                                                                                  \
     }
 #define SBL_CASE(MM, TT)                                 \
     if (m == MM && t == TT) {                            \
@@ -908,7 +903,7 @@ int ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc, const v
     SBL_CASE(7, 3)
 #undef SBL_CASE
 #undef SBL_LAUNCH
-    return 2;
+    return L_NOT_SUPPORTED;
 }
 
 // host: the three tables of the layer in the layout the kernel expects
@@ -977,18 +972,20 @@ void k_gf2w64_mul_bitsliced(const uint4* a, const uint4* b, uint4* o, size_t nsl
             stg<true>(o + base + (size_t)r * 64, make_uint4(ov[2 * r], ov[16 + 2 * r], ov[2 * r + 1], ov[16 + 2 * r + 1]));
 }
 
-// returns the number of leading elements it has multiplied (all of them but the last one of an odd n; 0 = not applicable):
-// the caller sends the rest through the element-wise kernel
-size_t ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
-                                         hipStream_t st) {
+// *done: the number of leading elements it has multiplied (all of them but the last one of an odd n): the caller sends the
+// rest through the element-wise kernel.  L_DECLINED: not applicable, nothing launched
+LaunchStatus ffgpu_launch_gf2w64_mul_bitsliced(const void* policy, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
+                                               hipStream_t st, size_t* done) {
     const GF2W64& f = *reinterpret_cast<const GF2W64*>(policy);
-    if (f.n != 64 || f.red != 0x1bull || n < ((size_t)1 << 21) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15)) return 0;
+    *done = 0;
+    if (f.n != 64 || f.red != 0x1bull || n < ((size_t)1 << 21) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15)) return L_DECLINED;
     const size_t nvec4 = n / 2;
     const size_t nslab = (nvec4 + 511) / 512;
     const unsigned grid = (unsigned)((nslab + BLOCK / 64 - 1) / (BLOCK / 64));
     hipLaunchKernelGGL(k_gf2w64_mul_bitsliced, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)a, (const uint4*)b, (uint4*)out, nslab,
                        nvec4);
-    return nvec4 * 2;
+    *done = nvec4 * 2;
+    return launched();
 }
 
 // ---- GF(2^n), n <= 8: multiplication through log / antilog tables in LDS ---------------------
@@ -1038,7 +1035,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_mul_tab(Gf8Tables tb, const uint8
 }
 
 // host: build the tables for GF(2^n) (any irreducible modulus of degree n <= 8)
-int ffgpu_gf8_build_tables(const void* policy, void* tables_out) {
+bool ffgpu_gf8_build_tables(const void* policy, void* tables_out) {
     const GF2P8& f = *reinterpret_cast<const GF2P8*>(policy);
     Gf8Tables* tb = reinterpret_cast<Gf8Tables*>(tables_out);
     const uint32_t q1 = (1u << f.n) - 1;  // multiplicative order
@@ -1047,7 +1044,7 @@ int ffgpu_gf8_build_tables(const void* policy, void* tables_out) {
         tb->lg[0] = 2;
         tb->lg[1] = 0;
         tb->ex[0] = 1;
-        return 0;
+        return true;
     }
     for (uint32_t g = 2; g <= q1; ++g) {
         // order of g
@@ -1066,12 +1063,12 @@ int ffgpu_gf8_build_tables(const void* policy, void* tables_out) {
         }
         tb->lg[0] = (uint16_t)(2 * q1);   // 2*q1 .. 4*q1 stay zero in ex[]
         for (uint32_t v = q1 + 1; v < 256; ++v) tb->lg[v] = (uint16_t)(2 * q1);  // non-canonical bytes -> 0
-        return 0;
+        return true;
     }
-    return 1;
+    return false;
 }
 
-int ffgpu_launch_gf8_mul_tab(const void* tables, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
+LaunchStatus ffgpu_launch_gf8_mul_tab(const void* tables, const LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                              hipStream_t st) {
     const Gf8Tables& tb = *reinterpret_cast<const Gf8Tables*>(tables);
     bool vec = aligned16(a) && aligned16(b) && aligned16(out);
@@ -1079,8 +1076,7 @@ int ffgpu_launch_gf8_mul_tab(const void* tables, const LaunchCfg& lc, const void
     unsigned grid = grid_for(nvec ? nvec : n, lc);      // uncapped: the per-workgroup table copy is cheap (measured best)
     hipLaunchKernelGGL(k_gf8_mul_tab, dim3(grid), dim3(BLOCK), 0, st, tb, (const uint8_t*)a, (const uint8_t*)b,
                        (uint8_t*)out, nvec, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- GF(2^n), 9 <= n <= 128: 4-bit window multiplication with tables in LDS --------------------
@@ -1253,7 +1249,7 @@ int ffgpu_gf2w_build_rtable(const void* policy, int limbs, void* rtable_out) {
     return 0;
 }
 
-int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const LaunchCfg& lc, const void* a,
+LaunchStatus ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const LaunchCfg& lc, const void* a,
                               const void* b, void* out, size_t n, hipStream_t st) {
     const Gf2wRTable& rt = *reinterpret_cast<const Gf2wRTable*>(rtable);
     unsigned grid = grid_for(n, lc);
@@ -1276,8 +1272,7 @@ int ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable,
             hipLaunchKernelGGL((k_gf2w_mul_win<1, false>), dim3(grid), dim3(BLOCK), 0, st, f, rt, (const uint64_t*)a,
                                (const uint64_t*)b, (uint64_t*)out, n);
     }
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // LDS read at an ABSOLUTE byte offset of the workgroup's allocation (ds_read with the constant part of the address
@@ -1469,7 +1464,7 @@ __global__ __launch_bounds__(REC_BLOCK) __attribute__((amdgpu_waves_per_eu(DEEP 
 }
 
 template <int LIMBS, int KT, bool DEEP>
-static int launch_gf2w_rec(const void* policy, const LaunchCfg& lc, const Gf2wRecArgs<LIMBS>& ra, void* out, size_t n, hipStream_t st) {
+static LaunchStatus launch_gf2w_rec(const void* policy, const LaunchCfg& lc, const Gf2wRecArgs<LIMBS>& ra, void* out, size_t n, hipStream_t st) {
     typedef Gf2wTraits<LIMBS> Tr;
     const typename Tr::F& f = *reinterpret_cast<const typename Tr::F*>(policy);
     const size_t lds = (size_t)KT * 16 * LIMBS * 16 * sizeof(typename Tr::L);
@@ -1494,12 +1489,11 @@ static int launch_gf2w_rec(const void* policy, const LaunchCfg& lc, const Gf2wRe
     }
     hipLaunchKernelGGL((k_gf2w_recombine_tab<LIMBS, KT, DEEP>), dim3(grid ? grid : 1), dim3(REC_BLOCK), lds, st, f, ra,
                        (typename Tr::E*)out, n);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 template <int LIMBS>
-static int dispatch_gf2w_rec(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k, void* out,
+static LaunchStatus dispatch_gf2w_rec(const void* policy, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k, void* out,
                              size_t n, hipStream_t st) {
     Gf2wRecArgs<LIMBS> ra;
     memset(&ra, 0, sizeof(ra));
@@ -1538,21 +1532,18 @@ static int dispatch_gf2w_rec(const void* policy, const LaunchCfg& lc, const void
         }
     }
     // (DEEP = 16 look-ups per batch in flight for every table count > 0: the round-3 measurement; kt = 0 is a plain XOR)
-#define GF2W_REC_CASE(KK)                                                                         \
-    case KK:                                                                                      \
-        return launch_gf2w_rec<LIMBS, KK, (KK > 0)>(policy, lc, ra, out, n, st);
-    switch (kt) {
-        GF2W_REC_CASE(0) GF2W_REC_CASE(1) GF2W_REC_CASE(2) GF2W_REC_CASE(3) GF2W_REC_CASE(4) GF2W_REC_CASE(5)
-        GF2W_REC_CASE(6) GF2W_REC_CASE(7) GF2W_REC_CASE(8) GF2W_REC_CASE(9)
-        default: return 2;
-    }
-#undef GF2W_REC_CASE
+    LaunchStatus s = L_DECLINED;
+    dispatch_int(IntRange<0, REC_MAXK>(), kt, [&](auto kt_) {
+        constexpr int KK = decltype(kt_)::value;
+        s = launch_gf2w_rec<LIMBS, KK, (KK > 0)>(policy, lc, ra, out, n, st);
+    });
+    return s;
 }
 
-// k rows (1..9), one output row; limbs selects GF2W64 / GF2W128.  Returns 2 if the shape is not covered.
-int ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2,
+// k rows (1..9), one output row; limbs selects GF2W64 / GF2W128.  L_DECLINED if the shape is not covered.
+LaunchStatus ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2,
                                 int k, void* out, size_t n, hipStream_t st) {
-    if (k < 1 || k > REC_MAXK) return 2;
+    if (k < 1 || k > REC_MAXK) return L_DECLINED;
     return limbs == 2 ? dispatch_gf2w_rec<2>(policy, lc, rows, lam2, k, out, n, st)
                       : dispatch_gf2w_rec<1>(policy, lc, rows, lam2, k, out, n, st);
 }
@@ -1567,13 +1558,12 @@ __global__ __launch_bounds__(BLOCK) void k_copy16(const uint4* __restrict__ src,
     }
 }
 
-int ffgpu_launch_copy(const LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st) {
-    if (!aligned16(src) || !aligned16(dst) || (bytes & 15)) return 1;
+LaunchStatus ffgpu_launch_copy(const LaunchCfg& lc, const void* src, void* dst, size_t bytes, hipStream_t st) {
+    if (!aligned16(src) || !aligned16(dst) || (bytes & 15)) return L_BAD_ARG;
     size_t nvec = bytes / 16;
     unsigned grid = grid_for(nvec, lc);
     hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec, lc.keep_out);
-    FFGPU_CHECK_LAUNCH();
-    return 0;
+    return launched();
 }
 
 // ---- VALU issue-rate yardstick (the compute-side counterpart of k_copy16) --------------------------------------------
@@ -1634,17 +1624,17 @@ __global__ __launch_bounds__(BLOCK) void k_valu_probe(uint32_t* __restrict__ sin
 }
 
 // out[0] = lane-operations per second, out[1] = shader clock in MHz, out[2] = shader cycles per wave instruction and SIMD
-int ffgpu_launch_valu_probe(const LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st) {
+LaunchStatus ffgpu_launch_valu_probe(const LaunchCfg& lc, int op, int iters, int waves_per_simd, void* scratch32, double* out, hipStream_t st) {
     // SYNCHRONISES the stream (event + a blocking read-back of the cycle counts): a measurement aid, not capturable
-    if (op < 0 || op > 13 || iters < 1 || waves_per_simd < 1 || waves_per_simd > 8) return 1;
+    if (op < 0 || op > 13 || iters < 1 || waves_per_simd < 1 || waves_per_simd > 8) return L_BAD_ARG;
     const unsigned grid = (unsigned)(lc.num_cu * waves_per_simd);           // 256 threads = 4 waves = one per SIMD
     uint32_t* sink = (uint32_t*)scratch32;
     uint64_t* clk = (uint64_t*)((char*)scratch32 + 16);
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess) return 1;
+    if (hipEventCreate(&e0) != hipSuccess) return L_BAD_ARG;
     if (hipEventCreate(&e1) != hipSuccess) {
         (void)hipEventDestroy(e0);
-        return 1;
+        return L_BAD_ARG;
     }
     auto launch = [&](int n_it) {
 #define FF_PROBE_CASE(OPV) case OPV: hipLaunchKernelGGL(k_valu_probe<OPV>, dim3(grid), dim3(BLOCK), 0, st, sink, clk, n_it); break;
@@ -1665,10 +1655,10 @@ int ffgpu_launch_valu_probe(const LaunchCfg& lc, int op, int iters, int waves_pe
     if (err == hipSuccess) err = hipMemcpy(host_clk, clk, 16, hipMemcpyDeviceToHost);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (err != hipSuccess || ms <= 0.f) return 1;
+    if (err != hipSuccess || ms <= 0.f) return L_BAD_ARG;    // (a measurement aid: every failure reads "invalid argument")
     const double wave_instr = (double)grid * 4.0 * (double)iters * 128.0;
     out[0] = wave_instr * 64.0 / ((double)ms * 1e-3);
     out[1] = host_clk[1] ? (double)host_clk[0] / (double)host_clk[1] * 100.0 : 0.0;
     out[2] = (double)host_clk[0] / ((double)iters * 128.0 * (double)waves_per_simd);     // the timed wave shared its SIMD with the others
-    return 0;
+    return L_OK;
 }

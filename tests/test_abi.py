@@ -137,3 +137,110 @@ def test_empty_inputs_are_ok_everywhere(L):
     assert L.ffgpu_split(h, p, p, 0, 3, 3, p, 0, 0, None) == _ffi.EINVAL      # t must be < m
     assert L.ffgpu_gate_rng(h, rows, lam, 3, None, None, 0, key, 0, 20, None, 4, 9, p, 0, 0, None) == _ffi.ENOTSUP
     L.ffgpu_ctx_destroy(h)
+
+
+def test_statuses_before_device_work(L):
+    """Calls that every compute entry point answers before any device work (so this runs without a GPU), with the
+    status each one gives.  The values are those of the library before its host layer got one launcher status and one
+    call scope; they are pinned here so that a change of that layer cannot move them."""
+    from mpyc_amd import _ffi
+    EINVAL, ENOTSUP = _ffi.EINVAL, _ffi.ENOTSUP
+    h = mk(L, _ffi.PRIME, 2**61 - 1)[1]           # 2^61 - 1 = 3 mod 4: no Cipolla-Lehmer square roots
+    h13 = mk(L, _ffi.PRIME, 13)[1]                # 13 = 1 mod 4
+    hb = mk(L, _ffi.BINARY, 0x11b)[1]
+    buf = ctypes.create_string_buffer(1 << 16)
+    base = (ctypes.cast(buf, ctypes.c_void_p).value + 255) & ~255
+    A, B, C, W = base, base + 8192, base + 16384, base + 32768
+    four = (ctypes.c_uint64 * 4)(1, 0, 0, 0)
+    rows = (ctypes.c_void_p * 3)(A, A, A)
+    lam = (ctypes.c_uint64 * 6)(1, 0, 1, 0, 1, 0)
+    key = bytes(32)
+    keys40 = (ctypes.c_uint8 * 80)()
+    m17 = (ctypes.c_uint64 * (2 * 17 * 3))()
+    m64 = (ctypes.c_uint64 * 128)()
+    rows8 = (ctypes.c_uint8 * 8)()
+    out3 = ctypes.cast(C, ctypes.POINTER(ctypes.c_double))
+    # scans and axis reductions: k = 0, unknown operation, overlapping ranges, misaligned workspace
+    assert L.ffgpu_scan(h, 0, A, B, 1, 0, 1, 0, None, 0, None) == EINVAL
+    assert L.ffgpu_scan(h, 7, A, B, 1, 8, 1, 0, None, 0, None) == EINVAL
+    assert L.ffgpu_scan(h, 0, A, A + 8, 1, 8, 1, 0, None, 0, None) == EINVAL
+    assert L.ffgpu_scan(h, 0, A, B, 1, 8, 1, 0, W + 8, 64, None) == EINVAL
+    assert L.ffgpu_scan(h, 0, A, B, 1, 8, 1, 0, A, 64, None) == EINVAL            # workspace inside the input
+    assert L.ffgpu_axis_reduce(h, 0, A, B, 1, 0, 1, None, 0, None) == EINVAL
+    assert L.ffgpu_axis_reduce(h, 0, A, A, 4, 8, 1, None, 0, None) == EINVAL      # a reduction is never in place
+    assert L.ffgpu_axis_reduce(h, 0, A, B, 1, 8, 1, W + 8, 64, None) == EINVAL
+    assert L.ffgpu_scan_workspace_bytes(h, 1, 0, 1) == 0
+    assert L.ffgpu_scan_workspace_bytes(None, 1, 8, 1) == 0
+    # convolution: the output overlaps an operand, an empty operand
+    assert L.ffgpu_convolve(h, A, 8, B, 4, A + 16, None) == EINVAL
+    assert L.ffgpu_convolve(h, A, 4, B, 8, B + 16, None) == EINVAL
+    assert L.ffgpu_convolve(h, A, 8, B, 0, C, None) == EINVAL
+    # gates: batch of 256, a host nonce that reaches the batch-row bits, a device-state nonce offset above 32 bits
+    assert L.ffgpu_gate_rng_batch(h, rows, lam, 3, 8, None, None, 0, 0, key, 0, 20, None, 0, 1, 3, C, 8, 64, 8, 256, None) == EINVAL
+    assert L.ffgpu_gate_rng_batch(h, rows, lam, 3, 8, None, None, 0, 0, key, 1 << 40, 20, None, 0, 1, 3, C, 8, 64, 8, 2, None) == EINVAL
+    assert L.ffgpu_gate_rng_batch(h, rows, lam, 3, 8, None, None, 0, 0, None, 1 << 32, 20, W, 0, 1, 3, C, 8, 64, 8, 2, None) == EINVAL
+    assert L.ffgpu_gate_rng_batch(h, rows, lam, 3, 8, None, None, 0, 0, key, 0, 20, None, 0, 4, 9, C, 8, 64, 8, 1, None) == ENOTSUP
+    assert L.ffgpu_gate_rng_batch(h, rows, lam, 8, 8, None, None, 0, 0, key, 0, 20, None, 0, 1, 3, C, 8, 64, 8, 1, None) == ENOTSUP
+    assert L.ffgpu_gate_rng(h, rows, lam, 3, None, None, 0, key, 0, 5, None, 1, 3, C, 8, 8, None) == EINVAL    # 5 rounds
+    # pseudo-random secret sharing
+    assert L.ffgpu_prss_chacha(h, keys40, 2, 1, 8, 0, 7, lam, 0, C, 8, None) == EINVAL
+    assert L.ffgpu_prss_chacha(h, None, 2, 1, 8, 0, 20, lam, 0, C, 8, None) == EINVAL
+    assert L.ffgpu_prss_combine(h, rows, 2, 1, 65, 0, lam, 0, C, 8, None) == EINVAL
+    assert L.ffgpu_prss_combine(h, None, 2, 1, 8, 0, lam, 0, C, 8, None) == EINVAL
+    # linear algebra
+    assert L.ffgpu_group_matvec(h, m17, None, 17, 3, A, B, 8, None) == ENOTSUP
+    assert L.ffgpu_group_matvec(h, m17, None, 0, 3, A, B, 8, None) == EINVAL
+    assert L.ffgpu_matmul(h, A, 4, B, 4, C, 2, 4, 4, 4, None) == EINVAL           # ldc < N
+    assert L.ffgpu_matmul(h, A, 2, B, 4, C, 4, 4, 4, 4, None) == EINVAL           # lda < K
+    assert L.ffgpu_gauss(h, A, 3, 2, 1, 0, None, B, None) == EINVAL               # fewer columns than rows
+    assert L.ffgpu_gauss(h, A, 3, 3, 1, 1, None, B, None) == EINVAL               # determinants wanted, nowhere to put them
+    assert L.ffgpu_dot(h, A, None, C, W, 8, None) == EINVAL
+    assert L.ffgpu_sum(h, A, None, W, 8, None) == EINVAL
+    # powers, inverses, square roots
+    assert L.ffgpu_pow(h, A, four, 4, B, 8, None) == EINVAL
+    assert L.ffgpu_pow(h, A, None, 1, B, 8, None) == EINVAL
+    assert L.ffgpu_inv(h, None, B, 8, None, None) == EINVAL
+    assert L.ffgpu_sqrt_cl(h, A, B, 8, None) == ENOTSUP
+    assert L.ffgpu_sqrt_cl(hb, A, B, 8, None) == ENOTSUP
+    assert L.ffgpu_sqrt_cl(h13, None, B, 8, None) == EINVAL
+    # element-wise calls
+    assert L.ffgpu_add(h, A, None, C, 8, None) == EINVAL
+    assert L.ffgpu_sub(h, A, B, None, 8, None) == EINVAL
+    assert L.ffgpu_neg(h, None, B, 8, None) == EINVAL
+    assert L.ffgpu_reduce(h, A, None, 8, None) == EINVAL
+    assert L.ffgpu_muladd(h, A, B, None, C, 8, None) == EINVAL
+    assert L.ffgpu_add_scalar(h, A, None, B, 8, None) == EINVAL
+    assert L.ffgpu_mul_scalar(h, A, None, B, 8, None) == EINVAL
+    assert L.ffgpu_rsub_scalar(h, A, None, B, 8, None) == EINVAL
+    assert L.ffgpu_beaver_combine(h, A, A, A, A, None, 0, B, 8, None) == EINVAL
+    assert L.ffgpu_copy(h, None, B, 16, None) == EINVAL
+    # share generation with the device generator
+    assert L.ffgpu_rng_coeffs(h, key, 0, 20, 0, C, 8, 8, None) == EINVAL          # t = 0
+    assert L.ffgpu_rng_coeffs(h, None, 0, 20, 1, C, 8, 8, None) == EINVAL
+    assert L.ffgpu_split_rng(h, A, key, 0, 5, 1, 3, C, 8, 8, None) == EINVAL      # 5 rounds
+    assert L.ffgpu_mul_split_rng(h, A, None, key, 0, 20, 1, 3, C, 8, 8, None) == EINVAL
+    assert L.ffgpu_mul_split(h, A, None, C, 8, 1, 3, C, 8, 8, None) == EINVAL
+    assert L.ffgpu_split_rng_state(h, A, None, None, 1, 3, C, 8, 8, None) == EINVAL
+    assert L.ffgpu_split_rng_state(h, A, None, W, 3, 3, C, 8, 8, None) == EINVAL
+    assert L.ffgpu_rng_state_init(h, None, key, 0, 20, None) == EINVAL
+    assert L.ffgpu_rng_state_init(h, W, key, 0, 7, None) == EINVAL
+    assert L.ffgpu_rng_state_advance(h, None, 1, None) == EINVAL
+    assert L.ffgpu_recombine(h, rows, lam, 3, 2, C, 4, 8, None) == EINVAL         # out_stride < n
+    # the GF(2^8) family on a prime context, and its own limits on a GF(2^8) context
+    assert L.ffgpu_gf256_to_bits(h, A, None, B, 8, None) == ENOTSUP
+    assert L.ffgpu_gf256_bit_affine(h, m64, None, 0, A, B, 8, None) == ENOTSUP
+    assert L.ffgpu_gf256_mask_open(h, rows, lam, 3, None, None, 0, C, 8, None) == ENOTSUP
+    assert L.ffgpu_gf256_bits_affine_fold(h, m64, None, A, B, 64, C, 8, 8, 1, None) == ENOTSUP
+    assert L.ffgpu_gf256_sbox_layer(h, m64, None, lam, lam, 1, 3, A, 8, B, 64, C, 8, 8, key, 0, 20, None, 0, None) == ENOTSUP
+    assert L.ffgpu_gf256_sbox(h, A, rows8, 0, B, 8, None) == ENOTSUP
+    assert L.ffgpu_gf256_mask_open(hb, rows, lam, 33, None, None, 0, C, 8, None) == ENOTSUP
+    assert L.ffgpu_gf256_mask_open(hb, rows, lam, 0, None, None, 0, C, 8, None) == EINVAL
+    assert L.ffgpu_gf256_sbox_layer(hb, m64, None, lam, lam, 4, 9, A, 8, B, 64, C, 8, 8, key, 0, 20, None, 0, None) == ENOTSUP
+    assert L.ffgpu_gf256_sbox_layer(hb, m64, None, lam, lam, 1, 2, A, 8, B, 64, C, 8, 8, key, 0, 20, None, 0, None) == EINVAL
+    assert L.ffgpu_gf256_bit_affine(hb, m64, None, 0, A + 1, B, 8, None) == EINVAL
+    assert L.ffgpu_gf256_bits_affine_fold(hb, m64, None, A, B, 64, C, 8, 8, 0, None) == EINVAL
+    assert L.ffgpu_gf256_to_bits(hb, None, None, B, 8, None) == EINVAL
+    assert L.ffgpu_gf256_sbox(hb, None, rows8, 0, B, 8, None) == EINVAL
+    assert L.ffgpu_valu_probe(h, 14, 1, 1, A, out3, None) == EINVAL
+    for ctx in (h, h13, hb):
+        L.ffgpu_ctx_destroy(ctx)
