@@ -22,11 +22,11 @@ __global__ __launch_bounds__(BLOCK) void k_convolve(F f, const typename F::elem*
     typedef typename F::word W;
     constexpr int R = S::R;
     static_assert((int)S::THREADS == (int)BLOCK, "ConvShape is laid out for the library's workgroup");
-    constexpr bool LZ = HasLazyAcc<F>::value;
+    constexpr bool LZ = DotAcc<F>::lazy;
     constexpr int NL = MatmulDigits<F, LZ>::NL;
     constexpr int FLUSH = AccFlush<F>::TERMS;
     static_assert(FLUSH % S::PER == 0, "the flush test follows whole chunks");
-    using Acc = typename std::conditional<LZ, typename LazyAccOf<F>::type, typename F::acc>::type;
+    using Acc = typename DotAcc<F>::type;
     __shared__ W Ws[LZ ? 1 : S::WIN];
     __shared__ W Ts[LZ ? 1 : S::TV];
     __shared__ uint32_t Wd[NL][LZ ? S::WIN : 1];

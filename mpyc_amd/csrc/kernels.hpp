@@ -313,6 +313,29 @@ __device__ __forceinline__ void st_elem(typename F::elem* p, size_t i, typename 
     }
 }
 
+// at(idx) for an index 0 <= idx < N known at run time only, where at(x) names a register for every constant x (an element
+// of an array held in registers): a chain of selects over all N.  Indexing the array by idx itself would move the whole
+// array to scratch memory.
+template <int N, class At>
+__device__ __forceinline__ auto reg_select(int idx, At at) {
+    auto v = at(0);
+#pragma unroll
+    for (int x = 1; x < N; ++x) {
+        const auto a = at(x);                    // read first, then select between two values
+        v = (x == idx) ? a : v;
+    }
+    return v;
+}
+// element e of the array out of the drawn pack that holds it (rng_draw_pack: one row of coefficients, N words): its word,
+// and for packed fields its byte of that word
+template <class F, int N>
+__device__ __forceinline__ typename F::word drawn_elem(const typename F::word (&pack)[N], size_t e) {
+    typedef typename F::word W;
+    W v = reg_select<N>((int)((e % (N * F::EPW)) / F::EPW), [&](int q) { return pack[q]; });
+    if constexpr (F::EPW > 1) v = (W)((v >> (8 * (e % F::EPW))) & 0xffu);
+    return v;
+}
+
 template <class F, int OP>
 __device__ __forceinline__ typename F::word ew_apply(const F& f, typename F::word a, typename F::word b) {
     if constexpr (OP == OP_ADD) return f.add(a, b);
@@ -324,32 +347,47 @@ __device__ __forceinline__ typename F::word ew_apply(const F& f, typename F::wor
     else return a;
 }
 
+// ---- the streaming shape, written once: o[i] = fn(in0[i], in1[i], ...) ------------------------------------------------
+// One pack per thread; the loads of a pack are issued in argument order and then finished in argument order (the
+// 24-byte path stages every finish through the wave's one LDS region: the order is part of the kernel), fn runs lane by
+// lane, one store follows.  The scalar tail takes the elements past the last full pack (n not a multiple of the pack
+// size), or all of them (unaligned pointers: nvec == 0).  `keep` is the kernel's argument (stgw_k), or StreamOut.
+// A kernel's lambda captures the kernel's arguments by copy: captured by reference they get an address, and k_ew1 then
+// compiled to other code over half the policies (k_ew1<GF2W128, MUL>: 90 -> 36 registers; profiles/r11_streaming_shape.md).
+struct StreamOut {};          // store policy of a kernel without a `keep` argument: always nt, no scalar branch, no fences
+template <bool NT, class P, class X>
+__device__ __forceinline__ void stgw_k(P* p, const X& x, StreamOut) { stgw<NT>(p, x); }
+template <class Fn, class P, size_t... J>
+__device__ __forceinline__ auto map_lane(const Fn& fn, const P* x, int q, std::index_sequence<J...>) { return fn(x[J].w[q]...); }
+
+template <class F, bool NT, class Keep, class Fn, class... E>
+__device__ __forceinline__ void stream_map(typename F::elem* o, size_t nvec, size_t n, Keep keep, Fn fn, const E*... in) {
+    typedef Pack<typename F::word> P;
+    typedef typename MemPack<F>::type MP;
+    constexpr int K = sizeof...(E);
+    MP* ov = reinterpret_cast<MP*>(o);
+    const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    const size_t gsz = (size_t)gridDim.x * BLOCK;
+    for (size_t i = gid; i < nvec; i += gsz) {
+        // (a braced list is evaluated left to right; function arguments are not)
+        const decltype(ldgw_issue<NT>(ov)) raw[K] = {ldgw_issue<NT>(reinterpret_cast<const MP*>(in) + i)...};
+        P x[K], r;
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[j] = ldgw_finish(raw[j]);
+#pragma unroll
+        for (int q = 0; q < P::N; ++q) r.w[q] = map_lane(fn, x, q, std::make_index_sequence<K>());
+        stgw_k<NT>(ov + i, r, keep);
+    }
+    const size_t done = nvec * (size_t)(P::N * F::EPW);
+    for (size_t e = done + gid; e < n; e += gsz) st_elem<F>(o, e, fn(ld_elem<F>(in, e)...));
+}
+
 // ---- out = a (op) b --------------------------------------------------------
 template <class F, int OP, bool NT>
 __device__ __forceinline__ void ew2_body(const F& f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ b,
                                          typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
-    typedef Pack<typename F::word> P;
-    typedef typename MemPack<F>::type MP;
-    const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
-    const MP* __restrict__ bv = reinterpret_cast<const MP*>(b);
-    MP* __restrict__ ov = reinterpret_cast<MP*>(o);
-    const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t gsz = (size_t)gridDim.x * BLOCK;
-    for (size_t i = gid; i < nvec; i += gsz) {
-        const auto rx = ldgw_issue<NT>(av + i);
-        const auto ry = ldgw_issue<NT>(bv + i);
-        P x = ldgw_finish(rx);
-        P y = ldgw_finish(ry);
-        P r;
-#pragma unroll
-        for (int q = 0; q < P::N; ++q) r.w[q] = ew_apply<F, OP>(f, x.w[q], y.w[q]);
-        stgw_k<NT>(ov + i, r, keep);
-    }
-    // scalar tail (n not a multiple of the pack size, or unaligned pointers: nvec == 0)
-    const size_t done = nvec * (size_t)(P::N * F::EPW);
-    for (size_t e = done + gid; e < n; e += gsz) {
-        st_elem<F>(o, e, ew_apply<F, OP>(f, ld_elem<F>(a, e), ld_elem<F>(b, e)));
-    }
+    typedef typename F::word W;
+    stream_map<F, NT>(o, nvec, n, keep, [&](W x, W y) { return ew_apply<F, OP>(f, x, y); }, a, b);
 }
 template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew2(F f, const typename F::elem* __restrict__ a,
@@ -378,23 +416,8 @@ template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew1(F f, const typename F::elem* __restrict__ a,
                                                 typename F::word s, typename F::elem* __restrict__ o,
                                                 size_t nvec, size_t n, int keep) {
-    typedef Pack<typename F::word> P;
-    typedef typename MemPack<F>::type MP;
-    const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
-    MP* __restrict__ ov = reinterpret_cast<MP*>(o);
-    const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t gsz = (size_t)gridDim.x * BLOCK;
-    for (size_t i = gid; i < nvec; i += gsz) {
-        P x = ldgw_finish(ldgw_issue<NT>(av + i));
-        P r;
-#pragma unroll
-        for (int q = 0; q < P::N; ++q) r.w[q] = ew_apply<F, OP>(f, x.w[q], s);
-        stgw_k<NT>(ov + i, r, keep);
-    }
-    const size_t done = nvec * (size_t)(P::N * F::EPW);
-    for (size_t e = done + gid; e < n; e += gsz) {
-        st_elem<F>(o, e, ew_apply<F, OP>(f, ld_elem<F>(a, e), s));
-    }
+    typedef typename F::word W;
+    stream_map<F, NT>(o, nvec, n, keep, [=](W x) { return ew_apply<F, OP>(f, x, s); }, a);
 }
 
 // ---- out = a*b + c ---------------------------------------------------------
@@ -403,30 +426,8 @@ __global__ __launch_bounds__(BLOCK) void k_muladd(F f, const typename F::elem* _
                                                    const typename F::elem* __restrict__ b,
                                                    const typename F::elem* __restrict__ c,
                                                    typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
-    typedef Pack<typename F::word> P;
-    typedef typename MemPack<F>::type MP;
-    const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
-    const MP* __restrict__ bv = reinterpret_cast<const MP*>(b);
-    const MP* __restrict__ cv = reinterpret_cast<const MP*>(c);
-    MP* __restrict__ ov = reinterpret_cast<MP*>(o);
-    const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t gsz = (size_t)gridDim.x * BLOCK;
-    for (size_t i = gid; i < nvec; i += gsz) {
-        const auto rx = ldgw_issue<NT>(av + i);
-        const auto ry = ldgw_issue<NT>(bv + i);
-        const auto rz = ldgw_issue<NT>(cv + i);
-        P x = ldgw_finish(rx);
-        P y = ldgw_finish(ry);
-        P z = ldgw_finish(rz);
-        P r;
-#pragma unroll
-        for (int q = 0; q < P::N; ++q) r.w[q] = f.muladd(x.w[q], y.w[q], z.w[q]);
-        stgw_k<NT>(ov + i, r, keep);
-    }
-    const size_t done = nvec * (size_t)(P::N * F::EPW);
-    for (size_t e = done + gid; e < n; e += gsz) {
-        st_elem<F>(o, e, f.muladd(ld_elem<F>(a, e), ld_elem<F>(b, e), ld_elem<F>(c, e)));
-    }
+    typedef typename F::word W;
+    stream_map<F, NT>(o, nvec, n, keep, [=](W x, W y, W z) { return f.muladd(x, y, z); }, a, b, c);
 }
 
 // ---- Beaver-triple combination: out = z + d*y + e*x + d*e ---------------------------------------
@@ -441,28 +442,12 @@ __global__ __launch_bounds__(BLOCK) void k_beaver(F f, const typename F::elem* _
                                                    const typename F::elem* __restrict__ d,
                                                    const typename F::elem* __restrict__ e,
                                                    typename F::elem* __restrict__ o, int add_de, size_t nvec, size_t n) {
-    typedef Pack<typename F::word> P;
-    typedef typename MemPack<F>::type MP;
     typedef typename F::word W;
-    const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t gsz = (size_t)gridDim.x * BLOCK;
-    auto comb = [&](W zz, W xx, W yy, W dd, W ee) -> W {
+    stream_map<F, NT>(o, nvec, n, StreamOut(), [=](W zz, W xx, W yy, W dd, W ee) -> W {
         W c = f.muladd(dd, yy, zz);
         c = f.muladd(ee, xx, c);
         return add_de ? f.muladd(dd, ee, c) : c;       // public term: all parties (Shamir) / one party (additive)
-    };
-    for (size_t i = gid; i < nvec; i += gsz) {
-        const auto rz = ldgw_issue<NT>(reinterpret_cast<const MP*>(z) + i), rx = ldgw_issue<NT>(reinterpret_cast<const MP*>(x) + i);
-        const auto ry = ldgw_issue<NT>(reinterpret_cast<const MP*>(y) + i), rd = ldgw_issue<NT>(reinterpret_cast<const MP*>(d) + i);
-        const auto re = ldgw_issue<NT>(reinterpret_cast<const MP*>(e) + i);
-        P pz = ldgw_finish(rz), px = ldgw_finish(rx), py = ldgw_finish(ry), pd = ldgw_finish(rd), pe = ldgw_finish(re), r;
-#pragma unroll
-        for (int q = 0; q < P::N; ++q) r.w[q] = comb(pz.w[q], px.w[q], py.w[q], pd.w[q], pe.w[q]);
-        stgw<NT>(reinterpret_cast<MP*>(o) + i, r);
-    }
-    const size_t done = nvec * (size_t)(P::N * F::EPW);
-    for (size_t k_ = done + gid; k_ < n; k_ += gsz)
-        st_elem<F>(o, k_, comb(ld_elem<F>(z, k_), ld_elem<F>(x, k_), ld_elem<F>(y, k_), ld_elem<F>(d, k_), ld_elem<F>(e, k_)));
+    }, z, x, y, d, e);
 }
 
 // ---- Shamir share generation (thresha.py:47-64), optionally fused with the
@@ -512,19 +497,26 @@ struct GateSrc {
 
 // Policies with a dot product in 28-bit digits (fields.hpp LazyDot: the multi-limb 2^k - c primes) take it for sums of at
 // most FF_D28_MAX_TERMS terms -- the recombination kernels' K <= MAXK rows; everything else accumulates in F::acc.
+// DotAcc<F> is the one or the other: the sum of products lam * x of a pack loop (the scalar tails keep F::acc).
 template <class F, class = void>
-struct HasLazyAcc : std::false_type {};
-template <class F>
-struct HasLazyAcc<F, std::void_t<typename F::lacc> > : std::true_type {};
-static_assert(MAXK <= FF_D28_MAX_TERMS, "the digit accumulator's column bound");
-template <class F, class = void>
-struct LazyAccOf {
+struct DotAcc {
+    static constexpr bool lazy = false;
     typedef typename F::acc type;
+    type s;
+    __device__ __forceinline__ void zero(const F& f) { f.acc_zero(s); }
+    __device__ __forceinline__ void mac(const F& f, const typename F::word& lam, const typename F::word& x) { f.acc_mac(s, lam, x); }
+    __device__ __forceinline__ typename F::word reduce(const F& f) const { return f.acc_reduce(s); }
 };
 template <class F>
-struct LazyAccOf<F, std::void_t<typename F::lacc> > {
+struct DotAcc<F, std::void_t<typename F::lacc> > {
+    static constexpr bool lazy = true;
     typedef typename F::lacc type;
+    type s;
+    __device__ __forceinline__ void zero(const F& f) { f.lacc_zero(s); }
+    __device__ __forceinline__ void mac(const F& f, const typename F::word& lam, const typename F::word& x) { f.lacc_mac(s, lam, x); }
+    __device__ __forceinline__ typename F::word reduce(const F& f) const { return f.lacc_reduce(s); }
 };
+static_assert(MAXK <= FF_D28_MAX_TERMS, "the digit accumulator's column bound");
 
 template <class F, bool NT>
 __device__ __forceinline__ Pack<typename F::word> gate_load(const F& f, const typename F::elem* const* rows,
@@ -532,12 +524,9 @@ __device__ __forceinline__ Pack<typename F::word> gate_load(const F& f, const ty
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     static_assert(GATE_MAXK <= FF_D28_MAX_TERMS, "the digit accumulator's column bound");
-    using Acc = typename std::conditional<HasLazyAcc<F>::value, typename LazyAccOf<F>::type, typename F::acc>::type;
-    Acc acc[P::N];
+    DotAcc<F> acc[P::N];
 #pragma unroll
-    for (int q = 0; q < P::N; ++q) {
-        if constexpr (HasLazyAcc<F>::value) f.lacc_zero(acc[q]); else f.acc_zero(acc[q]);
-    }
+    for (int q = 0; q < P::N; ++q) acc[q].zero(f);
     // rows in chunks of four: the loads of a chunk are issued together and waited for once (k is wave-uniform, the
     // guards are scalar branches) -- one load, one wait, one multiply-add per row would expose k memory latencies
     for (int j0 = 0; j0 < k; j0 += 4) {
@@ -549,17 +538,12 @@ __device__ __forceinline__ Pack<typename F::word> gate_load(const F& f, const ty
         for (int u = 0; u < 4; ++u)
             if (j0 + u < k) {
 #pragma unroll
-                for (int q = 0; q < P::N; ++q) {
-                    if constexpr (HasLazyAcc<F>::value) f.lacc_mac(acc[q], lam[j0 + u], x[u].w[q]);
-                    else f.acc_mac(acc[q], lam[j0 + u], x[u].w[q]);
-                }
+                for (int q = 0; q < P::N; ++q) acc[q].mac(f, lam[j0 + u], x[u].w[q]);
             }
     }
     P r;
 #pragma unroll
-    for (int q = 0; q < P::N; ++q) {
-        if constexpr (HasLazyAcc<F>::value) r.w[q] = f.lacc_reduce(acc[q]); else r.w[q] = f.acc_reduce(acc[q]);
-    }
+    for (int q = 0; q < P::N; ++q) r.w[q] = acc[q].reduce(f);
     return r;
 }
 template <class F>
@@ -826,15 +810,8 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
         if constexpr (RNG && T > 0) {
             W cc[TT][P::N];
             rng_draw_pack<F, T, P::N>(f, ra.rk, ra.r0, ra.r1, (uint64_t)(e / EPV), (uint64_t)((n + EPV - 1) / EPV), cc);
-            const int q = (int)((e % EPV) / F::EPW);
 #pragma unroll
-            for (int j = 0; j < T; ++j) {
-                W v = cc[j][0];
-#pragma unroll
-                for (int qq = 1; qq < P::N; ++qq) v = (qq == q) ? cc[j][qq] : v;
-                if constexpr (F::EPW > 1) v = (W)((v >> (8 * (e % F::EPW))) & 0xffu);
-                c[j] = v;
-            }
+            for (int j = 0; j < T; ++j) c[j] = drawn_elem<F>(cc[j], e);
         } else {
 #pragma unroll
             for (int j = 0; j < T; ++j) c[j] = ld_elem<F>(coef + (size_t)j * cstride, e);
@@ -879,12 +856,7 @@ __global__ __launch_bounds__(BLOCK) void k_rng_coeffs(F f, typename F::elem* __r
                 for (int j = 0; j < T; ++j) {
                     P t_;
 #pragma unroll
-                    for (int q = 0; q < P::N; ++q) {
-                        W v = cg[0][j][q];
-#pragma unroll
-                        for (int uu = 1; uu < G; ++uu) v = (uu == u) ? cg[uu][j][q] : v;
-                        t_.w[q] = v;
-                    }
+                    for (int q = 0; q < P::N; ++q) t_.w[q] = reg_select<G>(u, [&](int uu) { return cg[uu][j][q]; });
                     stg<true>(reinterpret_cast<MP*>(coef + (size_t)j * cstride) + i, t_);
                 }
             } else {
@@ -893,8 +865,7 @@ __global__ __launch_bounds__(BLOCK) void k_rng_coeffs(F f, typename F::elem* __r
                         for (int b_ = 0; b_ < F::EPW; ++b_) {
                             size_t e = i * EPV + (size_t)q * F::EPW + b_;
                             if (e < n) {
-                                W v = cg[0][j][q];
-                                for (int uu = 1; uu < G; ++uu) v = (uu == u) ? cg[uu][j][q] : v;
+                                W v = reg_select<G>(u, [&](int uu) { return cg[uu][j][q]; });
                                 if constexpr (F::EPW > 1) v = (W)((v >> (8 * b_)) & 0xffu);
                                 st_elem<F>(coef + (size_t)j * cstride, e, v);
                             }
@@ -924,12 +895,7 @@ __global__ __launch_bounds__(BLOCK) void k_split_any(F f, const typename F::elem
             rj.rk.nonce[1] += (uint32_t)(j + 1);
             W cc[1][P::N];
             rng_draw_pack<F, 1, P::N>(f, rj.rk, rj.r0, rj.r1, (uint64_t)(e / EPV), (uint64_t)((n + EPV - 1) / EPV), cc);
-            const int q = (int)((e % EPV) / F::EPW);
-            W v = cc[0][0];
-#pragma unroll
-            for (int qq = 1; qq < P::N; ++qq) v = (qq == q) ? cc[0][qq] : v;
-            if constexpr (F::EPW > 1) v = (W)((v >> (8 * (e % F::EPW))) & 0xffu);
-            return v;
+            return drawn_elem<F>(cc[0], e);
         } else {
             return ld_elem<F>(coef + (size_t)j * cstride, e);
         }
@@ -1005,19 +971,11 @@ __global__ __launch_bounds__(BLOCK) void k_recombine(F f, RecArgs<F, K> ra, int 
             P y;
 #pragma unroll
             for (int q = 0; q < P::N; ++q) {
-                if constexpr (HasLazyAcc<F>::value) {
-                    typename F::lacc s;
-                    f.lacc_zero(s);
+                DotAcc<F> s;
+                s.zero(f);
 #pragma unroll
-                    for (int j = 0; j < K; ++j) f.lacc_mac(s, ra.lam[r * K + j], x[j].w[q]);
-                    y.w[q] = f.lacc_reduce(s);
-                } else {
-                    typename F::acc s;
-                    f.acc_zero(s);
-#pragma unroll
-                    for (int j = 0; j < K; ++j) f.acc_mac(s, ra.lam[r * K + j], x[j].w[q]);
-                    y.w[q] = f.acc_reduce(s);
-                }
+                for (int j = 0; j < K; ++j) s.mac(f, ra.lam[r * K + j], x[j].w[q]);
+                y.w[q] = s.reduce(f);
             }
             stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)r * ostride) + i, y, keep);
         }

@@ -44,7 +44,7 @@ struct MatmulDigits<F, true> {
 // FF_D28_MAX_TERMS (fields.hpp).  k_matmul and k_convolve (convolve.hpp) flush on this bound.
 template <class F>
 struct AccFlush {
-    enum { TERMS = HasLazyAcc<F>::value ? (int)FF_D28_MAX_TERMS : 192 };
+    enum { TERMS = DotAcc<F>::lazy ? (int)FF_D28_MAX_TERMS : 192 };
 };
 template <class F, int TM, int TN>
 __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* __restrict__ A, size_t lda,
@@ -62,11 +62,11 @@ __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* _
     }
     // multi-limb 2^k - c primes (round 6): the tiles are staged as 28-bit DIGITS and every term is NL^2 multiply-adds into
     // column sums (fields.hpp LazyDot), reduced every 32 terms -- ~100 instructions per term with the 128-bit limb arithmetic
-    constexpr bool LZ = HasLazyAcc<F>::value;
+    constexpr bool LZ = DotAcc<F>::lazy;
     constexpr int NL = MatmulDigits<F, LZ>::NL;
     constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = AccFlush<F>::TERMS;
     static_assert(FLUSH % BK == 0, "the flush test follows whole k-steps");
-    using Acc = typename std::conditional<LZ, typename LazyAccOf<F>::type, typename F::acc>::type;
+    using Acc = typename DotAcc<F>::type;
     __shared__ W As[LZ ? 1 : BK][LZ ? 1 : BM + 1];
     __shared__ W Bs[LZ ? 1 : BK][LZ ? 1 : BN + 1];
     __shared__ uint32_t Ad[LZ ? BK : 1][LZ ? BM + 1 : 1][NL];
@@ -747,8 +747,8 @@ enum { SKINNY_MAX = 8, SKINNY_FLUSH = 192 };
 // multi-limb 2^k - c primes, round 6: ~45 instead of ~100 instructions per term, flushed every 32 terms), else F::acc.
 template <class F>
 struct SkinnyAcc {
-    static constexpr bool LZ = HasLazyAcc<F>::value;
-    typedef typename std::conditional<LZ, typename LazyAccOf<F>::type, typename F::acc>::type T;
+    static constexpr bool LZ = DotAcc<F>::lazy;
+    typedef typename DotAcc<F>::type T;
     enum { FLUSH = LZ ? (int)FF_D28_MAX_TERMS : (int)SKINNY_FLUSH };
     static __device__ __forceinline__ void zero(const F& f, T& a) {
         if constexpr (LZ) f.lacc_zero(a); else f.acc_zero(a);
@@ -1200,11 +1200,11 @@ __global__ __launch_bounds__(BLOCK) void k_vecmat_partial(F f, const typename F:
     typedef typename F::word W;
     constexpr int CW = VEC ? P::N : 1;                              // columns per thread
     constexpr int KT = VECMAT_KT;
-    constexpr bool LZ = HasLazyAcc<F>::value;                      // digit accumulators (staged A: its digits live in LDS)
+    constexpr bool LZ = DotAcc<F>::lazy;                           // digit accumulators (staged A: its digits live in LDS)
     constexpr int NL = VecmatDigits<F, LZ>::NL;
     constexpr int FLUSH = LZ ? (int)FF_D28_MAX_TERMS : (int)SKINNY_FLUSH;
     static_assert(!LZ || FF_D28_MAX_TERMS % UNR == 0, "the flush test follows whole groups");
-    using Acc = typename std::conditional<LZ, typename LazyAccOf<F>::type, typename F::acc>::type;
+    using Acc = typename DotAcc<F>::type;
     __shared__ W sa[(STAGE && !LZ) ? MM : 1][(STAGE && !LZ) ? KT : 1];
     __shared__ uint32_t sad[(LZ && STAGE) ? MM : 1][(LZ && STAGE) ? KT : 1][NL];
     const int j = (blockIdx.x * BLOCK + threadIdx.x) * CW;

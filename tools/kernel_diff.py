@@ -5,9 +5,12 @@
 The directories hold the object files of `make -C mpyc_amd/csrc` (build/ffgpu/*.o).  For every translation unit the
 device code is taken out of .hip_fatbin (llvm-objcopy, clang-offload-bundler) and compared kernel by kernel:
 disassembly (llvm-objdump -d, comments and addresses dropped) and the metadata of the notes (registers, LDS, scratch,
-kernarg size).  Prints kernels before -> after, the kernels removed and added, those whose code or metadata changed, and those whose
-only difference is the PC-relative distance to a callee that was not inlined.
-A refactor of the host side must show 0 added and 0 changed (profiles/r10_host_layer.md)."""
+kernarg size).  Prints kernels before -> after, the kernels removed and added, those whose code or metadata changed (with
+the metadata and the instruction count before -> after), and apart from them, not counted as changed:
+  * those whose only difference is the PC-relative distance to a callee that was not inlined;
+  * those with the same instructions in another order: the sorted instruction lines and all metadata are equal.
+A refactor of the host side must show 0 added and 0 changed (profiles/r10_host_layer.md); a refactor of the kernel source may
+show changed kernels only among the templates it touched (profiles/r11_streaming_shape.md)."""
 import glob
 import hashlib
 import os
@@ -36,11 +39,12 @@ def extract(obj, tmp, tag):
 
 
 def digest(buf):
-    """(exact, position-free): the second with the displacement of `s_getpc_b64; s_add_u32 lo, lo, DISP` masked -- the
-    distance to a callee that was not inlined moves when code between the two is removed, the instructions do not"""
+    """(exact, position-free, order-free, instructions): the second with the displacement of `s_getpc_b64; s_add_u32 lo,
+    lo, DISP` masked -- the distance to a callee that was not inlined moves when code between the two is removed, the
+    instructions do not; the third over the sorted lines of the second"""
     free = [re.sub(r'0x[0-9a-f]+$', 'DISP', l) if l.startswith('s_add_u32') and i and buf[i - 1].startswith('s_getpc_b64') else l
             for i, l in enumerate(buf)]
-    return tuple(hashlib.sha256('\n'.join(b).encode()).hexdigest() for b in (buf, free))
+    return tuple(hashlib.sha256('\n'.join(b).encode()).hexdigest() for b in (buf, free, sorted(free))) + (sum(1 for l in buf if l),)
 
 
 def code(co):
@@ -80,17 +84,23 @@ def main():
                 continue
             ca, cb, ma, mb = code(a), code(b), metadata(a), metadata(b)
             removed, added = sorted(set(ma) - set(mb)), sorted(set(mb) - set(ma))
-            changed = [k for k in ca if k in cb and ca[k][1] != cb[k][1]]
+            differ = [k for k in ca if k in cb and ca[k][1] != cb[k][1]]
+            reordered = [k for k in differ if ca[k][2] == cb[k][2] and ma.get(k) == mb.get(k)]
+            changed = [k for k in differ if k not in reordered]
             moved = [k for k in ca if k in cb and ca[k][1] == cb[k][1] and ca[k][0] != cb[k][0]]
             mchanged = [k for k in ma if k in mb and ma[k] != mb[k]]
             total[0] += len(ma)
             total[1] += len(mb)
             bad += bool(added or changed or mchanged)
             print(f'{u}: kernels {len(ma)} -> {len(mb)}; removed {len(removed)}, added {len(added)}, '
-                  f'code changed {len(changed)}, metadata changed {len(mchanged)}, same code at another distance from a callee {len(moved)}')
-            for tag, names in (('-', removed), ('+', added), ('~', changed), ('m', mchanged), ('d', moved)):
+                  f'code changed {len(changed)}, metadata changed {len(mchanged)}, same code at another distance from a callee {len(moved)}, '
+                  f'same instructions in another order {len(reordered)}')
+            for tag, names in (('-', removed), ('+', added), ('~', changed), ('m', mchanged), ('d', moved), ('o', reordered)):
                 for k in names:
                     print('   ', tag, k)
+                    if tag in '~m':
+                        print('        instructions', ca[k][3], '->', cb[k][3],
+                              *(f'{x.split(":")[0]} {x.split()[-1]} -> {y.split()[-1]}' for x, y in zip(ma[k], mb[k]) if x != y))
     print(f'total kernels {total[0]} -> {total[1]}; units with added or changed kernels: {bad}')
     return 1 if bad else 0
 
