@@ -281,6 +281,24 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
 int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
                  size_t M, size_t K, size_t N, void* stream);
 
+/* ---- stacks of matrix products ------------------------------------------------------ */
+/* C[b] (M x N) = A[b] (M x K) @ B[b] (K x N) for b < batch, matrix b of an operand at element offset b * stride (row-major,
+ * leading dimensions as for ffgpu_matmul).  stride_a == 0 or stride_b == 0: the one matrix is shared by the whole stack (no
+ * expanded copy is needed).  Every matrix of the result is bit-identical to ffgpu_matmul on that pair.  Small and medium
+ * matrices are ONE launch whatever the batch and need no scratch: M*N <= 256 -> several consecutive matrices per workgroup,
+ * staged in LDS with coalesced loads, one output per thread; otherwise the LDS-tiled vector-ALU kernel with the matrix
+ * index folded into the grid.  Matrices that ffgpu_matmul would give to the matrix cores, or with M*N*K at or above
+ * FFGPU_MM_STACK_LOOP_MIN, run through ffgpu_matmul's routes one after the other inside
+ * this call (same scratch rules).
+ * batch == 0, M == 0 or N == 0: FFGPU_OK, nothing is touched; K == 0: zeros, as ffgpu_matmul.  FFGPU_EINVAL, nothing
+ * launched: a leading dimension that is too short; a non-zero stride smaller than a matrix ((rows - 1) * ld + columns
+ * elements); stride_c smaller than a matrix (zero only with batch == 1); sizes whose byte ranges overflow; more
+ * workgroups than a grid holds; a C range that overlaps the A or B range.
+ * replaces: finfields.py:1126-1135 (__matmul__ on stacks: NumPy's object matmul with broadcasting, then one `%`), the
+ * local product of runtime.py:2481-2541 np_matmul "with broadcast" (A @ B at :2531).              */
+int ffgpu_matmul_stack(ffgpu_ctx* ctx, const void* A, size_t lda, size_t stride_a, const void* B, size_t ldb, size_t stride_b,
+                       void* C, size_t ldc, size_t stride_c, size_t M, size_t K, size_t N, size_t batch, void* stream);
+
 /* ---- convolution ---------------------------------------------------------------- */
 /* out[k] = sum_j a[k - j] * v[j] over the field, 0 <= k < na + nv - 1: the FULL convolution of two arrays
  * (np.convolve modes 'same' and 'valid' are slices of it, taken by the caller).  The operand order does not

@@ -75,6 +75,7 @@ _SIGS = {
     'ffgpu_split_rng_state': [_vp, _vp, _vp, _vp, _int, _int, _vp, _sz, _sz, _vp],
     'ffgpu_recombine': [_vp, ctypes.POINTER(_vp), _u64p, _int, _int, _vp, _sz, _sz, _vp],
     'ffgpu_matmul': [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _vp],
+    'ffgpu_matmul_stack': [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp],
     'ffgpu_convolve': [_vp, _vp, _sz, _vp, _sz, _vp, _vp],
     'ffgpu_scan': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _int, _vp, _sz, _vp],
     'ffgpu_axis_reduce': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp],

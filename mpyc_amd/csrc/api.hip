@@ -315,6 +315,7 @@ static const Switch SWITCHES[] = {
     {"FFGPU_BLOCKS_PER_CU", &LaunchCfg::blocks_per_cu, nullptr, 0, 0, INT_MAX},     // 0: uncapped
     {"FFGPU_MM_MFMA", &LaunchCfg::mm_mfma, nullptr, 1, INT_MIN, INT_MAX},
     {"FFGPU_MM_MFMA_MIN", nullptr, &LaunchCfg::mm_mfma_min, 8e7, 0, 0},
+    {"FFGPU_MM_STACK_LOOP_MIN", &LaunchCfg::mm_stack_loop_min, nullptr, 1 << 22, 0, INT_MAX},
     {"FFGPU_GF2W_BITSLICED", &LaunchCfg::gf2w_bitsliced, nullptr, 1, INT_MIN, INT_MAX},
     {"FFGPU_HANDOFF", &LaunchCfg::handoff, nullptr, 1, INT_MIN, INT_MAX},
     {"FFGPU_CONV_WIDE_PER_CU", &LaunchCfg::conv_wide_per_cu, nullptr, 2, 0, INT_MAX},
@@ -1048,13 +1049,10 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
                                          out_stride, n, cs.st));
 }
 
-int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
-                 size_t M, size_t K, size_t N, void* stream) {
-    ARGCHK(ctx);
-    if (M == 0 || N == 0) return FFGPU_OK;
-    ARGCHK(C && ldc >= N && M < (1u << 30) && N < (1u << 30) && K < (1u << 30));
-    ARGCHK(K == 0 || (A && B && lda >= K && ldb >= N));
-    CallScope cs(ctx, stream);
+// one product through Launchers::matmul with the scratch of the call's stream (ffgpu_matmul, and ffgpu_matmul_stack for
+// matrices that take the matrix-core, skinny or split-K routes)
+static int matmul_one(ffgpu_ctx* ctx, const CallScope& cs, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
+                      size_t M, size_t K, size_t N) {
     // scratch: int8 digit planes for the matrix-core product plus 64 MiB of split-K slabs (up to 8 GiB), else 64 MiB of
     // split-K partial sums.  (Asked for in whole 8 / 16 planes per operand: more than the 4 and 12 digits of 4- and
     // 12-byte elements need, and the split-K plans of the launcher see the size.)
@@ -1070,6 +1068,63 @@ int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_
         if (rc != FFGPU_OK) return rc;
     }
     return status_of(ctx->ops->matmul(ctx->policy, cs.lc, A, lda, B, ldb, C, ldc, (int)M, (int)K, (int)N, ws, ws_bytes, cs.st));
+}
+
+int ffgpu_matmul(ffgpu_ctx* ctx, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
+                 size_t M, size_t K, size_t N, void* stream) {
+    ARGCHK(ctx);
+    if (M == 0 || N == 0) return FFGPU_OK;
+    ARGCHK(C && ldc >= N && M < (1u << 30) && N < (1u << 30) && K < (1u << 30));
+    ARGCHK(K == 0 || (A && B && lda >= K && ldb >= N));
+    CallScope cs(ctx, stream);
+    return matmul_one(ctx, cs, A, lda, B, ldb, C, ldc, M, K, N);
+}
+
+// bytes that `batch` matrices of `rows` rows of `cols` elements span, leading dimension ld and batch stride `stride`
+// (0: one matrix); false when the sizes overflow
+static bool stack_span(size_t batch, size_t stride, size_t rows, size_t ld, size_t cols, size_t eb, size_t* matrix, size_t* bytes) {
+    size_t m, t;
+    if (__builtin_mul_overflow(rows - 1, ld, &m) || __builtin_add_overflow(m, cols, &m)) return false;
+    if (__builtin_mul_overflow(batch - 1, stride, &t) || __builtin_add_overflow(t, m, &t)) return false;
+    if (__builtin_mul_overflow(t, eb, bytes) || *bytes > (size_t)1 << 62) return false;
+    *matrix = m;
+    return true;
+}
+
+int ffgpu_matmul_stack(ffgpu_ctx* ctx, const void* A, size_t lda, size_t stride_a, const void* B, size_t ldb, size_t stride_b,
+                       void* C, size_t ldc, size_t stride_c, size_t M, size_t K, size_t N, size_t batch, void* stream) {
+    ARGCHK(ctx);
+    if (batch == 0 || M == 0 || N == 0) return FFGPU_OK;
+    ARGCHK(C && ldc >= N && M < (1u << 30) && N < (1u << 30) && K < (1u << 30));
+    ARGCHK(K == 0 || (A && B && lda >= K && ldb >= N));
+    const size_t eb = (size_t)ctx->elem_bytes;
+    size_t mc, bytes_c;
+    ARGCHK(stack_span(batch, stride_c, M, ldc, N, eb, &mc, &bytes_c));
+    ARGCHK(stride_c >= mc || (stride_c == 0 && batch == 1));
+    if (K > 0) {
+        size_t ma, mb, bytes_a, bytes_b;
+        ARGCHK(stack_span(batch, stride_a, M, lda, K, eb, &ma, &bytes_a) && stack_span(batch, stride_b, K, ldb, N, eb, &mb, &bytes_b));
+        ARGCHK((stride_a == 0 || stride_a >= ma) && (stride_b == 0 || stride_b >= mb));
+        const ByteRange o = byte_range(C, bytes_c);      // tiles and matrices are written while others are still read
+        ARGCHK(!overlaps(o, byte_range(A, bytes_a)) && !overlaps(o, byte_range(B, bytes_b)));
+    }
+    // Matrices that Launchers::matmul would give to the matrix cores, or that are large enough for its skinny and split-K
+    // routes to matter (FFGPU_MM_STACK_LOOP_MIN; default: just above the largest matrix the stack kernels were measured on and won, profiles/r12_matmul_stack.md), go through it one by one; the
+    // others are one launch of the stack kernels, whose plan must hold the whole stack in one grid
+    const bool loop = (double)M * (double)N * (double)K >= (double)ctx->lc.mm_stack_loop_min ||
+                      (ctx->kind == FFGPU_PRIME && mfma_plane_bytes(ctx->lc, eb <= 8 ? 8 : 16, M, K, N) != 0);
+    if (!loop)
+        ARGCHK(stack_plan(M, K, N, batch, (int)eb, ctx->lc.num_cu, ctx->ops->stack_slot, stride_a == 0, stride_b == 0).ok);
+    CallScope cs(ctx, stream);
+    if (!loop)
+        return status_of(ctx->ops->matmul_stack(ctx->policy, cs.lc, A, lda, stride_a, B, ldb, stride_b, C, ldc, stride_c, (int)M,
+                                                (int)K, (int)N, batch, cs.st));
+    for (size_t b = 0; b < batch; ++b) {
+        const int rc = matmul_one(ctx, cs, (const char*)A + b * stride_a * eb, lda, (const char*)B + b * stride_b * eb, ldb,
+                                  (char*)C + b * stride_c * eb, ldc, M, K, N);
+        if (rc != FFGPU_OK) return rc;
+    }
+    return FFGPU_OK;
 }
 
 int ffgpu_convolve(ffgpu_ctx* ctx, const void* a, size_t na, const void* v, size_t nv, void* out, void* stream) {

@@ -2173,6 +2173,7 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 }  // namespace ffgpu
 
 #include "matmul.hpp"   // dense, skinny and matrix-core products
+#include "matmul_stack.hpp" // stacks of small and medium products in one launch
 #include "convolve.hpp" // full convolution of two arrays
 #include "scan.hpp"     // prefix scans and reductions along one axis
 #include "launch.hpp"   // host side: FieldOps table + launchers

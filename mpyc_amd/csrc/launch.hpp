@@ -19,6 +19,8 @@ struct LaunchCfg {
                             // column walk, 2 = always row tiles (tests drive both at small sizes; never changes a result)
     int scan_tile_threads;  // FFGPU_SCAN_TILE_THREADS: threads of a row-tile workgroup that hold elements (default: all 256; tests
                             // lower it so that small arrays span many tiles)
+    int mm_stack_loop_min;  // FFGPU_MM_STACK_LOOP_MIN: ffgpu_matmul_stack loops over the single-product launcher from this M*N*K per
+                            // matrix on (0: always); below it the whole stack is one launch of the stack kernels (matmul_stack.hpp)
     int handoff;            // FFGPU_HANDOFF=0: every streamed output non-temporal (no hand-off tracking, handoff.hpp)
     int keep_out;           // PER LAUNCH, never set in the context's copy: this launch's outputs feed the next launch on its
                             // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
@@ -101,6 +103,11 @@ struct FieldOps {
     // keys40: ks x (32-byte ChaCha key + 8-byte nonce)
     LaunchStatus (*prss_chacha)(const void* F, const LaunchCfg& lc, const uint8_t* keys40, int ks, int d, int l, int mask_bits, int rounds,
                        const uint64_t* weights2, const uint64_t* r2, int accumulate, void* out, size_t n, hipStream_t st);
+    // C[b] = A[b] @ B[b], b < batch, in one launch without workspace; strides in elements, 0 = one matrix shared by the stack
+    // (L_PLAN_REFUSED: stack_plan() refuses the sizes)
+    LaunchStatus (*matmul_stack)(const void* F, const LaunchCfg& lc, const void* A, size_t lda, size_t sa, const void* B, size_t ldb,
+                        size_t sb, void* C, size_t ldc, size_t sc, int M, int K, int N, size_t batch, hipStream_t st);
+    int stack_slot;         // LDS bytes of one staged element of the stack kernels (stack_plan's slot_bytes)
     // full convolution, na >= nv >= 1, out: na + nv - 1 elements
     LaunchStatus (*convolve)(const void* F, const LaunchCfg& lc, const void* a, size_t na, const void* v, size_t nv, void* out,
                     hipStream_t st);
@@ -862,6 +869,50 @@ struct Launchers {
         if (!mm_skinny_n(f, lc, m) && !mm_skinny_m(f, lc, m) && !mm_mfma(f, lc, m) && !mm_mfma_wide(f, lc, m)) mm_valu(f, m);
         return launched();
     }
+    // ---- stacks of products: one launch, the shape from stack_plan (matmul_stack_geom.hpp), no workspace -------------
+    enum { STACK_SLOT = F::EPW > 1 ? 1 : (DotAcc<F>::lazy ? 4 * (int)MatmulDigits<F, DotAcc<F>::lazy>::NL : (int)sizeof(W)) };
+    // (named member functions launch the kernels, see the note at launch_glds)
+    static void launch_stack_packed(const F& f, const StackPlan& p, const StackArgs& s, const E* A, const E* B, E* C, hipStream_t st) {
+        hipLaunchKernelGGL((k_matmul_stack_packed<F>), dim3((unsigned)p.grid), dim3(BLOCK), p.lds_bytes, st, f, A, B, C, s);
+    }
+    static void launch_stack_tiled(const F& f, const StackPlan& p, const StackArgs& s, const E* A, const E* B, E* C, hipStream_t st) {
+        if constexpr (F::EPW > 1) {
+            hipLaunchKernelGGL((k_matmul_stack_tiled_bytes<F>), dim3((unsigned)p.grid), dim3(BLOCK), 0, st, f, (const uint8_t*)A,
+                               (const uint8_t*)B, (uint8_t*)C, s);
+        } else {
+            if constexpr (sizeof(W) < 16) {             // (two- and three-limb words: the plan never asks for 64-row tiles)
+                if (p.bm == 64) {
+                    hipLaunchKernelGGL((k_matmul_stack_tiled<F, 4, 2>), dim3((unsigned)p.grid), dim3(BLOCK), 0, st, f, A, B, C, s);
+                    return;
+                }
+            }
+            hipLaunchKernelGGL((k_matmul_stack_tiled<F, 2, 2>), dim3((unsigned)p.grid), dim3(BLOCK), 0, st, f, A, B, C, s);
+        }
+    }
+    static LaunchStatus matmul_stack(const void* Fp, const LaunchCfg& lc, const void* A, size_t lda, size_t sa, const void* B, size_t ldb,
+                                     size_t sb, void* C, size_t ldc, size_t sc, int M, int K, int N, size_t batch, hipStream_t st) {
+        const F& f = policy(Fp);
+        const StackPlan p = stack_plan((size_t)M, (size_t)K, (size_t)N, batch, (int)sizeof(E), lc.num_cu, STACK_SLOT, sa == 0, sb == 0);
+        if (!p.ok) return L_PLAN_REFUSED;
+        StackArgs s = {};
+        s.lda = lda; s.sa = sa; s.ldb = ldb; s.sb = sb; s.ldc = ldc; s.sc = sc; s.batch = batch;
+        s.M = M; s.K = K; s.N = N;
+        if (p.shape == STACK_PACKED) {
+            s.P = p.P; s.KC = p.KC > 0 ? p.KC : 1; s.rows_a = p.rows_a; s.rows_b = p.rows_b;
+            // 16-byte loads: the operand's matrices of every workgroup are one aligned run, staged whole (KC == K)
+            const bool whole = K > 0 && p.KC == K && sizeof(E) <= 8;
+            auto run_ok = [&](const void* X, size_t ld, size_t cols, size_t stride, size_t per) {
+                return whole && aligned16(X) && ld == cols && (stride == 0 || (stride == per && ((size_t)p.P * per * sizeof(E)) % 16 == 0));
+            };
+            s.vec_a = run_ok(A, lda, (size_t)K, sa, (size_t)M * K) ? 1 : 0;
+            s.vec_b = run_ok(B, ldb, (size_t)N, sb, (size_t)K * N) ? 1 : 0;
+            launch_stack_packed(f, p, s, (const E*)A, (const E*)B, (E*)C, st);
+        } else {
+            s.bm = p.bm; s.bn = p.bn; s.tiles_m = p.tiles_m; s.tiles_n = p.tiles_n;
+            launch_stack_tiled(f, p, s, (const E*)A, (const E*)B, (E*)C, st);
+        }
+        return launched();
+    }
     // Shape by output count (convolve_geom.hpp): wide tiles once they give every compute unit lc.conv_wide_per_cu of them,
     // narrow ones below that, so that few outputs with many taps still fill the chip.  Neither needs scratch.
     template <class S>
@@ -1066,7 +1117,7 @@ struct Launchers {
             .ew2 = &ew2, .ew1 = &ew1, .muladd = &muladd, .split = &split, .rng_coeffs = &rng_coeffs,
             .recombine = &recombine, .pow = &pow, .inv = &inv, .matmul = &matmul, .dot = &dot,
             .gate = &gate, .sqrt_cl = &sqrt_cl, .gauss = &gauss, .group_matvec = &group_matvec, .beaver = &beaver,
-            .prss = &prss, .prss_chacha = &prss_chacha, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce};
+            .prss = &prss, .prss_chacha = &prss_chacha, .matmul_stack = &matmul_stack, .stack_slot = STACK_SLOT, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce};
         return &ops;
     }
 };

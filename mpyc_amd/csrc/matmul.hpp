@@ -173,16 +173,142 @@ __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* _
         }
 }
 
+// k_matmul's tile body for the stacked product (matmul_stack.hpp: k_matmul_stack_tiled), tile origin (m0, n0) given.
+// A COPY, not shared with k_matmul: with the body moved into this function 15 of k_matmul's 28 instantiations changed
+// their register figures (MONT128 2x2: 90 -> 150 VGPRs, 5 -> 3 waves per SIMD; profiles/r12_matmul_stack.md), so
+// k_matmul keeps its own text.  Keep the two in step: nothing in the build enforces it, the only guard is the GPU test
+// that compares every matrix of a stack byte for byte with ffgpu_matmul (tests/test_gpu_matmul_stack.py).  Thread
+// ownership inside a tile (ty + 16 i, tx + 16 j) is restated as stack_tile_row / stack_tile_col in
+// matmul_stack_geom.hpp for the host walk; it is not called from here, so that this text stays k_matmul's.
+template <class F, int TM, int TN>
+__device__ __forceinline__ void matmul_tile(const F& f, const typename F::elem* __restrict__ A, size_t lda,
+                                            const typename F::elem* __restrict__ B, size_t ldb,
+                                            typename F::elem* __restrict__ C, size_t ldc, int M, int K, int N,
+                                            const int m0, const int n0) {
+    typedef typename F::word W;
+    static_assert(F::EPW == 1, "packed fields use the byte-wise instantiation");
+    // multi-limb 2^k - c primes (round 6): the tiles are staged as 28-bit DIGITS and every term is NL^2 multiply-adds into
+    // column sums (fields.hpp LazyDot), reduced every 32 terms -- ~100 instructions per term with the 128-bit limb arithmetic
+    constexpr bool LZ = DotAcc<F>::lazy;
+    constexpr int NL = MatmulDigits<F, LZ>::NL;
+    constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = AccFlush<F>::TERMS;
+    static_assert(FLUSH % BK == 0, "the flush test follows whole k-steps");
+    using Acc = typename DotAcc<F>::type;
+    __shared__ W As[LZ ? 1 : BK][LZ ? 1 : BM + 1];
+    __shared__ W Bs[LZ ? 1 : BK][LZ ? 1 : BN + 1];
+    __shared__ uint32_t Ad[LZ ? BK : 1][LZ ? BM + 1 : 1][NL];
+    __shared__ uint32_t Bd[LZ ? BK : 1][LZ ? BN + 1 : 1][NL];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    Acc acc[TM][TN];
+    W tot[TM][TN];
+    bool have = false;
+    auto zero = [&](Acc& a_) {
+        if constexpr (LZ) f.lacc_zero(a_); else f.acc_zero(a_);
+    };
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) zero(acc[i][j]);
+    int since = 0;
+    for (int k0 = 0; k0 < K; k0 += BK) {
+        // stage A (BM x BK) transposed and B (BK x BN)
+        for (int idx = threadIdx.x; idx < BM * BK; idx += BLOCK) {
+            int mm = idx / BK, kk = idx % BK;
+            int gm = m0 + mm, gk = k0 + kk;
+            const bool ok = gm < M && gk < K;      // out-of-range: read element 0, then zero it
+            const W v = ff_keep_if<W>(f.prep(ld_elem<F>(A, ok ? (size_t)gm * lda + gk : 0)), ok);
+            if constexpr (LZ) {
+                uint32_t d[NL];
+                f.lacc_digits(v, d);
+#pragma unroll
+                for (int t_ = 0; t_ < NL; ++t_) Ad[kk][mm][t_] = d[t_];
+            } else {
+                As[kk][mm] = v;
+            }
+        }
+        for (int idx = threadIdx.x; idx < BK * BN; idx += BLOCK) {
+            int kk = idx / BN, nn = idx % BN;
+            int gk = k0 + kk, gn = n0 + nn;
+            const bool ok = gk < K && gn < N;
+            const W v = ff_keep_if<W>(ld_elem<F>(B, ok ? (size_t)gk * ldb + gn : 0), ok);
+            if constexpr (LZ) {
+                uint32_t d[NL];
+                f.lacc_digits(v, d);
+#pragma unroll
+                for (int t_ = 0; t_ < NL; ++t_) Bd[kk][nn][t_] = d[t_];
+            } else {
+                Bs[kk][nn] = v;
+            }
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < BK; ++kk) {
+            if constexpr (LZ) {
+                uint32_t a[TM][NL], b[TN][NL];
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int t_ = 0; t_ < NL; ++t_) a[i][t_] = Ad[kk][ty + 16 * i][t_];
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int t_ = 0; t_ < NL; ++t_) b[j][t_] = Bd[kk][tx + 16 * j][t_];
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) f.lacc_mac_digits(acc[i][j], a[i], b[j]);
+            } else {
+                W a[TM], b[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) a[i] = As[kk][ty + 16 * i];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b[j] = Bs[kk][tx + 16 * j];
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) f.acc_mac(acc[i][j], a[i], b[j]);
+            }
+        }
+        __syncthreads();
+        since += BK;
+        if (since >= FLUSH) {   // keep the unreduced accumulators inside their headroom (2^8 products; digit columns: 32)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    W part;
+                    if constexpr (LZ) part = f.lacc_reduce(acc[i][j]); else part = f.acc_reduce(acc[i][j]);
+                    tot[i][j] = have ? f.add(tot[i][j], part) : part;
+                    zero(acc[i][j]);
+                }
+            have = true;
+            since = 0;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            int gm = m0 + ty + 16 * i, gn = n0 + tx + 16 * j;
+            if (gm < M && gn < N) {
+                W r;
+                if constexpr (LZ) r = f.lacc_reduce(acc[i][j]); else r = f.acc_reduce(acc[i][j]);
+                if (have) r = f.add(tot[i][j], r);
+                st_elem<F>(C, (size_t)gm * ldc + gn, r);
+            }
+        }
+}
+
 // GF(2^n <= 8): one element per byte, computed element-wise (word = one element in the low byte)
 template <class F>
-__global__ __launch_bounds__(BLOCK) void k_matmul_bytes(F f, const uint8_t* __restrict__ A, size_t lda,
-                                                         const uint8_t* __restrict__ B, size_t ldb,
-                                                         uint8_t* __restrict__ C, size_t ldc, int M, int K, int N) {
+__device__ __forceinline__ void matmul_bytes_tile(const F& f, const uint8_t* __restrict__ A, size_t lda,
+                                                  const uint8_t* __restrict__ B, size_t ldb,
+                                                  uint8_t* __restrict__ C, size_t ldc, int M, int K, int N,
+                                                  const int m0, const int n0) {
     constexpr int BK = 16, BM = 32, BN = 32;
     __shared__ uint8_t As[BK][BM + 4];
     __shared__ uint8_t Bs[BK][BN + 4];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
     uint32_t acc[2][2] = {{0, 0}, {0, 0}};
     for (int k0 = 0; k0 < K; k0 += BK) {
         for (int idx = threadIdx.x; idx < BM * BK; idx += BLOCK) {
@@ -211,6 +337,12 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_bytes(F f, const uint8_t* __re
     if (gm0 < M && gn1 < N) C[(size_t)gm0 * ldc + gn1] = (uint8_t)((r >> 8) & 0xff);
     if (gm1 < M && gn0 < N) C[(size_t)gm1 * ldc + gn0] = (uint8_t)((r >> 16) & 0xff);
     if (gm1 < M && gn1 < N) C[(size_t)gm1 * ldc + gn1] = (uint8_t)(r >> 24);
+}
+template <class F>
+__global__ __launch_bounds__(BLOCK) void k_matmul_bytes(F f, const uint8_t* __restrict__ A, size_t lda,
+                                                         const uint8_t* __restrict__ B, size_t ldb,
+                                                         uint8_t* __restrict__ C, size_t ldc, int M, int K, int N) {
+    matmul_bytes_tile<F>(f, A, lda, B, ldb, C, ldc, M, K, N, blockIdx.y * 32, blockIdx.x * 32);
 }
 
 

@@ -612,6 +612,31 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_matmul(self._h, A.ptr, K, B.ptr, N, out.ptr, N, M, K, N, self._stream()), 'matmul')
         return out
 
+    def matmul_stack(self, A: DevArray, B: DevArray, batch: int, M: int, K: int, N: int, a_stride: int, b_stride: int,
+                     out: Optional[DevArray] = None) -> DevArray:
+        """C[b] (M, N) = A[b] (M, K) @ B[b] (K, N) for b < batch in one library call (NumPy's matmul on stacks of matrices,
+        finfields.py:1126-1135; the local product of runtime.np_matmul, runtime.py:2481-2541).  Row-major matrices, matrix b
+        of an operand a_stride / b_stride ELEMENTS after matrix b - 1; stride 0: the one matrix is shared by the whole
+        stack.  The result is a contiguous stack of batch * M * N elements."""
+        if batch < 0 or M < 0 or K < 0 or N < 0:
+            raise ValueError('matmul_stack: negative size')
+        for what, x, stride, per in (('left', A, a_stride, M * K), ('right', B, b_stride, K * N)):
+            if stride != 0 and stride < per:
+                raise ValueError(f'matmul_stack: the {what} stride is smaller than a matrix')
+            if x.n < ((batch - 1) * stride + per if batch else 0):
+                raise ValueError('matmul_stack: operand sizes do not match the shapes')
+        n = batch * M * N
+        if out is not None:
+            self._same(n, out, what='matmul_stack output')
+            eb = self.elem_bytes
+            for x in (A, B):                       # matrices of C are written while others still read A and B
+                if out.ptr < x.ptr + x.n * eb and x.ptr < out.ptr + out.n * eb:
+                    raise ValueError('matmul_stack: the output overlaps an operand')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_matmul_stack(self._h, A.ptr, K, a_stride, B.ptr, N, b_stride, out.ptr, N, M * N,
+                                              M, K, N, batch, self._stream()), 'matmul_stack')
+        return out
+
     def convolve(self, a: DevArray, v: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Full convolution out[k] = sum_j a[k - j] * v[j], len(a) + len(v) - 1 elements, in one kernel with memory linear
         in the operands (finfields.py:796-801; the local part of runtime.np_convolve, runtime.py:2627).  The operand

@@ -1799,21 +1799,16 @@ class FieldArray:
         if self.ndim == 0 or other.ndim == 0:
             raise ValueError('matmul: Input operand does not have enough dimensions')
         if self.ndim > 2 or other.ndim > 2:
-            # stacks of matrices (NumPy's matmul broadcasting over the leading dimensions): one product per matrix
+            # stacks of matrices (NumPy's matmul broadcasting over the leading dimensions)
             A = self.reshape(1, -1) if self.ndim == 1 else self
             B = other.reshape(-1, 1) if other.ndim == 1 else other
             if A._shape[-1] != B._shape[-2]:
                 raise ValueError(f'matmul: shapes {self._shape} and {other._shape} not aligned')
             batch = tuple(np.broadcast_shapes(A._shape[:-2], B._shape[:-2]))
-            lb = (self.ctx.limbs,) if self.ctx.limbs else ()
-            At = A._limb_view().expand(*batch, *A._shape[-2:], *lb).reshape(-1, *A._shape[-2:], *lb)
-            Bt = B._limb_view().expand(*batch, *B._shape[-2:], *lb).reshape(-1, *B._shape[-2:], *lb)
-            outs = [self._from_limb_view(At[i]) @ self._from_limb_view(Bt[i]) for i in range(At.shape[0])]
-            mshape = (A._shape[-2], B._shape[-1])
-            if not outs:
-                res = cls(np.zeros(batch + mshape, dtype=object))
-            else:
-                res = _np_stack(outs, 0).reshape(batch + mshape)
+            if getattr(self.ctx, '_h', None) is not None:     # a context with a library handle: one call for the stack
+                res = _matmul_stack(cls, A, B, batch)
+            else:                                             # (the Python-integer stand-in of the CPU tests has none)
+                res = _matmul_per_matrix(cls, A, B, batch)
             if self.ndim == 1:
                 res = res.reshape(res._shape[:-2] + res._shape[-1:])
             elif other.ndim == 1:
@@ -2659,6 +2654,50 @@ def _np_array_equiv(a1, a2):
         return bool((a1 == a2).all())
     except ValueError:
         return False
+
+
+def _matmul_per_matrix(cls, A, B, batch):
+    """Stacks of matrices composed from existing operations: both operands expanded to the broadcast batch shape, one 2-D
+    product per matrix from Python, the results concatenated.  The route of a context that cannot run the stack kernels
+    (the Python-integer stand-in of the CPU tests) and the yardstick they are measured against.
+    One fix against the loop `@` used to hold inline: the batch is spelled out where that loop reshaped with -1, which
+    raised for K == 0 on a stack (a size-0 array cannot fill an unknown dimension); K == 0 now gives zeros of the result
+    shape, as NumPy's matmul does and as the 2-D product already did.  Every other result is unchanged."""
+    ctx = A.ctx
+    lb = (ctx.limbs,) if ctx.limbs else ()
+    nb = int(np.prod(batch, dtype=np.int64)) if batch else 1
+    At = A._limb_view().expand(*batch, *A._shape[-2:], *lb).reshape(nb, *A._shape[-2:], *lb)
+    Bt = B._limb_view().expand(*batch, *B._shape[-2:], *lb).reshape(nb, *B._shape[-2:], *lb)
+    outs = [A._from_limb_view(At[i]) @ A._from_limb_view(Bt[i]) for i in range(nb)]
+    mshape = (A._shape[-2], B._shape[-1])
+    if not outs:
+        return cls(np.zeros(batch + mshape, dtype=object))
+    return _np_stack(outs, 0).reshape(batch + mshape)
+
+
+def _matmul_stack(cls, A, B, batch):
+    """Stacks of matrices (A: batch_a + (M, K), B: batch_b + (K, N), both with at least two dimensions) in one library
+    call.  A contiguous stack times ONE matrix is a single 2-D product (batch * M, K) @ (K, N), which gets the skinny and
+    matrix-core routes of FieldContext.matmul; one matrix times a stack and stack times stack are one matmul_stack call,
+    an operand shared by the whole stack passed with stride 0 instead of an expanded copy; partial broadcasts
+    ((3, 1, M, K) @ (1, 2, K, N)) are expanded to contiguous stacks first."""
+    ctx = A.ctx
+    (M, K), N = A._shape[-2:], B._shape[-1]
+    nb = int(np.prod(batch, dtype=np.int64)) if batch else 1
+    shape = batch + (M, N)
+    if nb == 0 or M == 0 or N == 0:
+        return cls(np.zeros(shape, dtype=object))
+    na = int(np.prod(A._shape[:-2], dtype=np.int64)) if A.ndim > 2 else 1
+    nbb = int(np.prod(B._shape[:-2], dtype=np.int64)) if B.ndim > 2 else 1
+    lb = (ctx.limbs,) if ctx.limbs else ()
+    if na not in (1, nb):                          # a partial broadcast of A: a contiguous stack of the full batch
+        A, na = A._from_limb_view(A._limb_view().expand(*batch, M, K, *lb)), nb
+    if nbb not in (1, nb):
+        B, nbb = B._from_limb_view(B._limb_view().expand(*batch, K, N, *lb)), nb
+    if nbb == 1:                                   # (also a batch of one matrix on both sides)
+        return cls._wrap(ctx.matmul(A._dev, B._dev, nb * M, K, N), shape)
+    out = ctx.matmul_stack(A._dev, B._dev, nb, M, K, N, M * K if na == nb else 0, K * N)
+    return cls._wrap(out, shape)
 
 
 def _convolve_toeplitz(cls, a, v):
