@@ -7,7 +7,7 @@ namespace ffgpu {
 
 // c[k] = sum_j a[k - j] v[j] over the field, na >= nv >= 1.  Geometry and index arithmetic: convolve_geom.hpp.  The inner
 // operation is k_matmul's: the lazily reduced multiply-accumulate of the policy (acc_mac, or 28-bit digit columns for the
-// multi-limb 2^k - c primes, whose operands are staged in LDS as digits), reduced every AccFlush<F>::TERMS terms.  The
+// multi-limb 2^k - c primes, whose operands are staged in LDS as digits), reduced every DotAcc<F>::FLUSH terms.  The
 // lanes of a tap group read ONE tap per step (same address: LDS broadcast; the wide shape's group is the whole wave) and
 // consecutive window elements (digit-major for the digit policies), the groups of a wave neighbouring taps and
 // overlapping windows, so no access conflicts on a bank.  The taps are the constant operand: f.prep, as for A in k_matmul.
@@ -23,8 +23,8 @@ __global__ __launch_bounds__(BLOCK) void k_convolve(F f, const typename F::elem*
     constexpr int R = S::R;
     static_assert((int)S::THREADS == (int)BLOCK, "ConvShape is laid out for the library's workgroup");
     constexpr bool LZ = DotAcc<F>::lazy;
-    constexpr int NL = MatmulDigits<F, LZ>::NL;
-    constexpr int FLUSH = AccFlush<F>::TERMS;
+    constexpr int NL = DotAcc<F>::NL;
+    constexpr int FLUSH = DotAcc<F>::FLUSH;
     static_assert(FLUSH % S::PER == 0, "the flush test follows whole chunks");
     using Acc = typename DotAcc<F>::type;
     __shared__ W Ws[LZ ? 1 : S::WIN];

@@ -498,25 +498,62 @@ struct GateSrc {
 // Policies with a dot product in 28-bit digits (fields.hpp LazyDot: the multi-limb 2^k - c primes) take it for sums of at
 // most FF_D28_MAX_TERMS terms -- the recombination kernels' K <= MAXK rows; everything else accumulates in F::acc.
 // DotAcc<F> is the one or the other: the sum of products lam * x of a pack loop (the scalar tails keep F::acc).
+// FLUSH: the terms it takes between reductions (F::acc has headroom for 2^8 products, a digit column for
+// FF_D28_MAX_TERMS).  NL: the digits of an operand staged for mac_digits (kernels that keep operands in LDS cut them
+// into digits once, when they stage them), 1 where the operands stay words.
 template <class F, class = void>
 struct DotAcc {
     static constexpr bool lazy = false;
+    enum { NL = 1, FLUSH = 192 };
     typedef typename F::acc type;
     type s;
     __device__ __forceinline__ void zero(const F& f) { f.acc_zero(s); }
     __device__ __forceinline__ void mac(const F& f, const typename F::word& lam, const typename F::word& x) { f.acc_mac(s, lam, x); }
     __device__ __forceinline__ typename F::word reduce(const F& f) const { return f.acc_reduce(s); }
+    // the same three on an accumulator the caller holds as the raw type (k_matvec_rows, matmul.hpp)
+    static __device__ __forceinline__ void zero(const F& f, type& a) { f.acc_zero(a); }
+    static __device__ __forceinline__ void mac(const F& f, type& a, const typename F::word& lam, const typename F::word& x) { f.acc_mac(a, lam, x); }
+    static __device__ __forceinline__ typename F::word reduce(const F& f, const type& a) { return f.acc_reduce(a); }
 };
 template <class F>
 struct DotAcc<F, std::void_t<typename F::lacc> > {
     static constexpr bool lazy = true;
+    enum { NL = F::LAZY_NL, FLUSH = FF_D28_MAX_TERMS };
     typedef typename F::lacc type;
     type s;
     __device__ __forceinline__ void zero(const F& f) { f.lacc_zero(s); }
     __device__ __forceinline__ void mac(const F& f, const typename F::word& lam, const typename F::word& x) { f.lacc_mac(s, lam, x); }
     __device__ __forceinline__ typename F::word reduce(const F& f) const { return f.lacc_reduce(s); }
+    static __device__ __forceinline__ void zero(const F& f, type& a) { f.lacc_zero(a); }
+    static __device__ __forceinline__ void mac(const F& f, type& a, const typename F::word& lam, const typename F::word& x) { f.lacc_mac(a, lam, x); }
+    static __device__ __forceinline__ typename F::word reduce(const F& f, const type& a) { return f.lacc_reduce(a); }
+    static __device__ __forceinline__ void digits(const F& f, const typename F::word& w, uint32_t (&d)[NL]) { f.lacc_digits(w, d); }
+    __device__ __forceinline__ void mac_digits(const F& f, const uint32_t (&a)[NL], const uint32_t (&b)[NL]) { f.lacc_mac_digits(s, a, b); }
 };
 static_assert(MAXK <= FF_D28_MAX_TERMS, "the digit accumulator's column bound");
+
+// A running sum of more terms than DotAcc takes at once: the accumulator and the reduced total of the flushes so far.
+// `have` (a flush has happened) and the term count belong to the kernel: they are the same for every sum it keeps
+// and wave-uniform, so one scalar serves all of them.
+template <class F>
+struct DotSum {
+    typedef typename F::word W;
+    DotAcc<F> acc;
+    W tot;
+    __device__ __forceinline__ void zero(const F& f) { acc.zero(f); }
+    __device__ __forceinline__ void mac(const F& f, const W& lam, const W& x) { acc.mac(f, lam, x); }
+    template <class D>
+    __device__ __forceinline__ void mac_digits(const F& f, const D& a, const D& b) { acc.mac_digits(f, a, b); }
+    __device__ __forceinline__ void flush(const F& f, bool have) {      // reduce, add into the total or start it, zero
+        const W part = acc.reduce(f);
+        tot = have ? f.add(tot, part) : part;
+        acc.zero(f);
+    }
+    __device__ __forceinline__ W result(const F& f, bool have) const {
+        const W r = acc.reduce(f);
+        return have ? f.add(tot, r) : r;
+    }
+};
 
 template <class F, bool NT>
 __device__ __forceinline__ Pack<typename F::word> gate_load(const F& f, const typename F::elem* const* rows,
@@ -1880,6 +1917,28 @@ __device__ __forceinline__ typename F::word block_reduce_add(const F& f, typenam
         __syncthreads();
     }
     return sm[0];
+}
+// CNT sums over the workgroup at once, CNT <= BLOCK: thread t contributes get(c) to sum c; a butterfly inside each wave
+// (cross-lane moves, no barrier), then ONE exchange of the per-wave sums through LDS (sm: CNT * BLOCK / 64 words);
+// thread c < CNT adds them and hands sum c to put(c, sum).
+template <int CNT, class F, class Get, class Put>
+__device__ __forceinline__ void block_reduce_add_each(const F& f, typename F::word* sm, Get get, Put put) {
+    typedef typename F::word W;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < CNT; ++c) {
+        W v = get(c);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = f.add(v, wave_shfl_xor(v, off));
+        if (lane == 0) sm[c * (BLOCK / 64) + wv] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < CNT) {
+        W v = sm[threadIdx.x * (BLOCK / 64)];
+#pragma unroll
+        for (int w2 = 1; w2 < BLOCK / 64; ++w2) v = f.add(v, sm[threadIdx.x * (BLOCK / 64) + w2]);
+        put((int)threadIdx.x, v);
+    }
 }
 
 template <class F, bool HAS_B>

@@ -870,7 +870,7 @@ struct Launchers {
         return launched();
     }
     // ---- stacks of products: one launch, the shape from stack_plan (matmul_stack_geom.hpp), no workspace -------------
-    enum { STACK_SLOT = F::EPW > 1 ? 1 : (DotAcc<F>::lazy ? 4 * (int)MatmulDigits<F, DotAcc<F>::lazy>::NL : (int)sizeof(W)) };
+    enum { STACK_SLOT = F::EPW > 1 ? 1 : (DotAcc<F>::lazy ? 4 * (int)DotAcc<F>::NL : (int)sizeof(W)) };
     // (named member functions launch the kernels, see the note at launch_glds)
     static void launch_stack_packed(const F& f, const StackPlan& p, const StackArgs& s, const E* A, const E* B, E* C, hipStream_t st) {
         hipLaunchKernelGGL((k_matmul_stack_packed<F>), dim3((unsigned)p.grid), dim3(BLOCK), p.lds_bytes, st, f, A, B, C, s);

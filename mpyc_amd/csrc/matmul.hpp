@@ -32,27 +32,13 @@ __device__ __forceinline__ W ff_keep_if(W v, bool ok) {
 // B into its own (M x N) slab of C (slab stride zstride elements); k_splitk_sum adds the slabs.  Shapes whose
 // output gives fewer tiles than the chip has CUs (a batch of 64 activations times a 4096^2 weight matrix) would
 // otherwise leave most of it idle.
-template <class F, bool LZ>
-struct MatmulDigits {                      // digits per staged element when the policy accumulates in 28-bit digits (round 6)
-    enum { NL = 1 };
-};
-template <class F>
-struct MatmulDigits<F, true> {
-    enum { NL = F::LAZY_NL };
-};
-// terms an unreduced accumulator takes between reductions: F::acc has headroom for 2^8 products, a digit column for
-// FF_D28_MAX_TERMS (fields.hpp).  k_matmul and k_convolve (convolve.hpp) flush on this bound.
-template <class F>
-struct AccFlush {
-    enum { TERMS = DotAcc<F>::lazy ? (int)FF_D28_MAX_TERMS : 192 };
-};
+// The tile itself is matmul_tile_body.hpp, the one text of the tile that this kernel and k_matmul_stack_tiled
+// (matmul_stack.hpp) both expand.
 template <class F, int TM, int TN>
 __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* __restrict__ A, size_t lda,
                                                    const typename F::elem* __restrict__ B, size_t ldb,
                                                    typename F::elem* __restrict__ C, size_t ldc, int M, int K, int N,
                                                    int kchunk, size_t zstride) {
-    typedef typename F::word W;
-    static_assert(F::EPW == 1, "packed fields use the byte-wise instantiation");
     if (kchunk > 0) {
         const int kz = blockIdx.z * kchunk;
         A += kz;
@@ -60,243 +46,9 @@ __global__ __launch_bounds__(BLOCK) void k_matmul(F f, const typename F::elem* _
         C += (size_t)blockIdx.z * zstride;
         K = K - kz < kchunk ? K - kz : kchunk;
     }
-    // multi-limb 2^k - c primes (round 6): the tiles are staged as 28-bit DIGITS and every term is NL^2 multiply-adds into
-    // column sums (fields.hpp LazyDot), reduced every 32 terms -- ~100 instructions per term with the 128-bit limb arithmetic
-    constexpr bool LZ = DotAcc<F>::lazy;
-    constexpr int NL = MatmulDigits<F, LZ>::NL;
-    constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = AccFlush<F>::TERMS;
-    static_assert(FLUSH % BK == 0, "the flush test follows whole k-steps");
-    using Acc = typename DotAcc<F>::type;
-    __shared__ W As[LZ ? 1 : BK][LZ ? 1 : BM + 1];
-    __shared__ W Bs[LZ ? 1 : BK][LZ ? 1 : BN + 1];
-    __shared__ uint32_t Ad[LZ ? BK : 1][LZ ? BM + 1 : 1][NL];
-    __shared__ uint32_t Bd[LZ ? BK : 1][LZ ? BN + 1 : 1][NL];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    Acc acc[TM][TN];
-    W tot[TM][TN];
-    bool have = false;
-    auto zero = [&](Acc& a_) {
-        if constexpr (LZ) f.lacc_zero(a_); else f.acc_zero(a_);
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) zero(acc[i][j]);
-    int since = 0;
-    for (int k0 = 0; k0 < K; k0 += BK) {
-        // stage A (BM x BK) transposed and B (BK x BN)
-        for (int idx = threadIdx.x; idx < BM * BK; idx += BLOCK) {
-            int mm = idx / BK, kk = idx % BK;
-            int gm = m0 + mm, gk = k0 + kk;
-            const bool ok = gm < M && gk < K;      // out-of-range: read element 0, then zero it
-            const W v = ff_keep_if<W>(f.prep(ld_elem<F>(A, ok ? (size_t)gm * lda + gk : 0)), ok);
-            if constexpr (LZ) {
-                uint32_t d[NL];
-                f.lacc_digits(v, d);
-#pragma unroll
-                for (int t_ = 0; t_ < NL; ++t_) Ad[kk][mm][t_] = d[t_];
-            } else {
-                As[kk][mm] = v;
-            }
-        }
-        for (int idx = threadIdx.x; idx < BK * BN; idx += BLOCK) {
-            int kk = idx / BN, nn = idx % BN;
-            int gk = k0 + kk, gn = n0 + nn;
-            const bool ok = gk < K && gn < N;
-            const W v = ff_keep_if<W>(ld_elem<F>(B, ok ? (size_t)gk * ldb + gn : 0), ok);
-            if constexpr (LZ) {
-                uint32_t d[NL];
-                f.lacc_digits(v, d);
-#pragma unroll
-                for (int t_ = 0; t_ < NL; ++t_) Bd[kk][nn][t_] = d[t_];
-            } else {
-                Bs[kk][nn] = v;
-            }
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int kk = 0; kk < BK; ++kk) {
-            if constexpr (LZ) {
-                uint32_t a[TM][NL], b[TN][NL];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int t_ = 0; t_ < NL; ++t_) a[i][t_] = Ad[kk][ty + 16 * i][t_];
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int t_ = 0; t_ < NL; ++t_) b[j][t_] = Bd[kk][tx + 16 * j][t_];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) f.lacc_mac_digits(acc[i][j], a[i], b[j]);
-            } else {
-                W a[TM], b[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a[i] = As[kk][ty + 16 * i];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[j] = Bs[kk][tx + 16 * j];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) f.acc_mac(acc[i][j], a[i], b[j]);
-            }
-        }
-        __syncthreads();
-        since += BK;
-        if (since >= FLUSH) {   // keep the unreduced accumulators inside their headroom (2^8 products; digit columns: 32)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    W part;
-                    if constexpr (LZ) part = f.lacc_reduce(acc[i][j]); else part = f.acc_reduce(acc[i][j]);
-                    tot[i][j] = have ? f.add(tot[i][j], part) : part;
-                    zero(acc[i][j]);
-                }
-            have = true;
-            since = 0;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            int gm = m0 + ty + 16 * i, gn = n0 + tx + 16 * j;
-            if (gm < M && gn < N) {
-                W r;
-                if constexpr (LZ) r = f.lacc_reduce(acc[i][j]); else r = f.acc_reduce(acc[i][j]);
-                if (have) r = f.add(tot[i][j], r);
-                st_elem<F>(C, (size_t)gm * ldc + gn, r);
-            }
-        }
-}
-
-// k_matmul's tile body for the stacked product (matmul_stack.hpp: k_matmul_stack_tiled), tile origin (m0, n0) given.
-// A COPY, not shared with k_matmul: with the body moved into this function 15 of k_matmul's 28 instantiations changed
-// their register figures (MONT128 2x2: 90 -> 150 VGPRs, 5 -> 3 waves per SIMD; profiles/r12_matmul_stack.md), so
-// k_matmul keeps its own text.  Keep the two in step: nothing in the build enforces it, the only guard is the GPU test
-// that compares every matrix of a stack byte for byte with ffgpu_matmul (tests/test_gpu_matmul_stack.py).  Thread
-// ownership inside a tile (ty + 16 i, tx + 16 j) is restated as stack_tile_row / stack_tile_col in
-// matmul_stack_geom.hpp for the host walk; it is not called from here, so that this text stays k_matmul's.
-template <class F, int TM, int TN>
-__device__ __forceinline__ void matmul_tile(const F& f, const typename F::elem* __restrict__ A, size_t lda,
-                                            const typename F::elem* __restrict__ B, size_t ldb,
-                                            typename F::elem* __restrict__ C, size_t ldc, int M, int K, int N,
-                                            const int m0, const int n0) {
-    typedef typename F::word W;
-    static_assert(F::EPW == 1, "packed fields use the byte-wise instantiation");
-    // multi-limb 2^k - c primes (round 6): the tiles are staged as 28-bit DIGITS and every term is NL^2 multiply-adds into
-    // column sums (fields.hpp LazyDot), reduced every 32 terms -- ~100 instructions per term with the 128-bit limb arithmetic
-    constexpr bool LZ = DotAcc<F>::lazy;
-    constexpr int NL = MatmulDigits<F, LZ>::NL;
-    constexpr int BK = 16, BM = 16 * TM, BN = 16 * TN, FLUSH = AccFlush<F>::TERMS;
-    static_assert(FLUSH % BK == 0, "the flush test follows whole k-steps");
-    using Acc = typename DotAcc<F>::type;
-    __shared__ W As[LZ ? 1 : BK][LZ ? 1 : BM + 1];
-    __shared__ W Bs[LZ ? 1 : BK][LZ ? 1 : BN + 1];
-    __shared__ uint32_t Ad[LZ ? BK : 1][LZ ? BM + 1 : 1][NL];
-    __shared__ uint32_t Bd[LZ ? BK : 1][LZ ? BN + 1 : 1][NL];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    Acc acc[TM][TN];
-    W tot[TM][TN];
-    bool have = false;
-    auto zero = [&](Acc& a_) {
-        if constexpr (LZ) f.lacc_zero(a_); else f.acc_zero(a_);
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) zero(acc[i][j]);
-    int since = 0;
-    for (int k0 = 0; k0 < K; k0 += BK) {
-        // stage A (BM x BK) transposed and B (BK x BN)
-        for (int idx = threadIdx.x; idx < BM * BK; idx += BLOCK) {
-            int mm = idx / BK, kk = idx % BK;
-            int gm = m0 + mm, gk = k0 + kk;
-            const bool ok = gm < M && gk < K;      // out-of-range: read element 0, then zero it
-            const W v = ff_keep_if<W>(f.prep(ld_elem<F>(A, ok ? (size_t)gm * lda + gk : 0)), ok);
-            if constexpr (LZ) {
-                uint32_t d[NL];
-                f.lacc_digits(v, d);
-#pragma unroll
-                for (int t_ = 0; t_ < NL; ++t_) Ad[kk][mm][t_] = d[t_];
-            } else {
-                As[kk][mm] = v;
-            }
-        }
-        for (int idx = threadIdx.x; idx < BK * BN; idx += BLOCK) {
-            int kk = idx / BN, nn = idx % BN;
-            int gk = k0 + kk, gn = n0 + nn;
-            const bool ok = gk < K && gn < N;
-            const W v = ff_keep_if<W>(ld_elem<F>(B, ok ? (size_t)gk * ldb + gn : 0), ok);
-            if constexpr (LZ) {
-                uint32_t d[NL];
-                f.lacc_digits(v, d);
-#pragma unroll
-                for (int t_ = 0; t_ < NL; ++t_) Bd[kk][nn][t_] = d[t_];
-            } else {
-                Bs[kk][nn] = v;
-            }
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int kk = 0; kk < BK; ++kk) {
-            if constexpr (LZ) {
-                uint32_t a[TM][NL], b[TN][NL];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int t_ = 0; t_ < NL; ++t_) a[i][t_] = Ad[kk][ty + 16 * i][t_];
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int t_ = 0; t_ < NL; ++t_) b[j][t_] = Bd[kk][tx + 16 * j][t_];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) f.lacc_mac_digits(acc[i][j], a[i], b[j]);
-            } else {
-                W a[TM], b[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a[i] = As[kk][ty + 16 * i];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[j] = Bs[kk][tx + 16 * j];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) f.acc_mac(acc[i][j], a[i], b[j]);
-            }
-        }
-        __syncthreads();
-        since += BK;
-        if (since >= FLUSH) {   // keep the unreduced accumulators inside their headroom (2^8 products; digit columns: 32)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    W part;
-                    if constexpr (LZ) part = f.lacc_reduce(acc[i][j]); else part = f.acc_reduce(acc[i][j]);
-                    tot[i][j] = have ? f.add(tot[i][j], part) : part;
-                    zero(acc[i][j]);
-                }
-            have = true;
-            since = 0;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            int gm = m0 + ty + 16 * i, gn = n0 + tx + 16 * j;
-            if (gm < M && gn < N) {
-                W r;
-                if constexpr (LZ) r = f.lacc_reduce(acc[i][j]); else r = f.acc_reduce(acc[i][j]);
-                if (have) r = f.add(tot[i][j], r);
-                st_elem<F>(C, (size_t)gm * ldc + gn, r);
-            }
-        }
+    const int m0 = blockIdx.y * (16 * TM), n0 = blockIdx.x * (16 * TN);
+#include "matmul_tile_body.hpp"
 }
 
 // GF(2^n <= 8): one element per byte, computed element-wise (word = one element in the low byte)
@@ -870,28 +622,17 @@ __global__ __launch_bounds__(BLOCK) void k_limb_gemm_wide(F f, const int8_t* __r
 // bottleneck (demos/np_bnnmnist.py:10-15: `L @ W` with a 1 x 4096 activation row and a 4096 x 4096 weight
 // matrix, finfields.py:1126-1135) have one output dimension of 1..8.  Both are HBM-bound: the big operand is
 // read exactly once, coalesced, the small one stays in L2; products are accumulated unreduced (flush every
-// 192 terms, as k_dot_partial) and reduced once.
-enum { SKINNY_MAX = 8, SKINNY_FLUSH = 192 };
+// DotAcc<F>::FLUSH terms) and reduced once.
+enum { SKINNY_MAX = 8, SKINNY_FLUSH = 192 };    // SKINNY_FLUSH: the flush bound of the ColAcc kernels
 // (the column-sum kernels below test the count AFTER adding a whole group of terms: a flush happens at no more than
 // SKINNY_FLUSH - 1 + group terms, which must stay within ColAcc::MAX_TERMS = 256 -- asserted where each group size is known)
 
-// The accumulator of the matrix x few-columns kernels: the policy's dot product in 28-bit digits where it has one (the
-// multi-limb 2^k - c primes, round 6: ~45 instead of ~100 instructions per term, flushed every 32 terms), else F::acc.
-template <class F>
-struct SkinnyAcc {
-    static constexpr bool LZ = DotAcc<F>::lazy;
-    typedef typename DotAcc<F>::type T;
-    enum { FLUSH = LZ ? (int)FF_D28_MAX_TERMS : (int)SKINNY_FLUSH };
-    static __device__ __forceinline__ void zero(const F& f, T& a) {
-        if constexpr (LZ) f.lacc_zero(a); else f.acc_zero(a);
-    }
-    static __device__ __forceinline__ void mac(const F& f, T& a, const typename F::word& l, const typename F::word& x) {
-        if constexpr (LZ) f.lacc_mac(a, l, x); else f.acc_mac(a, l, x);
-    }
-    static __device__ __forceinline__ typename F::word reduce(const F& f, const T& a) {
-        if constexpr (LZ) return f.lacc_reduce(a); else return f.acc_reduce(a);
-    }
-};
+// The accumulator of the matrix x few-columns kernels is DotAcc<F>'s (kernels.hpp): the policy's dot product in 28-bit
+// digits where it has one (the multi-limb 2^k - c primes, round 6: ~45 instead of ~100 instructions per term, flushed
+// every 32 terms), else F::acc.  k_matvec_rows_r keeps its running sums in DotSum<F>; k_matvec_rows (and
+// k_vecmat_partial below) spell the same sum out by hand on the raw accumulator type (here through DotAcc's static
+// forms): as DotSum, as an array of DotAcc<F>, or with lambdas in place of the static functions, their eight-sum instantiations over GF(2^128) gained 128 bytes of scratch and k_matvec_rows<MONT128, 8>
+// lost a wave per SIMD and ran 10 % slower (profiles/r13_matmul_one_body.md).
 
 // C (M x N) = A (M x K) @ B (K x N), N <= SKINNY_MAX: one workgroup per row of A
 template <class F, int NN>
@@ -905,19 +646,19 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows(F f, const typename F::el
     __shared__ W sm[BLOCK];
     const size_t row = blockIdx.x;
     const typename F::elem* __restrict__ a = A + row * lda;
-    typedef SkinnyAcc<F> SA;
-    typename SA::T acc[NN];
+    typedef DotAcc<F> DA;
+    typename DA::type acc[NN];
     W total[NN];
     bool have = false;
     int cnt = 0;
 #pragma unroll
-    for (int j = 0; j < NN; ++j) SA::zero(f, acc[j]);
+    for (int j = 0; j < NN; ++j) DA::zero(f, acc[j]);
     auto flush = [&]() {
 #pragma unroll
         for (int j = 0; j < NN; ++j) {
-            W part = SA::reduce(f, acc[j]);
+            W part = DA::reduce(f, acc[j]);
             total[j] = have ? f.add(total[j], part) : part;
-            SA::zero(f, acc[j]);
+            DA::zero(f, acc[j]);
         }
         have = true;
         cnt = 0;
@@ -932,15 +673,15 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows(F f, const typename F::el
                     const P bp = ldg<false>(br + jp);
 #pragma unroll
                     for (int q = 0; q < P::N; ++q)
-                        if (jp * P::N + q < NN) SA::mac(f, acc[jp * P::N + q], xp, bp.w[q]);
+                        if (jp * P::N + q < NN) DA::mac(f, acc[jp * P::N + q], xp, bp.w[q]);
                 }
             }
         } else {
 #pragma unroll
             for (int j = 0; j < NN; ++j)
-                if (j < N) SA::mac(f, acc[j], xp, ld_elem<F>(B, kk * ldb + j));
+                if (j < N) DA::mac(f, acc[j], xp, ld_elem<F>(B, kk * ldb + j));
         }
-        if (++cnt >= SA::FLUSH) flush();
+        if (++cnt >= DA::FLUSH) flush();
     };
     constexpr int EPV = P::N;
     const int nvec = vec ? K / EPV : 0;
@@ -976,24 +717,18 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows_r(F f, const typename F::
     typedef typename F::word W;
     __shared__ W sm[BLOCK];
     const size_t row0 = (size_t)blockIdx.x * R;
-    typedef SkinnyAcc<F> SA;
-    typename SA::T acc[R][NN];
-    W total[R][NN];
+    DotSum<F> sum[R][NN];
     bool have = false;
     int cnt = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int j = 0; j < NN; ++j) SA::zero(f, acc[r][j]);
+        for (int j = 0; j < NN; ++j) sum[r][j].zero(f);
     auto flush = [&]() {
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int j = 0; j < NN; ++j) {
-                W part = SA::reduce(f, acc[r][j]);
-                total[r][j] = have ? f.add(total[r][j], part) : part;
-                SA::zero(f, acc[r][j]);
-            }
+            for (int j = 0; j < NN; ++j) sum[r][j].flush(f, have);
         have = true;
         cnt = 0;
     };
@@ -1001,7 +736,7 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows_r(F f, const typename F::
     const int nvec = vec ? K / EPV : 0;
     // (UN packs of every row and of B in flight before the first multiply-add: one pack at a time ran at the memory latency --
     // 16 dependent round trips for a 4096-element row of 12-byte elements: 53 us = 0.47 of HBM for 4096^2)
-    constexpr int UN = (SA::LZ && EPV == 1) ? 4 : 1;
+    constexpr int UN = (DotAcc<F>::lazy && EPV == 1) ? 4 : 1;
     auto packs = [&](int i0, auto un) {
         constexpr int U = decltype(un)::value;
         P x[U][R];
@@ -1032,9 +767,9 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows_r(F f, const typename F::
                 for (int q = 0; q < EPV; ++q)
 #pragma unroll
                     for (int j = 0; j < NN; ++j)
-                        if (j < N) SA::mac(f, acc[r][j], b[u][q][j], x[u][r].w[q]);
+                        if (j < N) sum[r][j].mac(f, b[u][q][j], x[u][r].w[q]);
             cnt += EPV;
-            if (cnt >= SA::FLUSH) flush();
+            if (cnt >= DotAcc<F>::FLUSH) flush();
         }
     };
     int i = threadIdx.x;
@@ -1048,31 +783,14 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows_r(F f, const typename F::
                 const W bp = f.prep(ld_elem<F>(B, (size_t)kk * ldb + j));
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    SA::mac(f, acc[r][j], bp, ld_elem<F>(A, (row0 + r < (size_t)M ? row0 + r : (size_t)M - 1) * lda + kk));
+                    sum[r][j].mac(f, bp, ld_elem<F>(A, (row0 + r < (size_t)M ? row0 + r : (size_t)M - 1) * lda + kk));
             }
-        if (++cnt >= SA::FLUSH) flush();
+        if (++cnt >= DotAcc<F>::FLUSH) flush();
     }
-    flush();
-    // R*NN sums over the workgroup: butterfly inside each wave (cross-lane moves, no barrier), then ONE exchange
-    // of the per-wave sums through LDS
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < NN; ++j) {
-            W v = total[r][j];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v = f.add(v, wave_shfl_xor(v, off));
-            if (lane == 0) sm[(r * NN + j) * (BLOCK / 64) + wv] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < R * NN) {
-        const int r = threadIdx.x / NN, j = threadIdx.x % NN;
-        W v = sm[threadIdx.x * (BLOCK / 64)];
-#pragma unroll
-        for (int w2 = 1; w2 < BLOCK / 64; ++w2) v = f.add(v, sm[threadIdx.x * (BLOCK / 64) + w2]);
+    block_reduce_add_each<R * NN>(f, sm, [&](int c) { return sum[c / NN][c % NN].result(f, have); }, [&](int c, const W& v) {
+        const int r = c / NN, j = c % NN;
         if (j < N && row0 + r < (size_t)M) st_elem<F>(C, (row0 + r) * ldc + j, v);
-    }
+    });
 }
 
 // Matrix x few columns (2 <= N <= 8) over one-word primes (col_mac_ok): column sums (fields.hpp ColAcc).  Here no operand is
@@ -1256,25 +974,10 @@ __global__ __launch_bounds__(BLOCK) void k_matvec_rows_col(F f, const typename F
         term(xr, b);
         if (++cnt >= SKINNY_FLUSH) flush();
     }
-    // R*NN sums over the workgroup: butterfly inside each wave, then one exchange of the per-wave sums through LDS
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < NN; ++j) {
-            W v = f.acc_reduce(acc[r][j].gather());
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v = f.add(v, wave_shfl_xor(v, off));
-            if (lane == 0) sm[(r * NN + j) * (BLOCK / 64) + wv] = v;
-        }
-    __syncthreads();
-    if (threadIdx.x < R * NN) {
-        const int r = threadIdx.x / NN, j = threadIdx.x % NN;
-        W v = sm[threadIdx.x * (BLOCK / 64)];
-#pragma unroll
-        for (int w2 = 1; w2 < BLOCK / 64; ++w2) v = f.add(v, sm[threadIdx.x * (BLOCK / 64) + w2]);
+    block_reduce_add_each<R * NN>(f, sm, [&](int c) { return f.acc_reduce(acc[c / NN][c % NN].gather()); }, [&](int c, const W& v) {
+        const int r = c / NN, j = c % NN;
         if (row0 + r < (size_t)M) st_elem<F>(C, (row0 + r) * ldc + j, v);
-    }
+    });
 }
 
 // Same product for SHORT rows (K <= 32, many rows: sums over a trailing axis, tall-thin least squares): one
@@ -1314,14 +1017,6 @@ constexpr int VECMAT_KT = 32;
 // the staged entries of A are stored as digits, a row of B is cut once per thread and used for all M rows, every term is NL^2
 // multiply-adds into column sums, reduced every FF_D28_MAX_TERMS terms -- 8 x 4096 @ 4096^2 over the 80-bit prime: 384 us with
 // the 128-bit limb arithmetic of acc_mac (~100 instructions per term).
-template <class F, bool LZ>
-struct VecmatDigits {                      // (only named when LZ)
-    enum { NL = 1 };
-};
-template <class F>
-struct VecmatDigits<F, true> {
-    enum { NL = F::LAZY_NL };
-};
 template <class F, int MM, bool VEC, bool STAGE, int UNR = 4>
 __global__ __launch_bounds__(BLOCK) void k_vecmat_partial(F f, const typename F::elem* __restrict__ A, size_t lda,
                                                            const typename F::elem* __restrict__ B, size_t ldb,
@@ -1333,9 +1028,9 @@ __global__ __launch_bounds__(BLOCK) void k_vecmat_partial(F f, const typename F:
     constexpr int CW = VEC ? P::N : 1;                              // columns per thread
     constexpr int KT = VECMAT_KT;
     constexpr bool LZ = DotAcc<F>::lazy;                           // digit accumulators (staged A: its digits live in LDS)
-    constexpr int NL = VecmatDigits<F, LZ>::NL;
-    constexpr int FLUSH = LZ ? (int)FF_D28_MAX_TERMS : (int)SKINNY_FLUSH;
-    static_assert(!LZ || FF_D28_MAX_TERMS % UNR == 0, "the flush test follows whole groups");
+    constexpr int NL = DotAcc<F>::NL;
+    constexpr int FLUSH = DotAcc<F>::FLUSH;
+    static_assert(!LZ || FLUSH % UNR == 0, "the flush test follows whole groups");
     using Acc = typename DotAcc<F>::type;
     __shared__ W sa[(STAGE && !LZ) ? MM : 1][(STAGE && !LZ) ? KT : 1];
     __shared__ uint32_t sad[(LZ && STAGE) ? MM : 1][(LZ && STAGE) ? KT : 1][NL];

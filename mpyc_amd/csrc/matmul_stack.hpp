@@ -19,8 +19,9 @@ struct StackArgs {
 
 // ---- packed shape: M N <= BLOCK, P matrices per workgroup, one output per thread --------------------------------
 // The inner operation is k_matmul's: the policy's lazily reduced multiply-accumulate (acc_mac, or 28-bit digit columns
-// for the multi-limb 2^k - c primes, staged in LDS as digits), flushed every AccFlush<F>::TERMS terms; the packed-byte
-// fields multiply four terms per SWAR word (k_matmul_bytes).  Results are canonical, so they equal k_matmul's bit for bit.
+// for the multi-limb 2^k - c primes, staged in LDS as digits), flushed every DotAcc<F>::FLUSH terms (DotSum,
+// kernels.hpp); the packed-byte fields multiply four terms per SWAR word (k_matmul_bytes).  Results are canonical, so
+// they equal k_matmul's bit for bit.
 // Staging: the P matrices of a contiguous stack are ONE run in memory, read by consecutive threads (16 bytes per lane
 // for elements of up to 8 bytes when the run is aligned; wider elements are 12 to 24 bytes per lane as they are).
 // LDS layout: operand X as [term][digit][row], row = (matrix in the workgroup) * M + i for A, * N + j for B.  For a fixed
@@ -35,9 +36,8 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_packed(F f, const typena
     typedef typename F::elem E;
     constexpr bool BY = F::EPW > 1;                    // one element per byte
     constexpr bool LZ = !BY && DotAcc<F>::lazy;
-    constexpr int NL = MatmulDigits<F, LZ>::NL;
-    constexpr int FLUSH = AccFlush<F>::TERMS;
-    using Acc = typename DotAcc<F>::type;
+    constexpr int NL = DotAcc<F>::NL;
+    constexpr int FLUSH = DotAcc<F>::FLUSH;
     extern __shared__ __attribute__((aligned(16))) unsigned char stack_smem[];
     const int M = s.M, K = s.K, N = s.N, P = s.P, tid = threadIdx.x;
     const size_t b0 = (size_t)blockIdx.x * (size_t)P;
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_packed(F f, const typena
             base[kk * rows + row] = (uint8_t)v;
         } else if constexpr (LZ) {
             uint32_t d[NL];
-            f.lacc_digits(v, d);
+            DotAcc<F>::digits(f, v, d);
             uint32_t* q = reinterpret_cast<uint32_t*>(base);
 #pragma unroll
             for (int t_ = 0; t_ < NL; ++t_) q[(kk * NL + t_) * rows + row] = d[t_];
@@ -101,14 +101,11 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_packed(F f, const typena
         }
     };
 
-    Acc acc;
+    DotSum<F> sum;
     uint32_t bacc = 0;
-    W tot;
     bool have = false;
     int since = 0;
-    if constexpr (!BY) {
-        if constexpr (LZ) f.lacc_zero(acc); else f.acc_zero(acc);
-    }
+    if constexpr (!BY) sum.zero(f);
     for (int k0 = 0; k0 < K; k0 += s.KC) {
         const int kc = K - k0 < s.KC ? K - k0 : s.KC;
         stage(std::true_type(), A, s.lda, s.sa, M, kc, k0, s.vec_a, sA, rows_a);
@@ -137,15 +134,12 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_packed(F f, const typena
                             a[t_] = qa[(kk * NL + t_) * rows_a + ra];
                             x[t_] = qb[(kk * NL + t_) * rows_b + rb];
                         }
-                        f.lacc_mac_digits(acc, a, x);
+                        sum.mac_digits(f, a, x);
                     } else {
-                        f.acc_mac(acc, reinterpret_cast<const W*>(sA)[kk * rows_a + ra], reinterpret_cast<const W*>(sB)[kk * rows_b + rb]);
+                        sum.mac(f, reinterpret_cast<const W*>(sA)[kk * rows_a + ra], reinterpret_cast<const W*>(sB)[kk * rows_b + rb]);
                     }
                     if (++since == FLUSH) {             // keep the unreduced accumulator inside its headroom
-                        W part;
-                        if constexpr (LZ) part = f.lacc_reduce(acc); else part = f.acc_reduce(acc);
-                        tot = have ? f.add(tot, part) : part;
-                        if constexpr (LZ) f.lacc_zero(acc); else f.acc_zero(acc);
+                        sum.flush(f, have);
                         have = true;
                         since = 0;
                     }
@@ -161,14 +155,22 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_packed(F f, const typena
         bacc ^= bacc >> 8;
         out[0] = (uint8_t)(bacc & 0xffu);
     } else {
-        W r;
-        if constexpr (LZ) r = f.lacc_reduce(acc); else r = f.acc_reduce(acc);
-        if (have) r = f.add(tot, r);
-        st_elem<F>(out, 0, r);
+        st_elem<F>(out, 0, sum.result(f, have));
     }
 }
 
 // ---- tiled shape: k_matmul's tile body, the matrix index folded into a flat tile index --------------------------
+// The second expansion of matmul_tile_body.hpp.  It sits in a function of its own, not in the kernel, for the
+// __restrict__ of the per-matrix pointers: expanded in the kernel, where only the stack's base pointers are parameters,
+// k_matmul_stack_tiled<MONT128, 2, 2> ran 4 to 17 % slower (profiles/r13_matmul_one_body.md).
+template <class F, int TM, int TN>
+__device__ __forceinline__ void stack_tile(const F& f, const typename F::elem* __restrict__ A, size_t lda,
+                                           const typename F::elem* __restrict__ B, size_t ldb,
+                                           typename F::elem* __restrict__ C, size_t ldc, int M, int K, int N,
+                                           const int m0, const int n0) {
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#include "matmul_tile_body.hpp"
+}
 template <class F, int TM, int TN>
 __global__ __launch_bounds__(BLOCK) void k_matmul_stack_tiled(F f, const typename F::elem* __restrict__ A,
                                                                const typename F::elem* __restrict__ B,
@@ -176,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void k_matmul_stack_tiled(F f, const typenam
     size_t b;
     int m0, n0;
     stack_tile_of(blockIdx.x, s.tiles_m, s.tiles_n, 16 * TM, 16 * TN, b, m0, n0);
-    matmul_tile<F, TM, TN>(f, A + b * s.sa, s.lda, B + b * s.sb, s.ldb, C + b * s.sc, s.ldc, s.M, s.K, s.N, m0, n0);
+    stack_tile<F, TM, TN>(f, A + b * s.sa, s.lda, B + b * s.sb, s.ldb, C + b * s.sc, s.ldc, s.M, s.K, s.N, m0, n0);
 }
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_matmul_stack_tiled_bytes(F f, const uint8_t* __restrict__ A, const uint8_t* __restrict__ B,

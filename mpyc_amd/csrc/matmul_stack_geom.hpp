@@ -110,7 +110,7 @@ FFSTACK_HD void stack_tile_of(size_t flat, size_t tiles_m, size_t tiles_n, int b
     n0 = (int)(r % tiles_n) * bn;
 }
 // tiled: thread t of a tile owns rows m0 + t / 16 + 16 u (u < bm / 16) and columns n0 + t % 16 + 16 v (v < bn / 16).
-// A RESTATEMENT for the host walk of what matmul_tile (matmul.hpp) computes inline as ty + 16 i, tx + 16 j: the kernel
+// A RESTATEMENT for the host walk of what the tile body (matmul_tile_body.hpp) computes inline as ty + 16 i, tx + 16 j: the kernel
 // does not call these two.
 FFSTACK_HD int stack_tile_row(int m0, int t, int u) { return m0 + (t >> 4) + 16 * u; }
 FFSTACK_HD int stack_tile_col(int n0, int t, int v) { return n0 + (t & 15) + 16 * v; }

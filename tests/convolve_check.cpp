@@ -13,7 +13,7 @@
 using namespace ffgpu;
 
 typedef PM64<false, true> F;            // p = 2^61 - 1
-enum { FLUSH = 192 };                   // AccFlush<F>::TERMS for a policy without digit accumulators (matmul.hpp)
+enum { FLUSH = 192 };                   // DotAcc<F>::FLUSH for a policy without digit accumulators (kernels.hpp)
 
 static F make_field() {
     F f;

@@ -746,8 +746,11 @@ def test_matmul(eng, coracle):
         eb = ctx.elem_bytes
         cf = coracle.CField(modulus, binary)
         slow = eb >= 12
-        for (M, K, N) in [(1, 1, 1), (64, 64, 64), (70, 130, 65), (3, 500, 5), (33, 17, 129)] if not slow else \
-                [(1, 1, 1), (33, 40, 35), (3, 300, 5)]:
+        # the last two: 81 tiles of 64 x 32, ragged on both edges -- k_matmul<F, 4, 2> for one-word fields (the others are
+        # below 64 tiles: 2 x 2); K = 50: one launch; K = 200: beyond the 192-term flush, and where the product stays on
+        # the VALU (binary fields; primes go to the matrix cores at this size) split-K slabs of 48 with a last slab of 8
+        for (M, K, N) in [(1, 1, 1), (64, 64, 64), (70, 130, 65), (3, 500, 5), (33, 17, 129), (520, 50, 260), (513, 200, 257)] \
+                if not slow else [(1, 1, 1), (33, 40, 35), (3, 300, 5)]:
             A, B = rand_np(F, eb, M * K, 81), rand_np(F, eb, K * N, 82)
             if not binary:
                 A[:K] = pack([F.order - 1] * K, eb)             # worst-case accumulation in row 0

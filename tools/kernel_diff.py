@@ -100,7 +100,7 @@ def main():
                     print('   ', tag, k)
                     if tag in '~m':
                         print('        instructions', ca[k][3], '->', cb[k][3],
-                              *(f'{x.split(":")[0]} {x.split()[-1]} -> {y.split()[-1]}' for x, y in zip(ma[k], mb[k]) if x != y))
+                              *(f'{x.split(":")[0]} {x.split()[-1]} -> {y.split()[-1]}' for x, y in zip(ma.get(k, ()), mb.get(k, ())) if x != y))
     print(f'total kernels {total[0]} -> {total[1]}; units with added or changed kernels: {bad}')
     return 1 if bad else 0
 
