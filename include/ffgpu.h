@@ -27,7 +27,12 @@
  *     Calls are asynchronous on that stream; nothing synchronises unless the
  *     name says so.
  *   - inputs are never written; `out` may alias an input of the same shape for
- *     the element-wise entry points (in-place operators, finfields.py:1068-1124).
+ *     the element-wise entry points (in-place operators, finfields.py:1068-1124):
+ *     ffgpu_reduce, ffgpu_add, ffgpu_sub, ffgpu_mul, ffgpu_neg, ffgpu_add_scalar,
+ *     ffgpu_mul_scalar, ffgpu_rsub_scalar, ffgpu_muladd, ffgpu_pow, ffgpu_inv and
+ *     ffgpu_beaver_combine.  Inputs may also alias each other (a == b).  Exact
+ *     alias only; partial overlap is undefined.  Elements are canonical on return
+ *     (tests/test_gpu_elementwise_contract.py).
  *   - thread-safety: the field description of a context is immutable after
  *     creation and a context may be shared between host threads and streams;
  *     its only mutable state -- the ffgpu_matmul scratch buffers (one per

@@ -1356,9 +1356,11 @@ __global__ __launch_bounds__(BLOCK) void k_inv_batch(F f, const typename F::elem
                     W v = (j < nvec) ? t_.w[q] : ff_one(f);
                     v = ff_zero_fix(f, v, zq);
                     if constexpr (F::EPW > 1) {
-                        // packed sub-elements: keep the per-byte mask of this word (at most 4 words per thread here)
-                        zbits |= (uint64_t)zq << (8 * (((g * CH + c) * P::N + q) & 7));
-                        static_assert(F::EPW == 1 || CH * G * P::N <= 8, "packed fields: 8 words per batch");
+                        // packed sub-elements: zq marks the zero bytes of this word at bits 0, 8, 16, 24; zbits is only ever
+                        // tested against zero, so the words share its low bits.  (A shift by 8 x the word's index pushed
+                        // the marks of bytes 1..3 of the last words past bit 63: a zero there was missed whenever it was
+                        // the only one of its wave -- no flag, and the unfixed second read zeroed its byte lane.)
+                        zbits |= (uint64_t)zq;
                     } else {
                         zbits |= (uint64_t)(zq & 1u) << ((g * CH + c) * P::N + q);
                     }

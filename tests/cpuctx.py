@@ -84,6 +84,14 @@ class CpuFieldContext(engine.FieldContext):
     def muladd(self, a, b, c, out=None):
         return self._map(lambda x, y, z: po.add(self.F, po.mul(self.F, x, y), z), out, a, b, c)
 
+    def beaver_combine(self, z, x, y, d, e, add_de, out=None):
+        F = self.F
+
+        def one(z_, x_, y_, d_, e_):
+            r = po.add(F, po.add(F, z_, po.mul(F, d_, y_)), po.mul(F, e_, x_))
+            return po.add(F, r, po.mul(F, d_, e_)) if add_de else r
+        return self._map(one, out, z, x, y, d, e)
+
     def _pow1(self, x, e):
         r = 1
         while e:

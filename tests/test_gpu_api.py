@@ -871,3 +871,47 @@ def test_public_operand_uploads_are_keyed_by_content(api):
     r += 5
     s3 = (bits + v)._real()                       # ... and the cached operand still holds the values of `bits`
     assert (s3 == s2).all() and (d._real() == (want - bits.astype(object)) % F.order).all()
+
+
+def _contract_fields():
+    import ew_contract
+    return ew_contract.contract_fields()
+
+
+@pytest.mark.parametrize('modulus,binary', _contract_fields(), ids=[('gf2:' if b else '') + hex(m) for m, b in _contract_fields()])
+def test_in_place_operators_on_aliased_operands(api, modulus, binary):
+    """A *= A, A += A, A -= A (ctx.mul(a, a, out=a), ...) and the scalar forms in place, on every field policy, against the
+    Python-integer oracle; the right operand of A *= B is left as it was (include/ffgpu.h: inputs are never written, `out` may
+    alias an input; tests/test_gpu_elementwise_contract.py checks the same at the C ABI)."""
+    from oracle import pyoracle as po
+    finfields, gfpx, _ = api
+    F = finfields.GF(gfpx.BinaryPolynomial(modulus)) if binary else finfields.GF(modulus)
+    Fo = po.Field(modulus, binary)
+    q = Fo.order
+    r = random.Random(modulus % 1009)
+    n = 1025
+    a, b = [r.randrange(q) for _ in range(n)], [r.randrange(q) for _ in range(n)]
+    a[:3] = [0, 1, q - 1]
+    s = r.randrange(q)
+
+    def imul(x, y):
+        x *= y
+        return x
+
+    def iadd(x, y):
+        x += y
+        return x
+
+    def isub(x, y):
+        x -= y
+        return x
+    for op, ref in ((imul, po.mul), (iadd, po.add), (isub, po.sub)):
+        A = F.array(a)
+        got = op(A, A)
+        assert got is A and ints(A) == [ref(Fo, x, x) for x in a], (hex(modulus), ref.__name__, 'A op= A')
+        A = F.array(a)
+        got = op(A, s)
+        assert got is A and ints(A) == [ref(Fo, x, s) for x in a], (hex(modulus), ref.__name__, 'A op= s')
+    A, B = F.array(a), F.array(b)
+    A *= B
+    assert ints(B) == b and ints(A) == [po.mul(Fo, x, y) for x, y in zip(a, b)]
