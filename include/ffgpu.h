@@ -344,6 +344,41 @@ int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t o
                       void* workspace, size_t workspace_bytes, void* stream);
 size_t ffgpu_scan_workspace_bytes(ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner);
 
+/* ---- secure comparison: the local steps of np_sgn ----------------------------------- */
+/* What one party computes between the openings of runtime.np_sgn (a < 0, a == 0, sign), on its own shares.  Prime fields
+ * only (FFGPU_ENOTSUP for GF(2^n)), integers (frac_length 0).  n values of bit length l; everything is mod p; bit index i
+ * runs most significant first, as shifts = arange(l-1, -1, -1) does.  Shares are arbitrary canonical field elements:
+ *   a[n]        the values;
+ *   rbits[n*l]  element-major: rbits[h*l + i] is the share of the random bit of weight 2^(l-1-i) of element h;
+ *   sbit[n]     the share of the sign-mask bit (the reference takes the last n random bits);
+ *   rdivl[n]    the share of the high mask.
+ * ffgpu_sgn_mask:   masked[h] = a[h] + 2^l + sum_i rbits[h*l+i] 2^(l-1-i) + rdivl[h] 2^l -- the value that is opened.
+ *   replaces: runtime.py:3649-3657 (reshape, `r_bits << shifts`, the row sum, a_r, `a_r + (r_divl << l)`).
+ * ffgpu_sgn_expand: c[n] is the opened public value (canonical).  With cl = c[h] mod 2^l (the canonical integer),
+ *   cb_i = bit l-1-i of cl, r_i = rbits[h*l+i], s = 2 sbit[h] - 1, x_i = cb_i ? 1 - r_i : r_i, S_i = x_0 + ... + x_(i-1):
+ *     e_out[i*n+h]  = s - cb_i + r_i + 3 S_i for i < l, e_out[l*n+h] = s - 1 + 3 S_l      bit-major (l+1, n)
+ *     nx_out[i*n+h] = 1 - x_i                                                             bit-major (l, n)
+ *     z_out[h]      = cl - a[h] - 2^l - sum_i r_i 2^(l-1-i)
+ *   Each of e_out, nx_out, z_out may be NULL (all three: FFGPU_EINVAL); sbit may be NULL only when e_out is (the
+ *   equality test draws no sign bit).  One kernel: a workgroup stages a tile of rbits through LDS with coalesced loads
+ *   and every thread walks the bits of its own element, so the transposed outputs are written coalesced too
+ *   (csrc/sgn_geom.hpp).
+ *   replaces: runtime.py:3658-3671 (`c & mask`, z, right_shift.outer, the transpose, Xor, vstack, cumsum, e) and the
+ *   `1 - Xor` of :3679 -- and the host-built c_bits with its upload.
+ * ffgpu_sgn_finish: w[n] is the opened masked product of the rows of e; with g = (w[h] == 0):
+ *     lt_out[h] = (z[h] + ((1 - 2g) s + 3) 2^(l-1)) 2^-l        -- the share of [a < 0].
+ *   replaces: runtime.py:3674-3676 (g from the opened value, h, `Zp.array(z + (h << l-1)) >> l`).
+ * All three are asynchronous on `stream`, allocate nothing and never synchronise (they can be captured in a HIP graph);
+ * inputs are never written, outputs are canonical.  n == 0: FFGPU_OK.  FFGPU_EINVAL, nothing launched: a null context or
+ * required pointer; l < 1, l > 64 or l > bit_length(p) - 2 (2^l, 2^(l-1) and 2^-l must be field elements); n*l or its
+ * byte size overflowing; an output range that overlaps an input or another output.                              */
+int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, int l, void* masked, size_t n,
+                   void* stream);
+int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* rbits, const void* sbit, int l, void* e_out,
+                     void* nx_out, void* z_out, size_t n, void* stream);
+int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void* z, int l, void* lt_out, size_t n,
+                     void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

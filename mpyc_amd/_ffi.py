@@ -80,6 +80,9 @@ _SIGS = {
     'ffgpu_scan': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _int, _vp, _sz, _vp],
     'ffgpu_axis_reduce': [_vp, _int, _vp, _vp, _sz, _sz, _sz, _vp, _sz, _vp],
     'ffgpu_scan_workspace_bytes': [_vp, _sz, _sz, _sz],
+    'ffgpu_sgn_mask': [_vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
+    'ffgpu_sgn_expand': [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _sz, _vp],
+    'ffgpu_sgn_finish': [_vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
     'ffgpu_sqrt_cl': [_vp, _vp, _vp, _sz, _vp],
     'ffgpu_gauss': [_vp, _vp, _int, _int, _sz, _int, _vp, _vp, _vp],
     'ffgpu_group_matvec': [_vp, _u64p, _u64p, _int, _int, _vp, _vp, _sz, _vp],

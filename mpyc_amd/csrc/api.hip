@@ -1189,6 +1189,104 @@ int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t o
     return do_scan(ctx, true, op, a, out, outer, k, inner, 0, workspace, workspace_bytes, stream);
 }
 
+// ---- secure comparison: the local steps of np_sgn (sgn.hpp) -------------------------------------------------------------
+// 2^l, 2^(l-1) and 2^-l mod p as host scalars of the context's limb count; false unless 1 <= l <= 64 and
+// l <= bit_length(p) - 2 (the three constants are then field elements, 2^l < p / 2)
+static bool sgn_consts(const ffgpu_ctx* ctx, int l, uint64_t out[9]) {
+    const uint64_t* p = ctx->modulus;
+    const int top = p[2] ? 2 : p[1] ? 1 : 0;
+    const int bits = 64 * top + (64 - __builtin_clzll(p[top] | 1));
+    if (l < 1 || l > SGN_MAX_L || l > bits - 2) return false;
+    const int sl = ffgpu_ctx_scalar_limbs(ctx);
+    for (int i = 0; i < 9; ++i) out[i] = 0;
+    out[0 * sl + l / 64] = 1ull << (l % 64);
+    out[1 * sl + (l - 1) / 64] = 1ull << ((l - 1) % 64);
+    uint64_t x[4] = {1, 0, 0, 0};                       // halve l times: x <- x / 2 mod p (x + p when x is odd)
+    for (int i = 0; i < l; ++i) {
+        if (x[0] & 1) {
+            unsigned __int128 carry = 0;
+            for (int j = 0; j < 4; ++j) {
+                carry += (unsigned __int128)x[j] + (j < 3 ? p[j] : 0);
+                x[j] = (uint64_t)carry;
+                carry >>= 64;
+            }
+        }
+        for (int j = 0; j < 4; ++j) x[j] = (x[j] >> 1) | (j < 3 ? x[j + 1] << 63 : 0);
+    }
+    for (int j = 0; j < sl; ++j) out[2 * sl + j] = x[j];
+    return true;
+}
+// no output range may overlap an input or another output
+static bool sgn_ranges_ok(const ByteRange* in, int nin, const ByteRange* out, int nout) {
+    for (int j = 0; j < nout; ++j) {
+        for (int i = 0; i < nin; ++i)
+            if (overlaps(out[j], in[i])) return false;
+        for (int i = 0; i < j; ++i)
+            if (overlaps(out[j], out[i])) return false;
+    }
+    return true;
+}
+
+int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, int l, void* masked, size_t n,
+                   void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t consts[9];
+    ARGCHK(sgn_consts(ctx, l, consts));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && rbits && rdivl && masked);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, l, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
+    const ByteRange o = byte_range(masked, n * eb);
+    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->sgn_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
+}
+
+int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* rbits, const void* sbit, int l, void* e_out,
+                     void* nx_out, void* z_out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t consts[9];
+    ARGCHK(sgn_consts(ctx, l, consts));
+    ARGCHK(e_out || nx_out || z_out);
+    ARGCHK(sbit || !e_out);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(c && a && rbits);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, l, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[4] = {byte_range(c, n * eb), byte_range(a, n * eb), byte_range(rbits, p.nl * eb),
+                             byte_range(sbit, sbit ? n * eb : 0)};
+    ByteRange o[3];
+    int no = 0;
+    if (e_out) o[no++] = byte_range(e_out, (p.nl + n) * eb);
+    if (nx_out) o[no++] = byte_range(nx_out, p.nl * eb);
+    if (z_out) o[no++] = byte_range(z_out, n * eb);
+    ARGCHK(sgn_ranges_ok(in, 4, o, no));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->sgn_expand(ctx->policy, cs.lc, c, a, rbits, e_out ? sbit : nullptr, l, consts, e_out, nx_out, z_out,
+                                          n, cs.st));
+}
+
+int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void* z, int l, void* lt_out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t consts[9];
+    ARGCHK(sgn_consts(ctx, l, consts));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(w && sbit && z && lt_out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(n <= ((size_t)1 << 62) / eb);                 // n * eb cannot overflow
+    const ByteRange in[3] = {byte_range(w, n * eb), byte_range(sbit, n * eb), byte_range(z, n * eb)};
+    const ByteRange o = byte_range(lt_out, n * eb);
+    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

@@ -2237,4 +2237,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "matmul_stack.hpp" // stacks of small and medium products in one launch
 #include "convolve.hpp" // full convolution of two arrays
 #include "scan.hpp"     // prefix scans and reductions along one axis
+#include "sgn.hpp"      // local steps of the secure comparison (np_sgn)
 #include "launch.hpp"   // host side: FieldOps table + launchers

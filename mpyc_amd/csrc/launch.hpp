@@ -117,6 +117,14 @@ struct FieldOps {
                 int with_initial, void* workspace, size_t workspace_bytes, hipStream_t st);
     LaunchStatus (*axis_reduce)(const void* F, const LaunchCfg& lc, int mul, const void* a, void* out, size_t outer, size_t k,
                        size_t inner, void* workspace, size_t workspace_bytes, hipStream_t st);
+    // local steps of the secure comparison (sgn.hpp), prime fields only; consts: the host scalars 2^l, 2^(l-1), 2^-l
+    // (L_PLAN_REFUSED: sgn_plan() refuses the sizes)
+    LaunchStatus (*sgn_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivl, int l,
+                    const uint64_t* consts, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*sgn_expand)(const void* F, const LaunchCfg& lc, const void* c, const void* a, const void* rbits, const void* sbit,
+                      int l, const uint64_t* consts, void* e, void* nx, void* z, size_t n, hipStream_t st);
+    LaunchStatus (*sgn_finish)(const void* F, const LaunchCfg& lc, const void* w, const void* sbit, const void* z, int l,
+                      const uint64_t* consts, void* out, size_t n, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -983,6 +991,46 @@ struct Launchers {
         if (mul) return go_scan<true, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
         return go_scan<false, true>(f, lc, (const E*)a, (E*)out, outer, k, inner, 0, (E*)workspace, workspace_bytes, st);
     }
+    // The local steps of the secure comparison (sgn.hpp): a workgroup per tile of SGN_TILE elements for mask and expand,
+    // the streaming plan for finish.  Constants (2^l, 2^(l-1), 2^-l) travel as kernel arguments.
+    static LaunchStatus sgn_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivl, int l,
+                        const uint64_t* consts, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan p = sgn_plan(n, l, sizeof(E));
+            if (!p.ok) return L_PLAN_REFUSED;
+            hipLaunchKernelGGL((k_sgn_mask<F>), dim3((unsigned)p.tiles), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)rbits,
+                               (const E*)rdivl, l, word_at<F>(f, consts, 0), (E*)out, n);
+            return launched();
+        }
+    }
+    static LaunchStatus sgn_expand(const void* Fp, const LaunchCfg& lc, const void* c, const void* a, const void* rbits,
+                          const void* sbit, int l, const uint64_t* consts, void* e, void* nx, void* z, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan p = sgn_plan(n, l, sizeof(E));
+            if (!p.ok) return L_PLAN_REFUSED;
+            hipLaunchKernelGGL((k_sgn_expand<F>), dim3((unsigned)p.tiles), dim3(BLOCK), 0, st, f, (const E*)c, (const E*)a,
+                               (const E*)rbits, (const E*)sbit, l, word_at<F>(f, consts, 0), (E*)e, (E*)nx, (E*)z, n);
+            return launched();
+        }
+    }
+    static LaunchStatus sgn_finish(const void* Fp, const LaunchCfg& lc, const void* w, const void* sbit, const void* z, int l,
+                          const uint64_t* consts, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const Plan p = plan(n, al(w) && al(sbit) && al(z) && al(out), lc);
+            hipLaunchKernelGGL((k_sgn_finish<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)w, (const E*)sbit, (const E*)z,
+                               word_at<F>(f, consts, 1), word_at<F>(f, consts, 2), (E*)out, p.nvec, n, p.keep);
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1117,7 +1165,8 @@ struct Launchers {
             .ew2 = &ew2, .ew1 = &ew1, .muladd = &muladd, .split = &split, .rng_coeffs = &rng_coeffs,
             .recombine = &recombine, .pow = &pow, .inv = &inv, .matmul = &matmul, .dot = &dot,
             .gate = &gate, .sqrt_cl = &sqrt_cl, .gauss = &gauss, .group_matvec = &group_matvec, .beaver = &beaver,
-            .prss = &prss, .prss_chacha = &prss_chacha, .matmul_stack = &matmul_stack, .stack_slot = STACK_SLOT, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce};
+            .prss = &prss, .prss_chacha = &prss_chacha, .matmul_stack = &matmul_stack, .stack_slot = STACK_SLOT, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce,
+            .sgn_mask = &sgn_mask, .sgn_expand = &sgn_expand, .sgn_finish = &sgn_finish};
         return &ops;
     }
 };

@@ -700,6 +700,44 @@ class FieldContext:
                                              self._stream()), 'axis_reduce')
         return out
 
+    # ---- secure comparison: the local steps of runtime.np_sgn (runtime.py:3622-3693), prime fields ----
+    def sgn_mask(self, a: DevArray, rbits: DevArray, rdivl: DevArray, l: int, out: Optional[DevArray] = None) -> DevArray:
+        """masked[h] = a[h] + 2^l + sum_i rbits[h*l+i] 2^(l-1-i) + rdivl[h] 2^l, the value np_sgn opens
+        (runtime.py:3649-3657).  rbits: n*l bit shares, element-major, most significant bit first."""
+        n = a.n
+        self._same(n, rdivl, out, what='sgn_mask operand')
+        self._same(n * l, rbits, what='sgn_mask bit shares')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_sgn_mask(self._h, a.ptr, rbits.ptr, rdivl.ptr, l, out.ptr, n, self._stream()), 'sgn_mask')
+        return out
+
+    def sgn_expand(self, c: DevArray, a: DevArray, rbits: DevArray, sbit: Optional[DevArray], l: int, want_e: bool = True,
+                   want_nx: bool = False):
+        """From the opened c: (e, nx, z) of runtime.py:3658-3671, :3679 -- e the (l+1, n) operands of the product tree,
+        nx = 1 - Xor as (l, n), both bit-major, z = (c mod 2^l) - a_r.  e / nx are None unless asked for; sbit (the
+        sign-mask bit shares) may be None when want_e is False."""
+        n = a.n
+        self._same(n, c, sbit, what='sgn_expand operand')
+        self._same(n * l, rbits, what='sgn_expand bit shares')
+        if want_e and sbit is None:
+            raise ValueError('sgn_expand: e needs the sign-mask bit shares')
+        e = self.empty((l + 1) * n) if want_e else None
+        nx = self.empty(l * n) if want_nx else None
+        z = self.empty(n)
+        _ffi.check(self._L.ffgpu_sgn_expand(self._h, c.ptr, a.ptr, rbits.ptr, sbit.ptr if sbit is not None else None, l,
+                                            e.ptr if want_e else None, nx.ptr if want_nx else None, z.ptr, n,
+                                            self._stream()), 'sgn_expand')
+        return e, nx, z
+
+    def sgn_finish(self, w: DevArray, sbit: DevArray, z: DevArray, l: int, out: Optional[DevArray] = None) -> DevArray:
+        """lt[h] = (z[h] + ((1 - 2 [w[h] == 0]) (2 sbit[h] - 1) + 3) 2^(l-1)) 2^-l: the share of [a < 0] from the
+        opened masked product w (runtime.py:3674-3676)."""
+        n = w.n
+        self._same(n, sbit, z, out, what='sgn_finish operand')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_sgn_finish(self._h, w.ptr, sbit.ptr, z.ptr, l, out.ptr, n, self._stream()), 'sgn_finish')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

@@ -159,6 +159,68 @@ def from_bits(ctx: FieldContext, bits: Shares, l: int = 8) -> Shares:
     return [ctx.group_matvec(b, weights) for b in bits]
 
 
+# ---- secure comparison over a prime field (runtime.np_sgn, runtime.py:3622-3693) -------------------------------
+def _rows(ctx: FieldContext, x: DevArray, lo: int, hi: int, n: int) -> DevArray:
+    """rows lo .. hi-1 of a bit-major (rows, n) array: a view"""
+    return DevArray(ctx, x.t[lo * n:hi * n], (hi - lo) * n)
+
+
+def prod_rows(ctx: FieldContext, field, xs: Shares, rows: int, t: int, rng=None) -> Shares:
+    """runtime.np_prod along the leading axis (runtime.py:2198-2203) of a bit-major (rows, n) sharing: each level
+    multiplies the lower half of the rows with the upper half in one secure multiplication, an odd leading row is carried
+    over to the next level; ceil(log2 rows) rounds.  Returns shares of the n products."""
+    if rows < 1 or xs[0].n % rows:
+        raise ValueError('prod_rows: the arrays are not (rows, n)')
+    n = xs[0].n // rows
+    while rows > 1:
+        n0, half = rows % 2, (rows + 1) // 2
+        prod = multiply(ctx, field, [_rows(ctx, x, n0, half, n) for x in xs], [_rows(ctx, x, half, rows, n) for x in xs], t, rng)
+        xs = [_cat(ctx, [_rows(ctx, x, 0, 1, n), p]) for x, p in zip(xs, prod)] if n0 else prod
+        rows = half
+    return list(xs)
+
+
+def is_zero_public(ctx: FieldContext, field, xs: Shares, rzero: Shares, t: int) -> DevArray:
+    """runtime.np_is_zero_public for large fields (runtime.py:946-949 and the opening at threshold 2t): every party
+    multiplies its share with its share of nonzero randomness (a degree-2t sharing of x r) and the product is opened from
+    2t+1 parties.  Returns the PUBLIC w = x r: zero exactly where x is.  rzero: a caller-supplied sharing of nonzero
+    random values."""
+    k = 2 * t + 1
+    if len(xs) < k:
+        raise ValueError('the zero test opens a degree-2t sharing: m >= 2t+1 parties')
+    return open_(ctx, field, [ctx.mul(xs[i], rzero[i]) for i in range(k)], t, degree=2 * t)
+
+
+def compare_zero(ctx: FieldContext, field, xs: Shares, rbits: Shares, sbits: Optional[Shares], rdivl: Shares,
+                 rzero: Optional[Shares], t: int, l: int, mode: str = 'lt', rng=None) -> Shares:
+    """runtime.np_sgn (runtime.py:3622-3693) on integers for all parties: mask -> open -> expand -> prod_rows(e) ->
+    is_zero_public -> finish, the three local steps one kernel each (ffgpu_sgn_mask / _expand / _finish).
+
+    mode 'lt': shares of [a < 0] (LT=True); 'eq': shares of [a == 0] = prod_rows(1 - Xor) (EQ=True; sbits and rzero are
+    not used and may be None); 'sgn': shares of the sign, (eq - 1) (2 lt - 1), one more multiplication.
+
+    It is assumed that -2^(l-1) <= a < 2^(l-1), and the caller guarantees 2^(l+1) + 2^l max(rdivl) < p so that the opened
+    value does not wrap.  The random inputs are sharings supplied by the caller: rbits n*l random bits per party
+    (element-major, most significant first), sbits n random bits, rdivl n random values below the statistical bound,
+    rzero n nonzero random values."""
+    if mode not in ('lt', 'eq', 'sgn'):
+        raise ValueError("mode is 'lt', 'eq' or 'sgn'")
+    m = len(xs)
+    c = open_(ctx, field, [ctx.sgn_mask(xs[i], rbits[i], rdivl[i], l) for i in range(t + 1)], t)
+    want_e, want_nx = mode != 'eq', mode != 'lt'
+    ex = [ctx.sgn_expand(c, xs[i], rbits[i], sbits[i] if want_e else None, l, want_e=want_e, want_nx=want_nx) for i in range(m)]
+    eq = prod_rows(ctx, field, [x[1] for x in ex], l, t, rng) if want_nx else None
+    if mode == 'eq':
+        return eq
+    w = is_zero_public(ctx, field, prod_rows(ctx, field, [x[0] for x in ex], l + 1, t, rng), rzero, t)
+    lt = [ctx.sgn_finish(w, sbits[i], ex[i][2], l) for i in range(m)]
+    if mode == 'lt':
+        return lt
+    p = ctx.modulus
+    return multiply(ctx, field, [ctx.add_scalar(x, p - 1) for x in eq],
+                    [ctx.add_scalar(ctx.mul_scalar(x, 2), p - 1) for x in lt], t, rng)
+
+
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
 # The per-party functions above issue one launch per party and step (what each MPyC party does in its own
 # process).  When all m parties of a computation sit on one GPU the parties' launches of a step are identical
