@@ -379,6 +379,34 @@ int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* r
 int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void* z, int l, void* lt_out, size_t n,
                      void* stream);
 
+/* ---- sorting network: the two ends of a compare-exchange stage ------------------------ */
+/* runtime.np_sort is Batcher's merge-exchange network along one axis.  The array is contiguous row-major (outer, k, inner),
+ * element (o, j, i) at (o*k + j)*inner + i, the network runs along k (the convention of ffgpu_scan).  A stage is (p, d, r)
+ * from the reference's loop: p a power of two and either r == 0, d == p, or r == p with d + p a larger power of two.  Its
+ * index set I = { i < k - d : i & p == r } has P = ffgpu_cx_pairs(k, p, d, r) members, the j-th is
+ * I_j = (j / p) * 2p + (j % p) + r, and I and I + d are disjoint (csrc/sort_geom.hpp).  Prime fields only (FFGPU_ENOTSUP
+ * for GF(2^n)); everything is mod p.
+ * ffgpu_cx_pairs: P; 0 for an invalid stage.  Needs no context and no device.
+ * ffgpu_cx_diff:  out[(o*P + j)*inner + i] = a[o, I_j + d, i] - a[o, I_j, i] -- compact (outer, P, inner), the values
+ *   the caller compares with zero.
+ *   replaces: runtime.py:1764-1767 (the index array I, the gathers a[..., I] and a[..., I + d], b1 - b0).
+ * ffgpu_cx_apply: with h = sum_s lambda[s] * rows[s][(o*P + j)*inner + i]:  a[o, I_j, i] += h and a[o, I_j + d, i] -= h,
+ *   in place.  rows / lambda as for ffgpu_recombine (w = 1): the nrows sub-share rows of the re-shared product
+ *   [b1 < b0] * (b1 - b0) a party received and the Lagrange vector, recombined in registers on the way; nrows = 1 with
+ *   lambda = [1] applies an h that already exists.  1 <= nrows <= 9; more rows: FFGPU_ENOTSUP, the status
+ *   ffgpu_recombine gives for more rows than it takes.  Positions of `a` outside I and I + d are not touched.
+ *   replaces: runtime.py:1768-1770 (b0 + h, b1 - h, the two np_update scatters) and the recombination of the product
+ *   before them (thresha.py:119-132).
+ * Both are asynchronous on `stream`, allocate nothing and never synchronise (they can be captured in a HIP graph); inputs
+ * are never written, outputs are canonical.  FFGPU_OK, nothing launched: outer*inner == 0 or P == 0.  FFGPU_EINVAL,
+ * nothing launched: a null context or pointer; k < 2; (p, d, r) not a stage; nrows < 1; outer*k*inner or its byte size
+ * overflowing; `out` or a row overlapping `a`.                                                                  */
+size_t ffgpu_cx_pairs(size_t k, size_t p, size_t d, size_t r);
+int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r,
+                  void* stream);
+int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, size_t outer,
+                   size_t k, size_t inner, size_t p, size_t d, size_t r, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

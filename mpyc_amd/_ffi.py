@@ -83,6 +83,9 @@ _SIGS = {
     'ffgpu_sgn_mask': [_vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
     'ffgpu_sgn_expand': [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _sz, _vp],
     'ffgpu_sgn_finish': [_vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
+    'ffgpu_cx_pairs': [_sz, _sz, _sz, _sz],
+    'ffgpu_cx_diff': [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp],
+    'ffgpu_cx_apply': [_vp, _vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _sz, _sz, _sz, _sz, _sz, _vp],
     'ffgpu_sqrt_cl': [_vp, _vp, _vp, _sz, _vp],
     'ffgpu_gauss': [_vp, _vp, _int, _int, _sz, _int, _vp, _vp, _vp],
     'ffgpu_group_matvec': [_vp, _u64p, _u64p, _int, _int, _vp, _vp, _sz, _vp],
@@ -117,7 +120,8 @@ _SIGS = {
     'ffgpu_ipc_close': [_vp, _vp],
 }
 _RESTYPES = {'ffgpu_strerror': ctypes.c_char_p, 'ffgpu_last_hip_error': ctypes.c_char_p,
-             'ffgpu_rng_state_bytes': ctypes.c_size_t, 'ffgpu_scan_workspace_bytes': ctypes.c_size_t, 'ffgpu_shake128_close': None}
+             'ffgpu_rng_state_bytes': ctypes.c_size_t, 'ffgpu_scan_workspace_bytes': ctypes.c_size_t, 'ffgpu_cx_pairs': ctypes.c_size_t,
+             'ffgpu_shake128_close': None}
 
 EXPORTED = tuple(_SIGS)
 

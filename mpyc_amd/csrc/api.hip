@@ -1287,6 +1287,53 @@ int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void
     return status_of(ctx->ops->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
 }
 
+// ---- sorting network: the two ends of a compare-exchange stage (sort.hpp) ------------------------------------------------
+size_t ffgpu_cx_pairs(size_t k, size_t p, size_t d, size_t r) { return cx_pairs(k, p, d, r); }
+
+// what both entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
+static int cx_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, CxPlan* pl, bool* work) {
+    ARGCHK(k >= 2 && cx_stage_valid(k, p, d, r));
+    *work = false;
+    if (outer == 0 || inner == 0) return FFGPU_OK;
+    *pl = cx_plan(outer, k, inner, p, d, r, (size_t)ctx->elem_bytes, false);
+    ARGCHK(pl->ok);                                      // the byte count of `a` overflows
+    *work = pl->pairs != 0;
+    return FFGPU_OK;
+}
+
+int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r,
+                  void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    CxPlan pl;
+    bool work;
+    const int rc = cx_args(ctx, outer, k, inner, p, d, r, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(a && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->cx_diff(ctx->policy, cs.lc, a, out, outer, k, inner, p, d, r, cs.st));
+}
+
+int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, size_t outer,
+                   size_t k, size_t inner, size_t p, size_t d, size_t r, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    CxPlan pl;
+    bool work;
+    const int rc = cx_args(ctx, outer, k, inner, p, d, r, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(a && host_rows && host_lambda);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange ar = byte_range(a, outer * k * inner * eb);
+    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
+    for (int s = 0; s < nin; ++s) ARGCHK(host_rows[s] && !overlaps(byte_range(host_rows[s], outer * pl.row_elems * eb), ar));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

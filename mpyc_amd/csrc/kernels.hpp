@@ -2238,4 +2238,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "convolve.hpp" // full convolution of two arrays
 #include "scan.hpp"     // prefix scans and reductions along one axis
 #include "sgn.hpp"      // local steps of the secure comparison (np_sgn)
+#include "sort.hpp"     // the two ends of a compare-exchange stage of the sorting network (np_sort)
 #include "launch.hpp"   // host side: FieldOps table + launchers

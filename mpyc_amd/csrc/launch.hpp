@@ -125,6 +125,12 @@ struct FieldOps {
                       int l, const uint64_t* consts, void* e, void* nx, void* z, size_t n, hipStream_t st);
     LaunchStatus (*sgn_finish)(const void* F, const LaunchCfg& lc, const void* w, const void* sbit, const void* z, int l,
                       const uint64_t* consts, void* out, size_t n, hipStream_t st);
+    // the two ends of a compare-exchange stage of the sorting network (sort.hpp), prime fields only (L_PLAN_REFUSED:
+    // cx_plan() refuses the stage or the sizes; L_NOT_SUPPORTED: more than MAXK rows)
+    LaunchStatus (*cx_diff)(const void* F, const LaunchCfg& lc, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                   size_t p, size_t d, size_t r, hipStream_t st);
+    LaunchStatus (*cx_apply)(const void* F, const LaunchCfg& lc, void* a, const void* const* rows, const uint64_t* lam2, int nrows,
+                    size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1031,6 +1037,52 @@ struct Launchers {
             return launched();
         }
     }
+    // The two ends of a compare-exchange stage (sort.hpp): one flat streaming loop over the compact pair array, a unit (a pack
+    // where cx_plan() admits packs, else an element) per thread up to the grid cap.
+    static_assert(cx_pack(sizeof(E)) == (F::BINARY ? cx_pack(sizeof(E)) : (unsigned)EPV), "sort_geom.hpp counts this field's pack");
+    static_assert(cx_align(sizeof(E)) == (unsigned)PACK_ALIGN, "sort_geom.hpp states this field's pack alignment");
+    static LaunchStatus cx_diff(const void* Fp, const LaunchCfg& lc, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                       size_t p, size_t d, size_t r, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const CxPlan pl = cx_plan(outer, k, inner, p, d, r, sizeof(E), al(a) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_cx_diff<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)a, (E*)out, pl);
+            return launched();
+        }
+    }
+    template <int K>
+    static void go_cx_apply(const F& f, const LaunchCfg& lc, E* a, const void* const* rows, const uint64_t* lam2, size_t outer,
+                            size_t k, size_t inner, size_t p, size_t d, size_t r, hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(a);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const CxPlan pl = cx_plan(outer, k, inner, p, d, r, sizeof(E), vec);
+        hipLaunchKernelGGL((k_cx_apply<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, pl);
+    }
+    static LaunchStatus cx_apply(const void* Fp, const LaunchCfg& lc, void* a, const void* const* rows, const uint64_t* lam2, int nrows,
+                        size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows > MAXK) return L_NOT_SUPPORTED;
+            const CxPlan pl = cx_plan(outer, k, inner, p, d, r, sizeof(E), false);
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
+                              [&](auto k_) { go_cx_apply<decltype(k_)::value>(f, lc, (E*)a, rows, lam2, outer, k, inner, p, d, r, st); }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1166,7 +1218,8 @@ struct Launchers {
             .recombine = &recombine, .pow = &pow, .inv = &inv, .matmul = &matmul, .dot = &dot,
             .gate = &gate, .sqrt_cl = &sqrt_cl, .gauss = &gauss, .group_matvec = &group_matvec, .beaver = &beaver,
             .prss = &prss, .prss_chacha = &prss_chacha, .matmul_stack = &matmul_stack, .stack_slot = STACK_SLOT, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce,
-            .sgn_mask = &sgn_mask, .sgn_expand = &sgn_expand, .sgn_finish = &sgn_finish};
+            .sgn_mask = &sgn_mask, .sgn_expand = &sgn_expand, .sgn_finish = &sgn_finish,
+            .cx_diff = &cx_diff, .cx_apply = &cx_apply};
         return &ops;
     }
 };

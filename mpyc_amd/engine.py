@@ -738,6 +738,46 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_sgn_finish(self._h, w.ptr, sbit.ptr, z.ptr, l, out.ptr, n, self._stream()), 'sgn_finish')
         return out
 
+    # ---- sorting network: the two ends of a compare-exchange stage of runtime.np_sort (runtime.py:1764-1770), prime fields ----
+    def cx_pairs(self, k: int, p: int, d: int, r: int) -> int:
+        """pairs of stage (p, d, r) of Batcher's merge-exchange network over k elements: |{i < k - d : i & p == r}|;
+        0 when (p, d, r) is not a stage"""
+        if min(k, p, d, r) < 0:
+            return 0
+        return int(self._L.ffgpu_cx_pairs(k, p, d, r))
+
+    def _cx_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, p: int, d: int, r: int) -> int:
+        if outer < 1 or k < 1 or inner < 1:
+            raise ValueError(f'{what}: outer, k and inner must be at least 1')
+        if min(p, d, r) < 0:
+            raise ValueError(f'{what}: ({p}, {d}, {r}) is not a stage')
+        self._same(outer * k * inner, a, what=f'{what} operand')
+        return self.cx_pairs(k, p, d, r)
+
+    def cx_diff(self, a: DevArray, outer: int, k: int, inner: int, p: int, d: int, r: int,
+                out: Optional[DevArray] = None) -> DevArray:
+        """out[o, j, i] = a[o, I_j + d, i] - a[o, I_j, i] over the contiguous (outer, k, inner) array `a`, I the index set of
+        stage (p, d, r): the compact (outer, P, inner) differences np_sort compares with zero (runtime.py:1764-1767)."""
+        P = self._cx_args('cx_diff', a, outer, k, inner, p, d, r)
+        nout = outer * P * inner
+        if out is not None:
+            self._same(nout, out, what='cx_diff output')
+        out = out or self.empty(nout)
+        _ffi.check(self._L.ffgpu_cx_diff(self._h, a.ptr, out.ptr, outer, k, inner, p, d, r, self._stream()), 'cx_diff')
+        return out
+
+    def cx_apply(self, a: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], outer: int, k: int, inner: int, p: int,
+                 d: int, r: int) -> DevArray:
+        """a[o, I_j, i] += h, a[o, I_j + d, i] -= h in place with h = sum_s lambdas[s] * rows[s] over the compact
+        (outer, P, inner) rows: the exchange of np_sort (runtime.py:1768-1770) with the recombination of the re-shared
+        product folded in.  Returns a."""
+        P = self._cx_args('cx_apply', a, outer, k, inner, p, d, r)
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(outer * P * inner, *rows, what='cx_apply row')
+        _ffi.check(self._L.ffgpu_cx_apply(self._h, a.ptr, ptrs, lam, nrows, outer, k, inner, p, d, r, self._stream()),
+                   'cx_apply')
+        return a
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

@@ -221,6 +221,59 @@ def compare_zero(ctx: FieldContext, field, xs: Shares, rbits: Shares, sbits: Opt
                     [ctx.add_scalar(ctx.mul_scalar(x, 2), p - 1) for x in lt], t, rng)
 
 
+# ---- sorting along one axis (runtime.np_sort, runtime.py:1738-1774) ---------------------------------------------
+def sort_stages(k: int):
+    """The stages (p, d, r) of Batcher's merge-exchange network over k elements (Knuth 5.2.2M), in the order of the
+    reference's loop (runtime.py:1759-1772): stage (p, d, r) compares position i with i + d for every i < k - d with
+    i & p == r."""
+    if k < 2:
+        return
+    t = (k - 1).bit_length()
+    p = 1 << t - 1
+    while p:
+        d, q, r = p, 1 << t - 1, 0
+        while d:
+            yield p, d, r
+            d, q, r = q - p, q >> 1, p
+        p >>= 1
+
+
+def sort(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, l: int, rand, rng=None) -> Shares:
+    """runtime.np_sort along k of a sharing of the contiguous (outer, k, inner) integer array, ascending, for all parties:
+    every party's share is copied once (np_copy, runtime.py:1750), then per stage (p, d, r) of sort_stages(k)
+      cx_diff per party: the compact differences b1 - b0 (ffgpu_cx_diff),
+      compare_zero(..., mode='lt') on them: shares of [b1 < b0],
+      the first 2t+1 parties re-share [b1 < b0] (b1 - b0) (the product inside ffgpu_mul_split_rng),
+      cx_apply per party: the received sub-shares recombined and added to b0, subtracted from b1 in place (ffgpu_cx_apply).
+    Returns the sorted sharing; xs is not written.
+
+    rand(count) returns (rbits, sbits, rdivl, rzero) as Shares for `count` comparisons of bit length l -- count * l random
+    bits (element-major), count random bits, count values below the statistical bound, count nonzero values: the inputs
+    of compare_zero, drawn by the caller per stage.
+
+    It is assumed that every difference of two values along k lies in [-2^(l-1), 2^(l-1)), and, as for compare_zero, that
+    2^(l+1) + 2^l max(rdivl) < p.  Needs m >= 2t+1 parties."""
+    m = len(xs)
+    kk = 2 * t + 1
+    if m < kk:
+        raise ValueError('sorting multiplies: m >= 2t+1 parties')
+    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs) or xs[0].n != outer * k * inner:
+        raise ValueError('sort: the shares are not (outer, k, inner) arrays')
+    a = [x.clone() for x in xs]
+    lam = _lagrange(field, range(1, kk + 1))
+    for p, d, r in sort_stages(k):
+        pairs = ctx.cx_pairs(k, p, d, r)
+        if pairs == 0:
+            continue
+        diff = [ctx.cx_diff(x, outer, k, inner, p, d, r) for x in a]
+        rbits, sbits, rdivl, rzero = rand(outer * pairs * inner)
+        c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
+        sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]       # sender i -> row j for party j
+        for j in range(m):
+            ctx.cx_apply(a[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, p, d, r)
+    return a
+
+
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
 # The per-party functions above issue one launch per party and step (what each MPyC party does in its own
 # process).  When all m parties of a computation sit on one GPU the parties' launches of a step are identical
