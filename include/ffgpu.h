@@ -33,6 +33,16 @@
  *     ffgpu_beaver_combine.  Inputs may also alias each other (a == b).  Exact
  *     alias only; partial overlap is undefined.  Elements are canonical on return
  *     (tests/test_gpu_elementwise_contract.py).
+ *   - share generation, the fused gate and recombination (ffgpu_split, ffgpu_mul_split, ffgpu_rng_coeffs,
+ *     ffgpu_split_rng, ffgpu_mul_split_rng, ffgpu_split_rng_state, ffgpu_gate_rng, ffgpu_gate_rng_batch,
+ *     ffgpu_recombine): inputs are never written, and nothing outside the n elements of each output row is
+ *     written -- not the padding between n and the row stride, not a pack or a wave rounded up past a row's end.
+ *     Any row stride >= n is allowed, whatever its alignment (strides and bases that keep rows 16-byte aligned take
+ *     the vector paths; the result is the same).  Overlap: ffgpu_recombine with w == 1 may have `out` be EXACTLY one
+ *     of its rows (every route loads an element of all rows before it stores that element); partial overlap is
+ *     undefined.  For w > 1, and for every share-generation and gate call, the output block (all its rows, padding
+ *     included) must not overlap any input: rows are re-read per output row.  Elements are canonical on return
+ *     (tests/test_gpu_share_contract.py).
  *   - thread-safety: the field description of a context is immutable after
  *     creation and a context may be shared between host threads and streams;
  *     its only mutable state -- the ffgpu_matmul scratch buffers (one per

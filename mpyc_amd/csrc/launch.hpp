@@ -232,6 +232,8 @@ struct Launchers {
     // (RngLayout::G) on half as many threads as packs, a slightly larger grid is harmless; below ~2.6e5 packs it cannot
     // fill the chip and every thread takes one pack instead (ra.spread).  Small grids let the kernel's last workgroup
     // advance the device-resident nonce (ra.release, gy gates per launch counted); otherwise rng_advance follows.
+    // (The 262144 packs at which the spread loop ends are named by tests/test_gpu_share_contract.py, SPREAD_MAX_PACKS: its
+    // grouped-loop cases sit just above it.  Move the two together.)
     static Plan plan_rng(size_t n, bool vec, const LaunchCfg& lc, RngArgs& ra, unsigned gy = 1) {
         Plan p = plan(n, vec, lc);
         const bool spread = p.nvec > 0 && p.nvec < 262144;
