@@ -417,6 +417,66 @@ int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t
 int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, size_t outer,
                    size_t k, size_t inner, size_t p, size_t d, size_t r, void* stream);
 
+/* ---- bit decomposition over a prime field: the local steps of np_to_bits -------------- */
+/* What one party computes between the messages of runtime.np_to_bits over a prime field, on its own shares: the masked value
+ * that is opened, and the addition of the opening's public bits to the shared random bits by the prefix-carry network of
+ * runtime.np_add_bits.  Prime fields only (FFGPU_ENOTSUP for GF(2^n), which have ffgpu_gf256_to_bits), integers
+ * (frac_length 0).  n values of l bits, 1 <= l <= 64 and l <= bit_length(p) - 2; everything is mod p; bit index k runs
+ * LEAST significant first, as shifts = arange(l) does (the opposite of ffgpu_sgn_*).  Shares are arbitrary canonical field
+ * elements:
+ *   a[n]         the values;             rdivl[n]   the share of the high mask;
+ *   rbits[n*l]   element-major: rbits[h*l + k] is the share of the random bit of weight 2^k of element h;
+ *   g, p [l*n]   bit-major generate / propagate (carry) values: row k is the n contiguous elements at k*n.
+ * The network (csrc/bits_geom.hpp): the reference's recursion f(i, j, high) splits [i, j) at h = i + (j-i)/2 and merges with
+ * c2 += c1[-1] * d2 and, when high (i > 0), d2 *= d1[-1].  A merge runs in round ceil(log2(j - i)); round rho = 1 ..
+ * ffgpu_carry_rounds(l) = ceil(log2 l) is a list of Rc c-products g[q]*p[k] for every k of the right half of every merge
+ * of the round, q = h - 1, k ascending, then Rd d-products p[q]*p[k] for the same (k, q) of the merges with i > 0, k
+ * ascending; R = Rc + Rd <= 63.  Within a round the k are distinct, no q is among them, and every product reads values
+ * from before the round.
+ * ffgpu_carry_rounds: the number of rounds (0 for l == 1); -1 unless 1 <= l <= 64.
+ * ffgpu_carry_rows:   *rc = Rc, *rd = Rd of the round.
+ * ffgpu_carry_level:  k_out[j], q_out[j] for the R product rows of the round, the c-products first (room for 63 each).
+ *   These three are host functions: no context, no device.  FFGPU_EINVAL: l or round out of range, a null pointer.
+ * ffgpu_bits_mask:   masked[h] = a[h] + offset + rdivl[h] 2^l - sum_k rbits[h*l+k] 2^k -- the value that is opened.
+ *   host_offset: one canonical host scalar (ffgpu_ctx_scalar_limbs words); the reference uses 2^bit_length.
+ *   replaces: runtime.py:4414-4415 (`r_bits << shifts`, the row sum) and :4446 (a + offset + (r_divl << l) - r_modl).
+ * ffgpu_bits_expand: c[n] is the opened public value (canonical).  With cb_k = bit k of the canonical integer
+ *   c[h] mod 2^l and r = rbits[h*l+k]:  g_out[k*n+h] = cb_k ? r : 0,  p_out[k*n+h] = cb_k ? 1 - r : r  -- the leaves
+ *   a_i*b_i and a_i + b_i - 2 a_i b_i of the network for a public b.  One kernel: a workgroup stages a tile of rbits
+ *   through LDS with coalesced loads (the tiles and chunks of csrc/sgn_geom.hpp) and every thread walks the bits of its own
+ *   element, so both bit-major outputs are written coalesced.
+ *   replaces: runtime.py:4447-4448 (`(c >> shifts) & 1`, np_add_bits), the leaf case of :4309-4314, and the host-built
+ *   c_bits with its upload.
+ * ffgpu_carry_prod:  out[j*n+h] = g[q_j*n+h] * p[k_j*n+h] for j < Rc, out[(Rc+j)*n+h] = p[q_j*n+h] * p[k_j*n+h] for the
+ *   d-products: compact (R, n), the party's local degree-2t products of the round.  Every operand element is read once per
+ *   product row; nothing else is read or written.
+ *   replaces: the gathers and `c1[-1] * d2`, `d2 * d1[-1]` of runtime.py:4320-4325 (the local part of np_multiply).
+ * ffgpu_carry_apply: with v = sum_s lambda[s] * rows[s][j*n+h] recombined in registers:  g[k_j*n+h] += v for the c-rows,
+ *   p[k_j*n+h] = v for the d-rows, in place.  rows / lambda as for ffgpu_cx_apply: the nrows sub-share rows of the re-shared
+ *   products a party received and the Lagrange vector; 1 <= nrows <= 9, more rows: FFGPU_ENOTSUP.  Rows of g and p
+ *   outside the round's k are not touched.
+ *   replaces: runtime.py:4320-4325 (c2 + ..., the new d2, the concatenations) and the recombination of _reshare before
+ *   it (thresha.py:119-132).
+ * ffgpu_bits_finish: out[h*l+k] = rbits[h*l+k] + cb_k - 2 g[k*n+h] + (k > 0 ? g[(k-1)*n+h] : 0), element-major, g the
+ *   prefix carries after the last round.  The loads of rbits and the stores of out both go through the LDS tile, so both
+ *   element-major sides are coalesced.
+ *   replaces: runtime.py:4332-4334 (the shifted carries, a + b - 2c + c_shifted) with the transposes around it.
+ * The five device entries are asynchronous on `stream`, allocate nothing and never synchronise (the round's table travels in
+ * the kernel arguments: they can be captured in a HIP graph); inputs are never written, outputs are canonical.  FFGPU_OK,
+ * nothing launched: n == 0, or a round without product rows.  FFGPU_EINVAL, nothing launched: a null context or required
+ * pointer; l < 1, l > 64 or l > bit_length(p) - 2; round < 1 or round > ffgpu_carry_rounds(l); nrows < 1; n*l or its byte
+ * size overflowing; an output range that overlaps an input or another output, g overlapping p, a row overlapping g or p. */
+int ffgpu_carry_rounds(int l);
+int ffgpu_carry_rows(int l, int round, int* rc, int* rd);
+int ffgpu_carry_level(int l, int round, uint8_t* k_out, uint8_t* q_out);
+int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, const uint64_t* host_offset, int l,
+                    void* masked, size_t n, void* stream);
+int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, void* g_out, void* p_out, size_t n, void* stream);
+int ffgpu_carry_prod(ffgpu_ctx* ctx, const void* g, const void* p, int l, int round, void* out, size_t n, void* stream);
+int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
+                      int l, int round, size_t n, void* stream);
+int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const void* g, int l, void* out, size_t n, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

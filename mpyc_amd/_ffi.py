@@ -86,6 +86,14 @@ _SIGS = {
     'ffgpu_cx_pairs': [_sz, _sz, _sz, _sz],
     'ffgpu_cx_diff': [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp],
     'ffgpu_cx_apply': [_vp, _vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _sz, _sz, _sz, _sz, _sz, _vp],
+    'ffgpu_carry_rounds': [_int],
+    'ffgpu_carry_rows': [_int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)],
+    'ffgpu_carry_level': [_int, _int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8)],
+    'ffgpu_bits_mask': [_vp, _vp, _vp, _vp, _u64p, _int, _vp, _sz, _vp],
+    'ffgpu_bits_expand': [_vp, _vp, _vp, _int, _vp, _vp, _sz, _vp],
+    'ffgpu_carry_prod': [_vp, _vp, _vp, _int, _int, _vp, _sz, _vp],
+    'ffgpu_carry_apply': [_vp, _vp, _vp, ctypes.POINTER(_vp), _u64p, _int, _int, _int, _sz, _vp],
+    'ffgpu_bits_finish': [_vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
     'ffgpu_sqrt_cl': [_vp, _vp, _vp, _sz, _vp],
     'ffgpu_gauss': [_vp, _vp, _int, _int, _sz, _int, _vp, _vp, _vp],
     'ffgpu_group_matvec': [_vp, _u64p, _u64p, _int, _int, _vp, _vp, _sz, _vp],

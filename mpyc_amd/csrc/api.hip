@@ -1334,6 +1334,141 @@ int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const 
     return status_of(ctx->ops->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
 }
 
+// ---- bit decomposition over a prime field: the local steps of np_to_bits (bits.hpp) --------------------------------------
+int ffgpu_carry_rounds(int l) { return bits_rounds(l); }
+int ffgpu_carry_rows(int l, int round, int* rc, int* rd) {
+    BitsLevel lv;
+    ARGCHK(rc && rd && bits_level(l, round, lv));
+    *rc = lv.rc;
+    *rd = lv.rd;
+    return FFGPU_OK;
+}
+int ffgpu_carry_level(int l, int round, uint8_t* k_out, uint8_t* q_out) {
+    BitsLevel lv;
+    ARGCHK(k_out && q_out && bits_level(l, round, lv));
+    for (int j = 0; j < lv.rc + lv.rd; ++j) {
+        k_out[j] = lv.k[j];
+        q_out[j] = lv.q[j];
+    }
+    return FFGPU_OK;
+}
+
+// l as for the secure comparison (1 <= l <= 64, l <= bit_length(p) - 2: 2^l is a field element); 2^l as a host scalar
+static bool bits_two_l(const ffgpu_ctx* ctx, int l, uint64_t out[3]) {
+    uint64_t consts[9];
+    if (!sgn_consts(ctx, l, consts)) return false;
+    const int sl = ffgpu_ctx_scalar_limbs(ctx);
+    for (int j = 0; j < 3; ++j) out[j] = j < sl ? consts[j] : 0;       // (scalar 0 of sgn_consts)
+    return true;
+}
+
+int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, const uint64_t* host_offset, int l,
+                    void* masked, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t two_l[3], consts[6] = {0, 0, 0, 0, 0, 0};
+    ARGCHK(bits_two_l(ctx, l, two_l) && host_offset);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && rbits && rdivl && masked);
+    const int sl = ffgpu_ctx_scalar_limbs(ctx);
+    for (int j = 0; j < sl; ++j) {
+        consts[j] = two_l[j];
+        consts[sl + j] = host_offset[j];
+    }
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, l, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
+    const ByteRange o = byte_range(masked, n * eb);
+    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->bits_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
+}
+
+int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, void* g_out, void* p_out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t two_l[3];
+    ARGCHK(bits_two_l(ctx, l, two_l));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(c && rbits && g_out && p_out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, l, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[2] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb)};
+    const ByteRange o[2] = {byte_range(g_out, p.nl * eb), byte_range(p_out, p.nl * eb)};
+    ARGCHK(sgn_ranges_ok(in, 2, o, 2));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->bits_expand(ctx->policy, cs.lc, c, rbits, l, g_out, p_out, n, cs.st));
+}
+
+int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const void* g, int l, void* out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t two_l[3];
+    ARGCHK(bits_two_l(ctx, l, two_l));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(c && rbits && g && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, l, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[3] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb), byte_range(g, p.nl * eb)};
+    const ByteRange o = byte_range(out, p.nl * eb);
+    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->bits_finish(ctx->policy, cs.lc, c, rbits, g, l, out, n, cs.st));
+}
+
+// what both level entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
+static int carry_args(const ffgpu_ctx* ctx, int l, int round, size_t n, BitsLevel* lv, bool* work) {
+    uint64_t two_l[3];
+    ARGCHK(bits_two_l(ctx, l, two_l) && bits_level(l, round, *lv));
+    *work = false;
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(sgn_plan(n, l, (size_t)ctx->elem_bytes).ok);  // n * l or its byte size overflows
+    *work = lv->rc + lv->rd != 0;
+    return FFGPU_OK;
+}
+
+int ffgpu_carry_prod(ffgpu_ctx* ctx, const void* g, const void* p, int l, int round, void* out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    BitsLevel lv;
+    bool work;
+    const int rc = carry_args(ctx, l, round, n, &lv, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(g && p && out);
+    const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
+    const ByteRange in[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
+    const ByteRange o = byte_range(out, (size_t)(lv.rc + lv.rd) * n * eb);
+    ARGCHK(sgn_ranges_ok(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->carry_prod(ctx->policy, cs.lc, g, p, l, lv, out, n, cs.st));
+}
+
+int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
+                      int round, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    BitsLevel lv;
+    bool work;
+    const int rc = carry_args(ctx, l, round, n, &lv, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(g && p && host_rows && host_lambda);
+    const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
+    const ByteRange gr = byte_range(g, nl * eb), pr = byte_range(p, nl * eb);
+    ARGCHK(!overlaps(gr, pr));
+    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
+    for (int s = 0; s < nin; ++s) {
+        ARGCHK(host_rows[s]);
+        const ByteRange rr = byte_range(host_rows[s], (size_t)(lv.rc + lv.rd) * n * eb);
+        ARGCHK(!overlaps(rr, gr) && !overlaps(rr, pr));
+    }
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

@@ -2239,4 +2239,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "scan.hpp"     // prefix scans and reductions along one axis
 #include "sgn.hpp"      // local steps of the secure comparison (np_sgn)
 #include "sort.hpp"     // the two ends of a compare-exchange stage of the sorting network (np_sort)
+#include "bits.hpp"     // local steps of bit decomposition over a prime field (np_to_bits)
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -131,6 +131,19 @@ struct FieldOps {
                    size_t p, size_t d, size_t r, hipStream_t st);
     LaunchStatus (*cx_apply)(const void* F, const LaunchCfg& lc, void* a, const void* const* rows, const uint64_t* lam2, int nrows,
                     size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, hipStream_t st);
+    // local steps of bit decomposition (bits.hpp), prime fields only; consts: the host scalars 2^l and offset; lv: the
+    // round's table (bits_level) (L_PLAN_REFUSED: sgn_plan() / bits_plan() refuses the sizes; L_NOT_SUPPORTED: more than
+    // MAXK rows)
+    LaunchStatus (*bits_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivl, int l,
+                     const uint64_t* consts, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*bits_expand)(const void* F, const LaunchCfg& lc, const void* c, const void* rbits, int l, void* g, void* p, size_t n,
+                       hipStream_t st);
+    LaunchStatus (*carry_prod)(const void* F, const LaunchCfg& lc, const void* g, const void* p, int l, const BitsLevel& lv, void* out,
+                      size_t n, hipStream_t st);
+    LaunchStatus (*carry_apply)(const void* F, const LaunchCfg& lc, void* g, void* p, const void* const* rows, const uint64_t* lam2,
+                       int nrows, int l, const BitsLevel& lv, size_t n, hipStream_t st);
+    LaunchStatus (*bits_finish)(const void* F, const LaunchCfg& lc, const void* c, const void* rbits, const void* g, int l, void* out,
+                       size_t n, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1085,6 +1098,94 @@ struct Launchers {
             return launched();
         }
     }
+    // The local steps of bit decomposition (bits.hpp): a workgroup per tile of SGN_TILE elements for mask, expand and finish;
+    // grid (gx, R) for the two ends of a round, a unit (a pack where bits_plan() admits packs, else an element) per thread up
+    // to the grid cap.
+    static LaunchStatus bits_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivl, int l,
+                         const uint64_t* consts, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan p = sgn_plan(n, l, sizeof(E));
+            if (!p.ok) return L_PLAN_REFUSED;
+            hipLaunchKernelGGL((k_bits_mask<F>), dim3((unsigned)p.tiles), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)rbits,
+                               (const E*)rdivl, l, word_at<F>(f, consts, 0), word_at<F>(f, consts, 1), (E*)out, n);
+            return launched();
+        }
+    }
+    static LaunchStatus bits_expand(const void* Fp, const LaunchCfg& lc, const void* c, const void* rbits, int l, void* g, void* p,
+                           size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan pl = sgn_plan(n, l, sizeof(E));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            hipLaunchKernelGGL((k_bits_expand<F>), dim3((unsigned)pl.tiles), dim3(BLOCK), 0, st, f, (const E*)c, (const E*)rbits, l,
+                               (E*)g, (E*)p, n);
+            return launched();
+        }
+    }
+    static LaunchStatus bits_finish(const void* Fp, const LaunchCfg& lc, const void* c, const void* rbits, const void* g, int l,
+                           void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan pl = sgn_plan(n, l, sizeof(E));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            hipLaunchKernelGGL((k_bits_finish<F>), dim3((unsigned)pl.tiles), dim3(BLOCK), 0, st, f, (const E*)c, (const E*)rbits,
+                               (const E*)g, l, (E*)out, n);
+            return launched();
+        }
+    }
+    static size_t bits_max_blocks(const LaunchCfg& lc) {
+        return lc.blocks_per_cu > 0 ? (size_t)lc.blocks_per_cu * (size_t)lc.num_cu : (size_t)CX_MAX_GRID;
+    }
+    static LaunchStatus carry_prod(const void* Fp, const LaunchCfg& lc, const void* g, const void* p, int l, const BitsLevel& lv,
+                          void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const BitsPlan pl = bits_plan(n, l, lv.rc + lv.rd, sizeof(E), al(g) && al(p) && al(out), bits_max_blocks(lc));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.rows == 0 || n == 0) return L_OK;
+            hipLaunchKernelGGL((k_carry_prod<F>), dim3(pl.gx, (unsigned)pl.rows), dim3(BLOCK), 0, st, f, (const E*)g, (const E*)p,
+                               (E*)out, lv, pl);
+            return launched();
+        }
+    }
+    template <int K>
+    static void go_carry_apply(const F& f, const LaunchCfg& lc, E* g, E* p, const void* const* rows, const uint64_t* lam2, int l,
+                               const BitsLevel& lv, size_t n, hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(g) && al(p);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const BitsPlan pl = bits_plan(n, l, lv.rc + lv.rd, sizeof(E), vec, bits_max_blocks(lc));
+        hipLaunchKernelGGL((k_carry_apply<F, K>), dim3(pl.gx, (unsigned)pl.rows), dim3(BLOCK), 0, st, f, ra, g, p, lv, pl);
+    }
+    static LaunchStatus carry_apply(const void* Fp, const LaunchCfg& lc, void* g, void* p, const void* const* rows, const uint64_t* lam2,
+                           int nrows, int l, const BitsLevel& lv, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows > MAXK) return L_NOT_SUPPORTED;
+            const BitsPlan pl = bits_plan(n, l, lv.rc + lv.rd, sizeof(E), false, bits_max_blocks(lc));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.rows == 0 || n == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
+                              [&](auto k_) { go_carry_apply<decltype(k_)::value>(f, lc, (E*)g, (E*)p, rows, lam2, l, lv, n, st); }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1221,7 +1322,9 @@ struct Launchers {
             .gate = &gate, .sqrt_cl = &sqrt_cl, .gauss = &gauss, .group_matvec = &group_matvec, .beaver = &beaver,
             .prss = &prss, .prss_chacha = &prss_chacha, .matmul_stack = &matmul_stack, .stack_slot = STACK_SLOT, .convolve = &convolve, .scan = &scan, .axis_reduce = &axis_reduce,
             .sgn_mask = &sgn_mask, .sgn_expand = &sgn_expand, .sgn_finish = &sgn_finish,
-            .cx_diff = &cx_diff, .cx_apply = &cx_apply};
+            .cx_diff = &cx_diff, .cx_apply = &cx_apply,
+            .bits_mask = &bits_mask, .bits_expand = &bits_expand, .carry_prod = &carry_prod, .carry_apply = &carry_apply,
+            .bits_finish = &bits_finish};
         return &ops;
     }
 };

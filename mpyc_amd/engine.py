@@ -778,6 +778,86 @@ class FieldContext:
                    'cx_apply')
         return a
 
+    # ---- bit decomposition: the local steps of runtime.np_to_bits (runtime.py:4391-4456) and the carry network of
+    # np_add_bits (runtime.py:4301-4334), prime fields; bit index k least significant first ----
+    def carry_rounds(self, l: int) -> int:
+        """rounds of the prefix-carry network over l bits: ceil(log2 l)"""
+        r = int(self._L.ffgpu_carry_rounds(l))
+        if r < 0:
+            raise ValueError('carry_rounds: bit length out of range')
+        return r
+
+    def carry_level(self, l: int, round: int):
+        """(Rc, Rd, [(k, q), ...]) of a round: Rc c-products G[q] P[k], then Rd d-products P[q] P[k] (csrc/bits_geom.hpp)"""
+        rc, rd = ctypes.c_int(), ctypes.c_int()
+        _ffi.check(self._L.ffgpu_carry_rows(l, round, ctypes.byref(rc), ctypes.byref(rd)), 'carry_rows')
+        ks, qs = (ctypes.c_uint8 * 63)(), (ctypes.c_uint8 * 63)()
+        _ffi.check(self._L.ffgpu_carry_level(l, round, ks, qs), 'carry_level')
+        return rc.value, rd.value, [(ks[j], qs[j]) for j in range(rc.value + rd.value)]
+
+    def carry_rows(self, l: int, round: int) -> int:
+        """product rows R = Rc + Rd of a round"""
+        rc, rd, _ = self.carry_level(l, round)
+        return rc + rd
+
+    def bits_mask(self, a: DevArray, rbits: DevArray, rdivl: DevArray, l: int, offset: int,
+                  out: Optional[DevArray] = None) -> DevArray:
+        """masked[h] = a[h] + offset + rdivl[h] 2^l - sum_k rbits[h*l+k] 2^k, the value np_to_bits opens
+        (runtime.py:4414-4415, 4446).  rbits: n*l bit shares, element-major, least significant bit first."""
+        n = a.n
+        self._same(n, rdivl, out, what='bits_mask operand')
+        self._same(n * l, rbits, what='bits_mask bit shares')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_bits_mask(self._h, a.ptr, rbits.ptr, rdivl.ptr, self._scalars([int(offset) % self.modulus]), l,
+                                           out.ptr, n, self._stream()), 'bits_mask')
+        return out
+
+    def bits_expand(self, c: DevArray, rbits: DevArray, l: int):
+        """From the opened c: (G, P), bit-major (l, n): G[k] = cb_k ? r_k : 0, P[k] = cb_k ? 1 - r_k : r_k with cb_k bit k
+        of c mod 2^l -- the leaves of np_add_bits for public bits (runtime.py:4309-4314, 4447-4448)."""
+        n = c.n
+        self._same(n * l, rbits, what='bits_expand bit shares')
+        g, p = self.empty(l * n), self.empty(l * n)
+        _ffi.check(self._L.ffgpu_bits_expand(self._h, c.ptr, rbits.ptr, l, g.ptr, p.ptr, n, self._stream()), 'bits_expand')
+        return g, p
+
+    def carry_prod(self, g: DevArray, p: DevArray, l: int, round: int, out: Optional[DevArray] = None) -> DevArray:
+        """The local products of a round, compact (R, n): G[q_j] P[k_j] for the c-rows, then P[q_j] P[k_j] for the d-rows
+        (runtime.py:4320-4325)."""
+        if l < 1 or g.n % l:
+            raise ValueError('carry_prod: G is not (l, n)')
+        n = g.n // l
+        self._same(l * n, p, what='carry_prod operand')
+        R = self.carry_rows(l, round)
+        self._same(R * n, out, what='carry_prod output')
+        out = out or self.empty(R * n)
+        _ffi.check(self._L.ffgpu_carry_prod(self._h, g.ptr, p.ptr, l, round, out.ptr, n, self._stream()), 'carry_prod')
+        return out
+
+    def carry_apply(self, g: DevArray, p: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], l: int, round: int):
+        """G[k_j] += v for the c-rows, P[k_j] = v for the d-rows, in place, with v = sum_s lambdas[s] * rows[s] over the compact
+        (R, n) rows: the merge of np_add_bits (runtime.py:4320-4325) with the recombination of the re-shared products folded
+        in.  Returns (g, p)."""
+        if l < 1 or g.n % l:
+            raise ValueError('carry_apply: G is not (l, n)')
+        n = g.n // l
+        self._same(l * n, p, what='carry_apply operand')
+        R = self.carry_rows(l, round)
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(R * n, *rows, what='carry_apply row')
+        _ffi.check(self._L.ffgpu_carry_apply(self._h, g.ptr, p.ptr, ptrs, lam, nrows, l, round, n, self._stream()),
+                   'carry_apply')
+        return g, p
+
+    def bits_finish(self, c: DevArray, rbits: DevArray, g: DevArray, l: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[h*l+k] = rbits[h*l+k] + cb_k - 2 G[k*n+h] + G[(k-1)*n+h]: the shares of the bits, element-major
+        (runtime.py:4332-4334)."""
+        n = c.n
+        self._same(n * l, rbits, g, out, what='bits_finish operand')
+        out = out or self.empty(n * l)
+        _ffi.check(self._L.ffgpu_bits_finish(self._h, c.ptr, rbits.ptr, g.ptr, l, out.ptr, n, self._stream()), 'bits_finish')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

@@ -154,9 +154,15 @@ def to_bits_gf256(ctx: FieldContext, field, xs: Shares, rbits: Shares, t: int) -
 
 
 def from_bits(ctx: FieldContext, bits: Shares, l: int = 8) -> Shares:
-    """runtime.np_from_bits (runtime.py:4475-4484): sum_j x_j 2^j over the last axis (local)."""
-    weights = [[1 << j for j in range(l)]]
-    return [ctx.group_matvec(b, weights) for b in bits]
+    """runtime.np_from_bits (runtime.py:4475-4484): sum_j x_j 2^j over the last axis (local).  Groups of more than 16 bits
+    (ffgpu_group_matvec serves up to 16) are the product of the (n, l) bit matrix with the power vector."""
+    if l <= 16:
+        weights = [[1 << j for j in range(l)]]
+        return [ctx.group_matvec(b, weights) for b in bits]
+    if any(b.n % l for b in bits):
+        raise ValueError('array length is not a multiple of the group size')
+    pw = ctx.from_ints([(1 << j) % ctx.modulus for j in range(l)])
+    return [ctx.matmul(b, pw, b.n // l, l, 1) for b in bits]
 
 
 # ---- secure comparison over a prime field (runtime.np_sgn, runtime.py:3622-3693) -------------------------------
@@ -272,6 +278,54 @@ def sort(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
         for j in range(m):
             ctx.cx_apply(a[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, p, d, r)
     return a
+
+
+# ---- bit decomposition over a prime field (runtime.np_to_bits, runtime.py:4391-4456) ----------------------------
+def carry_prefix(ctx: FieldContext, field, G: Shares, P: Shares, l: int, n: int, t: int, rng=None) -> Shares:
+    """The prefix-carry network of runtime.np_add_bits (runtime.py:4301-4334) for all parties, on Shares of the bit-major
+    (l, n) generate / propagate values, ceil(log2 l) rounds (csrc/bits_geom.hpp); per round
+      carry_prod per party: the compact (R, n) local products of the round (ffgpu_carry_prod),
+      the first 2t+1 parties re-share them (ffgpu_split_rng),
+      carry_apply per party: the received sub-shares recombined and added into G / stored to P in place (ffgpu_carry_apply).
+    Overwrites G with the prefix carries (carry k = the carry out of bit positions 0..k) and returns it; P is overwritten
+    too.  Needs m >= 2t+1 parties."""
+    m = len(G)
+    kk = 2 * t + 1
+    if m < kk or len(P) != m:
+        raise ValueError('the carry network multiplies: m >= 2t+1 parties, G and P for each of them')
+    if l < 1 or n < 0 or any(x.n != l * n for x in G) or any(x.n != l * n for x in P):
+        raise ValueError('carry_prefix: the shares are not (l, n) arrays')
+    lam = _lagrange(field, range(1, kk + 1))
+    for rho in range(1, ctx.carry_rounds(l) + 1):
+        prod = [ctx.carry_prod(G[i], P[i], l, rho) for i in range(kk)]
+        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                  # sender i -> row j for party j
+        for j in range(m):
+            ctx.carry_apply(G[j], P[j], [sub[i].row(j) for i in range(kk)], lam, l, rho)
+    return G
+
+
+def to_bits(ctx: FieldContext, field, xs: Shares, rbits: Shares, rdivl: Shares, t: int, l: int, offset: Optional[int] = None,
+            rng=None) -> Shares:
+    """runtime.np_to_bits (runtime.py:4391-4456) on integers over a prime field, for all parties: bits_mask on t+1
+    parties -> open -> bits_expand -> carry_prefix -> bits_finish, each per party (ffgpu_bits_mask / _expand / _finish and
+    the two level kernels).  Returns Shares of the (n, l) bits, element-major, least significant first; from_bits(..., l)
+    is their inverse.
+
+    rbits: n*l random bits per party (element-major, least significant first), rdivl: n random values below the
+    statistical bound; offset (default 2^l) is added before the opening.  The caller guarantees that
+    -2^(l-1) <= a < 2^(l-1) or 0 <= a < 2^l, and that 0 <= a + offset + 2^l rdivl - r < p for every element (r the value of
+    the random bits), so that the opened value does not wrap.  Needs m >= 2t+1 parties."""
+    m = len(xs)
+    if m < 2 * t + 1:
+        raise ValueError('bit decomposition multiplies: m >= 2t+1 parties')
+    n = xs[0].n
+    if any(x.n != n for x in xs) or len(rbits) != m or len(rdivl) != m or any(r.n != n * l for r in rbits):
+        raise ValueError('to_bits: n values, n*l bit shares and n high masks per party')
+    off = (1 << l) if offset is None else int(offset)
+    c = open_(ctx, field, [ctx.bits_mask(xs[i], rbits[i], rdivl[i], l, off) for i in range(t + 1)], t)
+    gp = [ctx.bits_expand(c, rbits[i], l) for i in range(m)]
+    G = carry_prefix(ctx, field, [x[0] for x in gp], [x[1] for x in gp], l, n, t, rng)
+    return [ctx.bits_finish(c, rbits[i], G[i], l) for i in range(m)]
 
 
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
