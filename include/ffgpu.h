@@ -477,6 +477,49 @@ int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_
                       int l, int round, size_t n, void* stream);
 int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const void* g, int l, void* out, size_t n, void* stream);
 
+/* ---- tournament along an axis: the ends of a round ------------------------------------ */
+/* runtime.np_amax / np_amin and runtime.np_argmax / np_argmin halve an axis per round: pairs are compared, the winner of a
+ * pair survives.  The array is contiguous row-major (outer, k, inner), element (o, j, i) at (o*k + j)*inner + i, the round
+ * runs along k >= 2 (the convention of ffgpu_scan).  n0 = k % 2, h = k / 2 pairs, kc = h + n0 survivors; position 0 is the
+ * bye when n0.  Pair j < h is (first_j, second_j) (csrc/tour_geom.hpp):
+ *   FFGPU_TOUR_HALVES    (n0 + j, kc + j)           np_amax / np_amin, runtime.py:3415, 3464
+ *   FFGPU_TOUR_ODD_EVEN  (n0 + 2j, n0 + 2j + 1)     _np_argmax / _np_argmin, runtime.py:3807, 3935 (the first occurrence wins)
+ * Prime fields only (FFGPU_ENOTSUP for GF(2^n)), integers (frac_length 0); everything is mod p.
+ * ffgpu_tour_diff: out[(o*h + j)*inner + i] = a[o, second_j, i] - a[o, first_j, i] for neg = 0 (the minimum: the value
+ *   compared with zero is a2 - a1), a[o, first_j, i] - a[o, second_j, i] for neg = 1 (the maximum: c = [a1 < a2]) --
+ *   compact (outer, h, inner).
+ *   replaces: runtime.py:3415-3416, 3464-3465, 3807-3808, 3935-3936 (the two slices and their difference).
+ * ffgpu_tour_select: with v = sum_s lambda[s] * rows[s][(o*h + j)*inner + i]:  out[o, n0 + j, i] = a[o, first_j, i] + v for
+ *   neg = 0, - v for neg = 1, and out[o, 0, i] = a[o, 0, i] when n0; out is the next level (outer, kc, inner), not written
+ *   in place.  rows / lambda as for ffgpu_cx_apply: the nrows sub-share rows of the re-shared product c * (difference) a
+ *   party received and the Lagrange vector, recombined in registers on the way; nrows = 1 with lambda = [1] applies a v
+ *   that already exists.  1 <= nrows <= 9; more rows: FFGPU_ENOTSUP.
+ *   replaces: runtime.py:3416-3418, 3465-3467, 3810-3812, 3938-3940 (a1 + product, the concatenation with the bye) and the
+ *   recombination of the product before them (thresha.py:119-132).
+ * ffgpu_tour_unit_prod: out[(o*h + j)*inner + i] = u[o, n0 + j, i] * c[(o*h + j)*inner + i] -- compact; u is (outer, kc,
+ *   inner), the child level's unit vectors, c this level's kept comparison bits: the party's local degree-2t product of the
+ *   upward pass.
+ *   replaces: runtime.py:3815-3816, 3943-3944 (u[:, 1:] and the local part of u * c).
+ * ffgpu_tour_unit_expand: v as for ffgpu_tour_select:  out[o, n0 + 2j, i] = u[o, n0 + j, i] - v, out[o, n0 + 2j + 1, i] = v,
+ *   and out[o, 0, i] = u[o, 0, i] when n0; out is (outer, k, inner).  1 <= nrows <= 9 as above; rows = [c], lambda = [1] is
+ *   the round whose child has length 1 (runtime.py:3803, 3931).
+ *   replaces: runtime.py:3817-3820, 3945-3948 (u - u2, the concatenation, the order='F' reshape, u0 re-attached) and the
+ *   recombination of u * c before them.
+ * All four are asynchronous on `stream`, allocate nothing and never synchronise (they can be captured in a HIP graph);
+ * inputs are never written, outputs are canonical.  FFGPU_OK, nothing launched: outer*inner == 0.  FFGPU_EINVAL, nothing
+ * launched: a null context or pointer; k < 2; an unknown mode; nrows < 1; outer*k*inner or its byte size overflowing; an
+ * output overlapping an input or a row.                                                                           */
+#define FFGPU_TOUR_HALVES   0
+#define FFGPU_TOUR_ODD_EVEN 1
+int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, int mode, int neg,
+                    void* stream);
+int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
+                      void* out, size_t outer, size_t k, size_t inner, int mode, int neg, void* stream);
+int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out, size_t outer, size_t k, size_t inner,
+                         void* stream);
+int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
+                           void* out, size_t outer, size_t k, size_t inner, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

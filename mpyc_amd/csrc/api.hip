@@ -1334,6 +1334,89 @@ int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const 
     return status_of(ctx->ops->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
 }
 
+// ---- tournament along an axis: the ends of a round (tour.hpp) -------------------------------------------------------------
+static_assert((int)TOUR_HALVES == FFGPU_TOUR_HALVES && (int)TOUR_ODD_EVEN == FFGPU_TOUR_ODD_EVEN, "tour_geom.hpp and ffgpu.h name the pairings alike");
+// what the four entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
+static int tour_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner, int mode, TourPlan* pl, bool* work) {
+    ARGCHK(k >= 2 && tour_mode_valid(mode));
+    *work = false;
+    if (outer == 0 || inner == 0) return FFGPU_OK;
+    *pl = tour_plan(outer, k, inner, mode, (size_t)ctx->elem_bytes, false);
+    ARGCHK(pl->ok);                                      // the byte count of the full level overflows
+    *work = true;
+    return FFGPU_OK;
+}
+// the sub-share rows of select / unit_expand: compact arrays that `out` may not overlap
+static bool tour_rows_ok(const void* const* host_rows, int nrows, size_t bytes, const ByteRange& out) {
+    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
+    for (int s = 0; s < nin; ++s)
+        if (!host_rows[s] || overlaps(byte_range(host_rows[s], bytes), out)) return false;
+    return true;
+}
+
+int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, int mode, int neg, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    TourPlan pl;
+    bool work;
+    const int rc = tour_args(ctx, outer, k, inner, mode, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(a && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->tour_diff(ctx->policy, cs.lc, a, out, outer, k, inner, mode, neg, cs.st));
+}
+
+int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, void* out,
+                      size_t outer, size_t k, size_t inner, int mode, int neg, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    TourPlan pl;
+    bool work;
+    const int rc = tour_args(ctx, outer, k, inner, mode, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(a && host_rows && host_lambda && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, outer * pl.next * inner * eb);
+    ARGCHK(!overlaps(o, byte_range(a, outer * k * inner * eb)) && tour_rows_ok(host_rows, nrows, outer * pl.row_elems * eb, o));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->tour_select(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, out, outer, k, inner, mode, neg, cs.st));
+}
+
+int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out, size_t outer, size_t k, size_t inner, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    TourPlan pl;
+    bool work;
+    const int rc = tour_args(ctx, outer, k, inner, TOUR_HALVES, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(u && c && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, outer * pl.row_elems * eb);
+    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && !overlaps(o, byte_range(c, outer * pl.row_elems * eb)));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->tour_unit_prod(ctx->policy, cs.lc, u, c, out, outer, k, inner, cs.st));
+}
+
+int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
+                           void* out, size_t outer, size_t k, size_t inner, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    TourPlan pl;
+    bool work;
+    const int rc = tour_args(ctx, outer, k, inner, TOUR_ODD_EVEN, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(u && host_rows && host_lambda && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, outer * k * inner * eb);
+    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && tour_rows_ok(host_rows, nrows, outer * pl.row_elems * eb, o));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
+}
+
 // ---- bit decomposition over a prime field: the local steps of np_to_bits (bits.hpp) --------------------------------------
 int ffgpu_carry_rounds(int l) { return bits_rounds(l); }
 int ffgpu_carry_rows(int l, int round, int* rc, int* rd) {

@@ -144,6 +144,16 @@ struct FieldOps {
                        int nrows, int l, const BitsLevel& lv, size_t n, hipStream_t st);
     LaunchStatus (*bits_finish)(const void* F, const LaunchCfg& lc, const void* c, const void* rbits, const void* g, int l, void* out,
                        size_t n, hipStream_t st);
+    // the ends of a tournament round (tour.hpp), prime fields only (L_PLAN_REFUSED: tour_plan() refuses the round or the
+    // sizes; L_NOT_SUPPORTED: more than MAXK rows)
+    LaunchStatus (*tour_diff)(const void* F, const LaunchCfg& lc, const void* a, void* out, size_t outer, size_t k, size_t inner, int mode,
+                     int neg, hipStream_t st);
+    LaunchStatus (*tour_select)(const void* F, const LaunchCfg& lc, const void* a, const void* const* rows, const uint64_t* lam2,
+                       int nrows, void* out, size_t outer, size_t k, size_t inner, int mode, int neg, hipStream_t st);
+    LaunchStatus (*tour_unit_prod)(const void* F, const LaunchCfg& lc, const void* u, const void* c, void* out, size_t outer, size_t k,
+                          size_t inner, hipStream_t st);
+    LaunchStatus (*tour_unit_expand)(const void* F, const LaunchCfg& lc, const void* u, const void* const* rows, const uint64_t* lam2,
+                            int nrows, void* out, size_t outer, size_t k, size_t inner, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1186,6 +1196,78 @@ struct Launchers {
             return launched();
         }
     }
+    // The ends of a tournament round (tour.hpp): one flat streaming loop over the compact pair array, a unit (a pack where
+    // tour_plan() admits packs, else an element) per thread up to the grid cap.  unit_prod touches the half level and the
+    // compact arrays only, which lie as in a HALVES round; unit_expand interleaves: an ODD_EVEN round.
+    static LaunchStatus tour_diff(const void* Fp, const LaunchCfg& lc, const void* a, void* out, size_t outer, size_t k, size_t inner,
+                         int mode, int neg, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const TourPlan pl = tour_plan(outer, k, inner, mode, sizeof(E), al(a) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_tour_diff<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)a, (E*)out, pl,
+                               neg ? 1 : 0);
+            return launched();
+        }
+    }
+    static LaunchStatus tour_unit_prod(const void* Fp, const LaunchCfg& lc, const void* u, const void* c, void* out, size_t outer,
+                              size_t k, size_t inner, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const TourPlan pl = tour_plan(outer, k, inner, TOUR_HALVES, sizeof(E), al(u) && al(c) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_tour_unit_prod<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)u, (const E*)c,
+                               (E*)out, pl);
+            return launched();
+        }
+    }
+    // select (expand == false) and unit_expand share everything but the kernel
+    template <int K>
+    static void go_tour_rows(const F& f, const LaunchCfg& lc, bool expand, const E* a, const void* const* rows, const uint64_t* lam2,
+                             E* out, size_t outer, size_t k, size_t inner, int mode, int neg, hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(a) && al(out);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const TourPlan pl = tour_plan(outer, k, inner, mode, sizeof(E), vec);
+        if (expand) hipLaunchKernelGGL((k_tour_unit_expand<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, out, pl);
+        else hipLaunchKernelGGL((k_tour_select<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, out, pl, neg ? 1 : 0);
+    }
+    static LaunchStatus tour_rows(const void* Fp, const LaunchCfg& lc, bool expand, const void* a, const void* const* rows,
+                         const uint64_t* lam2, int nrows, void* out, size_t outer, size_t k, size_t inner, int mode, int neg,
+                         hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows > MAXK) return L_NOT_SUPPORTED;
+            const TourPlan pl = tour_plan(outer, k, inner, mode, sizeof(E), false);
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows, [&](auto k_) {
+                    go_tour_rows<decltype(k_)::value>(f, lc, expand, (const E*)a, rows, lam2, (E*)out, outer, k, inner, mode, neg, st);
+                }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
+    static LaunchStatus tour_select(const void* Fp, const LaunchCfg& lc, const void* a, const void* const* rows, const uint64_t* lam2,
+                           int nrows, void* out, size_t outer, size_t k, size_t inner, int mode, int neg, hipStream_t st) {
+        return tour_rows(Fp, lc, false, a, rows, lam2, nrows, out, outer, k, inner, mode, neg, st);
+    }
+    static LaunchStatus tour_unit_expand(const void* Fp, const LaunchCfg& lc, const void* u, const void* const* rows,
+                                const uint64_t* lam2, int nrows, void* out, size_t outer, size_t k, size_t inner, hipStream_t st) {
+        return tour_rows(Fp, lc, true, u, rows, lam2, nrows, out, outer, k, inner, TOUR_ODD_EVEN, 0, st);
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1324,7 +1406,9 @@ struct Launchers {
             .sgn_mask = &sgn_mask, .sgn_expand = &sgn_expand, .sgn_finish = &sgn_finish,
             .cx_diff = &cx_diff, .cx_apply = &cx_apply,
             .bits_mask = &bits_mask, .bits_expand = &bits_expand, .carry_prod = &carry_prod, .carry_apply = &carry_apply,
-            .bits_finish = &bits_finish};
+            .bits_finish = &bits_finish,
+            .tour_diff = &tour_diff, .tour_select = &tour_select, .tour_unit_prod = &tour_unit_prod,
+            .tour_unit_expand = &tour_unit_expand};
         return &ops;
     }
 };

@@ -858,6 +858,70 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_bits_finish(self._h, c.ptr, rbits.ptr, g.ptr, l, out.ptr, n, self._stream()), 'bits_finish')
         return out
 
+    # ---- tournament along an axis: the ends of a round of runtime.np_amax / np_amin (runtime.py:3413-3419, 3462-3468) and
+    # runtime._np_argmax / _np_argmin (runtime.py:3806-3820, 3934-3948), prime fields.  k >= 2, n0 = k % 2, h = k // 2 pairs,
+    # kc = h + n0 survivors; pair j is (n0 + j, kc + j) for TOUR_HALVES and (n0 + 2j, n0 + 2j + 1) for TOUR_ODD_EVEN ----
+    TOUR_HALVES, TOUR_ODD_EVEN = 0, 1
+
+    def _tour_args(self, what: str, a: DevArray, na: int, outer: int, k: int, inner: int, mode: int):
+        if outer < 1 or k < 2 or inner < 1:
+            raise ValueError(f'{what}: outer and inner must be at least 1, k at least 2')
+        if mode not in (self.TOUR_HALVES, self.TOUR_ODD_EVEN):
+            raise ValueError(f'{what}: unknown pairing {mode}')
+        self._same(outer * na * inner, a, what=f'{what} operand')
+        return k // 2, k // 2 + k % 2
+
+    def _tour_out(self, what: str, n: int, out: Optional[DevArray]) -> DevArray:
+        if out is not None:
+            self._same(n, out, what=f'{what} output')
+        return out if out is not None else self.empty(n)
+
+    def tour_diff(self, a: DevArray, outer: int, k: int, inner: int, mode: int, neg: bool = False,
+                  out: Optional[DevArray] = None) -> DevArray:
+        """out[o, j, i] = a[o, second_j, i] - a[o, first_j, i] (neg: first - second) over the contiguous (outer, k, inner)
+        array `a`: the compact (outer, h, inner) differences a round compares with zero (runtime.py:3415-3416, 3935-3936)."""
+        h, _ = self._tour_args('tour_diff', a, k, outer, k, inner, mode)
+        out = self._tour_out('tour_diff', outer * h * inner, out)
+        _ffi.check(self._L.ffgpu_tour_diff(self._h, a.ptr, out.ptr, outer, k, inner, mode, 1 if neg else 0, self._stream()),
+                   'tour_diff')
+        return out
+
+    def tour_select(self, a: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], outer: int, k: int, inner: int,
+                    mode: int, neg: bool = False, out: Optional[DevArray] = None) -> DevArray:
+        """The next level (outer, kc, inner): out[o, n0 + j, i] = a[o, first_j, i] + v (neg: - v) with
+        v = sum_s lambdas[s] * rows[s] over the compact (outer, h, inner) rows, and the bye out[o, 0, i] = a[o, 0, i] when k is
+        odd: the survivors of a round (runtime.py:3416-3418, 3938-3940) with the recombination of the re-shared product
+        folded in."""
+        h, kc = self._tour_args('tour_select', a, k, outer, k, inner, mode)
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(outer * h * inner, *rows, what='tour_select row')
+        out = self._tour_out('tour_select', outer * kc * inner, out)
+        _ffi.check(self._L.ffgpu_tour_select(self._h, a.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, mode, 1 if neg else 0,
+                                             self._stream()), 'tour_select')
+        return out
+
+    def tour_unit_prod(self, u: DevArray, c: DevArray, outer: int, k: int, inner: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[o, j, i] = u[o, n0 + j, i] * c[o, j, i], compact (outer, h, inner): the local product of the upward pass of
+        argmax, u the child level's (outer, kc, inner) unit vectors, c this level's comparison bits (runtime.py:3943-3944)."""
+        h, kc = self._tour_args('tour_unit_prod', u, k // 2 + k % 2, outer, k, inner, self.TOUR_HALVES)
+        self._same(outer * h * inner, c, what='tour_unit_prod bits')
+        out = self._tour_out('tour_unit_prod', outer * h * inner, out)
+        _ffi.check(self._L.ffgpu_tour_unit_prod(self._h, u.ptr, c.ptr, out.ptr, outer, k, inner, self._stream()), 'tour_unit_prod')
+        return out
+
+    def tour_unit_expand(self, u: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], outer: int, k: int, inner: int,
+                         out: Optional[DevArray] = None) -> DevArray:
+        """This level's unit vectors (outer, k, inner) from the child's (outer, kc, inner): out[o, n0 + 2j, i] =
+        u[o, n0 + j, i] - v, out[o, n0 + 2j + 1, i] = v with v = sum_s lambdas[s] * rows[s] over the compact rows, and
+        out[o, 0, i] = u[o, 0, i] when k is odd (runtime.py:3945-3948) with the recombination of u * c folded in."""
+        h, kc = self._tour_args('tour_unit_expand', u, k // 2 + k % 2, outer, k, inner, self.TOUR_ODD_EVEN)
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(outer * h * inner, *rows, what='tour_unit_expand row')
+        out = self._tour_out('tour_unit_expand', outer * k * inner, out)
+        _ffi.check(self._L.ffgpu_tour_unit_expand(self._h, u.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, self._stream()),
+                   'tour_unit_expand')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

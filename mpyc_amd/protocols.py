@@ -328,6 +328,145 @@ def to_bits(ctx: FieldContext, field, xs: Shares, rbits: Shares, rdivl: Shares, 
     return [ctx.bits_finish(c, rbits[i], G[i], l) for i in range(m)]
 
 
+# ---- maximum, minimum and their positions along one axis (runtime.np_amax / np_amin, runtime.py:3377-3473;
+# np_argmax / np_argmin, runtime.py:3695-3949; np_maximum / np_minimum, runtime.py:3346-3360) --------------------
+def _tour_check(what: str, xs: Shares, outer: int, k: int, inner: int, t: int):
+    if len(xs) < 2 * t + 1:
+        raise ValueError(f'{what} multiplies: m >= 2t+1 parties')
+    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs):
+        raise ValueError(f'{what}: the shares are not (outer, k, inner) arrays')
+
+
+def _tour_round(ctx: FieldContext, field, a: Shares, outer: int, k: int, inner: int, mode: int, neg: bool, t: int, l: int, rand,
+                rng):
+    """One round along k >= 2 for all parties: (the next level (outer, k // 2 + k % 2, inner), the comparison bits)."""
+    m, kk = len(a), 2 * t + 1
+    lam = _lagrange(field, range(1, kk + 1))
+    diff = [ctx.tour_diff(x, outer, k, inner, mode, neg) for x in a]
+    rbits, sbits, rdivl, rzero = rand(outer * (k // 2) * inner)
+    c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
+    sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]           # sender i -> row j for party j
+    return [ctx.tour_select(a[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, mode, neg) for j in range(m)], c
+
+
+def _amax(what: str, neg: bool, ctx, field, xs, outer, k, inner, t, l, rand, rng) -> Shares:
+    _tour_check(what, xs, outer, k, inner, t)
+    a = list(xs)
+    while k > 1:
+        a, _ = _tour_round(ctx, field, a, outer, k, inner, ctx.TOUR_HALVES, neg, t, l, rand, rng)
+        k = k // 2 + k % 2
+    return a if a[0] is not xs[0] else [x.clone() for x in xs]
+
+
+def amax(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, l: int, rand, rng=None) -> Shares:
+    """runtime.np_amax along k of a sharing of the contiguous (outer, k, inner) integer array, for all parties: rounds that
+    pair the lower half of the axis with the upper half (an odd leading position has a bye) until one position is left, per
+    round
+      tour_diff per party: the compact differences a1 - a2 (ffgpu_tour_diff),
+      compare_zero(..., mode='lt') on them: shares of [a1 < a2],
+      the first 2t+1 parties re-share [a1 < a2] (a1 - a2) (the product inside ffgpu_mul_split_rng),
+      tour_select per party: the received sub-shares recombined and subtracted from a1, the bye copied: the next level
+      (ffgpu_tour_select).
+    Returns shares of the (outer, 1, inner) maxima; xs is not written.
+
+    rand(count) returns (rbits, sbits, rdivl, rzero) as Shares for `count` comparisons of bit length l, as for sort(),
+    drawn by the caller per round.
+
+    It is assumed that every difference of two values along k lies in [-2^(l-1), 2^(l-1)), and, as for compare_zero, that
+    2^(l+1) + 2^l max(rdivl) < p.  Needs m >= 2t+1 parties."""
+    return _amax('amax', True, ctx, field, xs, outer, k, inner, t, l, rand, rng)
+
+
+def amin(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, l: int, rand, rng=None) -> Shares:
+    """runtime.np_amin along k: amax() with a2 - a1 compared and [a2 < a1] (a2 - a1) added to a1."""
+    return _amax('amin', False, ctx, field, xs, outer, k, inner, t, l, rand, rng)
+
+
+def _argmax(what: str, neg: bool, ctx, field, xs, outer, k, inner, t, l, rand, rng):
+    _tour_check(what, xs, outer, k, inner, t)
+    m, kk = len(xs), 2 * t + 1
+    lam = _lagrange(field, range(1, kk + 1))
+    a, kept = list(xs), []
+    while k > 1:                                        # downward: the values, every round's bits kept
+        a, c = _tour_round(ctx, field, a, outer, k, inner, ctx.TOUR_ODD_EVEN, neg, t, l, rand, rng)
+        kept.append((k, c))
+        k = k // 2 + k % 2
+    value = a if kept else [x.clone() for x in xs]
+    one = ctx.empty(outer * inner)
+    one.t.zero_()
+    one = ctx.add_scalar(one, 1)                        # the public 1: every party's share of it
+    u = [one] * m
+    for k, c in reversed(kept):                         # upward: the unit vectors
+        if k == 2:                                      # the child is the 1: (1 - c, c) without a multiplication
+            u = [ctx.tour_unit_expand(u[j], [c[j]], [1], outer, k, inner) for j in range(m)]
+            continue
+        prod = [ctx.tour_unit_prod(u[i], c[i], outer, k, inner) for i in range(kk)]
+        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                    # sender i -> row j for party j
+        u = [ctx.tour_unit_expand(u[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner) for j in range(m)]
+    return u, value
+
+
+def argmax(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, l: int, rand, rng=None):
+    """runtime.np_argmax(..., arg_unary=True, arg_only=False) along k of a sharing of the contiguous (outer, k, inner)
+    integer array, for all parties.  Downward, rounds as in amax() but pairing neighbours (position n0 + 2j with
+    n0 + 2j + 1), so that ties give the first occurrence; every round's comparison bits c are kept.  Upward, from the public
+    1, per round
+      tour_unit_prod on the first 2t+1 parties: the child's unit vector times c (ffgpu_tour_unit_prod),
+      they re-share the product (ffgpu_split_rng),
+      tour_unit_expand per party: the received sub-shares recombined to u c, and (u - u c, u c) interleaved
+      (ffgpu_tour_unit_expand);
+    the round whose child has length 1 needs no multiplication (the reference's n == 2 case).
+    Returns (unit, value): shares of the (outer, k, inner) unit vectors, one-hot along k at the first maximum, and of the
+    (outer, 1, inner) maxima; xs is not written.  arg_index() turns the unit vectors into positions.
+
+    rand, l and the number of parties: as for amax()."""
+    return _argmax('argmax', True, ctx, field, xs, outer, k, inner, t, l, rand, rng)
+
+
+def argmin(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, l: int, rand, rng=None):
+    """runtime.np_argmin(..., arg_unary=True, arg_only=False) along k: argmax() for the first minimum."""
+    return _argmax('argmin', False, ctx, field, xs, outer, k, inner, t, l, rand, rng)
+
+
+def arg_index(ctx: FieldContext, unit: Shares, outer: int, k: int, inner: int) -> Shares:
+    """The positions the unit vectors of argmax() / argmin() point at: u @ arange(k) along k (runtime.py:3754-3757, 3882-3885),
+    local.  Returns shares of the (outer, inner) positions."""
+    if outer < 1 or k < 1 or inner < 1 or any(u.n != outer * k * inner for u in unit):
+        raise ValueError('arg_index: the shares are not (outer, k, inner) arrays')
+    iv = ctx.from_ints([j % ctx.modulus for j in range(k)])
+    if inner == 1:
+        return [ctx.matmul(u, iv, outer, k, 1) for u in unit]
+    return [ctx.matmul_stack(iv, u, outer, 1, k, inner, 0, k * inner) for u in unit]
+
+
+def _maximum(what: str, neg: bool, ctx, field, xs, ys, t, l, rand, rng) -> Shares:
+    m, kk = len(xs), 2 * t + 1
+    if m < kk or len(ys) != m:
+        raise ValueError(f'{what} multiplies: m >= 2t+1 parties, both operands for each of them')
+    n = xs[0].n
+    if any(x.n != n for x in xs) or any(y.n != n for y in ys):
+        raise ValueError(f'{what}: operands of different lengths')
+    lam = _lagrange(field, range(1, kk + 1))
+    diff = [ctx.sub(x, y) if neg else ctx.sub(y, x) for x, y in zip(xs, ys)]
+    rbits, sbits, rdivl, rzero = rand(n)
+    c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
+    sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]
+    v = [ctx.recombine([sub[i].row(j) for i in range(kk)], lam) for j in range(m)]
+    return [ctx.sub(x, w) if neg else ctx.add(x, w) for x, w in zip(xs, v)]
+
+
+def maximum(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, l: int, rand, rng=None) -> Shares:
+    """runtime.np_maximum (runtime.py:3354-3360) of two sharings of equal length, for all parties: x + [x < y] (y - x) as
+    x - [x < y] (x - y), one round without a gather, from sub, compare_zero, the re-shared product, recombine and sub.
+    rand, l and the number of parties: as for amax(), with x - y for the differences."""
+    return _maximum('maximum', True, ctx, field, xs, ys, t, l, rand, rng)
+
+
+def minimum(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, l: int, rand, rng=None) -> Shares:
+    """runtime.np_minimum (runtime.py:3346-3352): x + [y < x] (y - x)."""
+    return _maximum('minimum', False, ctx, field, xs, ys, t, l, rand, rng)
+
+
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
 # The per-party functions above issue one launch per party and step (what each MPyC party does in its own
 # process).  When all m parties of a computation sit on one GPU the parties' launches of a step are identical
