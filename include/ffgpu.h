@@ -535,6 +535,8 @@ int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stre
  *                 reference does not negate on row swaps, and neither does this), 0 if singular.
  * dev_singular: `batch` ints in device memory, set to 1 for singular matrices (whose contents are then
  *               unspecified); the caller raises ZeroDivisionError('no inverse exists') (finfields.py:893).
+ * Nothing but the matrices, the `batch` flags and, in mode 1, the `batch` elements of det_out is written; with
+ * batch = 0 or n = 0 nothing is written at all.
  * replaces: finfields.py:872-908 gauss_solve, :910-916 gauss_inv, :918-955 gauss_det
  *           (np.linalg.solve / inv / det / matrix_power with negative exponent on field arrays).     */
 int ffgpu_gauss(ffgpu_ctx* ctx, void* a, int n, int ncols, size_t batch, int mode, void* det_out,
@@ -551,7 +553,9 @@ int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64
 
 /* ---- reductions ------------------------------------------------------------- */
 /* out[0] = sum_i a[i]*b[i]  (ffgpu_dot)  /  sum_i a[i]  (ffgpu_sum), one field element.
- * workspace: device scratch of at least FFGPU_REDUCE_WORKSPACE_BYTES bytes (per concurrent call).
+ * workspace: device scratch of at least FFGPU_REDUCE_WORKSPACE_BYTES bytes (per concurrent call).  The library never
+ *            writes more than that many bytes of it, whatever the element size (the number of partial sums is bounded by
+ *            what the workspace holds), and writes none of it when n = 0; nothing else but out[0] is written.
  * replaces: the local part of runtime.py in_prod / np_sum-style reductions (sum(map(mul, x, y)) on
  * shares, then one reshare) and FiniteFieldArray reductions through __array_function__ (np.sum).    */
 #define FFGPU_REDUCE_WORKSPACE_BYTES (1024 * 16)

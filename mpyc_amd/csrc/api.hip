@@ -1590,6 +1590,8 @@ int ffgpu_gf256_bit_affine(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
                                              out, n, cs.st));
 }
 
+static_assert((size_t)DOT_WORKSPACE_BYTES == (size_t)FFGPU_REDUCE_WORKSPACE_BYTES,
+              "kernels.hpp bounds the grid of dot / sum by the workspace size that ffgpu.h names");
 static int do_dot(ffgpu_ctx* ctx, const void* a, const void* b, void* out, void* workspace, size_t n, void* stream) {
     ARGCHK(ctx && out);
     CallScope cs(ctx, stream);

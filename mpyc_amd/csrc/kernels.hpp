@@ -1894,7 +1894,14 @@ __global__ __launch_bounds__(BLOCK) void k_prss_chacha(F f, PrssCcArgs<F> pa, ty
 // then ONE reshare) and of FieldArray.sum().  Two launches: every workgroup reduces a slice (lazy
 // multiply-accumulate per thread, flushed every 192 terms, then an LDS tree with field additions) into
 // partial[blockIdx]; a single workgroup then folds the partials.
-enum { DOT_MAX_BLOCKS = 1024 };
+// One partial word per workgroup goes to the caller's workspace, which holds DOT_WORKSPACE_BYTES
+// (= FFGPU_REDUCE_WORKSPACE_BYTES of include/ffgpu.h; api.hip asserts it) and no more: dot_max_blocks.
+enum { DOT_MAX_BLOCKS = 1024, DOT_WORKSPACE_BYTES = 1024 * 16 };
+template <class W>
+constexpr unsigned dot_max_blocks() {
+    return DOT_WORKSPACE_BYTES / sizeof(W) < (size_t)DOT_MAX_BLOCKS ? (unsigned)(DOT_WORKSPACE_BYTES / sizeof(W))
+                                                                    : (unsigned)DOT_MAX_BLOCKS;
+}
 
 // cross-lane exchange of a field word (4, 8 or 16 bytes) within a wave, 32 bits at a time
 template <class W>

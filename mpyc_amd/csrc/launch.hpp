@@ -1274,7 +1274,11 @@ struct Launchers {
         const size_t nvec = plan(n, al(a) && (!b || al(b)), lc).nvec;
         size_t iters = nvec ? nvec : n;
         size_t want = (iters + (size_t)BLOCK * 8 - 1) / ((size_t)BLOCK * 8);     // >= 8 packs per thread
-        unsigned grid = (unsigned)(want < 1 ? 1 : want > DOT_MAX_BLOCKS ? DOT_MAX_BLOCKS : want);
+        // the grid is bounded by what the workspace holds: 1024 workgroups of words up to 16 bytes, 682 of the 24-byte words
+        constexpr size_t max_blocks = dot_max_blocks<W>();
+        static_assert(max_blocks >= 1 && max_blocks <= DOT_MAX_BLOCKS && max_blocks * sizeof(W) <= DOT_WORKSPACE_BYTES,
+                      "the partial sums of dot / sum must fit the workspace that include/ffgpu.h promises");
+        unsigned grid = (unsigned)(want < 1 ? 1 : want > max_blocks ? max_blocks : want);
         W* part = (W*)workspace;
         if (b)
             hipLaunchKernelGGL((k_dot_partial<F, true>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)b,

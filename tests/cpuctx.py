@@ -186,6 +186,8 @@ class CpuFieldContext(engine.FieldContext):
             Mx = [blk[i * ncols:(i + 1) * ncols] for i in range(n)]
             if det:
                 dets.append(po.gauss_det(self.F, [r[:n] for r in Mx]))
+                if dets[-1] == 0:                 # the flag is set in both modes (include/ffgpu.h)
+                    sing[bi] = 1
                 res += blk
             else:
                 try:
