@@ -520,6 +520,51 @@ int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out
 int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
                            void* out, size_t outer, size_t k, size_t inner, void* stream);
 
+/* ---- first occurrence along an axis: the ends of a round ------------------------------ */
+/* runtime.np_find (runtime.py:4603-4698) returns the index, or a function f of the index, of the first 0 along an axis of
+ * an array of shared bits (after its reduction of "first s" to "first 0").  A node of its tree is the stack (nf, v_1 .. v_F):
+ * nf = 1 for "no 0 in my interval", v_q the running value of the conditional-step function cs_f; two neighbouring intervals
+ * combine as L + nf_L * (R - L) (np_where(nf[0], R, L), runtime.py:4684).  The combine is associative and keeps order, so
+ * the rounds here pair neighbours as FFGPU_TOUR_ODD_EVEN does: over kk positions n0 = kk % 2, h = kk / 2 pairs
+ * (first_j, second_j) = (n0 + 2j, n0 + 2j + 1), kc = h + n0 survivors, position 0 the bye when n0 (csrc/find_geom.hpp).
+ * Prime fields only (FFGPU_ENOTSUP for GF(2^n)), integers (frac_length 0); everything is mod p.
+ *   bits   contiguous row-major (outer, k, inner), k >= 1: one party's shares of values in {0, 1}; the search runs along k.
+ *   level  component-major (C, outer, kk, inner), C = ncomp = 1 + F components, 1 <= F <= 4; component 0 is nf.
+ *   virt   0 or 1; the leaf round runs over kv = k + virt positions.  With virt, position k is the public leaf (1, f(e)):
+ *          the value for "not found" enters as a leaf, so the root's v is the answer and the reference's last gate
+ *          (np_where(nf, f(e), f_ix), runtime.py:4692) is not needed.  Position k is the second member of the last pair and
+ *          has no memory behind it.
+ *   tab    device array (F, 2, kv) of canonical elements: tab[q, 0, j] = cs_f(0, j)_q, tab[q, 1, j] = cs_f(1, j)_q -
+ *          cs_f(0, j)_q, and with virt tab[q, 0, k] = f(e)_q, tab[q, 1, k] = 0.
+ *   leaf j = (b', tab[q, 0, j] + b' * tab[q, 1, j]) with b' = bits[o, j, i] for flip = 0 and 1 - bits[o, j, i] for flip = 1
+ *          (the reference's public s = 1, runtime.py:4631-4632); the public leaf has b' = 1 and is not flipped.  leaf_0 is
+ *          b', leaf_q for q >= 1 the value component q.  The leaf level is never stored.
+ * ffgpu_find_leaf_prod: out[q, o, j, i] = leaf_0(first_j) * (leaf_q(second_j) - leaf_q(first_j)) -- compact (C, outer, h,
+ *   inner) over the kv positions: the party's local degree-2t product of the first round.
+ *   replaces: runtime.py:4679-4680 (the leaves and their stack) and the local part of the first np_where (:4684).
+ * ffgpu_find_leaf_apply: with v = sum_s lambda[s] * rows[s][q, o, j, i]:  out[q, o, n0 + j, i] = leaf_q(first_j) + v, and
+ *   out[q, o, 0, i] = leaf_q(0) when n0; out is the next level (C, outer, kc, inner).  rows / lambda as for
+ *   ffgpu_tour_select: the nrows compact (C, outer, h, inner) sub-share rows of the re-shared product and the Lagrange
+ *   vector, recombined in registers on the way; nrows = 1 with lambda = [1] applies a v that already exists.
+ *   replaces: the rest of the first np_where (runtime.py:4684) and the recombination before it (thresha.py:119-132).
+ * ffgpu_find_prod: for a stored level (C, outer, k, inner), k >= 2:  out[q, o, j, i] = level[0, o, first_j, i] *
+ *   (level[q, o, second_j, i] - level[q, o, first_j, i]) -- compact (C, outer, h, inner).
+ *   replaces: the local part of np_where(nf[0], cl(h, j), nf) of the inner nodes (runtime.py:4683-4684).
+ * The apply of a later round is ffgpu_tour_select on (C * outer, k, inner) with FFGPU_TOUR_ODD_EVEN and neg = 0: the
+ * components are more rows of the same round.
+ * All three are asynchronous on `stream`, allocate nothing and never synchronise (they can be captured in a HIP graph);
+ * inputs are never written, outputs are canonical.  In every case below nothing is written and nothing is launched.
+ * FFGPU_OK: outer*inner == 0.  FFGPU_EINVAL: a null context or pointer; k < 1 (k < 2 for ffgpu_find_prod); kv < 2 for the
+ * leaf calls; ncomp outside 2..5 (this one rule covers more than four value components too); flip or virt outside {0, 1};
+ * ncomp*outer*kv*inner or its byte size overflowing; an output overlapping the bits, the level, a row or the table.
+ * FFGPU_ENOTSUP: a GF(2^n) context; nrows outside 1..9.                                                            */
+int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void* out, size_t outer, size_t k, size_t inner,
+                         int ncomp, int flip, int virt, void* stream);
+int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, const void* const* host_rows,
+                          const uint64_t* host_lambda, int nrows, void* out, size_t outer, size_t k, size_t inner, int ncomp,
+                          int flip, int virt, void* stream);
+int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, size_t k, size_t inner, int ncomp, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

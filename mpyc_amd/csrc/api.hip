@@ -1417,6 +1417,70 @@ int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* hos
     return status_of(ctx->ops->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
 }
 
+// ---- first-occurrence search along an axis: the ends of a round (find.hpp) -------------------------------------------------
+// what the three entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do.
+// leaf: the bits are (outer, k, inner) and the round runs over k + virt positions; else a stored level (ncomp, outer, k, inner)
+static int find_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner, int ncomp, bool leaf, int flip, int virt, FindPlan* pl,
+                     bool* work) {
+    ARGCHK(find_comp_valid(ncomp) && (flip == 0 || flip == 1) && (virt == 0 || virt == 1));
+    ARGCHK(k >= 1 && k <= ((size_t)1 << 62) && k + (size_t)virt >= 2);
+    *work = false;
+    if (outer == 0 || inner == 0) return FFGPU_OK;
+    *pl = leaf ? find_leaf_plan(outer, k, inner, ncomp, virt, (size_t)ctx->elem_bytes, false)
+               : find_plan(outer, k, inner, ncomp, (size_t)ctx->elem_bytes, false);
+    ARGCHK(pl->t.ok);                                    // the byte count of a level overflows
+    *work = true;
+    return FFGPU_OK;
+}
+
+int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void* out, size_t outer, size_t k, size_t inner, int ncomp,
+                         int flip, int virt, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    FindPlan pl;
+    bool work;
+    const int rc = find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(bits && tab && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb);
+    ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->find_leaf_prod(ctx->policy, cs.lc, bits, tab, out, outer, k, inner, ncomp, flip, virt, cs.st));
+}
+
+int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, const void* const* host_rows, const uint64_t* host_lambda,
+                          int nrows, void* out, size_t outer, size_t k, size_t inner, int ncomp, int flip, int virt, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME || nrows < 1 || nrows > (int)MAXK) return FFGPU_ENOTSUP;
+    FindPlan pl;
+    bool work;
+    const int rc = find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(bits && tab && host_rows && host_lambda && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.next * inner * eb);
+    ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)) &&
+           tour_rows_ok(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb, o));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->find_leaf_apply(ctx->policy, cs.lc, bits, tab, host_rows, host_lambda, nrows, out, outer, k, inner, ncomp,
+                                               flip, virt, cs.st));
+}
+
+int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, size_t k, size_t inner, int ncomp, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    FindPlan pl;
+    bool work;
+    const int rc = find_args(ctx, outer, k, inner, ncomp, false, 0, 0, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(level && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(!overlaps(byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb), byte_range(level, (size_t)ncomp * outer * k * inner * eb)));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->find_prod(ctx->policy, cs.lc, level, out, outer, k, inner, ncomp, cs.st));
+}
+
 // ---- bit decomposition over a prime field: the local steps of np_to_bits (bits.hpp) --------------------------------------
 int ffgpu_carry_rounds(int l) { return bits_rounds(l); }
 int ffgpu_carry_rows(int l, int round, int* rc, int* rd) {

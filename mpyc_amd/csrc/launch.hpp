@@ -154,6 +154,15 @@ struct FieldOps {
                           size_t inner, hipStream_t st);
     LaunchStatus (*tour_unit_expand)(const void* F, const LaunchCfg& lc, const void* u, const void* const* rows, const uint64_t* lam2,
                             int nrows, void* out, size_t outer, size_t k, size_t inner, hipStream_t st);
+    // the ends of a round of the first-occurrence search (find.hpp), prime fields only (L_PLAN_REFUSED: find_plan() /
+    // find_leaf_plan() refuses the round or the sizes; L_NOT_SUPPORTED: fewer than one or more than MAXK rows)
+    LaunchStatus (*find_leaf_prod)(const void* F, const LaunchCfg& lc, const void* bits, const void* tab, void* out, size_t outer,
+                          size_t k, size_t inner, int ncomp, int flip, int virt, hipStream_t st);
+    LaunchStatus (*find_leaf_apply)(const void* F, const LaunchCfg& lc, const void* bits, const void* tab, const void* const* rows,
+                           const uint64_t* lam2, int nrows, void* out, size_t outer, size_t k, size_t inner, int ncomp, int flip,
+                           int virt, hipStream_t st);
+    LaunchStatus (*find_prod)(const void* F, const LaunchCfg& lc, const void* level, void* out, size_t outer, size_t k, size_t inner,
+                     int ncomp, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1268,6 +1277,71 @@ struct Launchers {
                                 const uint64_t* lam2, int nrows, void* out, size_t outer, size_t k, size_t inner, hipStream_t st) {
         return tour_rows(Fp, lc, true, u, rows, lam2, nrows, out, outer, k, inner, TOUR_ODD_EVEN, 0, st);
     }
+    // The ends of a round of the first-occurrence search (find.hpp): one flat streaming loop over the compact units of one
+    // component, a unit (a pack where the plan admits packs, else an element) per thread up to the grid cap; a thread walks
+    // the components of its unit.
+    static LaunchStatus find_leaf_prod(const void* Fp, const LaunchCfg& lc, const void* bits, const void* tab, void* out, size_t outer,
+                              size_t k, size_t inner, int ncomp, int flip, int virt, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const FindPlan pl = find_leaf_plan(outer, k, inner, ncomp, virt, sizeof(E), al(bits) && al(out));
+            if (!pl.t.ok) return L_PLAN_REFUSED;
+            if (pl.t.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_find_leaf_prod<F>), dim3(grid_for(pl.t.total, lc)), dim3(BLOCK), 0, st, f, (const E*)bits,
+                               (const E*)tab, (E*)out, pl, ncomp, flip ? 1 : 0);
+            return launched();
+        }
+    }
+    template <int K>
+    static void go_find_leaf_apply(const F& f, const LaunchCfg& lc, const E* bits, const E* tab, const void* const* rows,
+                                   const uint64_t* lam2, E* out, size_t outer, size_t k, size_t inner, int ncomp, int flip, int virt,
+                                   hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(bits) && al(out);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const FindPlan pl = find_leaf_plan(outer, k, inner, ncomp, virt, sizeof(E), vec);
+        hipLaunchKernelGGL((k_find_leaf_apply<F, K>), dim3(grid_for(pl.t.total, lc)), dim3(BLOCK), 0, st, f, ra, bits, tab, out, pl,
+                           ncomp, flip ? 1 : 0);
+    }
+    static LaunchStatus find_leaf_apply(const void* Fp, const LaunchCfg& lc, const void* bits, const void* tab, const void* const* rows,
+                               const uint64_t* lam2, int nrows, void* out, size_t outer, size_t k, size_t inner, int ncomp,
+                               int flip, int virt, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
+            const FindPlan pl = find_leaf_plan(outer, k, inner, ncomp, virt, sizeof(E), false);
+            if (!pl.t.ok) return L_PLAN_REFUSED;
+            if (pl.t.total == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows, [&](auto k_) {
+                    go_find_leaf_apply<decltype(k_)::value>(f, lc, (const E*)bits, (const E*)tab, rows, lam2, (E*)out, outer, k, inner,
+                                                            ncomp, flip, virt, st);
+                }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
+    static LaunchStatus find_prod(const void* Fp, const LaunchCfg& lc, const void* level, void* out, size_t outer, size_t k,
+                         size_t inner, int ncomp, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const FindPlan pl = find_plan(outer, k, inner, ncomp, sizeof(E), al(level) && al(out));
+            if (!pl.t.ok) return L_PLAN_REFUSED;
+            if (pl.t.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_find_prod<F>), dim3(grid_for(pl.t.total, lc)), dim3(BLOCK), 0, st, f, (const E*)level, (E*)out, pl,
+                               ncomp);
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1412,7 +1486,8 @@ struct Launchers {
             .bits_mask = &bits_mask, .bits_expand = &bits_expand, .carry_prod = &carry_prod, .carry_apply = &carry_apply,
             .bits_finish = &bits_finish,
             .tour_diff = &tour_diff, .tour_select = &tour_select, .tour_unit_prod = &tour_unit_prod,
-            .tour_unit_expand = &tour_unit_expand};
+            .tour_unit_expand = &tour_unit_expand,
+            .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod};
         return &ops;
     }
 };

@@ -922,6 +922,80 @@ class FieldContext:
                    'tour_unit_expand')
         return out
 
+    # ---- first occurrence along an axis: the ends of a round of runtime.np_find (runtime.py:4603-4698), prime fields.  A level
+    # is component-major (C, outer, kk, inner), component 0 = nf; rounds pair neighbours as TOUR_ODD_EVEN does; the leaf round
+    # runs over kv = k + virt positions of the (outer, k, inner) bits, position k the public leaf (1, f(e)) ----
+    FIND_MAX_VALUES = 4
+
+    def _find_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, ncomp: int, flip: int, virt: int, leaf: bool):
+        if outer < 1 or k < 1 or inner < 1:
+            raise ValueError(f'{what}: outer, k and inner must be at least 1')
+        if not 2 <= ncomp <= 1 + self.FIND_MAX_VALUES:
+            raise ValueError(f'{what}: 2 to {1 + self.FIND_MAX_VALUES} components')
+        if flip not in (0, 1) or virt not in (0, 1):
+            raise ValueError(f'{what}: flip and virt are 0 or 1')
+        kv = k + virt
+        if kv < 2:
+            raise ValueError(f'{what}: a round needs two positions')
+        self._same((1 if leaf else ncomp) * outer * k * inner, a, what=f'{what} operand')
+        return kv, kv // 2, kv // 2 + kv % 2
+
+    def find_table(self, k: int, cs0: Sequence, cs1: Sequence, fe=None) -> DevArray:
+        """The leaf table (F, 2, kv) of find_leaf_prod / find_leaf_apply from Python integers: cs0[j] and cs1[j] are the F
+        values of cs_f(0, j) and cs_f(1, j) for j < k (a plain integer counts as F = 1), fe the F values of f(e) for the public
+        leaf at position k (kv = k + 1) or None (kv = k).  Row (q, 0) is cs_f(0, .)_q, row (q, 1) cs_f(1, .)_q - cs_f(0, .)_q,
+        with (f(e)_q, 0) in column k; negative values are reduced mod p."""
+        if self.binary:
+            raise ValueError('find_table: prime fields only')
+        tup = lambda v: tuple(int(x) for x in v) if isinstance(v, (tuple, list)) else (int(v),)
+        if k < 1 or len(cs0) != k or len(cs1) != k:
+            raise ValueError('find_table: k values of cs_f(0, j) and of cs_f(1, j)')
+        c0, c1 = [tup(v) for v in cs0], [tup(v) for v in cs1]
+        nf_ = len(c0[0])
+        if fe is not None:
+            c0.append(tup(fe))
+            c1.append(c0[-1])
+        if not 1 <= nf_ <= self.FIND_MAX_VALUES or any(len(v) != nf_ for v in c0 + c1):
+            raise ValueError(f'find_table: 1 to {self.FIND_MAX_VALUES} values per position, the same number everywhere')
+        p = self.modulus
+        return self.from_ints([x for q in range(nf_) for x in ([v[q] % p for v in c0] + [(w[q] - v[q]) % p for v, w in zip(c0, c1)])])
+
+    def find_leaf_prod(self, bits: DevArray, tab: DevArray, outer: int, k: int, inner: int, ncomp: int, flip: int = 0, virt: int = 0,
+                       out: Optional[DevArray] = None) -> DevArray:
+        """out[q, o, j, i] = leaf_0(first_j) * (leaf_q(second_j) - leaf_q(first_j)), compact (ncomp, outer, h, inner): the local
+        product of the first round of np_find over the kv = k + virt positions, pair j = (n0 + 2j, n0 + 2j + 1); leaf j is
+        (b', tab[q, 0, j] + b' tab[q, 1, j]), b' = bits[o, j, i] (flip: 1 - bits), the public leaf (1, f(e)) at position k when
+        virt (runtime.py:4679-4684)."""
+        kv, h, _ = self._find_args('find_leaf_prod', bits, outer, k, inner, ncomp, flip, virt, True)
+        self._same((ncomp - 1) * 2 * kv, tab, what='find_leaf_prod table')
+        out = self._tour_out('find_leaf_prod', ncomp * outer * h * inner, out)
+        _ffi.check(self._L.ffgpu_find_leaf_prod(self._h, bits.ptr, tab.ptr, out.ptr, outer, k, inner, ncomp, flip, virt,
+                                                self._stream()), 'find_leaf_prod')
+        return out
+
+    def find_leaf_apply(self, bits: DevArray, tab: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], outer: int, k: int,
+                        inner: int, ncomp: int, flip: int = 0, virt: int = 0, out: Optional[DevArray] = None) -> DevArray:
+        """The level after the first round, (ncomp, outer, kc, inner): out[q, o, n0 + j, i] = leaf_q(first_j) + v with
+        v = sum_s lambdas[s] * rows[s] over the compact (ncomp, outer, h, inner) rows, and the bye out[q, o, 0, i] = leaf_q(0)
+        when kv is odd (runtime.py:4684) with the recombination of the re-shared product folded in."""
+        kv, h, kc = self._find_args('find_leaf_apply', bits, outer, k, inner, ncomp, flip, virt, True)
+        self._same((ncomp - 1) * 2 * kv, tab, what='find_leaf_apply table')
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(ncomp * outer * h * inner, *rows, what='find_leaf_apply row')
+        out = self._tour_out('find_leaf_apply', ncomp * outer * kc * inner, out)
+        _ffi.check(self._L.ffgpu_find_leaf_apply(self._h, bits.ptr, tab.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, ncomp, flip,
+                                                 virt, self._stream()), 'find_leaf_apply')
+        return out
+
+    def find_prod(self, level: DevArray, outer: int, k: int, inner: int, ncomp: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[q, o, j, i] = level[0, o, first_j, i] * (level[q, o, second_j, i] - level[q, o, first_j, i]), compact (ncomp,
+        outer, h, inner), for a stored level (ncomp, outer, k, inner), k >= 2: the local product of a later round
+        (runtime.py:4683-4684).  Its apply is tour_select on (ncomp * outer, k, inner) with TOUR_ODD_EVEN."""
+        _, h, _ = self._find_args('find_prod', level, outer, k, inner, ncomp, 0, 0, False)
+        out = self._tour_out('find_prod', ncomp * outer * h * inner, out)
+        _ffi.check(self._L.ffgpu_find_prod(self._h, level.ptr, out.ptr, outer, k, inner, ncomp, self._stream()), 'find_prod')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

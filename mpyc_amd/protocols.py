@@ -467,6 +467,99 @@ def minimum(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, l: int, ra
     return _maximum('minimum', False, ctx, field, xs, ys, t, l, rand, rng)
 
 
+# ---- first occurrence along one axis (runtime.np_find, runtime.py:4603-4698) -----------------------------------
+def _find_functions(f, cs_f):
+    """(f, cs_f, single) with tuple-valued f and cs_f, as the reference normalises them (runtime.py:4641-4663); single: the
+    caller's function is int-valued and one Shares comes back instead of a tuple."""
+    if cs_f is None:
+        if f is None:
+            return (lambda i: (i,)), (lambda b, i: (i + b,)), True
+        single = isinstance(f(0), int)
+        g = (lambda i: (f(i),)) if single else (lambda i: tuple(f(i)))
+        return g, (lambda b, i: tuple(b * (y - x) + x for x, y in zip(g(i), g(i + 1)))), single           # (**), runtime.py:4521
+    single = isinstance(cs_f(0, 0), int)
+    cs = (lambda b, i: (cs_f(b, i),)) if single else (lambda b, i: tuple(cs_f(b, i)))
+    if f is None:
+        return (lambda i: cs(0, i)), cs, single
+    return ((lambda i: (f(i),)) if isinstance(f(0), int) else (lambda i: tuple(f(i)))), cs, single
+
+
+def _find_root(ctx: FieldContext, field, b: Shares, tab: DevArray, outer: int, k: int, inner: int, C: int, flip: int, virt: int, t: int,
+               rng) -> Shares:
+    """The rounds of find() over the k + virt >= 2 leaves: every party's root (C, outer, 1, inner), component 0 = nf."""
+    m, kk = len(b), 2 * t + 1
+    lam = _lagrange(field, range(1, kk + 1))
+    prod = [ctx.find_leaf_prod(b[i], tab, outer, k, inner, C, flip, virt) for i in range(kk)]
+    sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                        # sender i -> row j for party j
+    level = [ctx.find_leaf_apply(b[j], tab, [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, C, flip, virt) for j in range(m)]
+    kp = (k + virt) // 2 + (k + virt) % 2
+    while kp > 1:
+        prod = [ctx.find_prod(level[i], outer, kp, inner, C) for i in range(kk)]
+        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]
+        level = [ctx.tour_select(level[j], [sub[i].row(j) for i in range(kk)], lam, C * outer, kp, inner, ctx.TOUR_ODD_EVEN)
+                 for j in range(m)]
+        kp = kp // 2 + kp % 2
+    return level
+
+
+def find(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t: int, s: int = 0, e='k', f=None, cs_f=None,
+         bits: bool = True, l: Optional[int] = None, rand=None, rng=None):
+    """runtime.np_find along k of a sharing of the contiguous (outer, k, inner) array, for all parties: the index ix of the
+    first occurrence of the public s, or f(ix).  s in {0, 1} on shared bits (bits=True); bits=False is for a public integer
+    s and arbitrary l-bit integers: [a == s] = compare_zero(a - s, mode='eq') with rand(outer * k * inner) as for sort() /
+    amax() is searched for its first 1 -- the complement of the reference's `a != s`, so no extra gate.
+
+    f, cs_f and e have the reference's meaning: cs_f(b, i) = f(i + b) for a bit b is the conditional step, derived from f by
+    (**) of runtime.py:4521 when only f is given; e is the index when s does not occur, a string e an expression in k
+    (default 'k'); e=None returns the raw pair (nf, values) with nf = 1 where s does not occur.  An int-valued f / cs_f gives
+    one Shares, a tuple-valued one (up to four values) a tuple of Shares, each (outer, inner).
+
+    The tree pairs neighbours (position n0 + 2j with n0 + 2j + 1; the combine L + nf_L (R - L) is associative), and the value
+    for "not found" is the public leaf (1, f(e)) at position k, so the root is the answer after bit_length(k) rounds (raw:
+    bit_length(k - 1)) instead of the reference's ceil(log2 k) + 1.  Per round
+      the product nf_L (R - L) on the first 2t+1 parties (ffgpu_find_leaf_prod, the leaves computed from the bits in
+      registers, in the first round; ffgpu_find_prod later),
+      they re-share it (ffgpu_split_rng),
+      the received sub-shares recombined and added to L, the bye carried over, per party (ffgpu_find_leaf_apply;
+      ffgpu_tour_select on the components as rows later).
+    k == 1 with e=None has no round.  Needs m >= 2t+1 parties; xs is not written."""
+    m, kk = len(xs), 2 * t + 1
+    if m < kk:
+        raise ValueError('find multiplies: m >= 2t+1 parties')
+    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs):
+        raise ValueError('find: the shares are not (outer, k, inner) arrays')
+    if not isinstance(s, int) or (bits and s not in (0, 1)):
+        raise ValueError('find: s is a public integer, 0 or 1 for bits')
+    f_, cs, single = _find_functions(f, cs_f)
+    if isinstance(e, str):
+        e = eval(e, {'__builtins__': {}}, {'k': k})
+    cs0, cs1 = [cs(0, j) for j in range(k)], [cs(1, j) for j in range(k)]
+    fe = None if e is None else f_(e)
+    nval = len(cs0[0])
+    if not 1 <= nval <= ctx.FIND_MAX_VALUES:
+        raise ValueError(f'find: 1 to {ctx.FIND_MAX_VALUES} values per index')
+    C, p = 1 + nval, ctx.modulus
+    if bits:
+        b, flip = list(xs), s
+    else:
+        if l is None or rand is None:
+            raise ValueError('find: bits=False compares: l and rand are needed')
+        rbits, _, rdivl, _ = rand(outer * k * inner)
+        b = compare_zero(ctx, field, [ctx.add_scalar(x, -s % p) for x in xs], rbits, None, rdivl, None, t, l, mode='eq', rng=rng)
+        flip = 1
+    virt = 0 if e is None else 1
+    plane = outer * inner
+    if k + virt == 1:                                   # one leaf, no round: (b', cs_f(0, 0) + b' (cs_f(1, 0) - cs_f(0, 0)))
+        nf = [ctx.rsub_scalar(x, 1) if flip else x.clone() for x in b]
+        vals = [[ctx.add_scalar(ctx.mul_scalar(x, (cs1[0][q] - cs0[0][q]) % p), cs0[0][q] % p) for x in nf] for q in range(nval)]
+        return nf, (vals[0] if single else tuple(vals))
+    level = _find_root(ctx, field, b, ctx.find_table(k, cs0, cs1, fe), outer, k, inner, C, flip, virt, t, rng)
+    comp = lambda q: [_rows(ctx, x, q, q + 1, plane) for x in level]                          # views of the root (C, outer, 1, inner)
+    vals = [comp(1 + q) for q in range(nval)]
+    y = vals[0] if single else tuple(vals)
+    return (comp(0), y) if e is None else y
+
+
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
 # The per-party functions above issue one launch per party and step (what each MPyC party does in its own
 # process).  When all m parties of a computation sit on one GPU the parties' launches of a step are identical
