@@ -565,6 +565,48 @@ int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, con
                           int flip, int virt, void* stream);
 int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, size_t k, size_t inner, int ncomp, void* stream);
 
+/* ---- fixed point: truncation and the gate of the normalisation ------------------------ */
+/* A fixed-point number with f fractional bits and bit length l is the field element a = round(x * 2^f), -2^(l-1) <= a <
+ * 2^(l-1); everything below is on these raw integers mod p.  runtime.np_trunc (runtime.py:839-873) divides by 2^f with
+ * probabilistic rounding: it masks a with f random bits and a high mask, opens the sum, and subtracts the opened value's low
+ * f bits again.  runtime._norm (runtime.py:4718-4727) decomposes a into bits, and searches the bits below the sign bit, most
+ * significant first, for the first one that equals the SECRET inverted sign bit s = 1 - x_top; the gate s + (1 - 2s) x turns
+ * that into the search for the first 0 that ffgpu_find_* serve.  Prime fields only (FFGPU_ENOTSUP for GF(2^n)).  Bit index
+ * k runs LEAST significant first, as for ffgpu_bits_*.  Shares are arbitrary canonical field elements:
+ *   a[n], rdivf[n], ar[n]   the values, the share of the high mask, a + the value of the random bits;
+ *   rbits[n*f]   element-major: rbits[h*f + k] is the share of the random bit of weight 2^k of element h;
+ *   bits[n*l]    what ffgpu_bits_finish writes: element-major, so x_top = bits[h*l + l-1] is the share of the sign bit.
+ * ffgpu_trunc_mask:  ar_out[h] = a[h] + sum_k rbits[h*f+k] 2^k;  masked_out[h] = ar_out[h] + offset + rdivf[h] 2^f -- the
+ *   value that is opened.  host_offset: one canonical host scalar as for ffgpu_bits_mask; the reference uses 2^(l-1) with l
+ *   the bit length of a.  Both outputs are required: ar is kept so that the finish reads one element per value, not f.  One
+ *   kernel, built as the one of ffgpu_bits_mask (the tiles and chunks of csrc/sgn_geom.hpp).
+ *   replaces: runtime.py:860-861 (`r_bits << arange(f)`, the row sum) and :869-870 (ar_modf += a, + 2^(l-1) + (r_divf << f)).
+ * ffgpu_trunc_finish: with c = sum_s lambda[s] * rows[s][h] recombined in registers and taken as its canonical integer:
+ *   out[h] = (ar[h] - (c mod 2^f)) * 2^-f.  rows / lambda as for ffgpu_tour_select: the nrows masked shares a party received
+ *   (t+1 of them) and the Lagrange vector, so the opened value never goes to memory; nrows = 1 with lambda = [1] takes a c
+ *   that is already open.  1 <= nrows <= 9; more rows: FFGPU_ENOTSUP.
+ *   replaces: the recombination inside output() (thresha.py:119-132) and runtime.py:871-872 (c & (2^f - 1), the shift).
+ * ffgpu_norm_prod:   out[h*(l-1) + j] = (2 x_top - 1) * bits[h*l + l-2-j] for j < l-1 -- compact (n, l-1): the party's
+ *   local degree-2t product of (1 - 2s) with the bits below the sign bit, reversed.  sign_out[h] = 1 - 2 x_top = 2s - 1
+ *   (local, degree t); it may be NULL.
+ *   replaces: runtime.py:4723-4725 (s, the slice, np.flip) and the local part of the gate at :4636.
+ * ffgpu_norm_apply:  out[h*(l-1) + j] = 1 - x_top + sum_s lambda[s] * rows[s][h*(l-1) + j] -- s + (1 - 2s) x as a dense
+ *   (outer = n, k = l-1, inner = 1) array: what ffgpu_find_leaf_prod / _apply search for its first 0.  rows: the nrows compact
+ *   (n, l-1) sub-share rows of the re-shared product.  1 <= nrows <= 9; more rows: FFGPU_ENOTSUP.
+ *   replaces: the rest of runtime.py:4636 and the recombination before it.
+ * All four are asynchronous on `stream`, allocate nothing and never synchronise (they can be captured in a HIP graph);
+ * inputs are never written, outputs are canonical.  In every case below nothing is written and nothing is launched.
+ * FFGPU_OK: n == 0.  FFGPU_EINVAL: a null context or required pointer; f < 1, f > 64 or f > bit_length(p) - 2; l < 2 or
+ * l > 64; nrows < 1; n*f, n*l or its byte size overflowing; an output overlapping an input, a row or another output.
+ * FFGPU_ENOTSUP: a GF(2^n) context; nrows > 9.                                                                       */
+int ffgpu_trunc_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivf, const uint64_t* host_offset, int f,
+                     void* ar_out, void* masked_out, size_t n, void* stream);
+int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int nrows, const void* ar, int f,
+                       void* out, size_t n, void* stream);
+int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* sign_out, size_t n, void* stream);
+int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
+                     void* out, size_t n, void* stream);
+
 /* ---- square roots, p = 1 (mod 4) --------------------------------------------- */
 /* out[i] = the square root the reference returns for a[i] (Cipolla-Lehmer with the smallest b such that
  * b^2 - 4a is a non-residue; 0 for a = 0).  Primes p = 3 (mod 4) and GF(2^n) take ffgpu_pow with the

@@ -101,6 +101,10 @@ _SIGS = {
     'ffgpu_find_leaf_prod': [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp],
     'ffgpu_find_leaf_apply': [_vp, _vp, _vp, ctypes.POINTER(_vp), _u64p, _int, _vp, _sz, _sz, _sz, _int, _int, _int, _vp],
     'ffgpu_find_prod': [_vp, _vp, _vp, _sz, _sz, _sz, _int, _vp],
+    'ffgpu_trunc_mask': [_vp, _vp, _vp, _vp, _u64p, _int, _vp, _vp, _sz, _vp],
+    'ffgpu_trunc_finish': [_vp, ctypes.POINTER(_vp), _u64p, _int, _vp, _int, _vp, _sz, _vp],
+    'ffgpu_norm_prod': [_vp, _vp, _int, _vp, _vp, _sz, _vp],
+    'ffgpu_norm_apply': [_vp, _vp, ctypes.POINTER(_vp), _u64p, _int, _int, _vp, _sz, _vp],
     'ffgpu_sqrt_cl': [_vp, _vp, _vp, _sz, _vp],
     'ffgpu_gauss': [_vp, _vp, _int, _int, _sz, _int, _vp, _vp, _vp],
     'ffgpu_group_matvec': [_vp, _u64p, _u64p, _int, _int, _vp, _vp, _sz, _vp],

@@ -1616,6 +1616,94 @@ int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_
     return status_of(ctx->ops->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
 }
 
+// ---- fixed point over a prime field: the local steps of np_trunc and of _norm (fxp.hpp) -------------------------------------
+int ffgpu_trunc_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivf, const uint64_t* host_offset, int f,
+                     void* ar_out, void* masked_out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    uint64_t two_f[3], consts[6] = {0, 0, 0, 0, 0, 0};
+    ARGCHK(bits_two_l(ctx, f, two_f) && host_offset);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && rbits && rdivf && ar_out && masked_out);
+    const int sl = ffgpu_ctx_scalar_limbs(ctx);
+    for (int j = 0; j < sl; ++j) {
+        consts[j] = two_f[j];
+        consts[sl + j] = host_offset[j];
+    }
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const SgnPlan p = sgn_plan(n, f, eb);
+    ARGCHK(p.ok);
+    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivf, n * eb)};
+    const ByteRange o[2] = {byte_range(ar_out, n * eb), byte_range(masked_out, n * eb)};
+    ARGCHK(sgn_ranges_ok(in, 3, o, 2));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->trunc_mask(ctx->policy, cs.lc, a, rbits, rdivf, f, consts, ar_out, masked_out, n, cs.st));
+}
+
+int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int nrows, const void* ar, int f,
+                       void* out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
+    uint64_t consts[9];
+    ARGCHK(sgn_consts(ctx, f, consts));                  // 1 <= f <= 64, f <= bit_length(p) - 2; scalar 2: 2^-f
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(host_rows && host_lambda && ar && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(sgn_plan(n, f, eb).ok);
+    const ByteRange o = byte_range(out, n * eb);
+    ARGCHK(!overlaps(o, byte_range(ar, n * eb)) && tour_rows_ok(host_rows, nrows, n * eb, o));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->trunc_finish(ctx->policy, cs.lc, host_rows, host_lambda, nrows, ar, f,
+                                            consts + 2 * ffgpu_ctx_scalar_limbs(ctx), out, n, cs.st));
+}
+
+// what both norm entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
+static int norm_args(const ffgpu_ctx* ctx, int l, size_t n, FxpNormPlan* pl, bool* work) {
+    ARGCHK(fxp_norm_l_valid(l));
+    *work = false;
+    if (n == 0) return FFGPU_OK;
+    *pl = fxp_norm_plan(n, l, (size_t)ctx->elem_bytes, false);
+    ARGCHK(pl->ok);                                      // n * l or its byte size overflows
+    *work = true;
+    return FFGPU_OK;
+}
+
+int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* sign_out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    FxpNormPlan pl;
+    bool work;
+    const int rc = norm_args(ctx, l, n, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(bits && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange in = byte_range(bits, n * pl.l * eb);
+    const ByteRange o[2] = {byte_range(out, pl.elems * eb), byte_range(sign_out, sign_out ? n * eb : 0)};
+    ARGCHK(sgn_ranges_ok(&in, 1, o, sign_out ? 2 : 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->norm_prod(ctx->policy, cs.lc, bits, l, out, sign_out, n, cs.st));
+}
+
+int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
+                     void* out, size_t n, void* stream) {
+    ARGCHK(ctx);
+    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    ARGCHK(nrows >= 1);
+    if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
+    FxpNormPlan pl;
+    bool work;
+    const int rc = norm_args(ctx, l, n, &pl, &work);
+    if (rc != FFGPU_OK || !work) return rc;
+    ARGCHK(bits && host_rows && host_lambda && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ByteRange o = byte_range(out, pl.elems * eb);
+    ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && tour_rows_ok(host_rows, nrows, pl.elems * eb, o));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

@@ -81,31 +81,52 @@ __device__ __forceinline__ void bits_unstage(const uint32_t* lds, typename F::el
 // (runtime.py:4414-4415, 4446: r_modl = np.sum(r_bits << shifts, axis=1); a + offset + (r_divl << l) - r_modl.)  The
 // weighted row sum by Horner from the most significant bit down, acc = 2 acc + r_k: the chunks are staged last to first
 // and every thread walks its columns backwards.  One product, rdivl 2^l.
+// What a thread of the mask kernels holds for its element h once the tile is walked: a[h], rdivl[h] and
+// acc = sum_k rbits[h l + k] 2^k.  The body of k_bits_mask and of k_trunc_mask (fxp.hpp): the two differ in the sign of acc and
+// in what they store.  lds: the workgroup's sgn_lds_words(EB) words.
 template <class F>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_bits_mask(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ rbits,
-                                                      const typename F::elem* __restrict__ rdivl, int l, typename F::word two_l,
-                                                      typename F::word offset, typename F::elem* __restrict__ out, size_t n) {
+struct BitsMaskSum {
+    typename F::word av, rd, acc;
+    size_t h;
+    bool live, wave_full;
+};
+template <class F>
+__device__ __forceinline__ BitsMaskSum<F> bits_mask_sum(const F& f, uint32_t* lds, const typename F::elem* __restrict__ a,
+                                                         const typename F::elem* __restrict__ rbits,
+                                                         const typename F::elem* __restrict__ rdivl, int l, size_t n) {
     typedef typename F::word W;
     constexpr size_t EB = sizeof(typename F::elem);
-    __shared__ uint32_t lds[sgn_lds_words(EB)];
     const size_t h0 = sgn_tile_base(blockIdx.x);
     const unsigned rows = sgn_tile_rows(n, h0), t = threadIdx.x;
-    const size_t h = h0 + t;
-    const bool live = t < rows, wave_full = h0 + (t | 63u) < n;
-    const W av = sgn_load<F>(a, h, live, wave_full);
-    const W rd = sgn_load<F>(rdivl, h, live, wave_full);
+    BitsMaskSum<F> m;
+    m.h = h0 + t;
+    m.live = t < rows;
+    m.wave_full = h0 + (t | 63u) < n;
+    m.av = sgn_load<F>(a, m.h, m.live, m.wave_full);
+    m.rd = sgn_load<F>(rdivl, m.h, m.live, m.wave_full);
     W acc = W();
     for (int i0 = (l - 1) / sgn_chunk(EB) * sgn_chunk(EB); i0 >= 0; i0 -= sgn_chunk(EB)) {
         const int cols = sgn_chunk_cols(l, i0, EB);
         sgn_stage<F>(lds, rbits, h0, rows, l, i0, cols);
         __syncthreads();
-        if (live) {
+        if (m.live) {
             for (int j = cols - 1; j >= 0; --j) acc = f.add(f.add(acc, acc), sgn_lds_elem<F>(lds + sgn_walk_lds_word(t, j, EB)));
         }
         __syncthreads();
     }
-    const W hi = f.mul(rd, two_l);
-    sgn_store<F>(out, h, f.sub(f.add(f.add(av, offset), hi), acc), live, wave_full);
+    m.acc = acc;
+    return m;
+}
+
+template <class F>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_bits_mask(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ rbits,
+                                                      const typename F::elem* __restrict__ rdivl, int l, typename F::word two_l,
+                                                      typename F::word offset, typename F::elem* __restrict__ out, size_t n) {
+    typedef typename F::word W;
+    __shared__ uint32_t lds[sgn_lds_words(sizeof(typename F::elem))];
+    const BitsMaskSum<F> m = bits_mask_sum<F>(f, lds, a, rbits, rdivl, l, n);
+    const W hi = f.mul(m.rd, two_l);
+    sgn_store<F>(out, m.h, f.sub(f.add(f.add(m.av, offset), hi), m.acc), m.live, m.wave_full);
 }
 
 // ---- expand: the leaves a_i b_i and a_i + b_i - 2 a_i b_i of np_add_bits for a public b (runtime.py:4309-4314, 4447-4448) --

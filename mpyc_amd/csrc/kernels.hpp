@@ -2249,4 +2249,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "bits.hpp"     // local steps of bit decomposition over a prime field (np_to_bits)
 #include "tour.hpp"     // the ends of a tournament round (np_amax / np_amin, np_argmax / np_argmin)
 #include "find.hpp"     // the ends of a round of the first-occurrence search (np_find)
+#include "fxp.hpp"      // local steps of fixed-point truncation and normalisation (np_trunc, _norm)
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -163,6 +163,17 @@ struct FieldOps {
                            int virt, hipStream_t st);
     LaunchStatus (*find_prod)(const void* F, const LaunchCfg& lc, const void* level, void* out, size_t outer, size_t k, size_t inner,
                      int ncomp, hipStream_t st);
+    // local steps of fixed-point truncation and normalisation (fxp.hpp), prime fields only; consts of trunc_mask: the host
+    // scalars 2^f and offset, of trunc_finish: 2^-f (L_PLAN_REFUSED: sgn_plan() / fxp_flat_plan() / fxp_norm_plan() refuses
+    // the sizes; L_NOT_SUPPORTED: fewer than one or more than MAXK rows)
+    LaunchStatus (*trunc_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivf, int f,
+                      const uint64_t* consts, void* ar, void* masked, size_t n, hipStream_t st);
+    LaunchStatus (*trunc_finish)(const void* F, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int nrows,
+                        const void* ar, int f, const uint64_t* consts, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*norm_prod)(const void* F, const LaunchCfg& lc, const void* bits, int l, void* out, void* sign_out, size_t n,
+                     hipStream_t st);
+    LaunchStatus (*norm_apply)(const void* F, const LaunchCfg& lc, const void* bits, const void* const* rows, const uint64_t* lam2,
+                      int nrows, int l, void* out, size_t n, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1342,6 +1353,96 @@ struct Launchers {
             return launched();
         }
     }
+    // The local steps of fixed-point truncation and normalisation (fxp.hpp): a workgroup per tile of SGN_TILE elements for
+    // the mask, as for bits_mask; one flat streaming loop for the other three, a unit (a pack where the plan admits packs,
+    // else an element) per thread up to the grid cap.
+    static LaunchStatus trunc_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivf, int fb,
+                          const uint64_t* consts, void* ar, void* masked, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const SgnPlan p = sgn_plan(n, fb, sizeof(E));
+            if (!p.ok) return L_PLAN_REFUSED;
+            if (n == 0) return L_OK;
+            hipLaunchKernelGGL((k_trunc_mask<F>), dim3((unsigned)p.tiles), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)rbits,
+                               (const E*)rdivf, fb, word_at<F>(f, consts, 0), word_at<F>(f, consts, 1), (E*)ar, (E*)masked, n);
+            return launched();
+        }
+    }
+    template <int K>
+    static void go_trunc_finish(const F& f, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, const E* ar, int fb,
+                                const uint64_t* consts, E* out, size_t n, hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(ar) && al(out);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const FxpFlatPlan pl = fxp_flat_plan(n, sizeof(E), vec);
+        const uint64_t cmask = fb >= 64 ? ~0ull : (1ull << fb) - 1;         // (no shift by 64)
+        hipLaunchKernelGGL((k_trunc_finish<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, ar, cmask,
+                           word_at<F>(f, consts, 0), out, pl);
+    }
+    static LaunchStatus trunc_finish(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int nrows,
+                            const void* ar, int fb, const uint64_t* consts, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
+            if (fb < 1 || fb > FXP_MAX_BITS || !fxp_flat_plan(n, sizeof(E), false).ok) return L_PLAN_REFUSED;
+            if (n == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
+                              [&](auto k_) { go_trunc_finish<decltype(k_)::value>(f, lc, rows, lam2, (const E*)ar, fb, consts, (E*)out, n, st); }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
+    static LaunchStatus norm_prod(const void* Fp, const LaunchCfg& lc, const void* bits, int l, void* out, void* sign_out, size_t n,
+                         hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_norm_prod<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)bits, (E*)out,
+                               (E*)sign_out, pl);
+            return launched();
+        }
+    }
+    template <int K>
+    static void go_norm_apply(const F& f, const LaunchCfg& lc, const E* bits, const void* const* rows, const uint64_t* lam2, int l,
+                              E* out, size_t n, hipStream_t st) {
+        CxRows<F, K> ra;
+        bool vec = al(out);
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(rows[j]);
+        }
+        const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), vec);
+        hipLaunchKernelGGL((k_norm_apply<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, bits, out, pl);
+    }
+    static LaunchStatus norm_apply(const void* Fp, const LaunchCfg& lc, const void* bits, const void* const* rows, const uint64_t* lam2,
+                          int nrows, int l, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
+            const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), false);
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
+                              [&](auto k_) { go_norm_apply<decltype(k_)::value>(f, lc, (const E*)bits, rows, lam2, l, (E*)out, n, st); }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1487,7 +1588,8 @@ struct Launchers {
             .bits_finish = &bits_finish,
             .tour_diff = &tour_diff, .tour_select = &tour_select, .tour_unit_prod = &tour_unit_prod,
             .tour_unit_expand = &tour_unit_expand,
-            .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod};
+            .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod,
+            .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply};
         return &ops;
     }
 };

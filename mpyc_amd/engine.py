@@ -996,6 +996,68 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_find_prod(self._h, level.ptr, out.ptr, outer, k, inner, ncomp, self._stream()), 'find_prod')
         return out
 
+    # ---- fixed point: the local steps of runtime.np_trunc (runtime.py:839-873) and the gate in front of the search of
+    # runtime._norm (runtime.py:4718-4727), prime fields, on raw integers a = round(x 2^f).  Bit index k least significant first ----
+    def trunc_mask(self, a: DevArray, rbits: DevArray, rdivf: DevArray, f: int, offset: int, ar_out: Optional[DevArray] = None,
+                   out: Optional[DevArray] = None):
+        """(ar, masked): ar[h] = a[h] + sum_k rbits[h*f+k] 2^k and masked[h] = ar[h] + offset + rdivf[h] 2^f, the value
+        np_trunc opens (runtime.py:860-861, 869-870).  rbits: n*f bit shares, element-major, least significant bit first; ar
+        is what trunc_finish subtracts the opened low bits from."""
+        n = a.n
+        self._same(n, rdivf, ar_out, out, what='trunc_mask operand')
+        self._same(n * f, rbits, what='trunc_mask bit shares')
+        ar_out = ar_out or self.empty(n)
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_trunc_mask(self._h, a.ptr, rbits.ptr, rdivf.ptr, self._scalars([int(offset) % self.modulus]), f,
+                                            ar_out.ptr, out.ptr, n, self._stream()), 'trunc_mask')
+        return ar_out, out
+
+    def trunc_finish(self, rows: Sequence[DevArray], lambdas: Sequence[int], ar: DevArray, f: int,
+                     out: Optional[DevArray] = None) -> DevArray:
+        """out[h] = (ar[h] - (c[h] mod 2^f)) 2^-f with c = sum_s lambdas[s] * rows[s] taken as its canonical integer: the
+        shares of the truncated values (runtime.py:871-872) with the opening of the masked shares folded in, so the opened
+        value never goes to memory.  rows = [c], lambdas = [1] takes a c that is already open."""
+        n = ar.n
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(n, *rows, what='trunc_finish row')
+        self._same(n, out, what='trunc_finish output')
+        out = out or self.empty(n)
+        _ffi.check(self._L.ffgpu_trunc_finish(self._h, ptrs, lam, nrows, ar.ptr, f, out.ptr, n, self._stream()), 'trunc_finish')
+        return out
+
+    def norm_prod(self, bits: DevArray, l: int, want_sign: bool = True, out: Optional[DevArray] = None,
+                  sign_out: Optional[DevArray] = None):
+        """(out, sign): out[h*(l-1)+j] = (2 x_top - 1) * bits[h*l + l-2-j], compact (n, l-1), with x_top = bits[h*l + l-1] the
+        sign bit of the element-major (n, l) bits of bits_finish: the local product of (1 - 2s), s = 1 - x_top, with the bits
+        below the sign bit, most significant first (runtime.py:4723-4725, the local part of :4636).  sign[h] = 1 - 2 x_top =
+        2s - 1, or None with want_sign=False."""
+        if l < 2 or bits.n % l:
+            raise ValueError('norm_prod: the bits are not (n, l), l >= 2')
+        n = bits.n // l
+        self._same(n * (l - 1), out, what='norm_prod output')
+        self._same(n, sign_out, what='norm_prod sign output')
+        out = out or self.empty(n * (l - 1))
+        if want_sign and sign_out is None:
+            sign_out = self.empty(n)
+        _ffi.check(self._L.ffgpu_norm_prod(self._h, bits.ptr, l, out.ptr, sign_out.ptr if sign_out is not None else None, n,
+                                           self._stream()), 'norm_prod')
+        return out, sign_out
+
+    def norm_apply(self, bits: DevArray, rows: Sequence[DevArray], lambdas: Sequence[int], l: int,
+                   out: Optional[DevArray] = None) -> DevArray:
+        """out[h*(l-1)+j] = 1 - x_top + v with v = sum_s lambdas[s] * rows[s] over the compact (n, l-1) rows: s + (1 - 2s) x as
+        a dense (n, l-1, 1) array, which find_leaf_prod / find_leaf_apply search for its first 0 (the rest of runtime.py:4636)
+        with the recombination of the re-shared product folded in."""
+        if l < 2 or bits.n % l:
+            raise ValueError('norm_apply: the bits are not (n, l), l >= 2')
+        n = bits.n // l
+        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
+        self._same(n * (l - 1), *rows, what='norm_apply row')
+        self._same(n * (l - 1), out, what='norm_apply output')
+        out = out or self.empty(n * (l - 1))
+        _ffi.check(self._L.ffgpu_norm_apply(self._h, bits.ptr, ptrs, lam, nrows, l, out.ptr, n, self._stream()), 'norm_apply')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = out or self.empty(a.n)

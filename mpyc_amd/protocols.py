@@ -560,6 +560,98 @@ def find(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
     return (comp(0), y) if e is None else y
 
 
+# ---- fixed point: truncation, product, normalisation, reciprocal and division (runtime.np_trunc, runtime.py:839-873;
+# _norm, _rec, runtime.py:4718-4745; np_divide) ----------------------------------------------------------------------
+# All on RAW integers: a fixed-point number with f fractional bits and bit length l is the shared field element
+# a = round(x 2^f), -2^(l-1) <= a < 2^(l-1).
+def trunc(ctx: FieldContext, field, xs: Shares, rbits: Shares, rdivf: Shares, t: int, f: int, L: int) -> Shares:
+    """runtime.np_trunc for all parties: shares of floor(a / 2^f) or of that plus one (the reference's probabilistic
+    rounding), from trunc_mask per party (ffgpu_trunc_mask: ar = a + r and the masked value ar + 2^(L-1) + 2^f R) and
+    trunc_finish per party on the masked shares of the first t+1 parties (ffgpu_trunc_finish: the opening in registers,
+    (ar - (c mod 2^f)) 2^-f).  The integer is fixed by the randomness: (a + r - ((a + 2^(L-1) + r + 2^f R) mod 2^f)) / 2^f
+    with r the value of the random bits and R of rdivf.
+
+    rbits: n*f random bits per party (element-major, least significant first), rdivf: n random values below the statistical
+    bound.  The caller guarantees |a| < 2^(L-1) and that the opened value a + 2^(L-1) + r + 2^f R stays below p.  xs is
+    not written."""
+    m = len(xs)
+    if m < t + 1:
+        raise ValueError('truncation opens a degree-t sharing: m >= t+1 parties')
+    n = xs[0].n
+    if any(x.n != n for x in xs) or len(rbits) != m or len(rdivf) != m or any(r.n != n * f for r in rbits):
+        raise ValueError('trunc: n values, n*f bit shares and n high masks per party')
+    lam = _lagrange(field, range(1, t + 2))
+    am = [ctx.trunc_mask(xs[j], rbits[j], rdivf[j], f, 1 << (L - 1)) for j in range(m)]
+    return [ctx.trunc_finish([am[i][1] for i in range(t + 1)], lam, am[j][0], f) for j in range(m)]
+
+
+def fxp_multiply(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, f: int, l: int, rand_trunc, rng=None) -> Shares:
+    """The product of two fixed-point sharings (runtime.np_multiply with frac_length f): multiply() -- the product inside
+    the share generation, then the recombination -- and trunc() by f bits with L = l + f.
+
+    rand_trunc(count, f) returns (rbits, rdivf) as Shares for `count` truncations by f bits: count * f random bits
+    (element-major, least significant first) and count values below the statistical bound, drawn by the caller per
+    truncation.  The caller guarantees |x y| < 2^(l+f-1) on the raw integers and, as for trunc(), that the opened value does
+    not wrap.  Needs m >= 2t+1 parties."""
+    prod = multiply(ctx, field, xs, ys, t, rng)
+    rbits, rdivf = rand_trunc(xs[0].n, f)
+    return trunc(ctx, field, prod, rbits, rdivf, t, f, l + f)
+
+
+def norm(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits, rng=None) -> Shares:
+    """runtime._norm for all parties: the signed normalisation factor v = (2s - 1) 2^(i + 2f - l + 1) with s the inverted
+    sign bit and i the number of leading bits below the sign bit that differ from s (i = l - 1 if all do), so that a v lies
+    in [2^(2f-1), 2^2f] -- 1/2 <= x v <= 1 after the truncation.  Steps:
+      to_bits (l bits, least significant first),
+      norm_prod on the first 2t+1 parties: (1 - 2s) times the bits below the sign bit, reversed (ffgpu_norm_prod),
+      they re-share it (ffgpu_split_rng),
+      norm_apply per party: s + (1 - 2s) x with the recombination folded in (ffgpu_norm_apply),
+      find(..., s=0, e=l-1, cs_f=lambda b, i: (b+1) << i) along the l - 1 bits: shares of 2^i,
+      one multiply() with 2s - 1 and the public factor 2^(2f-l+1).
+
+    rand_bits(count, l) returns (rbits, rdivl) as Shares: the inputs of to_bits().  Requires f <= l <= 2f + 1.  Needs
+    m >= 2t+1 parties; xs is not written."""
+    if not (f <= l <= 2 * f + 1) or l < 2:
+        raise ValueError('norm: f <= l <= 2f + 1 and l >= 2')
+    m, kk = len(xs), 2 * t + 1
+    if m < kk:
+        raise ValueError('norm multiplies: m >= 2t+1 parties')
+    n = xs[0].n
+    rbits, rdivl = rand_bits(n, l)
+    bits = to_bits(ctx, field, xs, rbits, rdivl, t, l, rng=rng)
+    lam = _lagrange(field, range(1, kk + 1))
+    ps = [ctx.norm_prod(bits[i], l) for i in range(kk)]
+    sub = [ctx.split_rng(ps[i][0], t, m, state=rng) for i in range(kk)]                       # sender i -> row j for party j
+    x = [ctx.norm_apply(bits[j], [sub[i].row(j) for i in range(kk)], lam, l) for j in range(m)]
+    nf = find(ctx, field, x, n, l - 1, 1, t, s=0, e=l - 1, cs_f=lambda b, i: (b + 1) << i, rng=rng)
+    v = multiply(ctx, field, nf, [p[1] for p in ps], t, rng)
+    return [ctx.mul_scalar(w, 1 << (2 * f - l + 1)) for w in v]
+
+
+def reciprocal(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits, rand_trunc, rng=None) -> Shares:
+    """runtime._rec for all parties: b = a v with v = norm(a), c = 2.9142135623731 - 2b, theta = ceil(log2((f+1)/3.54))
+    Newton steps c <- c (2 - c b), and c v; every product is fxp_multiply().
+
+    The caller guarantees a != 0 and a representable reciprocal, |a| > 2^(2f-l+1) on the raw integers.  rand_bits and
+    rand_trunc: as for norm() and fxp_multiply().  Needs m >= 2t+1 parties."""
+    import math
+    mul = lambda a, b: fxp_multiply(ctx, field, a, b, t, f, l, rand_trunc, rng)
+    v = norm(ctx, field, xs, t, l, f, rand_bits, rng)
+    b = mul(xs, v)
+    c = [ctx.rsub_scalar(ctx.mul_scalar(x, 2), round(2.9142135623731 * 2**f)) for x in b]
+    for _ in range(int(math.ceil(math.log2((f + 1) / 3.54)))):
+        cb = mul(c, b)
+        c = mul(c, [ctx.rsub_scalar(x, 1 << (f + 1)) for x in cb])
+    return mul(c, v)
+
+
+def divide(ctx: FieldContext, field, num: Shares, den: Shares, t: int, l: int, f: int, rand_bits, rand_trunc, rng=None) -> Shares:
+    """runtime.np_divide of two fixed-point sharings for all parties: fxp_multiply(reciprocal(den), num).
+
+    The caller guarantees den != 0 and a representable reciprocal, |den| > 2^(2f-l+1) on the raw integers."""
+    return fxp_multiply(ctx, field, reciprocal(ctx, field, den, t, l, f, rand_bits, rand_trunc, rng), num, t, f, l, rand_trunc, rng)
+
+
 # ---- the same layer with ALL parties in every launch ---------------------------------------------------------
 # The per-party functions above issue one launch per party and step (what each MPyC party does in its own
 # process).  When all m parties of a computation sit on one GPU the parties' launches of a step are identical
