@@ -224,9 +224,10 @@ struct LaunchTimer {
 
 // The scope of one compute call, opened once its arguments have been checked: the context's device is current, the
 // call's launches are timed when timing is on, `st` is its stream and `lc` its launch shape.  A tracked call (one whose
-// arrays take part in the hand-off, handoff.hpp) names its kind and byte ranges: lc.keep_out is then set when the
-// tracker predicts that the next launch on the stream reads this call's output, and what the call reads settles the
-// prediction for the call before it.
+// arrays take part in the hand-off, handoff.hpp) names its kind and byte ranges: lc.policy (CachePolicy, kernels.hpp) then
+// says to keep the outputs when the tracker predicts that the next launch on the stream reads them -- write-through for
+// share generation, the flavour measured for it, the default policy for the other kinds -- and whether the call reads what
+// the call before it kept; what the call reads settles the prediction for the call before it.
 struct CallScope {
     DeviceGuard dev;
     LaunchTimer timer;
@@ -237,7 +238,9 @@ struct CallScope {
     CallScope(ffgpu_ctx* ctx, void* stream, int kind, const ByteRange* in, int nin, const ByteRange& out) : CallScope(ctx, stream) {
         if (lc.handoff) {
             std::lock_guard<std::mutex> lk(ctx->handoff_mu);
-            lc.keep_out = ctx->handoff.launch(stream, kind, in, nin, &out, 1);
+            int fed = 0;
+            const int keep = ctx->handoff.launch(stream, kind, in, nin, &out, 1, &fed);
+            lc.policy = (keep ? (kind == HK_SPLIT ? CP_ST_SC1 : CP_ST_PLAIN) : CP_ST_NT) | (fed ? CP_FED : 0);
         }
     }
 };
@@ -595,7 +598,7 @@ int ffgpu_mul(ffgpu_ctx* ctx, const void* a, const void* b, void* out, size_t n,
     const bool bitsliced = ctx && ctx->policy_kind == POL_GF2W64 && ctx->lc.gf2w_bitsliced && n >= ((size_t)1 << 21);
     if (!ctx || n == 0 || !a || !b || !out || !(tables || ctx->gf2w_limbs || bitsliced)) return do_ew2(ctx, OP_MUL, a, b, out, n, stream);
     // one scope and one hand-off step for the call, whichever kernels serve it (only the element-wise kernel takes
-    // keep_out; ffgpu_last_kernel_ms reports the call, not its tail)
+    // the policy word; ffgpu_last_kernel_ms reports the call, not its tail)
     const size_t nb = rows_bytes(ctx, 1, 0, n);
     const ByteRange in[2] = {byte_range(a, nb), byte_range(b, nb)};
     CallScope cs(ctx, stream, HK_EW, in, 2, byte_range(out, nb));

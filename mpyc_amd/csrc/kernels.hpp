@@ -15,7 +15,7 @@
 //     no reuse to localise in an L2, hence no XCD remap;
 //   * streamed-once data carries the non-temporal hint (nt) on loads and stores -- except outputs that the next launch
 //     on the stream is predicted to read: those take the default policy and stay in the Infinity Cache for it
-//     (stg_k / stgw_k below, the prediction in handoff.hpp);
+//     (plain or write-through: the policy word at stg_k / stgw_k below, the prediction in handoff.hpp);
 //   * per-field constants (modulus, fold constant, Lagrange vector, party
 //     x-coordinates) are wave-uniform kernel arguments -> SGPRs, which beats
 //     staging them in LDS for fields this small.
@@ -258,31 +258,63 @@ __device__ __forceinline__ void stgw(u192e* p, const Pack<u192e>& x) {
     }
 }
 
-// Stores of outputs that the next launch on the stream reads back (Plan::keep, launch.hpp; handoff.hpp) take the default
-// cache policy, so the lines stay in the Infinity Cache for that launch; every other output streams past it (nt).  `keep`
-// is a kernel argument (a scalar branch): one kernel serves both policies.  The two empty asm statements (no instruction)
-// pin the default-policy store between two points that may touch *p: left alone, LLVM hoists or sinks two stores that differ
-// only in their cache hint into ONE store and drops the hint -- every output would then take the default policy, whatever
-// `keep` says.  (A bare memory clobber is not enough: the outputs are __restrict__, so it cannot reach them unless p is named.)
+// The cache policy of one launch: a small word, decided per launch on the host (CallScope in api.hip from what the hand-off
+// tracker says, handoff.hpp; carried as LaunchCfg::policy and Plan::pol) and obeyed here.  It holds
+//   * the store flavour of the outputs (CP_ST_*): nt for outputs nobody reads next -- they stream past the Infinity Cache;
+//     the default policy (plain) for outputs that the next launch on the stream reads back -- they stay in the cache for it;
+//     sc1 (write-through) for the kept shares of share generation: the lines stay in the cache as well, and the launch
+//     leaves no dirty L2 lines to write back at its end (tools/tune_handoff.hip, profiles/r19_handoff_account.md: the writer
+//     of three kept rows 71.5 -> 69.4 us, its reader unchanged).  16-byte accesses only: narrower sc1 stores are one fabric
+//     write each, so 12- and 24-byte elements take sc1 as plain;
+//   * CP_FED: the launch reads what the launch before it kept (the tracker's second answer).
+// The load flavours of cold and of fed operands have no bits: nt measured best for both (r19: default-policy loads of the
+// handed rows cost the pair +5 us, of the cold operands +3 us, both together +19 us), so every streamed load stays nt.
+// FFGPU_HANDOFF=0: the word is 0, every access nt.
+enum CachePolicy { CP_ST_NT = 0, CP_ST_PLAIN = 1, CP_ST_SC1 = 2, CP_ST_MASK = 3, CP_FED = 4 };
+// The word is a kernel argument (scalar branches): one kernel serves every policy.  The two empty asm statements (no
+// instruction) pin the default-policy store between two points that may touch *p: left alone, LLVM hoists or sinks two stores
+// that differ only in their cache hint into ONE store and drops the hint -- every output would then take the default policy,
+// whatever the word says.  (A bare memory clobber is not enough: the outputs are __restrict__, so it cannot reach them unless
+// p is named.)  The sc1 store is an asm statement of its own, which nothing merges; s_nop 1: the store reads its four data
+// registers over more than one cycle, and the compiler does not know an instruction is using them.
 #define FF_STORE_FENCE(p) asm volatile("" ::"v"(p) : "memory")
-template <bool NT, class P, class X>
-__device__ __forceinline__ void stg_k(P* p, const X& x, int keep) {
-    if (keep) {
-        FF_STORE_FENCE(p);
-        stg<false>(p, x);
-        FF_STORE_FENCE(p);
-    } else {
-        stg<NT>(p, x);
-    }
+template <class P>
+__device__ __forceinline__ void stg_sc1(P* p, const P& x) {
+    static_assert(sizeof(P) == 16, "16-byte packs only");
+    ff_u32x4 v;
+    __builtin_memcpy(&v, &x, 16);
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+template <class P, class X>
+__device__ __forceinline__ void stg_plain(P* p, const X& x) {
+    FF_STORE_FENCE(p);
+    stg<false>(p, x);
+    FF_STORE_FENCE(p);
 }
 template <bool NT, class P, class X>
-__device__ __forceinline__ void stgw_k(P* p, const X& x, int keep) {
-    if (keep) {
-        FF_STORE_FENCE(p);
-        stgw<false>(p, x);
-        FF_STORE_FENCE(p);
+__device__ __forceinline__ void stg_k(P* p, const X& x, int pol) {
+    const int st = pol & CP_ST_MASK;
+    if constexpr (std::is_same<P, X>::value && sizeof(P) == 16) {
+        if (st == CP_ST_SC1) {
+            stg_sc1(p, x);
+            return;
+        }
+    }
+    if (st != CP_ST_NT) stg_plain(p, x);
+    else stg<NT>(p, x);
+}
+template <bool NT, class P, class X>
+__device__ __forceinline__ void stgw_k(P* p, const X& x, int pol) {
+    if constexpr (std::is_same<P, u192e>::value) {
+        if ((pol & CP_ST_MASK) != CP_ST_NT) {
+            FF_STORE_FENCE(p);
+            stgw<false>(p, x);
+            FF_STORE_FENCE(p);
+        } else {
+            stgw<NT>(p, x);
+        }
     } else {
-        stgw<NT>(p, x);
+        stg_k<NT>(p, x, pol);
     }
 }
 
@@ -351,17 +383,17 @@ __device__ __forceinline__ typename F::word ew_apply(const F& f, typename F::wor
 // One pack per thread; the loads of a pack are issued in argument order and then finished in argument order (the
 // 24-byte path stages every finish through the wave's one LDS region: the order is part of the kernel), fn runs lane by
 // lane, one store follows.  The scalar tail takes the elements past the last full pack (n not a multiple of the pack
-// size), or all of them (unaligned pointers: nvec == 0).  `keep` is the kernel's argument (stgw_k), or StreamOut.
+// size), or all of them (unaligned pointers: nvec == 0).  `pol` is the kernel's policy word (stgw_k), or StreamOut.
 // A kernel's lambda captures the kernel's arguments by copy: captured by reference they get an address, and k_ew1 then
 // compiled to other code over half the policies (k_ew1<GF2W128, MUL>: 90 -> 36 registers; profiles/r11_streaming_shape.md).
-struct StreamOut {};          // store policy of a kernel without a `keep` argument: always nt, no scalar branch, no fences
+struct StreamOut {};          // store policy of a kernel without a policy word: always nt, no scalar branch, no fences
 template <bool NT, class P, class X>
 __device__ __forceinline__ void stgw_k(P* p, const X& x, StreamOut) { stgw<NT>(p, x); }
 template <class Fn, class P, size_t... J>
 __device__ __forceinline__ auto map_lane(const Fn& fn, const P* x, int q, std::index_sequence<J...>) { return fn(x[J].w[q]...); }
 
-template <class F, bool NT, class Keep, class Fn, class... E>
-__device__ __forceinline__ void stream_map(typename F::elem* o, size_t nvec, size_t n, Keep keep, Fn fn, const E*... in) {
+template <class F, bool NT, class Pol, class Fn, class... E>
+__device__ __forceinline__ void stream_map(typename F::elem* o, size_t nvec, size_t n, Pol pol, Fn fn, const E*... in) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     constexpr int K = sizeof...(E);
@@ -376,7 +408,7 @@ __device__ __forceinline__ void stream_map(typename F::elem* o, size_t nvec, siz
         for (int j = 0; j < K; ++j) x[j] = ldgw_finish(raw[j]);
 #pragma unroll
         for (int q = 0; q < P::N; ++q) r.w[q] = map_lane(fn, x, q, std::make_index_sequence<K>());
-        stgw_k<NT>(ov + i, r, keep);
+        stgw_k<NT>(ov + i, r, pol);
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);
     for (size_t e = done + gid; e < n; e += gsz) st_elem<F>(o, e, fn(ld_elem<F>(in, e)...));
@@ -385,15 +417,15 @@ __device__ __forceinline__ void stream_map(typename F::elem* o, size_t nvec, siz
 // ---- out = a (op) b --------------------------------------------------------
 template <class F, int OP, bool NT>
 __device__ __forceinline__ void ew2_body(const F& f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ b,
-                                         typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
+                                         typename F::elem* __restrict__ o, size_t nvec, size_t n, int pol) {
     typedef typename F::word W;
-    stream_map<F, NT>(o, nvec, n, keep, [&](W x, W y) { return ew_apply<F, OP>(f, x, y); }, a, b);
+    stream_map<F, NT>(o, nvec, n, pol, [&](W x, W y) { return ew_apply<F, OP>(f, x, y); }, a, b);
 }
 template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew2(F f, const typename F::elem* __restrict__ a,
                                                 const typename F::elem* __restrict__ b,
-                                                typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
-    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, keep);
+                                                typename F::elem* __restrict__ o, size_t nvec, size_t n, int pol) {
+    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, pol);
 }
 // The same kernel held to WAVES waves per SIMD, for products that the VALU limits: left alone the compiler hoists all nine
 // 32 x 32 carry-less products of a GF(2^128) multiplication side by side (129 registers, three waves per SIMD); told to keep
@@ -402,8 +434,8 @@ __global__ __launch_bounds__(BLOCK) void k_ew2(F f, const typename F::elem* __re
 template <class F, int OP, bool NT, int WAVES>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 void k_ew2_occ(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ b,
-               typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
-    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, keep);
+               typename F::elem* __restrict__ o, size_t nvec, size_t n, int pol) {
+    ew2_body<F, OP, NT>(f, a, b, o, nvec, n, pol);
 }
 template <class F, int OP> struct EwOccupancy { enum { waves = 0 }; };
 #ifndef FFGPU_GF2W128_OCC
@@ -415,9 +447,9 @@ template <> struct EwOccupancy<GF2W128, OP_MUL> { enum { waves = FFGPU_GF2W128_O
 template <class F, int OP, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_ew1(F f, const typename F::elem* __restrict__ a,
                                                 typename F::word s, typename F::elem* __restrict__ o,
-                                                size_t nvec, size_t n, int keep) {
+                                                size_t nvec, size_t n, int pol) {
     typedef typename F::word W;
-    stream_map<F, NT>(o, nvec, n, keep, [=](W x) { return ew_apply<F, OP>(f, x, s); }, a);
+    stream_map<F, NT>(o, nvec, n, pol, [=](W x) { return ew_apply<F, OP>(f, x, s); }, a);
 }
 
 // ---- out = a*b + c ---------------------------------------------------------
@@ -425,9 +457,9 @@ template <class F, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_muladd(F f, const typename F::elem* __restrict__ a,
                                                    const typename F::elem* __restrict__ b,
                                                    const typename F::elem* __restrict__ c,
-                                                   typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
+                                                   typename F::elem* __restrict__ o, size_t nvec, size_t n, int pol) {
     typedef typename F::word W;
-    stream_map<F, NT>(o, nvec, n, keep, [=](W x, W y, W z) { return f.muladd(x, y, z); }, a, b, c);
+    stream_map<F, NT>(o, nvec, n, pol, [=](W x, W y, W z) { return f.muladd(x, y, z); }, a, b, c);
 }
 
 // ---- Beaver-triple combination: out = z + d*y + e*x + d*e ---------------------------------------
@@ -636,7 +668,7 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
                                                   const typename F::elem* __restrict__ b,
                                                   const typename F::elem* __restrict__ coef, size_t cstride,
                                                   int m, typename F::elem* __restrict__ out, size_t ostride,
-                                                  size_t nvec, size_t n, RngArgs ra, GateSrc<F> gs, int keep) {
+                                                  size_t nvec, size_t n, RngArgs ra, GateSrc<F> gs, int pol) {
     rng_load_state(ra);
     // batched launch: gate y = blockIdx.y reads its operand rows yA / yB elements further on and writes yO further on.
     // (The offsets are added where the rows are indexed: the row-pointer arrays stay read-only kernel arguments --
@@ -761,8 +793,8 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
             for (int party = 1; party <= m; ++party) {
 #pragma unroll
                 for (int q = 0; q < P::N; ++q) y.w[q] = share_diff_next<F, TT>(f, y.w[q], dd[q]);
-                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
-                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
+                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, pol);
+                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, pol);
             }
         } else {
             // GF(2^n) (the points are field elements, not integers) and T = 0: Horner by the point
@@ -779,8 +811,8 @@ __global__ __launch_bounds__(BLOCK) void k_split(F f, const typename F::elem* __
                         y.w[q] = f.muladd_small(acc, (uint32_t)party, s.w[q]);
                     }
                 }
-                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
-                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, keep);
+                if constexpr (WC) stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, pol);
+                else stg_k<NT>(reinterpret_cast<MP*>(out + (size_t)(party - 1) * ostride) + i, y, pol);
             }
         }
     };
@@ -988,7 +1020,7 @@ struct RecArgs {
 template <class F, int K, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_recombine(F f, RecArgs<F, K> ra, int w,
                                                       typename F::elem* __restrict__ out, size_t ostride,
-                                                      size_t nvec, size_t n, int keep) {
+                                                      size_t nvec, size_t n, int pol) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -1014,7 +1046,7 @@ __global__ __launch_bounds__(BLOCK) void k_recombine(F f, RecArgs<F, K> ra, int 
                 for (int j = 0; j < K; ++j) s.mac(f, ra.lam[r * K + j], x[j].w[q]);
                 y.w[q] = s.reduce(f);
             }
-            stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)r * ostride) + i, y, keep);
+            stgw_k<NT>(reinterpret_cast<MP*>(out + (size_t)r * ostride) + i, y, pol);
         }
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);

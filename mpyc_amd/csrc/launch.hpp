@@ -22,8 +22,9 @@ struct LaunchCfg {
     int mm_stack_loop_min;  // FFGPU_MM_STACK_LOOP_MIN: ffgpu_matmul_stack loops over the single-product launcher from this M*N*K per
                             // matrix on (0: always); below it the whole stack is one launch of the stack kernels (matmul_stack.hpp)
     int handoff;            // FFGPU_HANDOFF=0: every streamed output non-temporal (no hand-off tracking, handoff.hpp)
-    int keep_out;           // PER LAUNCH, never set in the context's copy: this launch's outputs feed the next launch on its
-                            // stream -- store them with the default policy (handoff.hpp; api.hip hands the launcher a copy)
+    int policy;             // PER LAUNCH, never set in the context's copy: the launch's cache policy word (CachePolicy, kernels.hpp) --
+                            // how to store outputs that feed the next launch on the stream (handoff.hpp; api.hip hands the
+                            // launcher a copy); 0: every access nt
 };
 
 // What a launcher reports.  One value per meaning; api.hip maps them to FFGPU_* in one place (status_of).
@@ -261,15 +262,15 @@ struct Launchers {
     // The streaming plan of a launch: nvec packs through the vector loop, one pack per thread up to the grid cap (one element
     // per thread when the operands do not allow packs).  The one place where nvec_of and grid_for meet: every launcher takes
     // its nvec from here, so 24-byte fields get whole waves whatever grid it then picks.
-    // keep: the vector loop stores its outputs with the default cache policy instead of nt (LaunchCfg::keep_out).
+    // pol: the cache policy word of the launch (LaunchCfg::policy), which the vector loop obeys.
     struct Plan {
         size_t nvec;
         unsigned grid;
-        int keep;
+        int pol;
     };
     static Plan plan(size_t n, bool vec, const LaunchCfg& lc) {
         const size_t nvec = nvec_of(n, vec);
-        return {nvec, grid_for(nvec ? nvec : n, lc), lc.keep_out};
+        return {nvec, grid_for(nvec ? nvec : n, lc), lc.policy};
     }
     // share generation with in-kernel coefficients (k_split RNG, the gate): the grouped loop serves up to 4 packs per thread
     // (RngLayout::G) on half as many threads as packs, a slightly larger grid is harmless; below ~2.6e5 packs it cannot
@@ -318,9 +319,9 @@ struct Launchers {
         // (streamed loads and stores carry the non-temporal hint: +4-8 %, profiles/r01_tuning.md; the un-hinted instantiations
         // that rounds 1-5 kept behind FFGPU_NT=0 for A/B runs are gone)
         if constexpr (OCC > 0)
-            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.keep);
+            hipLaunchKernelGGL((k_ew2_occ<F, OP, true, OCC>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.pol);
         else
-            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.keep);
+            hipLaunchKernelGGL((k_ew2<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, b, o, p.nvec, n, p.pol);
     }
     static LaunchStatus ew2(const void* Fp, const LaunchCfg& lc, int op, const void* a, const void* b, void* o, size_t n,
                    hipStream_t st) {
@@ -336,7 +337,7 @@ struct Launchers {
     template <int OP>
     static void go_ew1(const F& f, const LaunchCfg& lc, const E* a, W s, E* o, size_t n, hipStream_t st) {
         const Plan p = plan(n, al(a) && al(o), lc);
-        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n, p.keep);
+        hipLaunchKernelGGL((k_ew1<F, OP, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, a, s, o, p.nvec, n, p.pol);
     }
     static LaunchStatus ew1(const void* Fp, const LaunchCfg& lc, int op, const void* a, const uint64_t* scalar2, void* o,
                    size_t n, hipStream_t st) {
@@ -354,7 +355,7 @@ struct Launchers {
         const F& f = policy(Fp);
         const Plan p = plan(n, al(a) && al(b) && al(c) && al(o), lc);
         hipLaunchKernelGGL((k_muladd<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)a,
-                           (const E*)b, (const E*)c, (E*)o, p.nvec, n, p.keep);
+                           (const E*)b, (const E*)c, (E*)o, p.nvec, n, p.pol);
         return launched();
     }
 
@@ -362,7 +363,7 @@ struct Launchers {
     static void go_split(const F& f, const Plan& p, const E* a, const E* b, const E* coef, size_t cstride, int m, E* out,
                          size_t ostride, size_t n, hipStream_t st, const RngArgs& ra, const GateSrc<F>& gs, unsigned gy = 1) {
         hipLaunchKernelGGL((k_split<F, T, FUSE, true, RNG, REC>), dim3(p.grid, gy), dim3(BLOCK), 0, st, f, a, b,
-                           coef, cstride, m, out, ostride, p.nvec, n, ra, gs, p.keep);
+                           coef, cstride, m, out, ostride, p.nvec, n, ra, gs, p.pol);
     }
     template <bool FUSE, bool RNG>
     static LaunchStatus split_t(const F& f, const LaunchCfg& lc, const E* a, const E* b, const E* coef, size_t cstride,
@@ -482,7 +483,7 @@ struct Launchers {
         for (int i = w * K; i < MAXW * K; ++i) ra.lam[i] = ra.lam[0];
         const Plan p = plan(n, vec, lc);
         hipLaunchKernelGGL((k_recombine<F, K, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, ra, w, out, ostride,
-                           p.nvec, n, p.keep);
+                           p.nvec, n, p.pol);
     }
     static LaunchStatus recombine(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int k,
                          int w, void* out, size_t ostride, size_t n, hipStream_t st) {
@@ -1078,7 +1079,7 @@ struct Launchers {
             const F& f = policy(Fp);
             const Plan p = plan(n, al(w) && al(sbit) && al(z) && al(out), lc);
             hipLaunchKernelGGL((k_sgn_finish<F, true>), dim3(p.grid), dim3(BLOCK), 0, st, f, (const E*)w, (const E*)sbit, (const E*)z,
-                               word_at<F>(f, consts, 1), word_at<F>(f, consts, 2), (E*)out, p.nvec, n, p.keep);
+                               word_at<F>(f, consts, 1), word_at<F>(f, consts, 2), (E*)out, p.nvec, n, p.pol);
             return launched();
         }
     }

@@ -1549,12 +1549,12 @@ LaunchStatus ffgpu_launch_gf2w_recombine(const void* policy, int limbs, const La
 }
 
 __global__ __launch_bounds__(BLOCK) void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
-                                                   size_t nvec, int keep) {
+                                                   size_t nvec, int pol) {
     const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     const size_t gsz = (size_t)gridDim.x * BLOCK;
     for (size_t i = gid; i < nvec; i += gsz) {
         uint4 x = ldg<true>(src + i);
-        stg_k<true>(dst + i, x, keep);
+        stg_k<true>(dst + i, x, pol);
     }
 }
 
@@ -1562,7 +1562,7 @@ LaunchStatus ffgpu_launch_copy(const LaunchCfg& lc, const void* src, void* dst, 
     if (!aligned16(src) || !aligned16(dst) || (bytes & 15)) return L_BAD_ARG;
     size_t nvec = bytes / 16;
     unsigned grid = grid_for(nvec, lc);
-    hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec, lc.keep_out);
+    hipLaunchKernelGGL(k_copy16, dim3(grid), dim3(BLOCK), 0, st, (const uint4*)src, (uint4*)dst, nvec, lc.policy);
     return launched();
 }
 

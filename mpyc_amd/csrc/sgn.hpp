@@ -260,11 +260,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) v
 template <class F, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_sgn_finish(F f, const typename F::elem* __restrict__ w, const typename F::elem* __restrict__ sbit,
                                                        const typename F::elem* __restrict__ z, typename F::word half, typename F::word inv,
-                                                       typename F::elem* __restrict__ o, size_t nvec, size_t n, int keep) {
+                                                       typename F::elem* __restrict__ o, size_t nvec, size_t n, int pol) {
     typedef typename F::word W;
     const W one = ff_one_elem(f);
     const W three = f.add(f.add(one, one), one);
-    stream_map<F, NT>(o, nvec, n, keep, [=](W wv, W sb, W zv) -> W {
+    stream_map<F, NT>(o, nvec, n, pol, [=](W wv, W sb, W zv) -> W {
         const W s = f.sub(f.add(sb, sb), one);
         const W v = f.add(ff_pick(sgn_is_zero(wv), f.neg(s), s), three);
         return f.mul(f.add(zv, f.mul(v, half)), inv);
