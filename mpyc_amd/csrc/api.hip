@@ -559,6 +559,20 @@ int ffgpu_stream_sync(ffgpu_ctx* ctx, void* stream) {
     do {             \
         if (!(cond)) return FFGPU_EINVAL; \
     } while (0)
+// the first line of an entry of the secure rounds: a context (FFGPU_EINVAL), over a prime field (FFGPU_ENOTSUP)
+#define PRIME_CTX(ctx) \
+    do {               \
+        ARGCHK(ctx);   \
+        if ((ctx)->kind != FFGPU_PRIME) return FFGPU_ENOTSUP; \
+    } while (0)
+// what an entry with an X_args function does before it looks at a pointer: `call` is X_args(..., &work); the entry returns
+// what X_args refused, and FFGPU_OK when there is nothing to do
+#define ARGS_OR_RETURN(call) \
+    do {                     \
+        bool work;           \
+        const int rc = (call); \
+        if (rc != FFGPU_OK || !work) return rc; \
+    } while (0)
 
 // bytes of `rows` rows of n elements, `stride` elements apart
 static size_t rows_bytes(const ffgpu_ctx* ctx, size_t rows, size_t stride, size_t n) {
@@ -1219,8 +1233,8 @@ static bool sgn_consts(const ffgpu_ctx* ctx, int l, uint64_t out[9]) {
     for (int j = 0; j < sl; ++j) out[2 * sl + j] = x[j];
     return true;
 }
-// no output range may overlap an input or another output
-static bool sgn_ranges_ok(const ByteRange* in, int nin, const ByteRange* out, int nout) {
+// no output range may overlap an input or another output (comparison, bit decomposition, carry network, fixed point)
+static bool outputs_disjoint(const ByteRange* in, int nin, const ByteRange* out, int nout) {
     for (int j = 0; j < nout; ++j) {
         for (int i = 0; i < nin; ++i)
             if (overlaps(out[j], in[i])) return false;
@@ -1229,11 +1243,20 @@ static bool sgn_ranges_ok(const ByteRange* in, int nin, const ByteRange* out, in
     }
     return true;
 }
+// the sub-share rows of an apply entry, `bytes` each: none is null, none overlaps one of the ranges the call writes
+static bool rows_clear_of(const void* const* host_rows, int nrows, size_t bytes, const ByteRange* ranges, int nranges) {
+    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
+    for (int s = 0; s < nin; ++s) {
+        if (!host_rows[s]) return false;
+        for (int i = 0; i < nranges; ++i)
+            if (overlaps(byte_range(host_rows[s], bytes), ranges[i])) return false;
+    }
+    return true;
+}
 
 int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, int l, void* masked, size_t n,
                    void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, l, consts));
     if (n == 0) return FFGPU_OK;
@@ -1243,15 +1266,14 @@ int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void*
     ARGCHK(p.ok);
     const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
     const ByteRange o = byte_range(masked, n * eb);
-    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->sgn_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
 
 int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* rbits, const void* sbit, int l, void* e_out,
                      void* nx_out, void* z_out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, l, consts));
     ARGCHK(e_out || nx_out || z_out);
@@ -1268,15 +1290,14 @@ int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* r
     if (e_out) o[no++] = byte_range(e_out, (p.nl + n) * eb);
     if (nx_out) o[no++] = byte_range(nx_out, p.nl * eb);
     if (z_out) o[no++] = byte_range(z_out, n * eb);
-    ARGCHK(sgn_ranges_ok(in, 4, o, no));
+    ARGCHK(outputs_disjoint(in, 4, o, no));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->sgn_expand(ctx->policy, cs.lc, c, a, rbits, e_out ? sbit : nullptr, l, consts, e_out, nx_out, z_out,
                                           n, cs.st));
 }
 
 int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void* z, int l, void* lt_out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, l, consts));
     if (n == 0) return FFGPU_OK;
@@ -1285,7 +1306,7 @@ int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void
     ARGCHK(n <= ((size_t)1 << 62) / eb);                 // n * eb cannot overflow
     const ByteRange in[3] = {byte_range(w, n * eb), byte_range(sbit, n * eb), byte_range(z, n * eb)};
     const ByteRange o = byte_range(lt_out, n * eb);
-    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
 }
@@ -1306,12 +1327,9 @@ static int cx_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner, s
 
 int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r,
                   void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     CxPlan pl;
-    bool work;
-    const int rc = cx_args(ctx, outer, k, inner, p, d, r, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(cx_args(ctx, outer, k, inner, p, d, r, &pl, &work));
     ARGCHK(a && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
@@ -1321,18 +1339,14 @@ int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t
 
 int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, size_t outer,
                    size_t k, size_t inner, size_t p, size_t d, size_t r, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     CxPlan pl;
-    bool work;
-    const int rc = cx_args(ctx, outer, k, inner, p, d, r, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(cx_args(ctx, outer, k, inner, p, d, r, &pl, &work));
     ARGCHK(a && host_rows && host_lambda);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange ar = byte_range(a, outer * k * inner * eb);
-    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
-    for (int s = 0; s < nin; ++s) ARGCHK(host_rows[s] && !overlaps(byte_range(host_rows[s], outer * pl.row_elems * eb), ar));
+    ARGCHK(rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &ar, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
 }
@@ -1349,21 +1363,11 @@ static int tour_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner,
     *work = true;
     return FFGPU_OK;
 }
-// the sub-share rows of select / unit_expand: compact arrays that `out` may not overlap
-static bool tour_rows_ok(const void* const* host_rows, int nrows, size_t bytes, const ByteRange& out) {
-    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
-    for (int s = 0; s < nin; ++s)
-        if (!host_rows[s] || overlaps(byte_range(host_rows[s], bytes), out)) return false;
-    return true;
-}
 
 int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t k, size_t inner, int mode, int neg, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     TourPlan pl;
-    bool work;
-    const int rc = tour_args(ctx, outer, k, inner, mode, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, mode, &pl, &work));
     ARGCHK(a && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
@@ -1373,28 +1377,22 @@ int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size
 
 int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, void* out,
                       size_t outer, size_t k, size_t inner, int mode, int neg, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     TourPlan pl;
-    bool work;
-    const int rc = tour_args(ctx, outer, k, inner, mode, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, mode, &pl, &work));
     ARGCHK(a && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, outer * pl.next * inner * eb);
-    ARGCHK(!overlaps(o, byte_range(a, outer * k * inner * eb)) && tour_rows_ok(host_rows, nrows, outer * pl.row_elems * eb, o));
+    ARGCHK(!overlaps(o, byte_range(a, outer * k * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->tour_select(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, out, outer, k, inner, mode, neg, cs.st));
 }
 
 int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out, size_t outer, size_t k, size_t inner, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     TourPlan pl;
-    bool work;
-    const int rc = tour_args(ctx, outer, k, inner, TOUR_HALVES, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, TOUR_HALVES, &pl, &work));
     ARGCHK(u && c && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, outer * pl.row_elems * eb);
@@ -1405,17 +1403,14 @@ int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out
 
 int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
                            void* out, size_t outer, size_t k, size_t inner, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     TourPlan pl;
-    bool work;
-    const int rc = tour_args(ctx, outer, k, inner, TOUR_ODD_EVEN, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, TOUR_ODD_EVEN, &pl, &work));
     ARGCHK(u && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, outer * k * inner * eb);
-    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && tour_rows_ok(host_rows, nrows, outer * pl.row_elems * eb, o));
+    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
 }
@@ -1438,12 +1433,9 @@ static int find_args(const ffgpu_ctx* ctx, size_t outer, size_t k, size_t inner,
 
 int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void* out, size_t outer, size_t k, size_t inner, int ncomp,
                          int flip, int virt, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     FindPlan pl;
-    bool work;
-    const int rc = find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work));
     ARGCHK(bits && tab && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb);
@@ -1454,29 +1446,24 @@ int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void
 
 int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, const void* const* host_rows, const uint64_t* host_lambda,
                           int nrows, void* out, size_t outer, size_t k, size_t inner, int ncomp, int flip, int virt, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME || nrows < 1 || nrows > (int)MAXK) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
+    if (nrows < 1 || nrows > (int)MAXK) return FFGPU_ENOTSUP;
     FindPlan pl;
-    bool work;
-    const int rc = find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work));
     ARGCHK(bits && tab && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.next * inner * eb);
     ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)) &&
-           tour_rows_ok(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb, o));
+           rows_clear_of(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->find_leaf_apply(ctx->policy, cs.lc, bits, tab, host_rows, host_lambda, nrows, out, outer, k, inner, ncomp,
                                                flip, virt, cs.st));
 }
 
 int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, size_t k, size_t inner, int ncomp, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     FindPlan pl;
-    bool work;
-    const int rc = find_args(ctx, outer, k, inner, ncomp, false, 0, 0, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, false, 0, 0, &pl, &work));
     ARGCHK(level && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb), byte_range(level, (size_t)ncomp * outer * k * inner * eb)));
@@ -1511,33 +1498,38 @@ static bool bits_two_l(const ffgpu_ctx* ctx, int l, uint64_t out[3]) {
     for (int j = 0; j < 3; ++j) out[j] = j < sl ? consts[j] : 0;       // (scalar 0 of sgn_consts)
     return true;
 }
-
-int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, const uint64_t* host_offset, int l,
-                    void* masked, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
-    uint64_t two_l[3], consts[6] = {0, 0, 0, 0, 0, 0};
-    ARGCHK(bits_two_l(ctx, l, two_l) && host_offset);
-    if (n == 0) return FFGPU_OK;
-    ARGCHK(a && rbits && rdivl && masked);
+// the two scalars of a mask entry, 2^l and the caller's offset, as the launcher reads them; false as bits_two_l, or without offset
+static bool mask_consts(const ffgpu_ctx* ctx, int l, const uint64_t* host_offset, uint64_t consts[6]) {
+    uint64_t two_l[3];
+    if (!bits_two_l(ctx, l, two_l) || !host_offset) return false;
     const int sl = ffgpu_ctx_scalar_limbs(ctx);
+    for (int j = 0; j < 6; ++j) consts[j] = 0;
     for (int j = 0; j < sl; ++j) {
         consts[j] = two_l[j];
         consts[sl + j] = host_offset[j];
     }
+    return true;
+}
+
+int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, const uint64_t* host_offset, int l,
+                    void* masked, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    uint64_t consts[6];
+    ARGCHK(mask_consts(ctx, l, host_offset, consts));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && rbits && rdivl && masked);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
     const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
     const ByteRange o = byte_range(masked, n * eb);
-    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->bits_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
 
 int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, void* g_out, void* p_out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     uint64_t two_l[3];
     ARGCHK(bits_two_l(ctx, l, two_l));
     if (n == 0) return FFGPU_OK;
@@ -1547,14 +1539,13 @@ int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, v
     ARGCHK(p.ok);
     const ByteRange in[2] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb)};
     const ByteRange o[2] = {byte_range(g_out, p.nl * eb), byte_range(p_out, p.nl * eb)};
-    ARGCHK(sgn_ranges_ok(in, 2, o, 2));
+    ARGCHK(outputs_disjoint(in, 2, o, 2));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->bits_expand(ctx->policy, cs.lc, c, rbits, l, g_out, p_out, n, cs.st));
 }
 
 int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const void* g, int l, void* out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     uint64_t two_l[3];
     ARGCHK(bits_two_l(ctx, l, two_l));
     if (n == 0) return FFGPU_OK;
@@ -1564,7 +1555,7 @@ int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const vo
     ARGCHK(p.ok);
     const ByteRange in[3] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb), byte_range(g, p.nl * eb)};
     const ByteRange o = byte_range(out, p.nl * eb);
-    ARGCHK(sgn_ranges_ok(in, 3, &o, 1));
+    ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->bits_finish(ctx->policy, cs.lc, c, rbits, g, l, out, n, cs.st));
 }
@@ -1581,40 +1572,28 @@ static int carry_args(const ffgpu_ctx* ctx, int l, int round, size_t n, BitsLeve
 }
 
 int ffgpu_carry_prod(ffgpu_ctx* ctx, const void* g, const void* p, int l, int round, void* out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     BitsLevel lv;
-    bool work;
-    const int rc = carry_args(ctx, l, round, n, &lv, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(carry_args(ctx, l, round, n, &lv, &work));
     ARGCHK(g && p && out);
     const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
     const ByteRange in[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
     const ByteRange o = byte_range(out, (size_t)(lv.rc + lv.rd) * n * eb);
-    ARGCHK(sgn_ranges_ok(in, 2, &o, 1));
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->carry_prod(ctx->policy, cs.lc, g, p, l, lv, out, n, cs.st));
 }
 
 int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
                       int round, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     BitsLevel lv;
-    bool work;
-    const int rc = carry_args(ctx, l, round, n, &lv, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(carry_args(ctx, l, round, n, &lv, &work));
     ARGCHK(g && p && host_rows && host_lambda);
     const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
-    const ByteRange gr = byte_range(g, nl * eb), pr = byte_range(p, nl * eb);
-    ARGCHK(!overlaps(gr, pr));
-    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
-    for (int s = 0; s < nin; ++s) {
-        ARGCHK(host_rows[s]);
-        const ByteRange rr = byte_range(host_rows[s], (size_t)(lv.rc + lv.rd) * n * eb);
-        ARGCHK(!overlaps(rr, gr) && !overlaps(rr, pr));
-    }
+    const ByteRange gp[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
+    ARGCHK(!overlaps(gp[0], gp[1]) && rows_clear_of(host_rows, nrows, (size_t)(lv.rc + lv.rd) * n * eb, gp, 2));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
 }
@@ -1622,31 +1601,24 @@ int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_
 // ---- fixed point over a prime field: the local steps of np_trunc and of _norm (fxp.hpp) -------------------------------------
 int ffgpu_trunc_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivf, const uint64_t* host_offset, int f,
                      void* ar_out, void* masked_out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
-    uint64_t two_f[3], consts[6] = {0, 0, 0, 0, 0, 0};
-    ARGCHK(bits_two_l(ctx, f, two_f) && host_offset);
+    PRIME_CTX(ctx);
+    uint64_t consts[6];
+    ARGCHK(mask_consts(ctx, f, host_offset, consts));
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && rbits && rdivf && ar_out && masked_out);
-    const int sl = ffgpu_ctx_scalar_limbs(ctx);
-    for (int j = 0; j < sl; ++j) {
-        consts[j] = two_f[j];
-        consts[sl + j] = host_offset[j];
-    }
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, f, eb);
     ARGCHK(p.ok);
     const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivf, n * eb)};
     const ByteRange o[2] = {byte_range(ar_out, n * eb), byte_range(masked_out, n * eb)};
-    ARGCHK(sgn_ranges_ok(in, 3, o, 2));
+    ARGCHK(outputs_disjoint(in, 3, o, 2));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->trunc_mask(ctx->policy, cs.lc, a, rbits, rdivf, f, consts, ar_out, masked_out, n, cs.st));
 }
 
 int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int nrows, const void* ar, int f,
                        void* out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
     uint64_t consts[9];
@@ -1656,7 +1628,7 @@ int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint6
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(sgn_plan(n, f, eb).ok);
     const ByteRange o = byte_range(out, n * eb);
-    ARGCHK(!overlaps(o, byte_range(ar, n * eb)) && tour_rows_ok(host_rows, nrows, n * eb, o));
+    ARGCHK(!overlaps(o, byte_range(ar, n * eb)) && rows_clear_of(host_rows, nrows, n * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->trunc_finish(ctx->policy, cs.lc, host_rows, host_lambda, nrows, ar, f,
                                             consts + 2 * ffgpu_ctx_scalar_limbs(ctx), out, n, cs.st));
@@ -1674,35 +1646,29 @@ static int norm_args(const ffgpu_ctx* ctx, int l, size_t n, FxpNormPlan* pl, boo
 }
 
 int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* sign_out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     FxpNormPlan pl;
-    bool work;
-    const int rc = norm_args(ctx, l, n, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
     ARGCHK(bits && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange in = byte_range(bits, n * pl.l * eb);
     const ByteRange o[2] = {byte_range(out, pl.elems * eb), byte_range(sign_out, sign_out ? n * eb : 0)};
-    ARGCHK(sgn_ranges_ok(&in, 1, o, sign_out ? 2 : 1));
+    ARGCHK(outputs_disjoint(&in, 1, o, sign_out ? 2 : 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->norm_prod(ctx->policy, cs.lc, bits, l, out, sign_out, n, cs.st));
 }
 
 int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
                      void* out, size_t n, void* stream) {
-    ARGCHK(ctx);
-    if (ctx->kind != FFGPU_PRIME) return FFGPU_ENOTSUP;
+    PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
     FxpNormPlan pl;
-    bool work;
-    const int rc = norm_args(ctx, l, n, &pl, &work);
-    if (rc != FFGPU_OK || !work) return rc;
+    ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
     ARGCHK(bits && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ByteRange o = byte_range(out, pl.elems * eb);
-    ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && tour_rows_ok(host_rows, nrows, pl.elems * eb, o));
+    ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && rows_clear_of(host_rows, nrows, pl.elems * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
 }

@@ -16,8 +16,8 @@
 // units, so both its element-major sides are coalesced.  The two level kernels are streaming kernels, one unit per thread
 // (BitsPlan): workgroup row y is product row y, so the (k, q) entry of the table is uniform over a workgroup.
 //
-// Memory policy: the bit shares and the sub-share rows are read once: non-temporal loads.  G and P are read and written
-// round after round, the products feed the re-sharing at once: default policy.
+// Memory policy: the bit shares are read once: non-temporal loads.  G and P are read and written round after round, the
+// products feed the re-sharing at once: default policy.  The sub-share rows of k_carry_apply: share_rows.hpp.
 #pragma once
 #include "bits_geom.hpp"
 
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void k_carry_prod(F f, const typename F::ele
 }
 
 template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_carry_apply(F f, CxRows<F, K> ra, typename F::elem* __restrict__ g, typename F::elem* __restrict__ p,
+__global__ __launch_bounds__(BLOCK) void k_carry_apply(F f, ShareRows<F, K> ra, typename F::elem* __restrict__ g, typename F::elem* __restrict__ p,
                                                         BitsLevel lv, BitsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;

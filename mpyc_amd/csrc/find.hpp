@@ -23,8 +23,8 @@
 // and apply issues the rows of component q + 1 before it computes component q.  The public leaf's bit is not loaded: the
 // plan gives it the first member's address (issued, not used) and the kernel selects the public 1.
 //
-// Memory policy: bits, levels and compact outputs are read again by the next call: default policy.  The sub-share rows are
-// read once: non-temporal loads.  The table is F * 2 * kv elements, read through the cache with default policy; with inner
+// Memory policy: bits, levels and compact outputs are read again by the next call: default policy.  The sub-share rows:
+// share_rows.hpp.  The table is F * 2 * kv elements, read through the cache with default policy; with inner
 // == 1 the position differs lane by lane (a gather over 2 * 64 adjacent entries per wave), with inner > 1 it is uniform over
 // a run.  With inner == 1 a pair is two adjacent elements: one 16-byte load per lane for 8-byte elements instead of two
 // element loads was built and measured at (10^6, 31, 1) and changed nothing (profiles/find_kernels.md), so the element path
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(BLOCK) void k_find_leaf_prod(F f, const typename F:
 }
 
 template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_find_leaf_apply(F f, CxRows<F, K> ra, const typename F::elem* __restrict__ bits,
+__global__ __launch_bounds__(BLOCK) void k_find_leaf_apply(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ bits,
                                                             const typename F::elem* __restrict__ tab, typename F::elem* __restrict__ out,
                                                             FindPlan pl, int ncomp, int flip) {
     typedef typename F::word W;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void k_find_leaf_apply(F f, CxRows<F, K> ra,
                     for (int j = 0; j < K; ++j)
                         rx[j] = ldgw_issue<true>(reinterpret_cast<const MP*>(ra.rows[j]) + (size_t)(q + 1) * pl.plane_c + at.c);
                 }
-                const P v = tour_recombine<F, K>(f, ra, x);
+                const P v = share_rows_pack<F, K>(f, ra, x);
                 P y;
                 if (q == 0) {
 #pragma unroll
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(BLOCK) void k_find_leaf_apply(F f, CxRows<F, K> ra,
             const FindAt at = find_leaf_at(pl, g);
             const W b1 = find_bit(f, ld_elem<F>(bits, at.first), one, flip, 0);
             for (int q = 0; q < ncomp; ++q) {
-                const W v = tour_recombine_elem<F, K>(f, ra, (size_t)q * pl.plane_c + at.c);
+                const W v = share_rows_elem<F, K>(f, ra, (size_t)q * pl.plane_c + at.c);
                 const W leaf = q == 0 ? b1 : find_leaf(f, find_tab<F>(tab, pl.kv, q, at.pos), b1);
                 st_elem<F>(out, (size_t)q * pl.plane_half + at.half, f.add(leaf, v));
             }

@@ -22,8 +22,8 @@
 // the low limb under a mask (sgn_low64, as k_sgn_expand takes c mod 2^l); the mask is built on the host, so f = 64 shifts
 // nothing by 64.
 //
-// Memory policy: bit shares and sub-share rows are read once: non-temporal loads.  ar, the bits and every output are read by
-// the next call: default policy.
+// Memory policy: bit shares are read once: non-temporal loads.  ar, the bits and every output are read by the next call:
+// default policy.  The sub-share rows of the finish and of the apply: share_rows.hpp.
 #pragma once
 #include "fxp_geom.hpp"
 
@@ -51,7 +51,7 @@ __device__ __forceinline__ typename F::word trunc_value(const F& f, const typena
 }
 
 template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, CxRows<F, K> ra, const typename F::elem* __restrict__ ar, uint64_t cmask,
+__global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ ar, uint64_t cmask,
                                                          typename F::word inv, typename F::elem* __restrict__ out, FxpFlatPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, CxRows<F, K> ra, co
                 for (int j = 0; j < K; ++j) x[j] = ldgw_finish(rx[j]);
                 x0 = ldgw_finish(r0);
             }
-            const P c = tour_recombine<F, K>(f, ra, x);
+            const P c = share_rows_pack<F, K>(f, ra, x);
             P y;
 #pragma unroll
             for (int q = 0; q < P::N; ++q) y.w[q] = trunc_value<F>(f, x0.w[q], c.w[q], cmask, inv);
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, CxRows<F, K> ra, co
         }
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
-            const W c = tour_recombine_elem<F, K>(f, ra, g);
+            const W c = share_rows_elem<F, K>(f, ra, g);
             st_elem<F>(out, g, trunc_value<F>(f, ld_elem<F>(ar, g), c, cmask, inv));
         }
     }
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem
 }
 
 template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, CxRows<F, K> ra, const typename F::elem* __restrict__ bits,
+__global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ bits,
                                                        typename F::elem* __restrict__ out, FxpNormPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, CxRows<F, K> ra, cons
 #pragma unroll
                 for (int j = 0; j < K; ++j) x[j] = ldgw_finish(rx[j]);
             }
-            const P v = tour_recombine<F, K>(f, ra, x);
+            const P v = share_rows_pack<F, K>(f, ra, x);
             P y;
 #pragma unroll
             for (int q = 0; q < P::N; ++q) y.w[q] = f.add(f.sub(one, xt[q]), v.w[q]);
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, CxRows<F, K> ra, cons
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
             const FxpNormAt at = fxp_norm_at(pl, g);
-            const W v = tour_recombine_elem<F, K>(f, ra, g);
+            const W v = share_rows_elem<F, K>(f, ra, g);
             st_elem<F>(out, g, f.add(f.sub(one, ld_elem<F>(bits, at.top)), v));
         }
     }

@@ -2277,6 +2277,7 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "convolve.hpp" // full convolution of two arrays
 #include "scan.hpp"     // prefix scans and reductions along one axis
 #include "sgn.hpp"      // local steps of the secure comparison (np_sgn)
+#include "share_rows.hpp" // the sub-share rows of a secure round, recombined in registers: the apply kernels below
 #include "sort.hpp"     // the two ends of a compare-exchange stage of the sorting network (np_sort)
 #include "bits.hpp"     // local steps of bit decomposition over a prime field (np_to_bits)
 #include "tour.hpp"     // the ends of a tournament round (np_amax / np_amin, np_argmax / np_argmin)

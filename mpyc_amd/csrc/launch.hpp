@@ -1083,6 +1083,31 @@ struct Launchers {
             return launched();
         }
     }
+    // The launchers that take the sub-share rows of a round (share_rows.hpp) share the staging of the rows and their frame.
+    // stage_rows: the rows and the prepared Lagrange vector as a kernel argument; *vec stays true only if every row is aligned
+    // for packs.  The go_*<K> below are: stage, plan with vec, launch.
+    template <int K>
+    static ShareRows<F, K> stage_rows(const F& f, const void* const* rows, const uint64_t* lam2, bool* vec) {
+        ShareRows<F, K> ra;
+        for (int j = 0; j < K; ++j) {
+            ra.rows[j] = (const E*)rows[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            *vec = *vec && al(rows[j]);
+        }
+        return ra;
+    }
+    // launch_rows: more than MAXK rows are L_NOT_SUPPORTED; then the plan's answer (refused, nothing to do); then go(k_) with
+    // nrows as an integral_constant.  Fewer than one row matches no K: L_BAD_ARG (the entry point should have refused it),
+    // unless the launcher documents L_NOT_SUPPORTED for it (FieldOps: find_leaf_apply, trunc_finish, norm_apply).
+    enum RowsBelowOne { BELOW_ONE_BAD_ARG, BELOW_ONE_NOT_SUPPORTED };
+    template <class Go>
+    static LaunchStatus launch_rows(int nrows, RowsBelowOne below, bool plan_ok, bool empty, Go&& go) {
+        if (nrows > MAXK || (below == BELOW_ONE_NOT_SUPPORTED && nrows < 1)) return L_NOT_SUPPORTED;
+        if (!plan_ok) return L_PLAN_REFUSED;
+        if (empty) return L_OK;
+        if (!dispatch_int(IntRange<1, MAXK>(), nrows, go)) return L_BAD_ARG;
+        return launched();
+    }
     // The two ends of a compare-exchange stage (sort.hpp): one flat streaming loop over the compact pair array, a unit (a pack
     // where cx_plan() admits packs, else an element) per thread up to the grid cap.
     static_assert(cx_pack(sizeof(E)) == (F::BINARY ? cx_pack(sizeof(E)) : (unsigned)EPV), "sort_geom.hpp counts this field's pack");
@@ -1103,13 +1128,8 @@ struct Launchers {
     template <int K>
     static void go_cx_apply(const F& f, const LaunchCfg& lc, E* a, const void* const* rows, const uint64_t* lam2, size_t outer,
                             size_t k, size_t inner, size_t p, size_t d, size_t r, hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(a);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const CxPlan pl = cx_plan(outer, k, inner, p, d, r, sizeof(E), vec);
         hipLaunchKernelGGL((k_cx_apply<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, pl);
     }
@@ -1119,14 +1139,10 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows > MAXK) return L_NOT_SUPPORTED;
             const CxPlan pl = cx_plan(outer, k, inner, p, d, r, sizeof(E), false);
-            if (!pl.ok) return L_PLAN_REFUSED;
-            if (pl.total == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
-                              [&](auto k_) { go_cx_apply<decltype(k_)::value>(f, lc, (E*)a, rows, lam2, outer, k, inner, p, d, r, st); }))
-                return L_BAD_ARG;
-            return launched();
+            return launch_rows(nrows, BELOW_ONE_BAD_ARG, pl.ok, pl.total == 0, [&](auto k_) {
+                go_cx_apply<decltype(k_)::value>(f, lc, (E*)a, rows, lam2, outer, k, inner, p, d, r, st);
+            });
         }
     }
     // The local steps of bit decomposition (bits.hpp): a workgroup per tile of SGN_TILE elements for mask, expand and finish;
@@ -1191,13 +1207,8 @@ struct Launchers {
     template <int K>
     static void go_carry_apply(const F& f, const LaunchCfg& lc, E* g, E* p, const void* const* rows, const uint64_t* lam2, int l,
                                const BitsLevel& lv, size_t n, hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(g) && al(p);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const BitsPlan pl = bits_plan(n, l, lv.rc + lv.rd, sizeof(E), vec, bits_max_blocks(lc));
         hipLaunchKernelGGL((k_carry_apply<F, K>), dim3(pl.gx, (unsigned)pl.rows), dim3(BLOCK), 0, st, f, ra, g, p, lv, pl);
     }
@@ -1207,14 +1218,10 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows > MAXK) return L_NOT_SUPPORTED;
             const BitsPlan pl = bits_plan(n, l, lv.rc + lv.rd, sizeof(E), false, bits_max_blocks(lc));
-            if (!pl.ok) return L_PLAN_REFUSED;
-            if (pl.rows == 0 || n == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
-                              [&](auto k_) { go_carry_apply<decltype(k_)::value>(f, lc, (E*)g, (E*)p, rows, lam2, l, lv, n, st); }))
-                return L_BAD_ARG;
-            return launched();
+            return launch_rows(nrows, BELOW_ONE_BAD_ARG, pl.ok, pl.rows == 0 || n == 0, [&](auto k_) {
+                go_carry_apply<decltype(k_)::value>(f, lc, (E*)g, (E*)p, rows, lam2, l, lv, n, st);
+            });
         }
     }
     // The ends of a tournament round (tour.hpp): one flat streaming loop over the compact pair array, a unit (a pack where
@@ -1252,13 +1259,8 @@ struct Launchers {
     template <int K>
     static void go_tour_rows(const F& f, const LaunchCfg& lc, bool expand, const E* a, const void* const* rows, const uint64_t* lam2,
                              E* out, size_t outer, size_t k, size_t inner, int mode, int neg, hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(a) && al(out);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const TourPlan pl = tour_plan(outer, k, inner, mode, sizeof(E), vec);
         if (expand) hipLaunchKernelGGL((k_tour_unit_expand<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, out, pl);
         else hipLaunchKernelGGL((k_tour_select<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, a, out, pl, neg ? 1 : 0);
@@ -1270,15 +1272,10 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows > MAXK) return L_NOT_SUPPORTED;
             const TourPlan pl = tour_plan(outer, k, inner, mode, sizeof(E), false);
-            if (!pl.ok) return L_PLAN_REFUSED;
-            if (pl.total == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows, [&](auto k_) {
+            return launch_rows(nrows, BELOW_ONE_BAD_ARG, pl.ok, pl.total == 0, [&](auto k_) {
                     go_tour_rows<decltype(k_)::value>(f, lc, expand, (const E*)a, rows, lam2, (E*)out, outer, k, inner, mode, neg, st);
-                }))
-                return L_BAD_ARG;
-            return launched();
+                });
         }
     }
     static LaunchStatus tour_select(const void* Fp, const LaunchCfg& lc, const void* a, const void* const* rows, const uint64_t* lam2,
@@ -1310,13 +1307,8 @@ struct Launchers {
     static void go_find_leaf_apply(const F& f, const LaunchCfg& lc, const E* bits, const E* tab, const void* const* rows,
                                    const uint64_t* lam2, E* out, size_t outer, size_t k, size_t inner, int ncomp, int flip, int virt,
                                    hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(bits) && al(out);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const FindPlan pl = find_leaf_plan(outer, k, inner, ncomp, virt, sizeof(E), vec);
         hipLaunchKernelGGL((k_find_leaf_apply<F, K>), dim3(grid_for(pl.t.total, lc)), dim3(BLOCK), 0, st, f, ra, bits, tab, out, pl,
                            ncomp, flip ? 1 : 0);
@@ -1328,16 +1320,11 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
             const FindPlan pl = find_leaf_plan(outer, k, inner, ncomp, virt, sizeof(E), false);
-            if (!pl.t.ok) return L_PLAN_REFUSED;
-            if (pl.t.total == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows, [&](auto k_) {
+            return launch_rows(nrows, BELOW_ONE_NOT_SUPPORTED, pl.t.ok, pl.t.total == 0, [&](auto k_) {
                     go_find_leaf_apply<decltype(k_)::value>(f, lc, (const E*)bits, (const E*)tab, rows, lam2, (E*)out, outer, k, inner,
                                                             ncomp, flip, virt, st);
-                }))
-                return L_BAD_ARG;
-            return launched();
+                });
         }
     }
     static LaunchStatus find_prod(const void* Fp, const LaunchCfg& lc, const void* level, void* out, size_t outer, size_t k,
@@ -1374,13 +1361,8 @@ struct Launchers {
     template <int K>
     static void go_trunc_finish(const F& f, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, const E* ar, int fb,
                                 const uint64_t* consts, E* out, size_t n, hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(ar) && al(out);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const FxpFlatPlan pl = fxp_flat_plan(n, sizeof(E), vec);
         const uint64_t cmask = fb >= 64 ? ~0ull : (1ull << fb) - 1;         // (no shift by 64)
         hipLaunchKernelGGL((k_trunc_finish<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, ar, cmask,
@@ -1392,13 +1374,10 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
-            if (fb < 1 || fb > FXP_MAX_BITS || !fxp_flat_plan(n, sizeof(E), false).ok) return L_PLAN_REFUSED;
-            if (n == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
-                              [&](auto k_) { go_trunc_finish<decltype(k_)::value>(f, lc, rows, lam2, (const E*)ar, fb, consts, (E*)out, n, st); }))
-                return L_BAD_ARG;
-            return launched();
+            const bool plan_ok = fb >= 1 && fb <= FXP_MAX_BITS && fxp_flat_plan(n, sizeof(E), false).ok;
+            return launch_rows(nrows, BELOW_ONE_NOT_SUPPORTED, plan_ok, n == 0, [&](auto k_) {
+                go_trunc_finish<decltype(k_)::value>(f, lc, rows, lam2, (const E*)ar, fb, consts, (E*)out, n, st);
+            });
         }
     }
     static LaunchStatus norm_prod(const void* Fp, const LaunchCfg& lc, const void* bits, int l, void* out, void* sign_out, size_t n,
@@ -1418,13 +1397,8 @@ struct Launchers {
     template <int K>
     static void go_norm_apply(const F& f, const LaunchCfg& lc, const E* bits, const void* const* rows, const uint64_t* lam2, int l,
                               E* out, size_t n, hipStream_t st) {
-        CxRows<F, K> ra;
         bool vec = al(out);
-        for (int j = 0; j < K; ++j) {
-            ra.rows[j] = (const E*)rows[j];
-            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
-            vec = vec && al(rows[j]);
-        }
+        const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
         const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), vec);
         hipLaunchKernelGGL((k_norm_apply<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, bits, out, pl);
     }
@@ -1434,14 +1408,10 @@ struct Launchers {
             return L_NOT_SUPPORTED;
         } else {
             const F& f = policy(Fp);
-            if (nrows < 1 || nrows > MAXK) return L_NOT_SUPPORTED;
             const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), false);
-            if (!pl.ok) return L_PLAN_REFUSED;
-            if (pl.total == 0) return L_OK;
-            if (!dispatch_int(IntRange<1, MAXK>(), nrows,
-                              [&](auto k_) { go_norm_apply<decltype(k_)::value>(f, lc, (const E*)bits, rows, lam2, l, (E*)out, n, st); }))
-                return L_BAD_ARG;
-            return launched();
+            return launch_rows(nrows, BELOW_ONE_NOT_SUPPORTED, pl.ok, pl.total == 0, [&](auto k_) {
+                go_norm_apply<decltype(k_)::value>(f, lc, (const E*)bits, rows, lam2, l, (E*)out, n, st);
+            });
         }
     }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,

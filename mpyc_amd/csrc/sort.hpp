@@ -5,7 +5,7 @@
 //   k_cx_diff    out[o, j, i] = a[o, I_j + d, i] - a[o, I_j, i]                       compact (outer, P, inner)
 //   k_cx_apply   h = sum_s lam[s] rows[s][o, j, i];  a[o, I_j, i] += h;  a[o, I_j + d, i] -= h        in place
 // Between the two the caller compares the differences with zero and multiplies the bit by the difference; the rows of
-// k_cx_apply are the sub-shares of that product a party received, so its recombination never goes to memory.
+// k_cx_apply are the sub-shares of that product a party received (share_rows.hpp).
 //
 // Both are streaming kernels over the compact index: one unit per thread, all loads of a unit issued before the first use.
 // A unit is a pack (16 bytes; one 12- or 24-byte element) when runs, compact rows and row pitch are whole packs and the
@@ -15,7 +15,7 @@
 // I and I + d are disjoint: the thread that owns a pair reads and writes both members, nothing synchronises.
 //
 // Memory policy: `a` is read by k_cx_diff, read and written by k_cx_apply and read again by the next stage, the differences
-// feed the comparison at once: default policy.  The sub-share rows are read once: non-temporal loads.
+// feed the comparison at once: default policy.  The sub-share rows: share_rows.hpp.
 #pragma once
 #include "sort_geom.hpp"
 
@@ -50,15 +50,8 @@ __global__ __launch_bounds__(BLOCK) void k_cx_diff(F f, const typename F::elem* 
     }
 }
 
-// the sub-share rows of k_cx_apply and their Lagrange vector (prepared: f.prep)
 template <class F, int K>
-struct CxRows {
-    const typename F::elem* rows[K];
-    typename F::word lam[K];
-};
-
-template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_cx_apply(F f, CxRows<F, K> ra, typename F::elem* __restrict__ a, CxPlan pl) {
+__global__ __launch_bounds__(BLOCK) void k_cx_apply(F f, ShareRows<F, K> ra, typename F::elem* __restrict__ a, CxPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
     typedef typename MemPack<F>::type MP;

@@ -10,8 +10,7 @@
 //   k_tour_unit_expand  v as above;  out[o, n0 + 2j, i] = u[o, n0 + j, i] - v;  out[o, n0 + 2j + 1, i] = v;
 //                       out[o, 0, i] = u[o, 0, i] when n0                                                   full level (outer, k, inner)
 // Between diff and select the caller compares the differences with zero and multiplies the bit by the difference; between
-// unit_prod and unit_expand it re-shares the product.  The rows are the sub-shares a party received, so their recombination
-// never goes to memory.
+// unit_prod and unit_expand it re-shares the product.  The rows are the sub-shares a party received (share_rows.hpp).
 //
 // All four are streaming kernels over the compact index: one unit per thread, all loads of a unit issued before the first
 // use.  A unit is a pack (16 bytes; one 12- or 24-byte element) when runs, compact rows and the bye are whole packs and the
@@ -20,8 +19,8 @@
 // lane L is at first + L, and a wave carries a piece of the bye with all its lanes or with none; the branch that selects the
 // path is a kernel argument (wave-uniform).  The units that carry the bye are the first of a compact row.
 //
-// Memory policy: the levels and the compact outputs are read by the next call: default policy.  The sub-share rows are read
-// once: non-temporal loads.
+// Memory policy: the levels and the compact outputs are read by the next call: default policy.  The sub-share rows:
+// share_rows.hpp.
 #pragma once
 #include "tour_geom.hpp"
 
@@ -55,32 +54,8 @@ __global__ __launch_bounds__(BLOCK) void k_tour_diff(F f, const typename F::elem
     }
 }
 
-// v = sum_j lam[j] rows[j][c] for the pack / the element at compact unit c
 template <class F, int K>
-__device__ __forceinline__ Pack<typename F::word> tour_recombine(const F& f, const CxRows<F, K>& ra, const Pack<typename F::word> (&x)[K]) {
-    typedef Pack<typename F::word> P;
-    P v;
-#pragma unroll
-    for (int q = 0; q < P::N; ++q) {
-        DotAcc<F> s;
-        s.zero(f);
-#pragma unroll
-        for (int j = 0; j < K; ++j) s.mac(f, ra.lam[j], x[j].w[q]);
-        v.w[q] = s.reduce(f);
-    }
-    return v;
-}
-template <class F, int K>
-__device__ __forceinline__ typename F::word tour_recombine_elem(const F& f, const CxRows<F, K>& ra, size_t c) {
-    typename F::acc s;
-    f.acc_zero(s);
-#pragma unroll
-    for (int j = 0; j < K; ++j) f.acc_mac(s, ra.lam[j], ld_elem<F>(ra.rows[j], c));
-    return f.acc_reduce(s);
-}
-
-template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_tour_select(F f, CxRows<F, K> ra, const typename F::elem* __restrict__ a,
+__global__ __launch_bounds__(BLOCK) void k_tour_select(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ a,
                                                         typename F::elem* __restrict__ out, TourPlan pl, int neg) {
     typedef typename F::word W;
     typedef Pack<W> P;
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void k_tour_select(F f, CxRows<F, K> ra, con
                 for (int j = 0; j < K; ++j) x[j] = ldgw_finish(rx[j]);
                 x0 = ldgw_finish(r0);
             }
-            const P v = tour_recombine<F, K>(f, ra, x);
+            const P v = share_rows_pack<F, K>(f, ra, x);
             P y;
 #pragma unroll
             for (int q = 0; q < P::N; ++q) y.w[q] = neg ? f.sub(x0.w[q], v.w[q]) : f.add(x0.w[q], v.w[q]);
@@ -115,7 +90,7 @@ __global__ __launch_bounds__(BLOCK) void k_tour_select(F f, CxRows<F, K> ra, con
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
             const TourAt at = tour_at(pl, g);
-            const W v = tour_recombine_elem<F, K>(f, ra, at.c);
+            const W v = share_rows_elem<F, K>(f, ra, at.c);
             const W x0 = ld_elem<F>(a, at.first);
             st_elem<F>(out, at.half, neg ? f.sub(x0, v) : f.add(x0, v));
             if (at.bye) st_elem<F>(out, at.bye_half, ld_elem<F>(a, at.bye_full));
@@ -152,7 +127,7 @@ __global__ __launch_bounds__(BLOCK) void k_tour_unit_prod(F f, const typename F:
 }
 
 template <class F, int K>
-__global__ __launch_bounds__(BLOCK) void k_tour_unit_expand(F f, CxRows<F, K> ra, const typename F::elem* __restrict__ u,
+__global__ __launch_bounds__(BLOCK) void k_tour_unit_expand(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ u,
                                                              typename F::elem* __restrict__ out, TourPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
@@ -174,7 +149,7 @@ __global__ __launch_bounds__(BLOCK) void k_tour_unit_expand(F f, CxRows<F, K> ra
                 for (int j = 0; j < K; ++j) x[j] = ldgw_finish(rx[j]);
                 x0 = ldgw_finish(r0);
             }
-            const P v = tour_recombine<F, K>(f, ra, x);
+            const P v = share_rows_pack<F, K>(f, ra, x);
             P y;
 #pragma unroll
             for (int q = 0; q < P::N; ++q) y.w[q] = f.sub(x0.w[q], v.w[q]);
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(BLOCK) void k_tour_unit_expand(F f, CxRows<F, K> ra
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
             const TourAt at = tour_at(pl, g);
-            const W v = tour_recombine_elem<F, K>(f, ra, at.c);
+            const W v = share_rows_elem<F, K>(f, ra, at.c);
             const W x0 = ld_elem<F>(u, at.half);
             st_elem<F>(out, at.first, f.sub(x0, v));
             st_elem<F>(out, at.second, v);

@@ -2,7 +2,8 @@
 mpyc_amd/csrc/bits.hpp) against Python integers computed here from the maps include/ffgpu.h states, over every prime
 policy; guard bytes around every output and the rows of G and P a round does not name, status codes, protocols.to_bits
 end to end for all parties on one GPU (the values and bits of tests/golden/bits/to_bits.json included), the same bytes from the
-calls the engine had before (row copies, mul, recombine, add), and one round trip replayed from a captured HIP graph."""
+calls the engine had before (row copies, mul, recombine, add), one round trip replayed from a captured HIP graph, and two
+and nine rows, the edges of the launcher's row dispatch, on both paths of carry_apply."""
 import ctypes
 import random
 
@@ -239,6 +240,38 @@ def test_views_at_odd_element_offsets_and_capped_grid(mods, monkeypatch, name):
                 assert same(ctx.carry_prod(g, pp, l, rho, out=out), want_prod.t), (name, l, n, rho, offset)
                 ctx.carry_apply(g, pp, [put(r, R * n) for r in rows], lam, l, rho)
                 assert same(g, want_g.t) and same(pp, want_p.t), (name, l, n, rho, offset)
+
+
+@pytest.mark.parametrize('name', ['pm64-k64', 'pm128', 'pm192'])
+def test_two_and_nine_rows_on_both_paths(mods, name):
+    """NROWS stops at seven; the launcher of carry_apply dispatches over 1 .. 9 rows, so both edges next to the ends: every
+    round of l = 7 with two and with nine rows over 8-, 16- and 24-byte storage.  n = 64: the pack path (whole waves of
+    24-byte elements); n = 65, and n = 64 one element into the buffers: the element path of 8- and 24-byte elements (a pack
+    of 16-byte elements is one element, aligned at every element offset: they stay on the pack path)"""
+    _ffi, engine, _, _ = mods
+    p = FIELDS[name]
+    ctx = engine.FieldContext(p, device=0)
+    rng = np.random.default_rng(37 + p % 997)
+    l = 7
+    for n, offset in ((64, 0), (65, 0), (64, 1)):
+        def put(vals, count):
+            buf = ctx.empty(count + offset)
+            buf.t[offset:].copy_(ctx.from_ints(vals.reshape(-1)).t)
+            return view(engine, ctx, buf, offset, offset + count)
+        G, P = draw(rng, p, l * n).reshape(l, n), draw(rng, p, l * n).reshape(l, n)
+        lam = [int(x) for x in draw(rng, p, 9)]
+        for rho in range(1, rounds(l) + 1):
+            rc_, rd_ = level(l, rho)
+            R = len(rc_) + len(rd_)
+            rows = [draw(rng, p, R * n).reshape(R, n) for _ in range(9)]
+            drows = [put(r, R * n) for r in rows]
+            keep = [x.t.clone() for x in drows]
+            for nr in (2, 9):
+                g2, p2 = apply_ref(p, G, P, rows[:nr], lam[:nr], rc_, rd_)
+                g, pp = put(G, l * n), put(P, l * n)
+                ctx.carry_apply(g, pp, drows[:nr], lam[:nr], l, rho)
+                assert same(g, ctx.from_ints(g2.reshape(-1)).t) and same(pp, ctx.from_ints(p2.reshape(-1)).t), (name, n, offset, rho, nr)
+            assert all(torch.equal(x.t, t) for x, t in zip(drows, keep)), 'a row was written'
 
 
 @pytest.mark.parametrize('name', ['rc32', 'pm64-k64', 'pm96', 'pm128', 'pm192'])

@@ -3,7 +3,8 @@ mpyc_amd/csrc/find.hpp) against Python integers computed here from the maps incl
 with and without the public leaf, flipped and not, two and three components; views at odd element offsets and a capped grid;
 guard bytes around every output; inputs and table untouched; status codes; the later rounds' apply through ffgpu_tour_select
 on the components as rows; protocols.find end to end for all parties on one GPU, the reference's own values included; a
-round trip through the calls replayed from a captured HIP graph."""
+round trip through the calls replayed from a captured HIP graph; two and nine rows, the edges of the launcher's row
+dispatch, on both paths."""
 import ctypes
 import random
 
@@ -85,7 +86,7 @@ class Data:
             r[:4] = [p - 1, 0, p - 2, 1]
         self.T = draw(rng, p, NT)
         self.T[:3] = [p - 1, 0, 1]
-        self.lam = [int(v) for v in draw(rng, p, max(NROWS))]
+        self.lam = [int(v) for v in draw(rng, p, max(nrows, max(NROWS)))]
         self.lam[0] = 1
         self.dA, self.dT = self._up(self.A), self._up(self.T)
         self.dR = [self._up(r) for r in self.R]
@@ -193,6 +194,23 @@ def test_views_at_odd_element_offsets(mods, name):
     p = FIELDS[name]
     ctx = engine.FieldContext(p, device=0)
     run_all(Data(engine, ctx, p, seed=11 + p % 997, offset=1))
+
+
+@pytest.mark.parametrize('name', ['pm64-k64', 'pm128', 'pm192'])
+def test_two_and_nine_rows_on_both_paths(mods, name):
+    """NROWS stops at seven; the launcher of leaf_apply dispatches over 1 .. 9 rows, so both edges next to the ends, over
+    8-, 16- and 24-byte storage, with and without the public leaf.  (3, 8, 64): the pack path (whole waves of 24-byte
+    elements); (2, 9, 3) and (3, 8, 64) one element into the buffers: the element path of 8- and 24-byte elements (a pack of
+    16-byte elements is one element, aligned at every element offset: they stay on the pack path)"""
+    _ffi, engine, _, _ = mods
+    p = FIELDS[name]
+    ctx = engine.FieldContext(p, device=0)
+    combos = {0: [(0, 3)], 1: [(1, 2)]}
+    for offset, shapes in ((0, ((3, 8, 64), (2, 9, 3))), (1, ((3, 8, 64),))):
+        d = Data(engine, ctx, p, seed=23 + offset + p % 997, na=3 * 8 * 64, nc=3 * 3 * 4 * 64, offset=offset, nrows=9,
+                 nout=3 * 3 * 5 * 64)
+        for outer, k, inner in shapes:
+            assert run_shape(d, outer, k, inner, (0, 1), combos, nrows=(2, 9), levels=()) == 2 * 3
 
 
 @pytest.mark.parametrize('name', ['pm64-k64', 'pm192'])

@@ -3,7 +3,7 @@ mpyc_amd/csrc/sort.hpp) against Python integers computed here from the maps incl
 policy, every stage of several k and four (outer, inner); shapes that reach the pack paths, views at odd element offsets
 and a capped grid; guard bytes around the outputs and the positions cx_apply must not touch; status codes; the same bytes
 as index_select / sub / recombine / add / sub / index_copy_ composed; protocols.sort end to end for all parties on one GPU;
-one stage replayed from a captured HIP graph."""
+one stage replayed from a captured HIP graph; two and nine rows, the edges of the launcher's row dispatch, on both paths."""
 import ctypes
 import random
 
@@ -85,11 +85,12 @@ def run_shape(engine, ctx, p, rng, outer, k, inner, stage_list, offset=0, nrows_
     n = outer * k * inner
     A = edges(draw(rng, p, n), p).reshape(outer, k, inner)
     pmax = max(len(I) for _, _, _, I in stage_list) * outer * inner
-    R = [edges(draw(rng, p, pmax), p) for _ in range(max(NROWS))]
+    row_counts = [nrows_of(s) for s in range(len(stage_list))]
+    R = [edges(draw(rng, p, pmax), p) for _ in range(max(NROWS + tuple(row_counts)))]
     want_d, want_a, lams = [], [], []
     for s, (_, d, _, I) in enumerate(stage_list):
         c = outer * len(I) * inner
-        nr = nrows_of(s)
+        nr = row_counts[s]
         lam = [int(v) for v in draw(rng, p, nr)]
         lams.append(lam)
         want_d.append(diff_ref(p, A, I, d).reshape(-1))
@@ -170,6 +171,21 @@ def test_views_at_odd_element_offsets_and_capped_grid(mods, monkeypatch, name):
     assert outer * (k // 2) * inner // 2 > threads           # more packs of 8-byte elements than threads in the grid
     for offset in (0, 1):
         run_shape(engine, capped, p, rng, outer, k, inner, pick_stages(k), offset=offset, nrows_of=lambda s: (3, 7, 1, 3)[s])
+
+
+@pytest.mark.parametrize('name', ['pm64-k64', 'pm128', 'pm192'])
+def test_two_and_nine_rows_on_both_paths(mods, name):
+    """NROWS stops at seven; the launcher dispatches over 1 .. 9 rows, so both edges next to the ends: every stage of
+    k = 3 with two and with nine rows over 8-, 16- and 24-byte storage.  (2, 3, 64): the pack path (whole waves of 24-byte
+    elements); (1, 3, 3) and (2, 3, 64) one element into the buffers: the element path of 8- and 24-byte elements (a pack
+    of 16-byte elements is one element, aligned at every element offset: they stay on the pack path)"""
+    _ffi, engine, _, _ = mods
+    p = FIELDS[name]
+    ctx = engine.FieldContext(p, device=0)
+    rng = np.random.default_rng(29 + p % 997)
+    for outer, k, inner, offset in ((2, 3, 64, 0), (1, 3, 3, 0), (2, 3, 64, 1)):
+        for nr in (2, 9):
+            assert run_shape(engine, ctx, p, rng, outer, k, inner, stages(k), offset=offset, nrows_of=lambda s: nr) == 3
 
 
 @pytest.mark.parametrize('name', ['rc32', 'pm64-k64', 'pm96', 'pm128', 'pm192'])

@@ -3,7 +3,8 @@ mpyc_amd/csrc/tour.hpp) against Python integers computed here from the maps incl
 policy and both pairings; views at odd element offsets and a capped grid; guard bytes around every output; status codes;
 protocols.amax / amin / argmax / argmin / arg_index / maximum / minimum end to end for all parties on one GPU, the
 reference's own values included; the same bytes as index_select / sub / mul / recombine / add / cat and the Fortran-order
-interleave composed; a round trip through the four calls replayed from a captured HIP graph."""
+interleave composed; a round trip through the four calls replayed from a captured HIP graph; two and nine rows, the edges of the launcher's
+row dispatch, on both paths."""
 import ctypes
 import random
 
@@ -74,15 +75,15 @@ class Data:
     """the inputs of one field, uploaded once `offset` elements into their buffers: a level of NA elements and seven
     sub-share rows of NC; every shape takes prefixes"""
 
-    def __init__(self, engine, ctx, p, seed, na=2 * 5003, nc=5003, offset=0):
+    def __init__(self, engine, ctx, p, seed, na=2 * 5003, nc=5003, offset=0, rows=max(NROWS)):
         rng = np.random.default_rng(seed)
         self.engine, self.ctx, self.p, self.offset, self.nc = engine, ctx, p, offset, nc
         self.A = draw(rng, p, na)
         self.A[:4] = [0, p - 1, 1, p - 2]
-        self.R = [draw(rng, p, nc) for _ in range(max(NROWS))]
+        self.R = [draw(rng, p, nc) for _ in range(rows)]
         for r in self.R:
             r[:4] = [p - 1, 0, p - 2, 1]
-        self.lam = [int(v) for v in draw(rng, p, max(NROWS))]
+        self.lam = [int(v) for v in draw(rng, p, rows)]
         self.lam[0] = 1
         self.dA = self._up(self.A)
         self.dR = [self._up(r) for r in self.R]
@@ -173,6 +174,21 @@ def test_views_at_odd_element_offsets_and_capped_grid(mods, monkeypatch, name):
     for offset in (0, 1):
         big = Data(engine, capped, p, seed=17 + offset, na=outer * k * inner, nc=c, offset=offset)
         run_shape(big, outer, k, inner, nrows=(3,))
+
+
+@pytest.mark.parametrize('name', ['pm64-k64', 'pm128', 'pm192'])
+def test_two_and_nine_rows_on_both_paths(mods, name):
+    """NROWS stops at seven; the launcher of select and unit_expand dispatches over 1 .. 9 rows, so both edges next to the
+    ends, over 8-, 16- and 24-byte storage.  (3, 8, 64): the pack path (whole waves of 24-byte elements); (2, 9, 3) and
+    (3, 8, 64) one element into the buffers: the element path of 8- and 24-byte elements (a pack of 16-byte elements is one
+    element, aligned at every element offset: they stay on the pack path)"""
+    _ffi, engine, _, _ = mods
+    p = FIELDS[name]
+    ctx = engine.FieldContext(p, device=0)
+    for offset, shapes in ((0, ((3, 8, 64), (2, 9, 3))), (1, ((3, 8, 64),))):
+        d = Data(engine, ctx, p, seed=23 + offset + p % 997, na=3 * 8 * 64, nc=3 * 4 * 64, offset=offset, rows=9)
+        for shape in shapes:
+            assert run_shape(d, *shape, nrows=(2, 9)) == 2 * 2 * 3 + 1 + 2
 
 
 @pytest.mark.parametrize('name', ['rc32', 'pm64-k64', 'pm96', 'pm128', 'pm192'])

@@ -1,6 +1,6 @@
 """Per-kernel comparison of the gfx950 code objects of two builds of the library (no GPU needed).
 
-    python tools/kernel_diff.py PARENT_OBJ_DIR NEW_OBJ_DIR [unit ...]
+    python tools/kernel_diff.py [--rename OLD=NEW] PARENT_OBJ_DIR NEW_OBJ_DIR [unit ...]
 
 The directories hold the object files of `make -C mpyc_amd/csrc` (build/ffgpu/*.o).  For every translation unit the
 device code is taken out of .hip_fatbin (llvm-objcopy, clang-offload-bundler) and compared kernel by kernel:
@@ -9,6 +9,9 @@ kernarg size).  Prints kernels before -> after, the kernels removed and added, t
 the metadata and the instruction count before -> after), and apart from them, not counted as changed:
   * those whose only difference is the PC-relative distance to a callee that was not inlined;
   * those with the same instructions in another order: the sorted instruction lines and all metadata are equal.
+--rename OLD=NEW: a type that appears in the kernels' mangled names was renamed and nothing else; OLD is replaced by NEW in
+the parent's names (both as mangled, with their length prefix: 6CxRows=9ShareRows) so that the kernels pair up by the rest of
+the name instead of showing as removed and added (profiles/r20_share_rows.md).
 A refactor of the host side must show 0 added and 0 changed (profiles/r10_host_layer.md); a refactor of the kernel source may
 show changed kernels only among the templates it touched (profiles/r11_streaming_shape.md)."""
 import glob
@@ -73,8 +76,13 @@ def metadata(co):
 
 
 def main():
-    pd, nd = sys.argv[1], sys.argv[2]
-    units = sys.argv[3:] or sorted(os.path.basename(f)[:-2] for f in glob.glob(os.path.join(pd, '*.o')))
+    args, old, new = sys.argv[1:], None, None
+    if args[0] == '--rename':
+        old, new = args[1].split('=')
+        args = args[2:]
+    renamed = lambda d: {(k.replace(old, new) if old else k): v for k, v in d.items()}
+    pd, nd = args[0], args[1]
+    units = args[2:] or sorted(os.path.basename(f)[:-2] for f in glob.glob(os.path.join(pd, '*.o')))
     total, bad = [0, 0], 0
     with tempfile.TemporaryDirectory() as tmp:
         for u in units:
@@ -82,7 +90,7 @@ def main():
             if a is None or b is None:
                 print(f'{u}: no device code')
                 continue
-            ca, cb, ma, mb = code(a), code(b), metadata(a), metadata(b)
+            ca, cb, ma, mb = renamed(code(a)), code(b), renamed(metadata(a)), metadata(b)
             removed, added = sorted(set(ma) - set(mb)), sorted(set(mb) - set(ma))
             differ = [k for k in ca if k in cb and ca[k][1] != cb[k][1]]
             reordered = [k for k in differ if ca[k][2] == cb[k][2] and ma.get(k) == mb.get(k)]
