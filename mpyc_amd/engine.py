@@ -340,6 +340,35 @@ class FieldContext:
             if a.n != n:
                 raise ValueError(f'{what} has {a.n} elements, expected {n}')
 
+    def _out(self, n: int, out: Optional[DevArray], what: str = 'output') -> DevArray:
+        """The caller's output, checked as an operand of n elements, or a fresh array.  The test is `is None`: an empty
+        DevArray is falsy, and the caller gets back the object it passed."""
+        if out is None:
+            return self.empty(n)
+        self._same(n, out, what=what)
+        return out
+
+    def _rows(self, rows: Sequence[DevArray], lambdas: Sequence[int], n: int, what: str):
+        """(nrows, row pointers, lambdas) of the sub-share rows an apply end recombines: rows of n elements each, one lambda
+        per row."""
+        args = self._rec_args(rows, lambdas, 1)
+        self._same(n, *rows, what=what)
+        return args
+
+    def _axis(self, what: str, a: DevArray, outer: int, k: int, inner: int, kmin: int = 1, na: Optional[int] = None,
+              stack: int = 1):
+        """An (outer, k, inner) call with k >= kmin whose operand is `stack` contiguous (outer, na, inner) arrays (na = k by
+        default)."""
+        if outer < 1 or k < kmin or inner < 1:
+            raise ValueError(f'{what}: outer and inner must be at least 1, k at least {kmin}')
+        self._same(stack * outer * (k if na is None else na) * inner, a, what=f'{what} operand')
+
+    def _bit_matrix(self, what: str, x: DevArray, l: int, lmin: int = 1) -> int:
+        """n of the (l, n) or (n, l) bit matrix x, l >= lmin"""
+        if l < lmin or x.n % l:
+            raise ValueError(f'{what}: the operand is not a bit matrix of l >= {lmin} bits per element')
+        return x.n // l
+
     def _out_matrix(self, out: Optional[DevMatrix], rows: int, n: int) -> DevMatrix:
         if out is None:
             return self.empty_matrix(rows, n)
@@ -349,8 +378,8 @@ class FieldContext:
 
     # ---- element-wise -----------------------------------------------------
     def _ew2(self, fn, a: DevArray, b: DevArray, out: Optional[DevArray]) -> DevArray:
-        self._same(a.n, b, out)
-        out = out or self.empty(a.n)
+        self._same(a.n, b)
+        out = self._out(a.n, out)
         _ffi.check(fn(self._h, a.ptr, b.ptr, out.ptr, a.n, self._stream()), fn.__name__)
         return out
 
@@ -364,20 +393,17 @@ class FieldContext:
         return self._ew2(self._L.ffgpu_mul, a, b, out)
 
     def neg(self, a, out=None):
-        self._same(a.n, out, what='output')
-        out = out or self.empty(a.n)
+        out = self._out(a.n, out)
         _ffi.check(self._L.ffgpu_neg(self._h, a.ptr, out.ptr, a.n, self._stream()), 'neg')
         return out
 
     def reduce(self, raw: DevArray, out=None):
-        self._same(raw.n, out, what='output')
-        out = out or self.empty(raw.n)
+        out = self._out(raw.n, out)
         _ffi.check(self._L.ffgpu_reduce(self._h, raw.ptr, out.ptr, raw.n, self._stream()), 'reduce')
         return out
 
     def _ews(self, fn, a, scalar: int, out):
-        self._same(a.n, out, what='output')
-        out = out or self.empty(a.n)
+        out = self._out(a.n, out)
         _ffi.check(fn(self._h, a.ptr, _ffi.limbs(scalar, self.scalar_limbs), out.ptr, a.n, self._stream()), fn.__name__)
         return out
 
@@ -391,8 +417,8 @@ class FieldContext:
         return self._ews(self._L.ffgpu_rsub_scalar, a, s, out)
 
     def muladd(self, a, b, c, out=None):
-        self._same(a.n, b, c, out)
-        out = out or self.empty(a.n)
+        self._same(a.n, b, c)
+        out = self._out(a.n, out)
         _ffi.check(self._L.ffgpu_muladd(self._h, a.ptr, b.ptr, c.ptr, out.ptr, a.n, self._stream()), 'muladd')
         return out
 
@@ -400,16 +426,14 @@ class FieldContext:
         """a ** e for a public exponent 0 <= e < 2^128, one kernel (finfields.py:1159-1187)."""
         if e < 0 or e >> 192:
             raise ValueError('exponent out of range')
-        self._same(a.n, out, what='output')
-        out = out or self.empty(a.n)
+        out = self._out(a.n, out)
         _ffi.check(self._L.ffgpu_pow(self._h, a.ptr, _ffi.limbs(e, 3), 3, out.ptr, a.n, self._stream()), 'pow')
         return out
 
     def inv(self, a, out=None, check_zero: bool = True):
         """Element-wise inverse (batched, one kernel).  Raises ZeroDivisionError like the reference
         if any element is zero (costs one device->host flag read); check_zero=False skips that."""
-        self._same(a.n, out, what='output')
-        out = out or self.empty(a.n)
+        out = self._out(a.n, out)
         flag = torch.zeros(1, dtype=torch.int32, device=self.torch_device) if check_zero else None
         _ffi.check(self._L.ffgpu_inv(self._h, a.ptr, out.ptr, a.n, flag.data_ptr() if check_zero else None,
                                      self._stream()), 'inv')
@@ -419,8 +443,8 @@ class FieldContext:
 
     def beaver_combine(self, z, x, y, d, e, add_de: bool, out=None):
         """z + d*y + e*x (+ d*e): local step of Beaver multiplication (not a reference function; see ffgpu.h)."""
-        self._same(z.n, x, y, d, e, out)
-        out = out or self.empty(z.n)
+        self._same(z.n, x, y, d, e)
+        out = self._out(z.n, out)
         _ffi.check(self._L.ffgpu_beaver_combine(self._h, z.ptr, x.ptr, y.ptr, d.ptr, e.ptr, int(bool(add_de)), out.ptr,
                                                 z.n, self._stream()), 'beaver_combine')
         return out
@@ -508,11 +532,7 @@ class FieldContext:
         import secrets as _secrets
         n = rows_a[0].n
         ka, pa, la = self._rec_args(rows_a, lam_a, 1)
-        if rows_b:
-            kb, pb, lb = self._rec_args(rows_b, lam_b, 1)
-        else:
-            kb, pb, lb = 0, None, None
-        self._same(n, *(rows_b or ()), what='share row')
+        kb, pb, lb = self._rows(rows_b, lam_b, n, 'share row') if rows_b else (0, None, None)
         out = self._out_matrix(out, m, n)
         if state is None and key is None:
             key = _secrets.token_bytes(32)
@@ -538,11 +558,7 @@ class FieldContext:
         if nbatch < 1 or out_rows_per_party < nbatch or out.rows < m * out_rows_per_party or out.n != n:
             raise ValueError('output block does not hold m x nbatch share rows of n elements')
         ka, pa, la = self._rec_args(rows_a, lam_a, 1)
-        if rows_b:
-            kb, pb, lb = self._rec_args(rows_b, lam_b, 1)
-            self._same(n, *rows_b, what='share row')
-        else:
-            kb, pb, lb = 0, None, None
+        kb, pb, lb = self._rows(rows_b, lam_b, n, 'share row') if rows_b else (0, None, None)
         if state is None and key is None:
             key = _secrets.token_bytes(32)
         defer = 0
@@ -570,8 +586,7 @@ class FieldContext:
         k, ptrs, lam = self._rec_args(rows, lambdas, w)
         n = rows[0].n
         if w == 1:
-            self._same(n, out, what='output')
-            out = out or self.empty(n)
+            out = self._out(n, out)
             stride = n
         else:
             out = self._out_matrix(out, w, n)
@@ -603,12 +618,11 @@ class FieldContext:
         if A.n != M * K or B.n != K * N:
             raise ValueError('matmul: operand sizes do not match the shapes')
         if out is not None:
-            self._same(M * N, out, what='matmul output')
             eb = self.elem_bytes
             for x in (A, B):                       # C is written while other tiles still read A and B
                 if out.ptr < x.ptr + x.n * eb and x.ptr < out.ptr + out.n * eb:
                     raise ValueError('matmul: the output overlaps an operand')
-        out = out or self.empty(M * N)
+        out = self._out(M * N, out, 'matmul output')
         _ffi.check(self._L.ffgpu_matmul(self._h, A.ptr, K, B.ptr, N, out.ptr, N, M, K, N, self._stream()), 'matmul')
         return out
 
@@ -627,12 +641,11 @@ class FieldContext:
                 raise ValueError('matmul_stack: operand sizes do not match the shapes')
         n = batch * M * N
         if out is not None:
-            self._same(n, out, what='matmul_stack output')
             eb = self.elem_bytes
             for x in (A, B):                       # matrices of C are written while others still read A and B
                 if out.ptr < x.ptr + x.n * eb and x.ptr < out.ptr + out.n * eb:
                     raise ValueError('matmul_stack: the output overlaps an operand')
-        out = out or self.empty(n)
+        out = self._out(n, out, 'matmul_stack output')
         _ffi.check(self._L.ffgpu_matmul_stack(self._h, A.ptr, K, a_stride, B.ptr, N, b_stride, out.ptr, N, M * N,
                                               M, K, N, batch, self._stream()), 'matmul_stack')
         return out
@@ -646,9 +659,7 @@ class FieldContext:
         n = a.n + v.n - 1
         self._same(a.n, a, what='convolve operand')
         self._same(v.n, v, what='convolve operand')
-        if out is not None:
-            self._same(n, out, what='convolve output')
-        out = out or self.empty(n)
+        out = self._out(n, out, 'convolve output')
         _ffi.check(self._L.ffgpu_convolve(self._h, a.ptr, a.n, v.ptr, v.n, out.ptr, self._stream()), 'convolve')
         return out
 
@@ -667,16 +678,13 @@ class FieldContext:
 
     def _scan_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, nout: int, out: Optional[DevArray],
                    in_place_ok: bool):
-        if outer < 1 or k < 1 or inner < 1:
-            raise ValueError(f'{what}: outer, k and inner must be at least 1')
-        self._same(outer * k * inner, a, what=f'{what} operand')
+        self._axis(what, a, outer, k, inner)
         if out is not None:
-            self._same(nout, out, what=f'{what} output')
             eb = self.elem_bytes
             if not (in_place_ok and out.ptr == a.ptr):    # tiles / columns are written while others are still read
                 if out.ptr < a.ptr + a.n * eb and a.ptr < out.ptr + out.n * eb:
                     raise ValueError(f'{what}: the output overlaps the operand')
-        return out or self.empty(nout)
+        return self._out(nout, out, f'{what} output')
 
     def scan(self, a: DevArray, outer: int, k: int, inner: int, mul: bool = False, with_initial: bool = False,
              out: Optional[DevArray] = None) -> DevArray:
@@ -705,9 +713,9 @@ class FieldContext:
         """masked[h] = a[h] + 2^l + sum_i rbits[h*l+i] 2^(l-1-i) + rdivl[h] 2^l, the value np_sgn opens
         (runtime.py:3649-3657).  rbits: n*l bit shares, element-major, most significant bit first."""
         n = a.n
-        self._same(n, rdivl, out, what='sgn_mask operand')
+        self._same(n, rdivl, what='sgn_mask operand')
         self._same(n * l, rbits, what='sgn_mask bit shares')
-        out = out or self.empty(n)
+        out = self._out(n, out, 'sgn_mask output')
         _ffi.check(self._L.ffgpu_sgn_mask(self._h, a.ptr, rbits.ptr, rdivl.ptr, l, out.ptr, n, self._stream()), 'sgn_mask')
         return out
 
@@ -733,8 +741,8 @@ class FieldContext:
         """lt[h] = (z[h] + ((1 - 2 [w[h] == 0]) (2 sbit[h] - 1) + 3) 2^(l-1)) 2^-l: the share of [a < 0] from the
         opened masked product w (runtime.py:3674-3676)."""
         n = w.n
-        self._same(n, sbit, z, out, what='sgn_finish operand')
-        out = out or self.empty(n)
+        self._same(n, sbit, z, what='sgn_finish operand')
+        out = self._out(n, out, 'sgn_finish output')
         _ffi.check(self._L.ffgpu_sgn_finish(self._h, w.ptr, sbit.ptr, z.ptr, l, out.ptr, n, self._stream()), 'sgn_finish')
         return out
 
@@ -747,11 +755,9 @@ class FieldContext:
         return int(self._L.ffgpu_cx_pairs(k, p, d, r))
 
     def _cx_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, p: int, d: int, r: int) -> int:
-        if outer < 1 or k < 1 or inner < 1:
-            raise ValueError(f'{what}: outer, k and inner must be at least 1')
+        self._axis(what, a, outer, k, inner)
         if min(p, d, r) < 0:
             raise ValueError(f'{what}: ({p}, {d}, {r}) is not a stage')
-        self._same(outer * k * inner, a, what=f'{what} operand')
         return self.cx_pairs(k, p, d, r)
 
     def cx_diff(self, a: DevArray, outer: int, k: int, inner: int, p: int, d: int, r: int,
@@ -759,10 +765,7 @@ class FieldContext:
         """out[o, j, i] = a[o, I_j + d, i] - a[o, I_j, i] over the contiguous (outer, k, inner) array `a`, I the index set of
         stage (p, d, r): the compact (outer, P, inner) differences np_sort compares with zero (runtime.py:1764-1767)."""
         P = self._cx_args('cx_diff', a, outer, k, inner, p, d, r)
-        nout = outer * P * inner
-        if out is not None:
-            self._same(nout, out, what='cx_diff output')
-        out = out or self.empty(nout)
+        out = self._out(outer * P * inner, out, 'cx_diff output')
         _ffi.check(self._L.ffgpu_cx_diff(self._h, a.ptr, out.ptr, outer, k, inner, p, d, r, self._stream()), 'cx_diff')
         return out
 
@@ -772,8 +775,7 @@ class FieldContext:
         (outer, P, inner) rows: the exchange of np_sort (runtime.py:1768-1770) with the recombination of the re-shared
         product folded in.  Returns a."""
         P = self._cx_args('cx_apply', a, outer, k, inner, p, d, r)
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(outer * P * inner, *rows, what='cx_apply row')
+        nrows, ptrs, lam = self._rows(rows, lambdas, outer * P * inner, 'cx_apply row')
         _ffi.check(self._L.ffgpu_cx_apply(self._h, a.ptr, ptrs, lam, nrows, outer, k, inner, p, d, r, self._stream()),
                    'cx_apply')
         return a
@@ -805,9 +807,9 @@ class FieldContext:
         """masked[h] = a[h] + offset + rdivl[h] 2^l - sum_k rbits[h*l+k] 2^k, the value np_to_bits opens
         (runtime.py:4414-4415, 4446).  rbits: n*l bit shares, element-major, least significant bit first."""
         n = a.n
-        self._same(n, rdivl, out, what='bits_mask operand')
+        self._same(n, rdivl, what='bits_mask operand')
         self._same(n * l, rbits, what='bits_mask bit shares')
-        out = out or self.empty(n)
+        out = self._out(n, out, 'bits_mask output')
         _ffi.check(self._L.ffgpu_bits_mask(self._h, a.ptr, rbits.ptr, rdivl.ptr, self._scalars([int(offset) % self.modulus]), l,
                                            out.ptr, n, self._stream()), 'bits_mask')
         return out
@@ -824,13 +826,9 @@ class FieldContext:
     def carry_prod(self, g: DevArray, p: DevArray, l: int, round: int, out: Optional[DevArray] = None) -> DevArray:
         """The local products of a round, compact (R, n): G[q_j] P[k_j] for the c-rows, then P[q_j] P[k_j] for the d-rows
         (runtime.py:4320-4325)."""
-        if l < 1 or g.n % l:
-            raise ValueError('carry_prod: G is not (l, n)')
-        n = g.n // l
+        n = self._bit_matrix('carry_prod', g, l)
         self._same(l * n, p, what='carry_prod operand')
-        R = self.carry_rows(l, round)
-        self._same(R * n, out, what='carry_prod output')
-        out = out or self.empty(R * n)
+        out = self._out(self.carry_rows(l, round) * n, out, 'carry_prod output')
         _ffi.check(self._L.ffgpu_carry_prod(self._h, g.ptr, p.ptr, l, round, out.ptr, n, self._stream()), 'carry_prod')
         return out
 
@@ -838,13 +836,9 @@ class FieldContext:
         """G[k_j] += v for the c-rows, P[k_j] = v for the d-rows, in place, with v = sum_s lambdas[s] * rows[s] over the compact
         (R, n) rows: the merge of np_add_bits (runtime.py:4320-4325) with the recombination of the re-shared products folded
         in.  Returns (g, p)."""
-        if l < 1 or g.n % l:
-            raise ValueError('carry_apply: G is not (l, n)')
-        n = g.n // l
+        n = self._bit_matrix('carry_apply', g, l)
         self._same(l * n, p, what='carry_apply operand')
-        R = self.carry_rows(l, round)
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(R * n, *rows, what='carry_apply row')
+        nrows, ptrs, lam = self._rows(rows, lambdas, self.carry_rows(l, round) * n, 'carry_apply row')
         _ffi.check(self._L.ffgpu_carry_apply(self._h, g.ptr, p.ptr, ptrs, lam, nrows, l, round, n, self._stream()),
                    'carry_apply')
         return g, p
@@ -853,8 +847,8 @@ class FieldContext:
         """out[h*l+k] = rbits[h*l+k] + cb_k - 2 G[k*n+h] + G[(k-1)*n+h]: the shares of the bits, element-major
         (runtime.py:4332-4334)."""
         n = c.n
-        self._same(n * l, rbits, g, out, what='bits_finish operand')
-        out = out or self.empty(n * l)
+        self._same(n * l, rbits, g, what='bits_finish operand')
+        out = self._out(n * l, out, 'bits_finish output')
         _ffi.check(self._L.ffgpu_bits_finish(self._h, c.ptr, rbits.ptr, g.ptr, l, out.ptr, n, self._stream()), 'bits_finish')
         return out
 
@@ -864,24 +858,17 @@ class FieldContext:
     TOUR_HALVES, TOUR_ODD_EVEN = 0, 1
 
     def _tour_args(self, what: str, a: DevArray, na: int, outer: int, k: int, inner: int, mode: int):
-        if outer < 1 or k < 2 or inner < 1:
-            raise ValueError(f'{what}: outer and inner must be at least 1, k at least 2')
+        self._axis(what, a, outer, k, inner, kmin=2, na=na)
         if mode not in (self.TOUR_HALVES, self.TOUR_ODD_EVEN):
             raise ValueError(f'{what}: unknown pairing {mode}')
-        self._same(outer * na * inner, a, what=f'{what} operand')
         return k // 2, k // 2 + k % 2
-
-    def _tour_out(self, what: str, n: int, out: Optional[DevArray]) -> DevArray:
-        if out is not None:
-            self._same(n, out, what=f'{what} output')
-        return out if out is not None else self.empty(n)
 
     def tour_diff(self, a: DevArray, outer: int, k: int, inner: int, mode: int, neg: bool = False,
                   out: Optional[DevArray] = None) -> DevArray:
         """out[o, j, i] = a[o, second_j, i] - a[o, first_j, i] (neg: first - second) over the contiguous (outer, k, inner)
         array `a`: the compact (outer, h, inner) differences a round compares with zero (runtime.py:3415-3416, 3935-3936)."""
         h, _ = self._tour_args('tour_diff', a, k, outer, k, inner, mode)
-        out = self._tour_out('tour_diff', outer * h * inner, out)
+        out = self._out(outer * h * inner, out, 'tour_diff output')
         _ffi.check(self._L.ffgpu_tour_diff(self._h, a.ptr, out.ptr, outer, k, inner, mode, 1 if neg else 0, self._stream()),
                    'tour_diff')
         return out
@@ -893,9 +880,8 @@ class FieldContext:
         odd: the survivors of a round (runtime.py:3416-3418, 3938-3940) with the recombination of the re-shared product
         folded in."""
         h, kc = self._tour_args('tour_select', a, k, outer, k, inner, mode)
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(outer * h * inner, *rows, what='tour_select row')
-        out = self._tour_out('tour_select', outer * kc * inner, out)
+        nrows, ptrs, lam = self._rows(rows, lambdas, outer * h * inner, 'tour_select row')
+        out = self._out(outer * kc * inner, out, 'tour_select output')
         _ffi.check(self._L.ffgpu_tour_select(self._h, a.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, mode, 1 if neg else 0,
                                              self._stream()), 'tour_select')
         return out
@@ -905,7 +891,7 @@ class FieldContext:
         argmax, u the child level's (outer, kc, inner) unit vectors, c this level's comparison bits (runtime.py:3943-3944)."""
         h, kc = self._tour_args('tour_unit_prod', u, k // 2 + k % 2, outer, k, inner, self.TOUR_HALVES)
         self._same(outer * h * inner, c, what='tour_unit_prod bits')
-        out = self._tour_out('tour_unit_prod', outer * h * inner, out)
+        out = self._out(outer * h * inner, out, 'tour_unit_prod output')
         _ffi.check(self._L.ffgpu_tour_unit_prod(self._h, u.ptr, c.ptr, out.ptr, outer, k, inner, self._stream()), 'tour_unit_prod')
         return out
 
@@ -915,9 +901,8 @@ class FieldContext:
         u[o, n0 + j, i] - v, out[o, n0 + 2j + 1, i] = v with v = sum_s lambdas[s] * rows[s] over the compact rows, and
         out[o, 0, i] = u[o, 0, i] when k is odd (runtime.py:3945-3948) with the recombination of u * c folded in."""
         h, kc = self._tour_args('tour_unit_expand', u, k // 2 + k % 2, outer, k, inner, self.TOUR_ODD_EVEN)
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(outer * h * inner, *rows, what='tour_unit_expand row')
-        out = self._tour_out('tour_unit_expand', outer * k * inner, out)
+        nrows, ptrs, lam = self._rows(rows, lambdas, outer * h * inner, 'tour_unit_expand row')
+        out = self._out(outer * k * inner, out, 'tour_unit_expand output')
         _ffi.check(self._L.ffgpu_tour_unit_expand(self._h, u.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, self._stream()),
                    'tour_unit_expand')
         return out
@@ -928,16 +913,12 @@ class FieldContext:
     FIND_MAX_VALUES = 4
 
     def _find_args(self, what: str, a: DevArray, outer: int, k: int, inner: int, ncomp: int, flip: int, virt: int, leaf: bool):
-        if outer < 1 or k < 1 or inner < 1:
-            raise ValueError(f'{what}: outer, k and inner must be at least 1')
         if not 2 <= ncomp <= 1 + self.FIND_MAX_VALUES:
             raise ValueError(f'{what}: 2 to {1 + self.FIND_MAX_VALUES} components')
         if flip not in (0, 1) or virt not in (0, 1):
             raise ValueError(f'{what}: flip and virt are 0 or 1')
+        self._axis(what, a, outer, k, inner, kmin=2 - virt, stack=1 if leaf else ncomp)     # a round needs two positions
         kv = k + virt
-        if kv < 2:
-            raise ValueError(f'{what}: a round needs two positions')
-        self._same((1 if leaf else ncomp) * outer * k * inner, a, what=f'{what} operand')
         return kv, kv // 2, kv // 2 + kv % 2
 
     def find_table(self, k: int, cs0: Sequence, cs1: Sequence, fe=None) -> DevArray:
@@ -968,7 +949,7 @@ class FieldContext:
         virt (runtime.py:4679-4684)."""
         kv, h, _ = self._find_args('find_leaf_prod', bits, outer, k, inner, ncomp, flip, virt, True)
         self._same((ncomp - 1) * 2 * kv, tab, what='find_leaf_prod table')
-        out = self._tour_out('find_leaf_prod', ncomp * outer * h * inner, out)
+        out = self._out(ncomp * outer * h * inner, out, 'find_leaf_prod output')
         _ffi.check(self._L.ffgpu_find_leaf_prod(self._h, bits.ptr, tab.ptr, out.ptr, outer, k, inner, ncomp, flip, virt,
                                                 self._stream()), 'find_leaf_prod')
         return out
@@ -980,9 +961,8 @@ class FieldContext:
         when kv is odd (runtime.py:4684) with the recombination of the re-shared product folded in."""
         kv, h, kc = self._find_args('find_leaf_apply', bits, outer, k, inner, ncomp, flip, virt, True)
         self._same((ncomp - 1) * 2 * kv, tab, what='find_leaf_apply table')
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(ncomp * outer * h * inner, *rows, what='find_leaf_apply row')
-        out = self._tour_out('find_leaf_apply', ncomp * outer * kc * inner, out)
+        nrows, ptrs, lam = self._rows(rows, lambdas, ncomp * outer * h * inner, 'find_leaf_apply row')
+        out = self._out(ncomp * outer * kc * inner, out, 'find_leaf_apply output')
         _ffi.check(self._L.ffgpu_find_leaf_apply(self._h, bits.ptr, tab.ptr, ptrs, lam, nrows, out.ptr, outer, k, inner, ncomp, flip,
                                                  virt, self._stream()), 'find_leaf_apply')
         return out
@@ -992,7 +972,7 @@ class FieldContext:
         outer, h, inner), for a stored level (ncomp, outer, k, inner), k >= 2: the local product of a later round
         (runtime.py:4683-4684).  Its apply is tour_select on (ncomp * outer, k, inner) with TOUR_ODD_EVEN."""
         _, h, _ = self._find_args('find_prod', level, outer, k, inner, ncomp, 0, 0, False)
-        out = self._tour_out('find_prod', ncomp * outer * h * inner, out)
+        out = self._out(ncomp * outer * h * inner, out, 'find_prod output')
         _ffi.check(self._L.ffgpu_find_prod(self._h, level.ptr, out.ptr, outer, k, inner, ncomp, self._stream()), 'find_prod')
         return out
 
@@ -1004,10 +984,9 @@ class FieldContext:
         np_trunc opens (runtime.py:860-861, 869-870).  rbits: n*f bit shares, element-major, least significant bit first; ar
         is what trunc_finish subtracts the opened low bits from."""
         n = a.n
-        self._same(n, rdivf, ar_out, out, what='trunc_mask operand')
+        self._same(n, rdivf, ar_out, out, what='trunc_mask operand')      # both outputs before either is allocated
         self._same(n * f, rbits, what='trunc_mask bit shares')
-        ar_out = ar_out or self.empty(n)
-        out = out or self.empty(n)
+        ar_out, out = self._out(n, ar_out), self._out(n, out)
         _ffi.check(self._L.ffgpu_trunc_mask(self._h, a.ptr, rbits.ptr, rdivf.ptr, self._scalars([int(offset) % self.modulus]), f,
                                             ar_out.ptr, out.ptr, n, self._stream()), 'trunc_mask')
         return ar_out, out
@@ -1018,10 +997,8 @@ class FieldContext:
         shares of the truncated values (runtime.py:871-872) with the opening of the masked shares folded in, so the opened
         value never goes to memory.  rows = [c], lambdas = [1] takes a c that is already open."""
         n = ar.n
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(n, *rows, what='trunc_finish row')
-        self._same(n, out, what='trunc_finish output')
-        out = out or self.empty(n)
+        nrows, ptrs, lam = self._rows(rows, lambdas, n, 'trunc_finish row')
+        out = self._out(n, out, 'trunc_finish output')
         _ffi.check(self._L.ffgpu_trunc_finish(self._h, ptrs, lam, nrows, ar.ptr, f, out.ptr, n, self._stream()), 'trunc_finish')
         return out
 
@@ -1031,12 +1008,9 @@ class FieldContext:
         sign bit of the element-major (n, l) bits of bits_finish: the local product of (1 - 2s), s = 1 - x_top, with the bits
         below the sign bit, most significant first (runtime.py:4723-4725, the local part of :4636).  sign[h] = 1 - 2 x_top =
         2s - 1, or None with want_sign=False."""
-        if l < 2 or bits.n % l:
-            raise ValueError('norm_prod: the bits are not (n, l), l >= 2')
-        n = bits.n // l
-        self._same(n * (l - 1), out, what='norm_prod output')
+        n = self._bit_matrix('norm_prod', bits, l, 2)
         self._same(n, sign_out, what='norm_prod sign output')
-        out = out or self.empty(n * (l - 1))
+        out = self._out(n * (l - 1), out, 'norm_prod output')
         if want_sign and sign_out is None:
             sign_out = self.empty(n)
         _ffi.check(self._L.ffgpu_norm_prod(self._h, bits.ptr, l, out.ptr, sign_out.ptr if sign_out is not None else None, n,
@@ -1048,19 +1022,15 @@ class FieldContext:
         """out[h*(l-1)+j] = 1 - x_top + v with v = sum_s lambdas[s] * rows[s] over the compact (n, l-1) rows: s + (1 - 2s) x as
         a dense (n, l-1, 1) array, which find_leaf_prod / find_leaf_apply search for its first 0 (the rest of runtime.py:4636)
         with the recombination of the re-shared product folded in."""
-        if l < 2 or bits.n % l:
-            raise ValueError('norm_apply: the bits are not (n, l), l >= 2')
-        n = bits.n // l
-        nrows, ptrs, lam = self._rec_args(rows, lambdas, 1)
-        self._same(n * (l - 1), *rows, what='norm_apply row')
-        self._same(n * (l - 1), out, what='norm_apply output')
-        out = out or self.empty(n * (l - 1))
+        n = self._bit_matrix('norm_apply', bits, l, 2)
+        nrows, ptrs, lam = self._rows(rows, lambdas, n * (l - 1), 'norm_apply row')
+        out = self._out(n * (l - 1), out, 'norm_apply output')
         _ffi.check(self._L.ffgpu_norm_apply(self._h, bits.ptr, ptrs, lam, nrows, l, out.ptr, n, self._stream()), 'norm_apply')
         return out
 
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
-        out = out or self.empty(a.n)
+        out = self._out(a.n, out)
         _ffi.check(self._L.ffgpu_sqrt_cl(self._h, a.ptr, out.ptr, a.n, self._stream()), 'sqrt_cl')
         return out
 
@@ -1084,7 +1054,7 @@ class FieldContext:
         if x.n % g:
             raise ValueError('array length is not a multiple of the group size')
         ng = x.n // g
-        out = out or self.empty(ng * r)
+        out = self._out(ng * r, out)
         m = self._scalars([v for row in matrix for v in row])
         b = self._scalars(bias) if bias is not None else None
         _ffi.check(self._L.ffgpu_group_matvec(self._h, m, b, r, g, x.ptr, out.ptr, ng, self._stream()), 'group_matvec')
@@ -1218,7 +1188,7 @@ class FieldContext:
         ks = len(streams)
         if len(weights) != ks * d:
             raise ValueError('need ks*d weights')
-        out = out or self.empty(n)
+        out = self._out(n, out)
         devs = []
         for sbytes in streams:
             if isinstance(sbytes, torch.Tensor):
@@ -1244,7 +1214,7 @@ class FieldContext:
         ks = len(keys40)
         if len(weights) != ks * d or any(len(k_) != 40 for k_ in keys40):
             raise ValueError('need ks 40-byte stream keys and ks*d weights')
-        out = out or self.empty(n)
+        out = self._out(n, out)
         w = self._scalars(weights)
         kb = ctypes.create_string_buffer(b''.join(bytes(k_) for k_ in keys40), 40 * ks)
         _ffi.check(self._L.ffgpu_prss_chacha(self._h, ctypes.cast(kb, ctypes.POINTER(ctypes.c_uint8)), ks, d, l, mask_bits,
@@ -1258,7 +1228,7 @@ class FieldContext:
         if bits.n % 8:
             raise ValueError('bit array length must be a multiple of 8')
         ng = bits.n // 8
-        out = out or self.empty(ng if from_bits else bits.n)
+        out = self._out(ng if from_bits else bits.n, out)
         m = (ctypes.c_uint64 * 128)()
         for i, v in enumerate(v for row in matrix for v in row):
             m[2 * i] = int(v)
@@ -1288,9 +1258,9 @@ class FieldContext:
         if len(rows) != len(coefs) or len(rbits) != len(mus) or not (rows or rbits):
             raise ValueError('one coefficient per row')
         n = rows[0].n if rows else rbits[0].n // 8
-        self._same(n, *rows, out, what='share row')
+        self._same(n, *rows, what='share row')
         self._same(8 * n, *rbits, what='bit-share row')
-        out = out or self.empty(n)
+        out = self._out(n, out)
         pr = (ctypes.c_void_p * max(1, len(rows)))(*[r.ptr for r in rows])
         pb = (ctypes.c_void_p * max(1, len(rbits)))(*[r.ptr for r in rbits])
         _ffi.check(self._L.ffgpu_gf256_mask_open(self._h, pr, self._scalars(coefs), len(rows), pb, self._scalars(mus),
@@ -1344,13 +1314,13 @@ class FieldContext:
 
     def to_bits(self, x: DevArray, addend: Optional[DevArray] = None, out: Optional[DevArray] = None) -> DevArray:
         """GF(2^n<=8): bits of PUBLIC bytes as field elements (8 per byte), plus `addend` (runtime.py:4418-4423)."""
-        out = out or self.empty(8 * x.n)
+        out = self._out(8 * x.n, out)
         _ffi.check(self._L.ffgpu_gf256_to_bits(self._h, x.ptr, addend.ptr if addend is not None else None, out.ptr,
                                                x.n, self._stream()), 'to_bits')
         return out
 
     def sbox(self, x: DevArray, rows8: Sequence[int], b: int, out=None):
-        out = out or self.empty(x.n)
+        out = self._out(x.n, out)
         r = (ctypes.c_uint8 * 8)(*rows8)
         _ffi.check(self._L.ffgpu_gf256_sbox(self._h, x.ptr, r, ctypes.c_uint8(b), out.ptr, x.n, self._stream()),
                    'sbox')

@@ -24,6 +24,20 @@ def _lagrange(field, xs: Sequence[int]) -> List[int]:
     return [int(v) for v in thresha._recombination_vector(field, tuple(xs), 0)]
 
 
+def _parties(what: str, t: int, m: int, *others: int) -> int:
+    """k = 2t+1, the number of parties that re-share a degree-2t product; refuses fewer than k parties and an operand
+    (`others`: how many parties each further operand has shares of) that is not there for every party."""
+    k = 2 * t + 1
+    if m < k or any(o != m for o in others):
+        raise ValueError(f'{what} needs m >= 2t+1 parties, and every operand for each of them')
+    return k
+
+
+def _axis_check(what: str, xs: Shares, outer: int, k: int, inner: int):
+    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs):
+        raise ValueError(f'{what}: the shares are not (outer, k, inner) arrays')
+
+
 def share(ctx: FieldContext, x: DevArray, t: int, m: int, rng=None) -> Shares:
     """np_random_split (thresha.py:47-64) with coefficients from the device CSPRNG; row i -> party i+1.
     rng: an engine.RngState (device-resident generator, required inside HIP-graph capture) or None (fresh
@@ -43,21 +57,7 @@ def add_public(ctx: FieldContext, xs: Shares, c: DevArray) -> Shares:
     return [ctx.add(x, c) for x in xs]
 
 
-def multiply(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, rng=None) -> Shares:
-    """runtime.np_multiply (runtime.py:1096-1141) = local product of shares (degree 2t) + _reshare
-    (runtime.py:603-689): each of the first 2t+1 parties re-shares its product with a fresh degree-t
-    polynomial -- the product is formed inside the share-generation kernel (ffgpu_mul_split_rng) --, then
-    every party recombines the 2t+1 sub-shares it received with the Lagrange vector for x = 0."""
-    m = len(xs)
-    k = 2 * t + 1
-    if m < k:
-        raise ValueError('multiplication needs m >= 2t+1 parties')
-    lam = _lagrange(field, range(1, k + 1))
-    sub = [ctx.split_rng(xs[i], t, m, mul_by=ys[i], state=rng) for i in range(k)]            # sender i -> row j for party j
-    return [ctx.recombine([sub[i].row(j) for i in range(k)], lam) for j in range(m)]
-
-
-# ---- chains of multiplications with the recombined share kept in registers ------------------------------
+# ---- the re-sharing round (runtime._reshare, runtime.py:603-689) -----------------------------------------------
 class Pending:
     """A secret-shared value each party holds as a RECOMBINATION it has not performed yet: party j's share
     is sum_i lam[i] * rows[j][i] (rows[j] = the sub-shares party j received).  A materialised sharing is the
@@ -72,6 +72,11 @@ class Pending:
     def of(cls, xs: Shares) -> 'Pending':
         return cls([[x] for x in xs], [1])
 
+    @classmethod
+    def dealt(cls, mats, lam, m: int) -> 'Pending':
+        """From the senders' share matrices: row j of mats[i] is what sender i dealt to party j."""
+        return cls([[mat.row(j) for mat in mats] for j in range(m)], lam)
+
 
 def materialize(ctx: FieldContext, x) -> Shares:
     """Pending -> the parties' shares (the recombination of runtime._reshare, runtime.py:677-689)."""
@@ -82,6 +87,27 @@ def materialize(ctx: FieldContext, x) -> Shares:
     return [ctx.recombine(r, x.lam) for r in x.rows]
 
 
+def reshare(ctx: FieldContext, field, xs, t: int, m: int, rng=None, mul_by: Optional[Shares] = None,
+            what: str = 'multiplication') -> Pending:
+    """The re-sharing of a secure round: each of the first 2t+1 parties deals its degree-2t value xs[i] (with mul_by: the
+    product xs[i] * mul_by[i], formed inside the share generation, ffgpu_mul_split_rng) to all m parties with a fresh
+    degree-t polynomial, senders in order.  The result is Pending: rows[j] are the sub-shares party j received, lam the
+    Lagrange vector for x = 0 -- materialize() recombines them, a round with a fused apply end hands rows[j] and lam to
+    its apply wrapper.  xs may be an iterator; only its first 2t+1 values are taken, each when its sender's turn comes."""
+    k = _parties(what, t, m)
+    mats = [ctx.split_rng(x, t, m, mul_by=None if mul_by is None else mul_by[i], state=rng) for i, x in zip(range(k), xs)]
+    return Pending.dealt(mats, _lagrange(field, range(1, k + 1)), m)
+
+
+def multiply(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, rng=None) -> Shares:
+    """runtime.np_multiply (runtime.py:1096-1141) = local product of shares (degree 2t) + _reshare
+    (runtime.py:603-689): each of the first 2t+1 parties re-shares its product with a fresh degree-t
+    polynomial -- the product is formed inside the share-generation kernel (ffgpu_mul_split_rng) --, then
+    every party recombines the 2t+1 sub-shares it received with the Lagrange vector for x = 0."""
+    return materialize(ctx, reshare(ctx, field, xs, t, len(xs), rng, mul_by=ys))
+
+
+# ---- chains of multiplications with the recombined share kept in registers ------------------------------
 def multiply_pending(ctx: FieldContext, field, x, y, t: int, rng=None) -> Pending:
     """multiply() for operands that may be Pending (y is x: a squaring): the first 2t+1 parties recombine both
     factors, multiply and re-share in ONE kernel (ffgpu_gate_rng); the result stays Pending, so the next
@@ -89,50 +115,16 @@ def multiply_pending(ctx: FieldContext, field, x, y, t: int, rng=None) -> Pendin
     px = x if isinstance(x, Pending) else Pending.of(x)
     py = None if y is x else (y if isinstance(y, Pending) else Pending.of(y))
     m = len(px.rows)
-    k = 2 * t + 1
-    if m < k:
-        raise ValueError('multiplication needs m >= 2t+1 parties')
-    lam = _lagrange(field, range(1, k + 1))
-    sub = [ctx.gate(px.rows[i], px.lam, py.rows[i] if py else None, py.lam if py else None, t, m, state=rng)
-           for i in range(k)]
-    return Pending([[sub[i].row(j) for i in range(k)] for j in range(m)], lam)
+    k = _parties('multiplication', t, m)
+    mats = [ctx.gate(px.rows[i], px.lam, py.rows[i] if py else None, py.lam if py else None, t, m, state=rng)
+            for i in range(k)]
+    return Pending.dealt(mats, _lagrange(field, range(1, k + 1)), m)
 
 
-def pow254_fused(ctx: FieldContext, field, xs: Shares, t: int, rng=None) -> Shares:
-    """pow254() with every intermediate share kept Pending: 11 fused gate kernels + 1 recombination per party
-    instead of 11 x (share generation + recombination)."""
-    mul = lambda a, b: multiply_pending(ctx, field, a, b, t, rng)
-    d = Pending.of(xs)
-    c = mul(d, d)
-    c = mul(c, c)
-    c = mul(c, c)
-    c = mul(c, d)
-    c = mul(c, c)
-    c, d = mul(c, c), mul(c, d)
-    c, d = mul(c, c), mul(c, d)
-    c = mul(c, d)
-    return materialize(ctx, mul(c, c))
-
-
-def matmul(ctx: FieldContext, field, xs: Shares, ys: Shares, M: int, K: int, N: int, t: int, rng=None) -> Shares:
-    """runtime.np_matmul (runtime.py:2481-2541): every party multiplies its share matrices locally
-    (`A @ B` then one reduction, :2531 -- the dense-product kernel) and the degree-2t result is re-shared as
-    in multiply().  xs: (M, K) and ys: (K, N) row-major share matrices; returns shares of the (M, N) product."""
-    m = len(xs)
-    k = 2 * t + 1
-    if m < k:
-        raise ValueError('multiplication needs m >= 2t+1 parties')
-    lam = _lagrange(field, range(1, k + 1))
-    sub = [ctx.split_rng(ctx.matmul(xs[i], ys[i], M, K, N), t, m, state=rng) for i in range(k)]
-    return [ctx.recombine([sub[i].row(j) for i in range(k)], lam) for j in range(m)]
-
-
-def pow254(ctx: FieldContext, field, xs: Shares, t: int, rng=None) -> Shares:
-    """x^254 by the reference's addition chain (runtime.py:1356-1367): 11 secure multiplications.  The
-    reference stacks (c, d) in two rounds to halve the number of MESSAGES; locally the stacked product is two
-    products, issued here as such (no concatenation traffic)."""
-    mul = lambda a, b: multiply(ctx, field, a, b, t, rng)
-    d = xs
+def _pow254_chain(mul, d):
+    """x^254 by the reference's addition chain (runtime.py:1356-1367): 11 multiplications.  The reference stacks
+    (c, d) in two rounds to halve the number of MESSAGES; locally the stacked product is two products, issued here
+    as such (no concatenation traffic)."""
     c = mul(d, d)
     c = mul(c, c)
     c = mul(c, c)
@@ -142,6 +134,25 @@ def pow254(ctx: FieldContext, field, xs: Shares, t: int, rng=None) -> Shares:
     c, d = mul(c, c), mul(c, d)
     c = mul(c, d)
     return mul(c, c)
+
+
+def pow254_fused(ctx: FieldContext, field, xs: Shares, t: int, rng=None) -> Shares:
+    """pow254() with every intermediate share kept Pending: 11 fused gate kernels + 1 recombination per party
+    instead of 11 x (share generation + recombination)."""
+    return materialize(ctx, _pow254_chain(lambda a, b: multiply_pending(ctx, field, a, b, t, rng), Pending.of(xs)))
+
+
+def matmul(ctx: FieldContext, field, xs: Shares, ys: Shares, M: int, K: int, N: int, t: int, rng=None) -> Shares:
+    """runtime.np_matmul (runtime.py:2481-2541): every party multiplies its share matrices locally
+    (`A @ B` then one reduction, :2531 -- the dense-product kernel) and the degree-2t result is re-shared as
+    in multiply().  xs: (M, K) and ys: (K, N) row-major share matrices; returns shares of the (M, N) product."""
+    prod = (ctx.matmul(x, y, M, K, N) for x, y in zip(xs, ys))             # each sender's product right before it deals it
+    return materialize(ctx, reshare(ctx, field, prod, t, len(xs), rng))
+
+
+def pow254(ctx: FieldContext, field, xs: Shares, t: int, rng=None) -> Shares:
+    """x^254 in 11 secure multiplications (_pow254_chain)."""
+    return _pow254_chain(lambda a, b: multiply(ctx, field, a, b, t, rng), xs)
 
 
 def to_bits_gf256(ctx: FieldContext, field, xs: Shares, rbits: Shares, t: int) -> Shares:
@@ -191,9 +202,7 @@ def is_zero_public(ctx: FieldContext, field, xs: Shares, rzero: Shares, t: int) 
     multiplies its share with its share of nonzero randomness (a degree-2t sharing of x r) and the product is opened from
     2t+1 parties.  Returns the PUBLIC w = x r: zero exactly where x is.  rzero: a caller-supplied sharing of nonzero
     random values."""
-    k = 2 * t + 1
-    if len(xs) < k:
-        raise ValueError('the zero test opens a degree-2t sharing: m >= 2t+1 parties')
+    k = _parties('the zero test', t, len(xs))
     return open_(ctx, field, [ctx.mul(xs[i], rzero[i]) for i in range(k)], t, degree=2 * t)
 
 
@@ -260,13 +269,9 @@ def sort(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
     It is assumed that every difference of two values along k lies in [-2^(l-1), 2^(l-1)), and, as for compare_zero, that
     2^(l+1) + 2^l max(rdivl) < p.  Needs m >= 2t+1 parties."""
     m = len(xs)
-    kk = 2 * t + 1
-    if m < kk:
-        raise ValueError('sorting multiplies: m >= 2t+1 parties')
-    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs) or xs[0].n != outer * k * inner:
-        raise ValueError('sort: the shares are not (outer, k, inner) arrays')
+    _parties('sort', t, m)
+    _axis_check('sort', xs, outer, k, inner)
     a = [x.clone() for x in xs]
-    lam = _lagrange(field, range(1, kk + 1))
     for p, d, r in sort_stages(k):
         pairs = ctx.cx_pairs(k, p, d, r)
         if pairs == 0:
@@ -274,9 +279,9 @@ def sort(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
         diff = [ctx.cx_diff(x, outer, k, inner, p, d, r) for x in a]
         rbits, sbits, rdivl, rzero = rand(outer * pairs * inner)
         c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
-        sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]       # sender i -> row j for party j
+        sub = reshare(ctx, field, c, t, m, rng, mul_by=diff)
         for j in range(m):
-            ctx.cx_apply(a[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, p, d, r)
+            ctx.cx_apply(a[j], sub.rows[j], sub.lam, outer, k, inner, p, d, r)
     return a
 
 
@@ -290,17 +295,13 @@ def carry_prefix(ctx: FieldContext, field, G: Shares, P: Shares, l: int, n: int,
     Overwrites G with the prefix carries (carry k = the carry out of bit positions 0..k) and returns it; P is overwritten
     too.  Needs m >= 2t+1 parties."""
     m = len(G)
-    kk = 2 * t + 1
-    if m < kk or len(P) != m:
-        raise ValueError('the carry network multiplies: m >= 2t+1 parties, G and P for each of them')
+    kk = _parties('the carry network', t, m, len(P))
     if l < 1 or n < 0 or any(x.n != l * n for x in G) or any(x.n != l * n for x in P):
         raise ValueError('carry_prefix: the shares are not (l, n) arrays')
-    lam = _lagrange(field, range(1, kk + 1))
     for rho in range(1, ctx.carry_rounds(l) + 1):
-        prod = [ctx.carry_prod(G[i], P[i], l, rho) for i in range(kk)]
-        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                  # sender i -> row j for party j
+        sub = reshare(ctx, field, [ctx.carry_prod(G[i], P[i], l, rho) for i in range(kk)], t, m, rng)
         for j in range(m):
-            ctx.carry_apply(G[j], P[j], [sub[i].row(j) for i in range(kk)], lam, l, rho)
+            ctx.carry_apply(G[j], P[j], sub.rows[j], sub.lam, l, rho)
     return G
 
 
@@ -316,8 +317,7 @@ def to_bits(ctx: FieldContext, field, xs: Shares, rbits: Shares, rdivl: Shares, 
     -2^(l-1) <= a < 2^(l-1) or 0 <= a < 2^l, and that 0 <= a + offset + 2^l rdivl - r < p for every element (r the value of
     the random bits), so that the opened value does not wrap.  Needs m >= 2t+1 parties."""
     m = len(xs)
-    if m < 2 * t + 1:
-        raise ValueError('bit decomposition multiplies: m >= 2t+1 parties')
+    _parties('bit decomposition', t, m)
     n = xs[0].n
     if any(x.n != n for x in xs) or len(rbits) != m or len(rdivl) != m or any(r.n != n * l for r in rbits):
         raise ValueError('to_bits: n values, n*l bit shares and n high masks per party')
@@ -330,27 +330,19 @@ def to_bits(ctx: FieldContext, field, xs: Shares, rbits: Shares, rdivl: Shares, 
 
 # ---- maximum, minimum and their positions along one axis (runtime.np_amax / np_amin, runtime.py:3377-3473;
 # np_argmax / np_argmin, runtime.py:3695-3949; np_maximum / np_minimum, runtime.py:3346-3360) --------------------
-def _tour_check(what: str, xs: Shares, outer: int, k: int, inner: int, t: int):
-    if len(xs) < 2 * t + 1:
-        raise ValueError(f'{what} multiplies: m >= 2t+1 parties')
-    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs):
-        raise ValueError(f'{what}: the shares are not (outer, k, inner) arrays')
-
-
 def _tour_round(ctx: FieldContext, field, a: Shares, outer: int, k: int, inner: int, mode: int, neg: bool, t: int, l: int, rand,
                 rng):
     """One round along k >= 2 for all parties: (the next level (outer, k // 2 + k % 2, inner), the comparison bits)."""
-    m, kk = len(a), 2 * t + 1
-    lam = _lagrange(field, range(1, kk + 1))
     diff = [ctx.tour_diff(x, outer, k, inner, mode, neg) for x in a]
     rbits, sbits, rdivl, rzero = rand(outer * (k // 2) * inner)
     c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
-    sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]           # sender i -> row j for party j
-    return [ctx.tour_select(a[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, mode, neg) for j in range(m)], c
+    sub = reshare(ctx, field, c, t, len(a), rng, mul_by=diff)
+    return [ctx.tour_select(x, rows, sub.lam, outer, k, inner, mode, neg) for x, rows in zip(a, sub.rows)], c
 
 
 def _amax(what: str, neg: bool, ctx, field, xs, outer, k, inner, t, l, rand, rng) -> Shares:
-    _tour_check(what, xs, outer, k, inner, t)
+    _parties(what, t, len(xs))
+    _axis_check(what, xs, outer, k, inner)
     a = list(xs)
     while k > 1:
         a, _ = _tour_round(ctx, field, a, outer, k, inner, ctx.TOUR_HALVES, neg, t, l, rand, rng)
@@ -383,9 +375,9 @@ def amin(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
 
 
 def _argmax(what: str, neg: bool, ctx, field, xs, outer, k, inner, t, l, rand, rng):
-    _tour_check(what, xs, outer, k, inner, t)
-    m, kk = len(xs), 2 * t + 1
-    lam = _lagrange(field, range(1, kk + 1))
+    m = len(xs)
+    kk = _parties(what, t, m)
+    _axis_check(what, xs, outer, k, inner)
     a, kept = list(xs), []
     while k > 1:                                        # downward: the values, every round's bits kept
         a, c = _tour_round(ctx, field, a, outer, k, inner, ctx.TOUR_ODD_EVEN, neg, t, l, rand, rng)
@@ -400,9 +392,8 @@ def _argmax(what: str, neg: bool, ctx, field, xs, outer, k, inner, t, l, rand, r
         if k == 2:                                      # the child is the 1: (1 - c, c) without a multiplication
             u = [ctx.tour_unit_expand(u[j], [c[j]], [1], outer, k, inner) for j in range(m)]
             continue
-        prod = [ctx.tour_unit_prod(u[i], c[i], outer, k, inner) for i in range(kk)]
-        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                    # sender i -> row j for party j
-        u = [ctx.tour_unit_expand(u[j], [sub[i].row(j) for i in range(kk)], lam, outer, k, inner) for j in range(m)]
+        sub = reshare(ctx, field, [ctx.tour_unit_prod(u[i], c[i], outer, k, inner) for i in range(kk)], t, m, rng)
+        u = [ctx.tour_unit_expand(u[j], sub.rows[j], sub.lam, outer, k, inner) for j in range(m)]
     return u, value
 
 
@@ -431,8 +422,7 @@ def argmin(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int,
 def arg_index(ctx: FieldContext, unit: Shares, outer: int, k: int, inner: int) -> Shares:
     """The positions the unit vectors of argmax() / argmin() point at: u @ arange(k) along k (runtime.py:3754-3757, 3882-3885),
     local.  Returns shares of the (outer, inner) positions."""
-    if outer < 1 or k < 1 or inner < 1 or any(u.n != outer * k * inner for u in unit):
-        raise ValueError('arg_index: the shares are not (outer, k, inner) arrays')
+    _axis_check('arg_index', unit, outer, k, inner)
     iv = ctx.from_ints([j % ctx.modulus for j in range(k)])
     if inner == 1:
         return [ctx.matmul(u, iv, outer, k, 1) for u in unit]
@@ -440,18 +430,15 @@ def arg_index(ctx: FieldContext, unit: Shares, outer: int, k: int, inner: int) -
 
 
 def _maximum(what: str, neg: bool, ctx, field, xs, ys, t, l, rand, rng) -> Shares:
-    m, kk = len(xs), 2 * t + 1
-    if m < kk or len(ys) != m:
-        raise ValueError(f'{what} multiplies: m >= 2t+1 parties, both operands for each of them')
+    m = len(xs)
+    _parties(what, t, m, len(ys))
     n = xs[0].n
     if any(x.n != n for x in xs) or any(y.n != n for y in ys):
         raise ValueError(f'{what}: operands of different lengths')
-    lam = _lagrange(field, range(1, kk + 1))
     diff = [ctx.sub(x, y) if neg else ctx.sub(y, x) for x, y in zip(xs, ys)]
     rbits, sbits, rdivl, rzero = rand(n)
     c = compare_zero(ctx, field, diff, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
-    sub = [ctx.split_rng(c[i], t, m, mul_by=diff[i], state=rng) for i in range(kk)]
-    v = [ctx.recombine([sub[i].row(j) for i in range(kk)], lam) for j in range(m)]
+    v = materialize(ctx, reshare(ctx, field, c, t, m, rng, mul_by=diff))
     return [ctx.sub(x, w) if neg else ctx.add(x, w) for x, w in zip(xs, v)]
 
 
@@ -487,17 +474,14 @@ def _find_functions(f, cs_f):
 def _find_root(ctx: FieldContext, field, b: Shares, tab: DevArray, outer: int, k: int, inner: int, C: int, flip: int, virt: int, t: int,
                rng) -> Shares:
     """The rounds of find() over the k + virt >= 2 leaves: every party's root (C, outer, 1, inner), component 0 = nf."""
-    m, kk = len(b), 2 * t + 1
-    lam = _lagrange(field, range(1, kk + 1))
-    prod = [ctx.find_leaf_prod(b[i], tab, outer, k, inner, C, flip, virt) for i in range(kk)]
-    sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]                        # sender i -> row j for party j
-    level = [ctx.find_leaf_apply(b[j], tab, [sub[i].row(j) for i in range(kk)], lam, outer, k, inner, C, flip, virt) for j in range(m)]
+    m = len(b)
+    kk = _parties('find', t, m)
+    sub = reshare(ctx, field, [ctx.find_leaf_prod(b[i], tab, outer, k, inner, C, flip, virt) for i in range(kk)], t, m, rng)
+    level = [ctx.find_leaf_apply(b[j], tab, sub.rows[j], sub.lam, outer, k, inner, C, flip, virt) for j in range(m)]
     kp = (k + virt) // 2 + (k + virt) % 2
     while kp > 1:
-        prod = [ctx.find_prod(level[i], outer, kp, inner, C) for i in range(kk)]
-        sub = [ctx.split_rng(prod[i], t, m, state=rng) for i in range(kk)]
-        level = [ctx.tour_select(level[j], [sub[i].row(j) for i in range(kk)], lam, C * outer, kp, inner, ctx.TOUR_ODD_EVEN)
-                 for j in range(m)]
+        sub = reshare(ctx, field, [ctx.find_prod(level[i], outer, kp, inner, C) for i in range(kk)], t, m, rng)
+        level = [ctx.tour_select(level[j], sub.rows[j], sub.lam, C * outer, kp, inner, ctx.TOUR_ODD_EVEN) for j in range(m)]
         kp = kp // 2 + kp % 2
     return level
 
@@ -523,11 +507,8 @@ def find(ctx: FieldContext, field, xs: Shares, outer: int, k: int, inner: int, t
       the received sub-shares recombined and added to L, the bye carried over, per party (ffgpu_find_leaf_apply;
       ffgpu_tour_select on the components as rows later).
     k == 1 with e=None has no round.  Needs m >= 2t+1 parties; xs is not written."""
-    m, kk = len(xs), 2 * t + 1
-    if m < kk:
-        raise ValueError('find multiplies: m >= 2t+1 parties')
-    if outer < 1 or k < 1 or inner < 1 or any(x.n != outer * k * inner for x in xs):
-        raise ValueError('find: the shares are not (outer, k, inner) arrays')
+    _parties('find', t, len(xs))
+    _axis_check('find', xs, outer, k, inner)
     if not isinstance(s, int) or (bits and s not in (0, 1)):
         raise ValueError('find: s is a public integer, 0 or 1 for bits')
     f_, cs, single = _find_functions(f, cs_f)
@@ -613,16 +594,14 @@ def norm(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits
     m >= 2t+1 parties; xs is not written."""
     if not (f <= l <= 2 * f + 1) or l < 2:
         raise ValueError('norm: f <= l <= 2f + 1 and l >= 2')
-    m, kk = len(xs), 2 * t + 1
-    if m < kk:
-        raise ValueError('norm multiplies: m >= 2t+1 parties')
+    m = len(xs)
+    kk = _parties('norm', t, m)
     n = xs[0].n
     rbits, rdivl = rand_bits(n, l)
     bits = to_bits(ctx, field, xs, rbits, rdivl, t, l, rng=rng)
-    lam = _lagrange(field, range(1, kk + 1))
     ps = [ctx.norm_prod(bits[i], l) for i in range(kk)]
-    sub = [ctx.split_rng(ps[i][0], t, m, state=rng) for i in range(kk)]                       # sender i -> row j for party j
-    x = [ctx.norm_apply(bits[j], [sub[i].row(j) for i in range(kk)], lam, l) for j in range(m)]
+    sub = reshare(ctx, field, [p[0] for p in ps], t, m, rng)
+    x = [ctx.norm_apply(bits[j], sub.rows[j], sub.lam, l) for j in range(m)]
     nf = find(ctx, field, x, n, l - 1, 1, t, s=0, e=l - 1, cs_f=lambda b, i: (b + 1) << i, rng=rng)
     v = multiply(ctx, field, nf, [p[1] for p in ps], t, rng)
     return [ctx.mul_scalar(w, 1 << (2 * f - l + 1)) for w in v]
@@ -684,8 +663,9 @@ def as_matrix(ctx: FieldContext, xs: Shares):
 
 
 class _Block:
-    """Sub-shares of one re-sharing round, all parties: row j * k + s of `mtx` = the sub-share sender s+1 dealt to
-    party j+1."""
+    """Pending for the all-parties layout: the sub-shares of one re-sharing round as ONE [recipient][sender] block, row
+    j * k + s of `mtx` = the sub-share sender s+1 dealt to party j+1.  `rows` and `lam` read as Pending's; rows_of(j) is
+    rows[j] without the other parties' views."""
 
     __slots__ = ('mtx', 'k', 'lam')
 
@@ -694,6 +674,10 @@ class _Block:
 
     def rows_of(self, j: int):
         return [self.mtx.row(j * self.k + s) for s in range(self.k)]
+
+    @property
+    def rows(self):
+        return [self.rows_of(j) for j in range(self.mtx.rows // self.k)]
 
 
 def _gate_all(ctx: FieldContext, x, y, t: int, m: int, lam, rng):
@@ -722,9 +706,8 @@ def sbox_layer_all(ctx: FieldContext, field, xs, rbits, t: int, A: Sequence[Sequ
     from .engine import DevMatrix
     X = xs if isinstance(xs, DevMatrix) else as_matrix(ctx, xs)
     R = rbits if isinstance(rbits, DevMatrix) else as_matrix(ctx, rbits)
-    m, k = X.rows, 2 * t + 1
-    if m < k or R.rows != m:
-        raise ValueError('multiplication needs m >= 2t+1 parties, and bit shares for each of them')
+    m = X.rows
+    k = _parties('the S-box layer', t, m, R.rows)
     lam = _lagrange(field, range(1, k + 1))
     if fused and ctx.elem_bytes == 1:
         # everything below is element-wise: one kernel carries the parties' shares through the whole layer in registers
@@ -735,17 +718,7 @@ def sbox_layer_all(ctx: FieldContext, field, xs, rbits, t: int, A: Sequence[Sequ
             return out
         except NotImplementedError:
             pass                                        # shape not covered: per-step kernels
-    mul = lambda a, b: _gate_all(ctx, a, b, t, m, lam, rng)
-    d = X                                               # x^254 by the reference's addition chain, runtime.py:1356-1367
-    c = mul(d, d)
-    c = mul(c, c)
-    c = mul(c, c)
-    c = mul(c, d)
-    c = mul(c, c)
-    c, d = mul(c, c), mul(c, d)
-    c, d = mul(c, c), mul(c, d)
-    c = mul(c, d)
-    y = mul(c, c)                                       # pending: party j holds sum_s lam[s] * y.rows_of(j)[s]
+    y = _pow254_chain(lambda a, b: _gate_all(ctx, a, b, t, m, lam, rng), X)    # pending: party j holds sum_s lam[s] * y.rows_of(j)[s]
     mu = _lagrange(field, range(1, t + 2))              # opening from the first t+1 parties (runtime.py:582-585)
     rows, coefs = [], []
     for p in range(t + 1):

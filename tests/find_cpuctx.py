@@ -79,16 +79,16 @@ class FindCpuFieldContext(TourCpuFieldContext):
     def find_leaf_prod(self, bits, tab, outer, k, inner, ncomp, flip=0, virt=0, out=None):
         self._find_chk(bits, tab, outer, k, inner, ncomp, flip, virt, True)
         lv = self._leaves(bits, tab, outer, k, inner, ncomp, flip, virt)
-        return self._tour_out(out, prod_ref(self.modulus, lv, outer, k + virt, inner, ncomp, not self.find_no_bye_shift))
+        return self._put_out(out, prod_ref(self.modulus, lv, outer, k + virt, inner, ncomp, not self.find_no_bye_shift))
 
     def find_leaf_apply(self, bits, tab, rows, lambdas, outer, k, inner, ncomp, flip=0, virt=0, out=None):
         self._find_chk(bits, tab, outer, k, inner, ncomp, flip, virt, True)
         kv = k + virt
         v = self._tour_v(rows, lambdas, ncomp * outer * (kv // 2) * inner)
         lv = self._leaves(bits, tab, outer, k, inner, ncomp, flip, virt)
-        return self._tour_out(out, apply_ref(self.modulus, lv, v, outer, kv, inner, ncomp, not self.find_no_bye_shift))
+        return self._put_out(out, apply_ref(self.modulus, lv, v, outer, kv, inner, ncomp, not self.find_no_bye_shift))
 
     def find_prod(self, level, outer, k, inner, ncomp, out=None):
         self._find_chk(level, None, outer, k, inner, ncomp, 0, 0, False)
         lv = level_ref(level.to_ints(), outer, k, inner, ncomp)
-        return self._tour_out(out, prod_ref(self.modulus, lv, outer, k, inner, ncomp))
+        return self._put_out(out, prod_ref(self.modulus, lv, outer, k, inner, ncomp))

@@ -254,6 +254,95 @@ def test_norm_refuses_bit_lengths_outside_f_to_2f_plus_1():
         protocols.norm(ctx, run.F, xs[:2], 1, 16, 8, run.rand_bits)
 
 
+# ---- the party-count and the axis-shape check, one each for all protocols ---------------------------------------------------
+def _no_draw(*_):
+    raise AssertionError('no randomness may be drawn')
+
+
+def _compare_zero(P, c, F, xs, ys, mode):
+    """three values of l = 4 bits: the first rows of xs as values and masks, ys as the 12 bit shares"""
+    three = [P._rows(c, x, 0, 1, 3) for x in xs]
+    return P.compare_zero(c, F, three, ys, three, three, three, 1, 4, mode=mode)
+
+
+# every protocol function that multiplies, as call(protocols, ctx, F, xs, ys) on sharings of 12 values; t = 1, l = 10
+MULTIPLYING = {
+    'multiply': lambda P, c, F, xs, ys: P.multiply(c, F, xs, ys, 1),
+    'multiply_pending': lambda P, c, F, xs, ys: P.multiply_pending(c, F, xs, ys, 1),
+    'multiply_pending_square': lambda P, c, F, xs, ys: P.multiply_pending(c, F, P.Pending.of(xs), P.Pending.of(xs), 1),
+    'reshare': lambda P, c, F, xs, ys: P.reshare(c, F, xs, 1, len(xs)),
+    'pow254': lambda P, c, F, xs, ys: P.pow254(c, F, xs, 1),
+    'pow254_fused': lambda P, c, F, xs, ys: P.pow254_fused(c, F, xs, 1),
+    'matmul': lambda P, c, F, xs, ys: P.matmul(c, F, xs, ys, 3, 4, 3, 1),
+    'prod_rows': lambda P, c, F, xs, ys: P.prod_rows(c, F, xs, 4, 1),
+    'is_zero_public': lambda P, c, F, xs, ys: P.is_zero_public(c, F, xs, ys, 1),
+    'compare_zero_lt': lambda P, c, F, xs, ys: _compare_zero(P, c, F, xs, ys, 'lt'),
+    'compare_zero_eq': lambda P, c, F, xs, ys: _compare_zero(P, c, F, xs, ys, 'eq'),
+    'sort': lambda P, c, F, xs, ys: P.sort(c, F, xs, 1, 12, 1, 1, 10, _no_draw),
+    'carry_prefix': lambda P, c, F, xs, ys: P.carry_prefix(c, F, xs, ys, 4, 3, 1),
+    'carry_prefix_P_short': lambda P, c, F, xs, ys: P.carry_prefix(c, F, xs + xs[:1], ys, 4, 3, 1),
+    'to_bits': lambda P, c, F, xs, ys: P.to_bits(c, F, [P._rows(c, x, 0, 1, 3) for x in xs], ys, [P._rows(c, x, 0, 1, 3) for x in xs], 1, 4),
+    'amax': lambda P, c, F, xs, ys: P.amax(c, F, xs, 1, 12, 1, 1, 10, _no_draw),
+    'amin': lambda P, c, F, xs, ys: P.amin(c, F, xs, 2, 3, 2, 1, 10, _no_draw),
+    'argmax': lambda P, c, F, xs, ys: P.argmax(c, F, xs, 1, 12, 1, 1, 10, _no_draw),
+    'argmin': lambda P, c, F, xs, ys: P.argmin(c, F, xs, 2, 3, 2, 1, 10, _no_draw),
+    'maximum': lambda P, c, F, xs, ys: P.maximum(c, F, xs, ys, 1, 10, _no_draw),
+    'minimum': lambda P, c, F, xs, ys: P.minimum(c, F, xs, ys, 1, 10, _no_draw),
+    'minimum_y_short': lambda P, c, F, xs, ys: P.minimum(c, F, xs + xs[:1], ys, 1, 10, _no_draw),
+    'find': lambda P, c, F, xs, ys: P.find(c, F, xs, 1, 12, 1, 1),
+    'find_integers': lambda P, c, F, xs, ys: P.find(c, F, xs, 1, 12, 1, 1, s=5, bits=False, l=10, rand=_no_draw),
+    'fxp_multiply': lambda P, c, F, xs, ys: P.fxp_multiply(c, F, xs, ys, 1, 4, 8, _no_draw),
+    'norm': lambda P, c, F, xs, ys: P.norm(c, F, xs, 1, 8, 4, _no_draw),
+    'reciprocal': lambda P, c, F, xs, ys: P.reciprocal(c, F, xs, 1, 8, 4, _no_draw, _no_draw),
+    'divide': lambda P, c, F, xs, ys: P.divide(c, F, xs, ys, 1, 8, 4, _no_draw, _no_draw),
+    'sbox_layer_all': lambda P, c, F, xs, ys: P.sbox_layer_all(c, F, xs, [P._cat(c, [y] * 8) for y in ys], 1, [[0] * 8] * 8, [0] * 8, fused=False),
+}
+
+
+@pytest.mark.parametrize('name', sorted(MULTIPLYING))
+def test_every_multiplying_protocol_refuses_2t_parties(name):
+    """m = 2t: the first 2t+1 parties re-share a product, so two parties at t = 1 are refused -- before any randomness is
+    drawn"""
+    from fxp_cpuctx import FxpCpuFieldContext
+    from mpyc_amd import protocols
+    ctx = FxpCpuFieldContext(P61)
+    run = Run(ctx, 3, 1, seed=2)
+    xs, ys = run.share(range(12)), run.share(range(1, 13))
+    with pytest.raises(ValueError):
+        MULTIPLYING[name](protocols, ctx, run.F, xs[:2], ys[:2])
+
+
+# every function that takes (outer, k, inner), as call(protocols, ctx, F, xs, outer, k, inner); t = 1, l = 10
+ALONG_AN_AXIS = {
+    'sort': lambda P, c, F, xs, o, k, i: P.sort(c, F, xs, o, k, i, 1, 10, _no_draw),
+    'amax': lambda P, c, F, xs, o, k, i: P.amax(c, F, xs, o, k, i, 1, 10, _no_draw),
+    'amin': lambda P, c, F, xs, o, k, i: P.amin(c, F, xs, o, k, i, 1, 10, _no_draw),
+    'argmax': lambda P, c, F, xs, o, k, i: P.argmax(c, F, xs, o, k, i, 1, 10, _no_draw),
+    'argmin': lambda P, c, F, xs, o, k, i: P.argmin(c, F, xs, o, k, i, 1, 10, _no_draw),
+    'arg_index': lambda P, c, F, xs, o, k, i: P.arg_index(c, xs, o, k, i),
+    'find': lambda P, c, F, xs, o, k, i: P.find(c, F, xs, o, k, i, 1),
+    'find_integers': lambda P, c, F, xs, o, k, i: P.find(c, F, xs, o, k, i, 1, s=5, bits=False, l=10, rand=_no_draw),
+}
+
+
+@pytest.mark.parametrize('name', sorted(ALONG_AN_AXIS))
+def test_every_protocol_along_an_axis_refuses_a_share_of_the_wrong_length(name):
+    """the LAST party's share one element short or long, every share of another length than outer * k * inner, and an extent
+    below 1"""
+    from fxp_cpuctx import FxpCpuFieldContext
+    from mpyc_amd import protocols
+    ctx = FxpCpuFieldContext(P61)
+    run = Run(ctx, 3, 1, seed=3)
+    xs = run.share(range(12))
+    call = lambda shares, *shape: ALONG_AN_AXIS[name](protocols, ctx, run.F, shares, *shape)
+    for last in (run.share(range(11))[2], run.share(range(13))[2]):
+        with pytest.raises(ValueError):
+            call(xs[:2] + [last], 2, 3, 2)
+    for shape in ((1, 13, 1), (2, 3, 3), (1, 11, 1), (0, 12, 1), (12, 0, 1), (1, 12, 0)):
+        with pytest.raises(ValueError):
+            call(xs, *shape)
+
+
 # ---- fxp_multiply, reciprocal, divide ----------------------------------------------------------------------------------------
 def within(y, lo, hi):
     """the tolerance of the issue: [min, max] of the reference's eight draws, widened on each side by its own width and by at

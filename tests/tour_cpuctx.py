@@ -76,30 +76,30 @@ class TourCpuFieldContext(SortCpuFieldContext):
             raise ValueError('rows are not compact (outer, h, inner) arrays')
         return self._rec_host(rows, [v % self.modulus for v in lambdas])
 
-    def _tour_out(self, out, vals):
+    def _put_out(self, out, vals):
         if out is not None and out.n != len(vals):
             raise ValueError('output of the wrong size')
         return self._put(out if out is not None else self.empty(len(vals)), vals)
 
     def tour_diff(self, a, outer, k, inner, mode, neg=False, out=None):
         self._tour_chk(a, k, outer, k, inner, mode)
-        return self._tour_out(out, diff_ref(self.modulus, a.to_ints(), outer, k, inner, mode, neg))
+        return self._put_out(out, diff_ref(self.modulus, a.to_ints(), outer, k, inner, mode, neg))
 
     def tour_select(self, a, rows, lambdas, outer, k, inner, mode, neg=False, out=None):
         self._tour_chk(a, k, outer, k, inner, mode)
         v = self._tour_v(rows, lambdas, outer * (k // 2) * inner)
-        return self._tour_out(out, select_ref(self.modulus, a.to_ints(), v, outer, k, inner, mode, bool(neg) != self.select_sign_swapped))
+        return self._put_out(out, select_ref(self.modulus, a.to_ints(), v, outer, k, inner, mode, bool(neg) != self.select_sign_swapped))
 
     def tour_unit_prod(self, u, c, outer, k, inner, out=None):
         self._tour_chk(u, k // 2 + k % 2, outer, k, inner, HALVES)
         if c.n != outer * (k // 2) * inner:
             raise ValueError('bits of the wrong size')
-        return self._tour_out(out, unit_prod_ref(self.modulus, u.to_ints(), c.to_ints(), outer, k, inner))
+        return self._put_out(out, unit_prod_ref(self.modulus, u.to_ints(), c.to_ints(), outer, k, inner))
 
     def tour_unit_expand(self, u, rows, lambdas, outer, k, inner, out=None):
         self._tour_chk(u, k // 2 + k % 2, outer, k, inner, ODD_EVEN)
         v = self._tour_v(rows, lambdas, outer * (k // 2) * inner)
-        return self._tour_out(out, unit_expand_ref(self.modulus, u.to_ints(), v, outer, k, inner, self.expand_even_gets_v))
+        return self._put_out(out, unit_expand_ref(self.modulus, u.to_ints(), v, outer, k, inner, self.expand_even_gets_v))
 
     def matmul_stack(self, A, B, batch, M, K, N, a_stride, b_stride, out=None):
         a, b = A.to_ints(), B.to_ints()
@@ -107,4 +107,4 @@ class TourCpuFieldContext(SortCpuFieldContext):
         for s in range(batch):
             x, y = a[s * a_stride:s * a_stride + M * K], b[s * b_stride:s * b_stride + K * N]
             res += [sum(x[i * K + q] * y[q * N + j] for q in range(K)) % self.modulus for i in range(M) for j in range(N)]
-        return self._tour_out(out, res)
+        return self._put_out(out, res)

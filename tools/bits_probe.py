@@ -135,17 +135,14 @@ class Composed:
         from mpyc_amd import protocols
         ctx, l = self.ctx, self.l
         m, kk = len(xs), 2 * T + 1
-        lam = protocols._lagrange(field, range(1, kk + 1))
         c = protocols.open_(ctx, field, [self.mask(xs[i], rbits[i], rdivl[i]) for i in range(T + 1)], T)
         CB, CBe = self.c_bits(c)
         gp = [self.expand(CB, rbits[i]) for i in range(m)]
         for rho in sorted(self.idx):
-            sub = []
-            for i in range(kk):
-                left, right = self.gather(gp[i][0], gp[i][1], rho)
-                sub.append(ctx.split_rng(left, T, m, mul_by=right))          # the product inside the share generation
+            left, right = zip(*[self.gather(gp[i][0], gp[i][1], rho) for i in range(kk)])
+            sub = protocols.reshare(ctx, field, left, T, m, mul_by=right)    # the product inside the share generation
             for j in range(m):
-                self.apply(gp[j][0], gp[j][1], [sub[i].row(j) for i in range(kk)], lam, rho)
+                self.apply(gp[j][0], gp[j][1], sub.rows[j], sub.lam, rho)
         return [self.finish(CBe, rbits[i], gp[i][0]) for i in range(m)]
 
 
