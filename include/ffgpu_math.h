@@ -1,0 +1,59 @@
+/*
+ * ffgpu_math.h -- second header of libffgpu.so: the local steps under the secure logarithm and exponential of fixed-point
+ * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945) that no entry of ffgpu.h serves.  Same
+ * library, same contexts (ffgpu_ctx of ffgpu.h), same conventions:
+ *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
+ *   - array arguments are DEVICE pointers unless the name says host; elements are canonical little-endian limbs in the
+ *     layouts ffgpu.h lists, host scalars little-endian 64-bit limbs, ffgpu_ctx_scalar_limbs() of them;
+ *   - `stream` is a hipStream_t passed as void*; calls are asynchronous on it, allocate nothing and never synchronise (they
+ *     can be captured in a HIP graph); inputs are never written, outputs are canonical;
+ *   - n == 0 returns FFGPU_OK whatever the pointers (the counts are still checked); in every refused case nothing is
+ *     written and nothing is launched;
+ *   - an output that overlaps an input is FFGPU_EINVAL (the one exception is stated at ffgm_powers_prod);
+ *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
+ * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
+ * log2(), log10(), pow_public_base(), exp2() and exp().
+ *
+ * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
+ *
+ * ffgm_powers_prod: out[j*n + e] = P[(h-1)*stride + e] * P[j*stride + e] for j < w, 1 <= w <= h -- the top power of a block
+ *   of h powers times its w lowest: the local (degree-2t) products of one doubling step of the power ladder, dense (w, n).
+ *   A thread keeps the top power in registers across its w products: w + 1 loads per element.  `out` may lie in the same
+ *   allocation as P from row h on (past the h rows read: at or after P + ((h-1)*stride + n) elements); any overlap with the
+ *   h rows read, padding between them included, is FFGPU_EINVAL.
+ *   replaces: runtime.py:4966-4967 (`b[:, -1:] * c`, the broadcast product before its re-sharing).
+ * ffgm_poly_dot: out[e] = c0 + sum_{j<theta} tab[j] * P[j*stride + e], 1 <= theta <= 64.  tab: a device table of theta
+ *   canonical elements (public coefficients), host_c0: one canonical host scalar.  One lazy accumulation and one reduction
+ *   per element; (theta + 1) * n elements of traffic.
+ *   replaces: runtime.py:4887 and :4934 (`ys @ coefficients` for public coefficients, runtime.py:2513-2531, and the constant).
+ * ffgm_pow_base: out[e] = g^((x[e] >> shift) mod 2^ebits) with x[e] taken as its canonical integer; the caller guarantees
+ *   x[e] >> shift < 2^ebits.  tab: the fixed-base window table of g, 15 * ceil(ebits/4) canonical elements,
+ *   tab[15*i + d - 1] = g^(d * 16^i) for d = 1..15.  At most ceil(ebits/4) - 1 products per element and no squarings; the
+ *   table is staged in LDS per workgroup.  1 <= ebits <= bit_length(p), 0 <= shift < 192.
+ *   replaces: runtime.py:1408 and :1422 (gmpy2.powmod_exp_list with a public base) and the shift at :1421.
+ * ffgm_bits_reverse: out[h*l + j] = bits[h*l + l-1-j] for the element-major (n, l) bits of ffgpu_bits_finish, 1 <= l <= 64.
+ *   replaces: runtime.py:4876 (np_flip along the bit axis).
+ *
+ * FFGPU_OK: n == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or theta > 64;
+ * ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; a size overflowing; an output
+ * overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context.                                                              */
+#ifndef FFGPU_MATH_H
+#define FFGPU_MATH_H
+
+#include "ffgpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w, void* out, size_t n, void* stream);
+int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const void* tab, const uint64_t* host_c0, void* out, size_t n,
+                  void* stream);
+int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const void* tab, void* out, size_t n, void* stream);
+int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t n, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* FFGPU_MATH_H */

@@ -1,4 +1,4 @@
-"""ctypes binding of libffgpu.so (C ABI in include/ffgpu.h).
+"""ctypes binding of libffgpu.so (C ABI in include/ffgpu.h and include/ffgpu_math.h).
 
 This is the only place the shared library is loaded.  There is no fallback: if the
 library is missing or a call fails, an exception is raised (FfgpuError or the
@@ -144,6 +144,15 @@ _RESTYPES = {'ffgpu_strerror': ctypes.c_char_p, 'ffgpu_last_hip_error': ctypes.c
 
 EXPORTED = tuple(_SIGS)
 
+# the entries of include/ffgpu_math.h (prefix ffgm_), exported by the same library
+_SIGS_MATH = {
+    'ffgm_powers_prod': [_vp, _vp, _sz, _int, _int, _vp, _sz, _vp],
+    'ffgm_poly_dot': [_vp, _vp, _sz, _int, _vp, _u64p, _vp, _sz, _vp],
+    'ffgm_pow_base': [_vp, _vp, _int, _int, _vp, _vp, _sz, _vp],
+    'ffgm_bits_reverse': [_vp, _vp, _int, _vp, _sz, _vp],
+}
+EXPORTED_MATH = tuple(_SIGS_MATH)
+
 
 def lib():
     """Load libffgpu.so (once).  Raises FfgpuError if it has not been built."""
@@ -162,6 +171,10 @@ def lib():
             fn = getattr(L, name)      # AttributeError if the symbol is missing
             fn.argtypes = args
             fn.restype = _RESTYPES.get(name, _int)
+        for name, args in _SIGS_MATH.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = _int
         if L.ffgpu_abi_version() != 1:
             raise FfgpuError('libffgpu ABI version mismatch')
         _lib = L

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "../../include/ffgpu.h"
+#include "../../include/ffgpu_math.h"
 #include "handoff.hpp"
 #include "kernels.hpp"
 #include "policy_build.hpp"
@@ -1671,6 +1672,75 @@ int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_r
     ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && rows_clear_of(host_rows, nrows, pl.elems * eb, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
+}
+
+// ---- logarithm and exponential of fixed-point numbers over a prime field: the local steps no other entry serves (explog.hpp;
+// include/ffgpu_math.h) -------------------------------------------------------------------------------------------------------
+static int modulus_bits(const ffgpu_ctx* ctx) {
+    const uint64_t* p = ctx->modulus;
+    const int top = p[2] ? 2 : p[1] ? 1 : 0;
+    return 64 * top + (64 - __builtin_clzll(p[top] | 1));
+}
+
+int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w, void* out, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(explog_prod_valid(h, w));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(P && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)h, stride, eb, false);
+    size_t wn;
+    ARGCHK(pl.ok && cx_mul_ok((size_t)w, n, wn) && wn <= ((size_t)1 << 62) / eb);
+    ARGCHK(!overlaps(byte_range(out, wn * eb), byte_range(P, pl.span * eb)));     // (rows h.. of P's allocation lie past the span)
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->powers_prod(ctx->policy, cs.lc, P, stride, h, w, out, n, cs.st));
+}
+
+int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const void* tab, const uint64_t* host_c0, void* out, size_t n,
+                  void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(explog_poly_valid(theta) && host_c0);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(P && tab && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)theta, stride, eb, false);
+    ARGCHK(pl.ok);
+    const ByteRange in[2] = {byte_range(P, pl.span * eb), byte_range(tab, (size_t)theta * eb)};
+    const ByteRange o = byte_range(out, n * eb);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->poly_dot(ctx->policy, cs.lc, P, stride, theta, tab, host_c0, out, n, cs.st));
+}
+
+int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const void* tab, void* out, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const int pbits = modulus_bits(ctx);
+    ARGCHK(pow_base_plan(0, shift, ebits, pbits, eb).ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(x && tab && out);
+    const PowBasePlan pl = pow_base_plan(n, shift, ebits, pbits, eb);
+    ARGCHK(pl.ok);
+    const ByteRange in[2] = {byte_range(x, n * eb), byte_range(tab, (size_t)pl.tab_elems * eb)};
+    const ByteRange o = byte_range(out, n * eb);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->pow_base(ctx->policy, cs.lc, x, shift, ebits, pbits, tab, out, n, cs.st));
+}
+
+int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(explog_rev_l_valid(l));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(bits && out);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const FxpNormPlan pl = explog_rev_plan(n, l, eb, false);
+    ARGCHK(pl.ok);
+    const ByteRange in = byte_range(bits, pl.elems * eb);
+    const ByteRange o = byte_range(out, pl.elems * eb);
+    ARGCHK(outputs_disjoint(&in, 1, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->bits_reverse(ctx->policy, cs.lc, bits, l, out, n, cs.st));
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,

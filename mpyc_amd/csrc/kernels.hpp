@@ -2283,4 +2283,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "tour.hpp"     // the ends of a tournament round (np_amax / np_amin, np_argmax / np_argmin)
 #include "find.hpp"     // the ends of a round of the first-occurrence search (np_find)
 #include "fxp.hpp"      // local steps of fixed-point truncation and normalisation (np_trunc, _norm)
+#include "explog.hpp"   // local steps under the secure logarithm and exponential (np_log, np_exp2)
 #include "launch.hpp"   // host side: FieldOps table + launchers

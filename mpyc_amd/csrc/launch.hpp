@@ -175,6 +175,16 @@ struct FieldOps {
                      hipStream_t st);
     LaunchStatus (*norm_apply)(const void* F, const LaunchCfg& lc, const void* bits, const void* const* rows, const uint64_t* lam2,
                       int nrows, int l, void* out, size_t n, hipStream_t st);
+    // local steps under the secure logarithm and exponential (explog.hpp), prime fields only; c0 of poly_dot: one host scalar;
+    // pbits of pow_base: the bit length of the modulus (L_PLAN_REFUSED: explog_rows_plan() / pow_base_plan() /
+    // explog_rev_plan() refuses the sizes or the counts)
+    LaunchStatus (*powers_prod)(const void* F, const LaunchCfg& lc, const void* P, size_t stride, int h, int w, void* out, size_t n,
+                       hipStream_t st);
+    LaunchStatus (*poly_dot)(const void* F, const LaunchCfg& lc, const void* P, size_t stride, int theta, const void* tab,
+                    const uint64_t* c0, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*pow_base)(const void* F, const LaunchCfg& lc, const void* x, int shift, int ebits, int pbits, const void* tab, void* out,
+                    size_t n, hipStream_t st);
+    LaunchStatus (*bits_reverse)(const void* F, const LaunchCfg& lc, const void* bits, int l, void* out, size_t n, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1414,6 +1424,65 @@ struct Launchers {
             });
         }
     }
+    // The local steps under the secure logarithm and exponential (explog.hpp): one flat streaming loop, a unit (a pack where
+    // the plan admits packs, else an element) per thread up to the grid cap; pow_base is bound by its products and stages its
+    // table per workgroup: eight workgroups per compute unit at the most, each over many elements.
+    static LaunchStatus powers_prod(const void* Fp, const LaunchCfg& lc, const void* P, size_t stride, int h, int w, void* out, size_t n,
+                           hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (!explog_prod_valid(h, w)) return L_PLAN_REFUSED;
+            const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)h, stride, sizeof(E), al(P) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_powers_prod<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)P, h, w, (E*)out, pl, n);
+            return launched();
+        }
+    }
+    static LaunchStatus poly_dot(const void* Fp, const LaunchCfg& lc, const void* P, size_t stride, int theta, const void* tab,
+                        const uint64_t* c0, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            if (!explog_poly_valid(theta)) return L_PLAN_REFUSED;
+            const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)theta, stride, sizeof(E), al(P) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_poly_dot<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)P, theta, (const E*)tab,
+                               word_at<F>(f, c0, 0), (E*)out, pl);
+            return launched();
+        }
+    }
+    static LaunchStatus pow_base(const void* Fp, const LaunchCfg& lc, const void* x, int shift, int ebits, int pbits, const void* tab,
+                        void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const PowBasePlan pl = pow_base_plan(n, shift, ebits, pbits, sizeof(E));
+            if (!pl.ok || pl.nwin > pow_base_max_windows(sizeof(E))) return L_PLAN_REFUSED;
+            if (n == 0) return L_OK;
+            const unsigned want = grid_for(n, lc), cap = (unsigned)(lc.num_cu > 0 ? lc.num_cu : 1) * 8u;
+            hipLaunchKernelGGL((k_pow_base<F>), dim3(want < cap ? want : cap), dim3(BLOCK), 0, st, f, (const E*)x, (const E*)tab, (E*)out,
+                               pl, n);
+            return launched();
+        }
+    }
+    static LaunchStatus bits_reverse(const void* Fp, const LaunchCfg& lc, const void* bits, int l, void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const FxpNormPlan pl = explog_rev_plan(n, l, sizeof(E), al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_bits_reverse<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)bits, (E*)out, pl);
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1560,7 +1629,8 @@ struct Launchers {
             .tour_diff = &tour_diff, .tour_select = &tour_select, .tour_unit_prod = &tour_unit_prod,
             .tour_unit_expand = &tour_unit_expand,
             .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod,
-            .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply};
+            .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply,
+            .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse};
         return &ops;
     }
 };

@@ -1028,6 +1028,96 @@ class FieldContext:
         _ffi.check(self._L.ffgpu_norm_apply(self._h, bits.ptr, ptrs, lam, nrows, l, out.ptr, n, self._stream()), 'norm_apply')
         return out
 
+    # ---- logarithm and exponential: the local steps under runtime.np_log / np_exp2 (runtime.py:4853-4945) that the calls above
+    # do not serve (include/ffgpu_math.h), prime fields.  A block of powers is power-major: row j holds y^(j+1) for the n
+    # elements, rows `stride` elements apart (default n) ----
+    POLY_MAX_TERMS = 64
+
+    def _power_rows(self, what: str, P: DevArray, n: int, rows: int, stride: Optional[int]) -> int:
+        stride = n if stride is None else stride
+        if self.binary:
+            raise NotImplementedError(f'{what}: prime fields only')
+        if n < 0 or rows < 1 or stride < n:
+            raise ValueError(f'{what}: at least one row of n elements, rows at least n elements apart')
+        self._same(P.n, P, what=f'{what} block')
+        if P.n < (rows - 1) * stride + n:
+            raise ValueError(f'{what}: the block has {P.n} elements, {rows} rows of {n} need {(rows - 1) * stride + n}')
+        return stride
+
+    def powers_prod(self, P: DevArray, n: int, h: int, w: int, stride: Optional[int] = None, out: Optional[DevArray] = None) -> DevArray:
+        """out[j*n + e] = P[(h-1)*stride + e] * P[j*stride + e] for j < w <= h, dense (w, n): the top power of a block of h
+        powers times its w lowest -- the local products of one doubling step of np_vander's ladder (runtime.py:4966-4967).
+        out may be a view of the same block from row h on."""
+        if not 1 <= w <= h:
+            raise ValueError('powers_prod: 1 <= w <= h')
+        stride = self._power_rows('powers_prod', P, n, h, stride)
+        out = self._out(w * n, out, 'powers_prod output')
+        _ffi.check(self._L.ffgm_powers_prod(self._h, P.ptr, stride, h, w, out.ptr, n, self._stream()), 'powers_prod')
+        return out
+
+    def poly_table(self, coefs: Sequence[int]) -> DevArray:
+        """The device table of poly_dot from 1 to 64 public integer coefficients (negative values are reduced mod p)."""
+        if self.binary:
+            raise ValueError('poly_table: prime fields only')
+        if not 1 <= len(coefs) <= self.POLY_MAX_TERMS:
+            raise ValueError(f'poly_table: 1 to {self.POLY_MAX_TERMS} coefficients')
+        return self.from_ints([int(c) % self.modulus for c in coefs])
+
+    def poly_dot(self, P: DevArray, n: int, tab: DevArray, c0: int, stride: Optional[int] = None, out: Optional[DevArray] = None) -> DevArray:
+        """out[e] = c0 + sum_j tab[j] * P[j*stride + e] over the tab.n rows of the block: a polynomial without its constant
+        term in the powers y^1.., plus the public constant (runtime.py:4887, 4934)."""
+        if not 1 <= tab.n <= self.POLY_MAX_TERMS:
+            raise ValueError(f'poly_dot: 1 to {self.POLY_MAX_TERMS} coefficients')
+        self._same(tab.n, tab, what='poly_dot table')
+        stride = self._power_rows('poly_dot', P, n, tab.n, stride)
+        out = self._out(n, out, 'poly_dot output')
+        _ffi.check(self._L.ffgm_poly_dot(self._h, P.ptr, stride, tab.n, tab.ptr, self._scalars([int(c0) % self.modulus]), out.ptr, n,
+                                         self._stream()), 'poly_dot')
+        return out
+
+    def _pow_bits(self, what: str, ebits: int) -> int:
+        if self.binary:
+            raise NotImplementedError(f'{what}: prime fields only')
+        if not 1 <= ebits <= self.modulus.bit_length():
+            raise ValueError(f'{what}: 1 <= ebits <= bit length of the modulus')
+        return (ebits + 3) // 4
+
+    def pow_table(self, g: int, ebits: int) -> DevArray:
+        """The fixed-base window table of pow_base for exponents below 2^ebits: g^(d * 16^i) at 15*i + d - 1, d = 1..15,
+        i < ceil(ebits/4).  g: a public integer, reduced mod p (g^-1 is pow(g, -1, p))."""
+        nwin, p = self._pow_bits('pow_table', ebits), self.modulus
+        tab, base = [], int(g) % p
+        for _ in range(nwin):
+            v = 1
+            for _ in range(15):
+                v = v * base % p
+                tab.append(v)
+            base = v * base % p                         # g^(16^(i+1))
+        return self.from_ints(tab)
+
+    def pow_base(self, x: DevArray, tab: DevArray, ebits: int, shift: int = 0, out: Optional[DevArray] = None) -> DevArray:
+        """out[e] = g^(x[e] >> shift) for the g of pow_table(g, ebits), x[e] as its canonical integer; the caller guarantees
+        x[e] >> shift < 2^ebits (runtime.py:1408, 1421-1422)."""
+        nwin = self._pow_bits('pow_base', ebits)
+        if not 0 <= shift < 192:
+            raise ValueError('pow_base: 0 <= shift < 192')
+        self._same(15 * nwin, tab, what='pow_base table')
+        out = self._out(x.n, out, 'pow_base output')
+        _ffi.check(self._L.ffgm_pow_base(self._h, x.ptr, shift, ebits, tab.ptr, out.ptr, x.n, self._stream()), 'pow_base')
+        return out
+
+    def bits_reverse(self, bits: DevArray, l: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[h*l + j] = bits[h*l + l-1-j] over the element-major (n, l) bits of bits_finish, 1 <= l <= 64: np_flip along the
+        bit axis (runtime.py:4876)."""
+        if self.binary:
+            raise NotImplementedError('bits_reverse: prime fields only')
+        n = self._bit_matrix('bits_reverse', bits, l, 1)
+        if l > 64:
+            raise ValueError('bits_reverse: l <= 64')
+        out = self._out(n * l, out, 'bits_reverse output')
+        _ffi.check(self._L.ffgm_bits_reverse(self._h, bits.ptr, l, out.ptr, n, self._stream()), 'bits_reverse')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = self._out(a.n, out)

@@ -876,3 +876,226 @@ def aes128_decrypt(ctx: FieldContext, field, K, state: Shares, nblk: int, rbits_
             nxt.append(_cat(ctx, [_row(ctx, x, r + 4 * ((c - r) % 4), nblk) for c in range(4) for r in range(4)]))
         s = sbox1_layer(ctx, field, nxt, rbits_fn(16 * nblk), t, A, B, rng=rng)
     return [ctx.add(s[pi], K[0][pi]) for pi in range(m)]
+
+
+# ---- fixed point: logarithm, exponential and powers (runtime.np_vander, runtime.py:4947-4977; np_log, np_log2, np_log10,
+# np_exp2, np_exp, runtime.py:4853-4945; _np_pow_public_int_base_secret_integral_exponent, runtime.py:1389-1425) -----------------
+# On RAW integers as above.  A public float c enters a product as the reference's np_multiply takes it (runtime.py:1114-1140):
+# b = round(c 2^f) loses its z <= f trailing zero bits, the product is truncated by f - z bits.
+def _public_float(c: float, f: int):
+    """(b >> z, f - z) for the public float c: the integer factor and the bits to truncate afterwards"""
+    b = round(c * 2**f)
+    z = max(0, min(f, (b & -b).bit_length() - 1))
+    return b >> z, f - z
+
+
+def _mul_public_float(ctx: FieldContext, field, xs: Shares, c: float, t: int, f: int, l: int, rand_trunc) -> Shares:
+    b, shift = _public_float(c, f)
+    prod = [ctx.mul_scalar(x, b % ctx.modulus) for x in xs]
+    if shift == 0:
+        return prod
+    rbits, rdivf = rand_trunc(xs[0].n, shift)
+    return trunc(ctx, field, prod, rbits, rdivf, t, shift, l + shift)
+
+
+def taylor_log_degree(f: int) -> int:
+    """runtime._taylor_log_degree (runtime.py:4855-4863): the degree k with 1/(k+1) w^-(k+1) <= 2^-f, w = 1/(sqrt 2 - 1)"""
+    import math
+    w = 1 / (math.sqrt(2) - 1)
+    k = f - 1
+    while math.log2(k) + k * math.log2(w) >= f:
+        k -= 1
+    return k
+
+
+def taylor_exp2_degree(f: int) -> int:
+    """runtime._taylor_exp2_degree (runtime.py:4903-4911)"""
+    import math
+    log2ln2 = math.log2(math.log(2))
+    k = 1
+    log2factorial = 1
+    while log2factorial - (k + 1) * log2ln2 < f + 1:
+        k += 1
+        log2factorial += math.log2(k + 1)
+    return k
+
+
+def power_ladder(N: int):
+    """The rounds (h, w) of np_vander's doubling recursion f(N) (runtime.py:4959-4968), first round first: from the powers
+    y^1..y^h, y^h times the w lowest gives y^(h+1)..y^(h+w); h = ceil(n/2) and w = n - h at every level n of the recursion."""
+    if N <= 1:
+        return []
+    h = (N + 1) // 2
+    return power_ladder(h) + [(h, N - h)]
+
+
+def powers(ctx: FieldContext, field, ys: Shares, N: int, t: int, f: int, l: int, rand_trunc, rng=None) -> Shares:
+    """The columns y^1..y^N of runtime.np_vander for a fixed-point sharing, for all parties: every party's POWER-MAJOR (N, n)
+    block, row j = y^(j+1).  The rounds are exactly those of the reference's recursion (power_ladder) -- which power
+    multiplies which fixes every rounding.  Per round (h, w)
+      powers_prod on the first 2t+1 parties: y^h times the w lowest powers (ffgm_powers_prod),
+      they re-share it (ffgpu_split_rng) and every party recombines into rows h.. of its block,
+      trunc() by f bits with L = l + f over the w n new elements.
+    rand_trunc: as for fxp_multiply().  Needs m >= 2t+1 parties; ys is not written."""
+    m = len(ys)
+    kk = _parties('powers', t, m)
+    n = ys[0].n
+    if N < 1 or any(y.n != n for y in ys):
+        raise ValueError('powers: N >= 1 and shares of one length')
+    blocks = [ctx.empty(N * n) for _ in range(m)]
+    for b, y in zip(blocks, ys):
+        _rows(ctx, b, 0, 1, n).t.copy_(y.t)
+    for h, w in power_ladder(N):
+        sub = reshare(ctx, field, [ctx.powers_prod(blocks[i], n, h, w) for i in range(kk)], t, m, rng)
+        new = [_rows(ctx, b, h, h + w, n) for b in blocks]
+        for j in range(m):
+            ctx.recombine(sub.rows[j], sub.lam, out=new[j])
+        rbits, rdivf = rand_trunc(w * n, f)
+        for v, r in zip(new, trunc(ctx, field, new, rbits, rdivf, t, f, l + f)):
+            v.t.copy_(r.t)
+    return blocks
+
+
+def _taylor(ctx: FieldContext, field, ys: Shares, coefs, c0: int, t: int, f: int, l: int, rand_trunc, rng) -> Shares:
+    """c0 + sum_j coefs[j] y^(j+1) on raw integers, truncated by f bits: powers(), one poly_dot per party, one trunc()."""
+    n = ys[0].n
+    blocks = powers(ctx, field, ys, len(coefs), t, f, l, rand_trunc, rng)
+    tab = ctx.poly_table(coefs)
+    acc = [ctx.poly_dot(b, n, tab, c0) for b in blocks]
+    rbits, rdivf = rand_trunc(n, f)
+    return trunc(ctx, field, acc, rbits, rdivf, t, f, l + f)
+
+
+def log(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits, rand_trunc, rng=None) -> Shares:
+    """runtime.np_log for all parties: the natural logarithm of a fixed-point sharing, a > 0.  Steps:
+      to_bits of the l - 1 bits below the sign bit, bits_reverse (ffgm_bits_reverse),
+      find(..., s=1, cs_f=lambda b, i: (i+1+b, (b+1) << i)): k = 1 + the number of leading zeros and v = 2^(k-1),
+      v scaled by the public 2^(2f-l+1) (2^(f-l+1) as a fixed-point number), b = fxp_multiply(a, v) in [1/2, 1),
+      y = b - round(2^f / sqrt 2), the Taylor polynomial of degree taylor_log_degree(f) in y around 1/sqrt 2: powers(),
+      poly_dot with the coefficients round(c_i 2^f) and the constant round(log(1/sqrt 2) 2^f) 2^f (ffgm_poly_dot), one trunc(),
+      minus (k - f) round(log 2 * 2^f), local.
+    rand_bits and rand_trunc: as for norm() and fxp_multiply().  Requires f + 2 <= l <= 2f + 1 (below, the reference takes an
+    integral path without truncation; above, its scale factor rounds to 0).  Needs m >= 2t+1 parties; xs is not written."""
+    import math
+    import numpy as np
+    if not f + 2 <= l <= 2 * f + 1:
+        raise ValueError('log: f + 2 <= l <= 2f + 1')
+    m = len(xs)
+    _parties('log', t, m)
+    n = xs[0].n
+    if any(x.n != n for x in xs):
+        raise ValueError('log: shares of one length')
+    p = ctx.modulus
+    rbits, rdivl = rand_bits(n, l - 1)
+    bits = to_bits(ctx, field, xs, rbits, rdivl, t, l - 1, offset=1 << l, rng=rng)
+    rev = [ctx.bits_reverse(b, l - 1) for b in bits]
+    k, v = find(ctx, field, rev, n, l - 1, 1, t, s=1, cs_f=lambda b, i: (i + 1 + b, (b + 1) << i), rng=rng)
+    v = [ctx.mul_scalar(x, 1 << (2 * f - l + 1)) for x in v]
+    b = fxp_multiply(ctx, field, xs, v, t, f, l, rand_trunc, rng)
+    alpha = 0.5 * math.sqrt(2)
+    y = [ctx.add_scalar(x, -round(alpha * 2**f) % p) for x in b]
+    i = np.arange(1, taylor_log_degree(f) + 1)
+    coefs = [int(c) for c in np.vectorize(round, otypes='O')((-1 / (i * (-alpha)**i)) * 2**f)]
+    c = _taylor(ctx, field, y, coefs, (round(math.log(alpha) * 2**f) << f) % p, t, f, l, rand_trunc, rng)
+    ln2, _ = _public_float(math.log(2), f)
+    ln2 <<= f - _
+    # c - (k - f) ln2 = c + f ln2 - k ln2
+    return [ctx.add_scalar(ctx.sub(cj, ctx.mul_scalar(kj, ln2 % p)), f * ln2 % p) for cj, kj in zip(c, k)]
+
+
+def log2(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits, rand_trunc, rng=None) -> Shares:
+    """runtime.np_log2: log() times the public float log2(e)."""
+    import math
+    return _mul_public_float(ctx, field, log(ctx, field, xs, t, l, f, rand_bits, rand_trunc, rng), math.log2(math.e), t, f, l, rand_trunc)
+
+
+def log10(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_bits, rand_trunc, rng=None) -> Shares:
+    """runtime.np_log10: log() times the public float log10(e)."""
+    import math
+    return _mul_public_float(ctx, field, log(ctx, field, xs, t, l, f, rand_bits, rand_trunc, rng), math.log10(math.e), t, f, l, rand_trunc)
+
+
+def _pow_public_base(ctx: FieldContext, field, g: int, bs: Shares, t: int, l: int, shift: int, rand_exp, rng, sec_param: int) -> Shares:
+    """Shares of g^(b >> shift) as plain integers (not scaled by 2^f), b a multiple of 2^shift."""
+    m = len(bs)
+    _parties('pow_public_base', t, m)
+    n = bs[0].n
+    if any(b.n != n for b in bs):
+        raise ValueError('pow_public_base: shares of one length')
+    p = ctx.modulus
+    rbound = 1 << (l + sec_param) // (t + 1)
+    rs = rand_exp(n, rbound)
+    if len(rs) != t + 1 or any(r.n != n for r in rs):
+        raise ValueError('pow_public_base: t+1 senders draw n exponents each')
+    rbits = max(1, (rbound - 1).bit_length())
+    inv_tab = ctx.pow_table(pow(g, -1, p), rbits)
+    r_sh = [share(ctx, r, t, m, rng) for r in rs]
+    gr_sh = [share(ctx, ctx.pow_base(r, inv_tab, rbits), t, m, rng) for r in rs]
+    rsum, gr = r_sh[0], gr_sh[0]
+    for i in range(1, t + 1):
+        rsum = [ctx.add(a, b) for a, b in zip(rsum, r_sh[i])]
+        gr = multiply(ctx, field, gr, gr_sh[i], t, rng)
+    masked = [ctx.add(b, ctx.mul_scalar(r, (1 << shift) % p)) for b, r in zip(bs[:t + 1], rsum)]
+    c = open_(ctx, field, masked, t)
+    ebits = max(l - shift, rbits + (t + 1).bit_length()) + 1
+    if ebits > p.bit_length():
+        raise ValueError('pow_public_base: the masked exponent does not fit the field')
+    gc = ctx.pow_base(c, ctx.pow_table(g, ebits), ebits, shift=shift)
+    return [ctx.mul(gc, x) for x in gr]
+
+
+def pow_public_base(ctx: FieldContext, field, g: int, bs: Shares, t: int, l: int, f: int, rand_exp, rng=None,
+                    sec_param: int = 30) -> Shares:
+    """runtime._np_pow_public_int_base_secret_integral_exponent for all parties: g^b for a public integer g and a sharing of
+    nonnegative INTEGRAL fixed-point exponents (raw b = B 2^f); the result g^B 2^f is exact.  Steps:
+      each of the first t+1 parties draws r_i below 2^((l + sec_param) // (t+1)), computes g^(-r_i) (ffgm_pow_base on the
+      window table of g^-1) and shares both,
+      the r sharings are summed, the t+1 sharings of g^(-r_i) multiplied (multiply()),
+      b + r 2^f is opened, g^((b + r 2^f) >> f) computed (ffgm_pow_base, shift = f), every party multiplies it by its share
+      of g^(-r), and by 2^f.
+    rand_exp(count, bound) returns the t+1 senders' plain draws as DevArrays of `count` values below bound.  The caller
+    guarantees 0 <= B < 2^(l-f) and that b + r 2^f stays below p.  Needs m >= 2t+1 parties; bs is not written."""
+    return [ctx.mul_scalar(x, (1 << f) % ctx.modulus) for x in _pow_public_base(ctx, field, g, bs, t, l, f, rand_exp, rng, sec_param)]
+
+
+def exp2(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_trunc, rand_exp, rng=None, sec_param: int = 30) -> Shares:
+    """runtime.np_exp2 for all parties: 2^a for a fixed-point sharing.  Domain: -f <= a and 2^a < 2^(l-1-f) on the values
+    (below -f the reference itself returns field garbage).  Steps:
+      the integral part: trunc() by f bits at L = max_a_bit_length + f, max_a_bit_length = f + bit_length(l-1-f) + 1,
+      y = a_frac log 2 (a public float: one trunc()),
+      the Taylor polynomial of degree taylor_exp2_degree(f): powers(), poly_dot with round(2^f / j!) and the constant 2^2f
+      (ffgm_poly_dot), one trunc(),
+      2^(a_int + 2^(l-1-f)) by pow_public_base's steps, one multiply(),
+      the product by the public field element 2^(-2^(l-1-f)) 2^f and a last trunc() by f bits.
+    rand_trunc and rand_exp: as for fxp_multiply() and pow_public_base().  Needs m >= 2t+1 parties; xs is not written."""
+    import math
+    m = len(xs)
+    _parties('exp2', t, m)
+    n = xs[0].n
+    if any(x.n != n for x in xs) or not 1 <= f < l - 1:
+        raise ValueError('exp2: shares of one length, 1 <= f < l - 1')
+    p = ctx.modulus
+    mabl = f + (l - 1 - f).bit_length() + 1
+    rbits, rdivf = rand_trunc(n, f)
+    a_int = trunc(ctx, field, xs, rbits, rdivf, t, f, mabl + f)
+    a_frac = [ctx.sub(x, ctx.mul_scalar(ai, (1 << f) % p)) for x, ai in zip(xs, a_int)]
+    y = _mul_public_float(ctx, field, a_frac, math.log(2), t, f, l, rand_trunc)
+    theta = taylor_exp2_degree(f)
+    coefs, fact = [], 1
+    for j in range(1, theta + 1):
+        fact *= j
+        coefs.append(round((1 / fact) * 2**f))
+    c = _taylor(ctx, field, y, coefs, (1 << 2 * f) % p, t, f, l, rand_trunc, rng)
+    E = 1 << (l - 1 - f)
+    pw = _pow_public_base(ctx, field, 2, [ctx.add_scalar(ai, E % p) for ai in a_int], t, l - f, 0, rand_exp, rng, sec_param + f)
+    c = multiply(ctx, field, c, pw, t, rng)
+    c = [ctx.mul_scalar(x, pow(2, -E, p) * (1 << f) % p) for x in c]
+    rbits, rdivf = rand_trunc(n, f)
+    return trunc(ctx, field, c, rbits, rdivf, t, f, l + f)
+
+
+def exp(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_trunc, rand_exp, rng=None, sec_param: int = 30) -> Shares:
+    """runtime.np_exp: exp2() of a times the public float log2(e)."""
+    import math
+    return exp2(ctx, field, _mul_public_float(ctx, field, xs, math.log2(math.e), t, f, l, rand_trunc), t, l, f, rand_trunc, rand_exp,
+                rng, sec_param)
