@@ -1071,6 +1071,7 @@ int ffgpu_recombine(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t
 // matrices that take the matrix-core, skinny or split-K routes)
 static int matmul_one(ffgpu_ctx* ctx, const CallScope& cs, const void* A, size_t lda, const void* B, size_t ldb, void* C, size_t ldc,
                       size_t M, size_t K, size_t N) {
+    // (restated in tests/matmul_contract.py, plan() -- move the two together)
     // scratch: int8 digit planes for the matrix-core product plus 64 MiB of split-K slabs (up to 8 GiB), else 64 MiB of
     // split-K partial sums.  (Asked for in whole 8 / 16 planes per operand: more than the 4 and 12 digits of 4- and
     // 12-byte elements need, and the split-K plans of the launcher see the size.)

@@ -248,6 +248,7 @@ inline bool dispatch_int(std::integer_sequence<int, V...>, int v, Fn&& fn) {
 // decision: ffgpu_matmul sizes the scratch with it, Launchers::matmul takes the route with it.
 // (from 9 rows / columns on: the tiles are padded to 64 -- a batch of 9..63 rows against 4096 x 4096 takes the 88 us of
 // 64 rows instead of 670-690 us on the vector ALUs)
+// (restated in tests/matmul_contract.py -- move the two together)
 inline size_t mfma_plane_bytes(const LaunchCfg& lc, size_t digits, size_t M, size_t K, size_t N) {
     if (!lc.mm_mfma || M <= SKINNY_MAX || N <= SKINNY_MAX || K < 64 || (double)M * N * K < lc.mm_mfma_min) return 0;
     const size_t Mp = (M + 63) / 64 * 64, Np = (N + 63) / 64 * 64, Kp = (K + 31) / 32 * 32;
@@ -636,6 +637,7 @@ struct Launchers {
     }
 
     // skinny shapes (one output dimension <= 8): HBM-bound kernels that read the big operand once
+    // (every choice from here to Launchers::matmul is restated in tests/matmul_contract.py, plan() -- move the two together)
     template <int NN>
     static void go_matvec(const F& f, const E* A, size_t lda, const E* B, size_t ldb, E* C, size_t ldc, int M, int K,
                           int N, hipStream_t st) {

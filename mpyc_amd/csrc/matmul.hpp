@@ -135,7 +135,7 @@ __global__ __launch_bounds__(BLOCK) void k_splitk_sum(F f, const typename F::ele
 // accumulator half of the register file; 4 waves per workgroup (64x64).
 typedef int ff_v4i __attribute__((ext_vector_type(4)));
 typedef int ff_v16i __attribute__((ext_vector_type(16)));
-enum { LIMB_KCHUNK = 8192 };
+enum { LIMB_KCHUNK = 8192 };          // (restated in tests/matmul_contract.py -- move the two together)
 
 // Digit-plane layout: TILED so that what a workgroup fetches per k-step is contiguous.  The digits of a 64-row block
 // for one 32-wide k-step form one block of L x 2 KiB, [digit l][k half][row][16 k] -- byte for byte the LDS image
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(BLOCK) void k_limb_gemm_glds(F f, const int8_t* __r
 // product runs in PASSES over ranges of diagonals [D0, D0+NDP): a pass issues only the MFMAs whose digit pair lies
 // on its diagonals (the work adds up to L^2 per k-step over all passes), evaluates its part by Horner and adds
 // 256^D0 times it to C.  K chunks of 4096 keep the i32 accumulators exact (16 * 128^2 * 4096 = 2^30).
-enum { LIMB_KCHUNK_WIDE = 4096 };
+enum { LIMB_KCHUNK_WIDE = 4096 };     // (restated in tests/matmul_contract.py -- move the two together)
 
 template <class F, int L>
 __global__ __launch_bounds__(BLOCK) void k_limb_split_a_wide(const typename F::elem* __restrict__ A, size_t lda, uint64_t plo,
@@ -624,6 +624,7 @@ __global__ __launch_bounds__(BLOCK) void k_limb_gemm_wide(F f, const int8_t* __r
 // read exactly once, coalesced, the small one stays in L2; products are accumulated unreduced (flush every
 // DotAcc<F>::FLUSH terms) and reduced once.
 enum { SKINNY_MAX = 8, SKINNY_FLUSH = 192 };    // SKINNY_FLUSH: the flush bound of the ColAcc kernels
+// (these two, MATVEC_SUB_KT, VECMAT_KT, VECMAT_COL_KT and VECMAT_FINAL_G are restated in tests/matmul_contract.py -- move them together)
 // (the column-sum kernels below test the count AFTER adding a whole group of terms: a flush happens at no more than
 // SKINNY_FLUSH - 1 + group terms, which must stay within ColAcc::MAX_TERMS = 256 -- asserted where each group size is known)
 

@@ -792,14 +792,16 @@ def test_skinny_products(eng, coracle):
             coracle.set_threads(1)
             assert (got == want).all(), (hex(modulus), M, K, N)
     # every operand p - 1, every M of the few-rows kernels (one instantiation each for one-word primes: column sums of
-    # 22 x 32-bit partial products, flushed every 192 terms), packed and ragged column counts
-    # (round 6: the multi-limb 2^k - c primes accumulate in 28-bit digits, flushed every 32 terms: the same at their extremes)
+    # 22 x 32-bit partial products), packed and ragged column counts; the multi-limb 2^k - c primes accumulate in 28-bit digits.
+    # (K is cut into chunks of 8 rows at these shapes, (6, 33, 300) goes to the tiled kernel: no accumulator is flushed here.
+    # The flushes -- 192 terms, 32 for the digits -- and the staged tiles are reached by tests/test_gpu_matmul_contract.py,
+    # whose plan() says which kernel a shape takes.)
     for modulus in (P61, P64, 6616326157076047771, 2**40 - 87, 2**80 - 65, 2**96 - 17, P128, 2**136 - 113):
         ctx = ctx_for(eng, modulus, False)
         eb = ctx.elem_bytes
         if eb > 8:
             rng_ = random.Random(eb)
-            for (M, K, N) in ((3, 97, 70), (8, 1000, 129), (6, 33, 300)):           # random operands, ragged K around the flush
+            for (M, K, N) in ((3, 97, 70), (8, 1000, 129), (6, 33, 300)):           # random operands, ragged K
                 a = [rng_.randrange(modulus) for _ in range(M * K)]
                 b = [rng_.randrange(modulus) for _ in range(K * N)]
                 got = unpack(ctx.matmul(ctx.from_numpy(pack(a, eb)), ctx.from_numpy(pack(b, eb)), M, K, N).to_numpy(), eb)
@@ -811,8 +813,9 @@ def test_skinny_products(eng, coracle):
                 B = pack([modulus - 1] * (K * N), eb)
                 got = unpack(ctx.matmul(ctx.from_numpy(A), ctx.from_numpy(B), M, K, N).to_numpy(), eb)
                 assert got == [K * (modulus - 1) ** 2 % modulus] * (M * N), (hex(modulus), M, K, N)
-        # matrix x few columns (k_matvec_rows_col: one instantiation per N, one or two rows per workgroup, the last workgroup
-        # ragged), K beyond one flush of a thread's column sums (192 terms x 256 threads)
+        # matrix x few columns, one instantiation per N: an even K takes k_matvec_sub_col<., ., 64>, an odd one -- an odd
+        # leading dimension -- the scalar loop of k_matvec_rows_col (one or two rows per workgroup, the last workgroup ragged),
+        # which at K = 60001 flushes a thread's column sums (235 terms)
         for N in range(2, 9):
             for (M, K) in ((71, 1000 + N), (130, 389)) + (((64, 60001),) if N in (3, 8) else ()):
                 A = pack([modulus - 1] * (M * K), eb)
