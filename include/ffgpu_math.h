@@ -1,7 +1,8 @@
 /*
  * ffgpu_math.h -- second header of libffgpu.so: the local steps under the secure logarithm and exponential of fixed-point
- * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945) that no entry of ffgpu.h serves.  Same
- * library, same contexts (ffgpu_ctx of ffgpu.h), same conventions:
+ * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945) and under the probabilistic zero test over a
+ * Blum prime (runtime._np_is_zero, runtime.py:3581-3620) that no entry of ffgpu.h serves.  Same library, same contexts
+ * (ffgpu_ctx of ffgpu.h), same conventions:
  *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
  *   - array arguments are DEVICE pointers unless the name says host; elements are canonical little-endian limbs in the
  *     layouts ffgpu.h lists, host scalars little-endian 64-bit limbs, ffgpu_ctx_scalar_limbs() of them;
@@ -12,7 +13,7 @@
  *   - an output that overlaps an input is FFGPU_EINVAL (the one exception is stated at ffgm_powers_prod);
  *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
- * log2(), log10(), pow_public_base(), exp2() and exp().
+ * log2(), log10(), pow_public_base(), exp2() and exp(), and into is_zero() and equal().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -34,9 +35,22 @@
  * ffgm_bits_reverse: out[h*l + j] = bits[h*l + l-1-j] for the element-major (n, l) bits of ffgpu_bits_finish, 1 <= l <= 64.
  *   replaces: runtime.py:4876 (np_flip along the bit axis).
  *
- * FFGPU_OK: n == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or theta > 64;
- * ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; a size overflowing; an output
- * overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context.                                                              */
+ * The masked copies of the zero test are ROW-MAJOR (k, n): row i holds the i-th copy of the n elements, rows n elements
+ * apart (the layout ffgpu_prod_rows consumes); count = k*n entries.  A code is one BYTE per entry.
+ *
+ * ffgm_iszero_mask: out[i*n + e] = a[e]*r[i*n + e] + (1 - 2*z[i*n + e])*u2[i*n + e] for i < k, k >= 1.  z holds SHARES of
+ *   bits (arbitrary field elements): two full products per entry, accumulated lazily, one reduction.  A thread keeps its
+ *   elements of `a` in registers across the k rows: (4k + 1)*n elements of traffic.
+ *   replaces: runtime.py:3608 (`a * r + (1 - (z << 1)) * u2`, the broadcast of a over the k rows included).
+ * ffgm_legendre_code: code[j] = 2 if c[j] == 0, else 1 if c[j]^((p-1)/2) == 1 (a quadratic residue), else 0.  The
+ *   exponentiation is the one ffgpu_pow launches for this exponent; only the ends differ.  p odd: FFGPU_ENOTSUP for p == 2.
+ *   replaces: finfields.py:1464-1470 (is_sqr: the Legendre symbols by gmpy2.legendre) and the test `c == 0` of runtime.py:3614.
+ * ffgm_iszero_finish: out[j] = z[j] if code[j] == 0, 1 - z[j] if code[j] == 1, 1 if code[j] == 2 (0 counts as a square).
+ *   replaces: runtime.py:3614-3615 (`np.where(c == 0, 0, z)`, `np.where(is_sqr, 1 - z, z)` and the 1 of a zero).
+ *
+ * FFGPU_OK: n == 0 / count == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or
+ * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; a size
+ * overflowing; an output overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context; ffgm_legendre_code over p == 2.       */
 #ifndef FFGPU_MATH_H
 #define FFGPU_MATH_H
 
@@ -51,6 +65,10 @@ int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const
                   void* stream);
 int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const void* tab, void* out, size_t n, void* stream);
 int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t n, void* stream);
+int ffgm_iszero_mask(ffgpu_ctx* ctx, const void* a, const void* r, const void* z, const void* u2, int k, void* out, size_t n,
+                     void* stream);
+int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t count, void* stream);
+int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void* out, size_t count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,9 @@ _SIGS_MATH = {
     'ffgm_poly_dot': [_vp, _vp, _sz, _int, _vp, _u64p, _vp, _sz, _vp],
     'ffgm_pow_base': [_vp, _vp, _int, _int, _vp, _vp, _sz, _vp],
     'ffgm_bits_reverse': [_vp, _vp, _int, _vp, _sz, _vp],
+    'ffgm_iszero_mask': [_vp, _vp, _vp, _vp, _vp, _int, _vp, _sz, _vp],
+    'ffgm_legendre_code': [_vp, _vp, _vp, _sz, _vp],
+    'ffgm_iszero_finish': [_vp, _vp, _vp, _vp, _sz, _vp],
 }
 EXPORTED_MATH = tuple(_SIGS_MATH)
 

@@ -788,27 +788,38 @@ static bool inverse_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
     return true;
 }
 
+// the Legendre exponent (p - 1) / 2 of an odd prime field
+static void legendre_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
+    if (three_limb_prime(ctx)) {
+        uint64_t l1[3];
+        sub_small3(ctx->modulus, 1, l1);
+        shr1_3(l1);
+        make_exp(l1, 3, ex);
+    } else {
+        const ff_u128 e1 = (ff_make128(ctx->modulus[1], ctx->modulus[0]) - 1) >> 1;
+        const uint64_t l1[2] = {ff_lo(e1), ff_hi(e1)};
+        make_exp(l1, 2, ex);
+    }
+}
+
 int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
     if (ctx->kind != FFGPU_PRIME || (ctx->modulus[0] & 3) != 1) return FFGPU_ENOTSUP;
     if (n == 0) return FFGPU_OK;
     ARGCHK(a && out);
     ExpArgs eleg, elad;
+    legendre_exponent(ctx, &eleg);
     if (three_limb_prime(ctx)) {
-        uint64_t l1[3], l2[3];
-        sub_small3(ctx->modulus, 1, l1);                   // (p-1)/2
-        shr1_3(l1);
+        uint64_t l2[3];
         sub_small3(ctx->modulus, 1, l2);                   // (p+1)/2 = (p-1)/2 + 1 (p odd: the low limb cannot wrap)
         shr1_3(l2);
         l2[0] += 1;
         if (l2[0] == 0 && ++l2[1] == 0) ++l2[2];
-        make_exp(l1, 3, &eleg);
         make_exp(l2, 3, &elad);
     } else {
         ff_u128 p = ff_make128(ctx->modulus[1], ctx->modulus[0]);
-        ff_u128 e1 = (p - 1) >> 1, e2 = (p >> 1) + 1;      // (p-1)/2 and (p+1)/2 (p odd; no overflow at 128 bits)
-        uint64_t l1[2] = {ff_lo(e1), ff_hi(e1)}, l2[2] = {ff_lo(e2), ff_hi(e2)};
-        make_exp(l1, 2, &eleg);
+        ff_u128 e2 = (p >> 1) + 1;                         // (p+1)/2 (p odd; no overflow at 128 bits)
+        uint64_t l2[2] = {ff_lo(e2), ff_hi(e2)};
         make_exp(l2, 2, &elad);
     }
     CallScope cs(ctx, stream);
@@ -1742,6 +1753,52 @@ int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t
     ARGCHK(outputs_disjoint(&in, 1, &o, 1));
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->bits_reverse(ctx->policy, cs.lc, bits, l, out, n, cs.st));
+}
+
+// ---- the Legendre zero test over a Blum prime: the local steps of runtime._np_is_zero (iszero.hpp; include/ffgpu_math.h) ----
+int ffgm_iszero_mask(ffgpu_ctx* ctx, const void* a, const void* r, const void* z, const void* u2, int k, void* out, size_t n,
+                     void* stream) {
+    PRIME_CTX(ctx);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(iszero_mask_plan(n, k, eb, false).ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && r && z && u2 && out);
+    const size_t kn = iszero_mask_plan(n, k, eb, false).span * eb;
+    const ByteRange in[4] = {byte_range(a, n * eb), byte_range(r, kn), byte_range(z, kn), byte_range(u2, kn)};
+    const ByteRange o = byte_range(out, kn);
+    ARGCHK(outputs_disjoint(in, 4, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->iszero_mask(ctx->policy, cs.lc, a, r, z, u2, k, out, n, cs.st));
+}
+
+int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t count, void* stream) {
+    PRIME_CTX(ctx);
+    if (!ctx->modulus[2] && !ctx->modulus[1] && ctx->modulus[0] == 2) return FFGPU_ENOTSUP;
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(legendre_plan(count, eb, false).ok);
+    if (count == 0) return FFGPU_OK;
+    ARGCHK(c && code);
+    const ByteRange in = byte_range(c, count * eb);
+    const ByteRange o = byte_range(code, count);
+    ARGCHK(outputs_disjoint(&in, 1, &o, 1));
+    ExpArgs ex;
+    legendre_exponent(ctx, &ex);
+    exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->legendre_code(ctx->policy, cs.lc, c, &ex, code, count, cs.st));
+}
+
+int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void* out, size_t count, void* stream) {
+    PRIME_CTX(ctx);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(iszero_flat_plan(count, eb, false).ok);
+    if (count == 0) return FFGPU_OK;
+    ARGCHK(code && z && out);
+    const ByteRange in[2] = {byte_range(code, count), byte_range(z, count * eb)};
+    const ByteRange o = byte_range(out, count * eb);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->iszero_finish(ctx->policy, cs.lc, code, z, out, count, cs.st));
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,

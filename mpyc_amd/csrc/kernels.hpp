@@ -1321,13 +1321,15 @@ __device__ __forceinline__ typename F::word ff_pow_digits(const F& f, typename F
 }
 
 // ---- out = a^e, public exponent e >= 1 (finfields.py:1159-1187, :1408-1414) ------------------
-template <class F, bool NT>
-__global__ __launch_bounds__(BLOCK) void k_pow(F f, const typename F::elem* __restrict__ a, ExpArgs ex,
-                                                typename F::elem* __restrict__ o, size_t nvec, size_t n) {
+// The body is generic over where a result goes: put.pack(i, x, r) takes pack i of the vector loop, put.elem(e, x, r) element e
+// of the scalar tail (x: the operand, r = x^e canonical).  k_pow stores the powers; k_legendre_code (iszero.hpp) compares
+// them against one and stores a byte.
+template <class F, bool NT, class Put>
+__device__ __forceinline__ void pow_stream(const F& f, const typename F::elem* __restrict__ a, const ExpArgs& ex, size_t nvec, size_t n,
+                                           const Put& put) {
     typedef Pack<typename F::word> P;
     typedef typename MemPack<F>::type MP;
     const MP* __restrict__ av = reinterpret_cast<const MP*>(a);
-    MP* __restrict__ ov = reinterpret_cast<MP*>(o);
     const size_t gid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     const size_t gsz = (size_t)gridDim.x * BLOCK;
     for (size_t i = gid; i < nvec; i += gsz) {
@@ -1335,10 +1337,26 @@ __global__ __launch_bounds__(BLOCK) void k_pow(F f, const typename F::elem* __re
         P r;
 #pragma unroll
         for (int q = 0; q < P::N; ++q) r.w[q] = ff_pow_digits(f, x.w[q], ex);
-        stg<NT>(ov + i, r);
+        put.pack(i, x, r);
     }
     const size_t done = nvec * (size_t)(P::N * F::EPW);
-    for (size_t e = done + gid; e < n; e += gsz) st_elem<F>(o, e, ff_pow(f, ld_elem<F>(a, e), ex));
+    for (size_t e = done + gid; e < n; e += gsz) {
+        const typename F::word x = ld_elem<F>(a, e);
+        put.elem(e, x, ff_pow(f, x, ex));
+    }
+}
+template <class F, bool NT>
+struct PowPutElems {
+    typedef Pack<typename F::word> P;
+    typedef typename MemPack<F>::type MP;
+    typename F::elem* __restrict__ o;
+    __device__ __forceinline__ void pack(size_t i, const P&, const P& r) const { stg<NT>(reinterpret_cast<MP*>(o) + i, r); }
+    __device__ __forceinline__ void elem(size_t e, const typename F::word&, const typename F::word& r) const { st_elem<F>(o, e, r); }
+};
+template <class F, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_pow(F f, const typename F::elem* __restrict__ a, ExpArgs ex,
+                                                typename F::elem* __restrict__ o, size_t nvec, size_t n) {
+    pow_stream<F, NT>(f, a, ex, nvec, n, PowPutElems<F, NT>{o});
 }
 
 // ---- out = a^-1, batched (finfields.py:1278-1281, :1416-1422) ----------------------------------
@@ -2284,4 +2302,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "find.hpp"     // the ends of a round of the first-occurrence search (np_find)
 #include "fxp.hpp"      // local steps of fixed-point truncation and normalisation (np_trunc, _norm)
 #include "explog.hpp"   // local steps under the secure logarithm and exponential (np_log, np_exp2)
+#include "iszero.hpp"   // local steps of the Legendre zero test over a Blum prime (_np_is_zero)
 #include "launch.hpp"   // host side: FieldOps table + launchers

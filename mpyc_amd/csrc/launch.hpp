@@ -185,6 +185,15 @@ struct FieldOps {
     LaunchStatus (*pow_base)(const void* F, const LaunchCfg& lc, const void* x, int shift, int ebits, int pbits, const void* tab, void* out,
                     size_t n, hipStream_t st);
     LaunchStatus (*bits_reverse)(const void* F, const LaunchCfg& lc, const void* bits, int l, void* out, size_t n, hipStream_t st);
+    // local steps of the Legendre zero test (iszero.hpp), prime fields only; the (k, n) arrays are row-major; ex of
+    // legendre_code: the exponent (p - 1) / 2 as ffgpu_pow hands it to pow (L_PLAN_REFUSED: iszero_mask_plan() /
+    // legendre_plan() / iszero_flat_plan() refuses the sizes or the count)
+    LaunchStatus (*iszero_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* r, const void* z, const void* u2, int k,
+                       void* out, size_t n, hipStream_t st);
+    LaunchStatus (*legendre_code)(const void* F, const LaunchCfg& lc, const void* c, const ExpArgs* ex, uint8_t* code, size_t count,
+                         hipStream_t st);
+    LaunchStatus (*iszero_finish)(const void* F, const LaunchCfg& lc, const uint8_t* code, const void* z, void* out, size_t count,
+                         hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1485,6 +1494,52 @@ struct Launchers {
             return launched();
         }
     }
+    // The local steps of the Legendre zero test (iszero.hpp).  mask and finish: one flat streaming loop, a unit (a pack where
+    // the plan admits packs, else an element) per thread up to the grid cap; whole packs also need the code bytes aligned to
+    // the one access that moves a pack's codes.  legendre_code is the launch of pow with a byte array for an output: the
+    // same packs through the vector loop and the same grid (legendre_plan restates plan(): tests/iszero_check.cpp).
+    static bool codes_al(const void* code) { return iszero_codes_aligned((uintptr_t)code, sizeof(E)); }
+    static LaunchStatus iszero_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* r, const void* z, const void* u2, int k,
+                           void* out, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const ExplogRowsPlan pl = iszero_mask_plan(n, k, sizeof(E), al(a) && al(r) && al(z) && al(u2) && al(out));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_iszero_mask<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)r,
+                               (const E*)z, (const E*)u2, k, (E*)out, pl);
+            return launched();
+        }
+    }
+    static LaunchStatus legendre_code(const void* Fp, const LaunchCfg& lc, const void* c, const ExpArgs* ex, uint8_t* code, size_t count,
+                             hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const LegendrePlan pl = legendre_plan(count, sizeof(E), al(c) && codes_al(code));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (count == 0) return L_OK;
+            hipLaunchKernelGGL((k_legendre_code<F>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, (const E*)c, *ex, code, pl.nvec,
+                               count);
+            return launched();
+        }
+    }
+    static LaunchStatus iszero_finish(const void* Fp, const LaunchCfg& lc, const uint8_t* code, const void* z, void* out, size_t count,
+                             hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const IszeroFlatPlan pl = iszero_flat_plan(count, sizeof(E), al(z) && al(out) && codes_al(code));
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (pl.total == 0) return L_OK;
+            hipLaunchKernelGGL((k_iszero_finish<F>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, code, (const E*)z, (E*)out, pl);
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1632,7 +1687,8 @@ struct Launchers {
             .tour_unit_expand = &tour_unit_expand,
             .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod,
             .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply,
-            .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse};
+            .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse,
+            .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish};
         return &ops;
     }
 };

@@ -1118,6 +1118,53 @@ class FieldContext:
         _ffi.check(self._L.ffgm_bits_reverse(self._h, bits.ptr, l, out.ptr, n, self._stream()), 'bits_reverse')
         return out
 
+    # ---- the Legendre zero test over a Blum prime: the local steps of runtime._np_is_zero (runtime.py:3581-3620;
+    # include/ffgpu_math.h), prime fields.  The masked copies are row-major (k, n): row i holds the i-th copy of the n
+    # elements; a code is one byte per entry: 0 a non-residue, 1 a residue, 2 zero ----
+    def _codes(self, what: str, code: torch.Tensor, count: int) -> torch.Tensor:
+        if (not isinstance(code, torch.Tensor) or code.dtype != torch.uint8 or code.dim() != 1 or code.numel() != count
+                or not code.is_contiguous() or code.device != torch.device(self.torch_device)):
+            raise ValueError(f'{what}: the codes are a contiguous torch.uint8 tensor of {count} bytes on the context\'s device')
+        return code
+
+    def iszero_mask(self, a: DevArray, r: DevArray, z: DevArray, u2: DevArray, k: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[i*n + e] = a[e]*r[i*n + e] + (1 - 2*z[i*n + e])*u2[i*n + e] for i < k, n = a.n: the k masked copies of every
+        element that are opened (runtime.py:3608); z holds shares of bits."""
+        if self.binary:
+            raise NotImplementedError('iszero_mask: prime fields only')
+        if k < 1:
+            raise ValueError('iszero_mask: k >= 1')
+        self._same(a.n, a, what='iszero_mask operand')
+        self._same(k * a.n, r, z, u2, what='iszero_mask operand')
+        out = self._out(k * a.n, out, 'iszero_mask output')
+        _ffi.check(self._L.ffgm_iszero_mask(self._h, a.ptr, r.ptr, z.ptr, u2.ptr, k, out.ptr, a.n, self._stream()), 'iszero_mask')
+        return out
+
+    def legendre_code(self, c: DevArray, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """code[j] = 2 if c[j] == 0, else 1 if c[j] is a quadratic residue, else 0: c.n bytes (finfields.py:1464-1470 and the
+        test c == 0 of runtime.py:3614)."""
+        if self.binary:
+            raise NotImplementedError('legendre_code: prime fields only')
+        if self.modulus == 2:
+            raise NotImplementedError('legendre_code: odd primes only')
+        self._same(c.n, c, what='legendre_code operand')
+        if out is None:
+            out = torch.empty(c.n, dtype=torch.uint8, device=self.torch_device)
+        self._codes('legendre_code', out, c.n)
+        _ffi.check(self._L.ffgm_legendre_code(self._h, c.ptr, out.data_ptr(), c.n, self._stream()), 'legendre_code')
+        return out
+
+    def iszero_finish(self, code: torch.Tensor, z: DevArray, out: Optional[DevArray] = None) -> DevArray:
+        """out[j] = z[j] if code[j] == 0, 1 - z[j] if code[j] == 1, 1 if code[j] == 2 (runtime.py:3614-3615; 0 counts as a
+        square)."""
+        if self.binary:
+            raise NotImplementedError('iszero_finish: prime fields only')
+        self._same(z.n, z, what='iszero_finish operand')
+        self._codes('iszero_finish', code, z.n)
+        out = self._out(z.n, out, 'iszero_finish output')
+        _ffi.check(self._L.ffgm_iszero_finish(self._h, code.data_ptr(), z.ptr, out.ptr, z.n, self._stream()), 'iszero_finish')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = self._out(a.n, out)

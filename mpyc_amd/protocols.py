@@ -236,6 +236,49 @@ def compare_zero(ctx: FieldContext, field, xs: Shares, rbits: Shares, sbits: Opt
                     [ctx.add_scalar(ctx.mul_scalar(x, 2), p - 1) for x in lt], t, rng)
 
 
+# ---- secure equality over a Blum prime: the Legendre zero test (runtime.np_equal, runtime.py:3569-3579; _np_is_zero,
+# runtime.py:3581-3620) ---------------------------------------------------------------------------------------------
+def equal_route(p: int, l: int, sec_param: int) -> str:
+    """The dispatch of runtime.np_equal (runtime.py:3576) for a secure integer or fixed-point type of bit length l over the
+    prime p: 'legendre' (the probabilistic zero test, is_zero) when l / 2 > sec_param >= 8 and p = 3 mod 4, else 'bits'
+    (np_sgn(EQ=True): compare_zero(mode='eq'))."""
+    return 'legendre' if l / 2 > sec_param >= 8 and p % 4 == 3 else 'bits'
+
+
+def is_zero(ctx: FieldContext, field, xs: Shares, t: int, k: int, rand_zero, rng=None) -> Shares:
+    """runtime._np_is_zero (runtime.py:3581-3620) for all parties: shares of [x == 0], wrong (1 for a nonzero x) with
+    probability 2^-k per element.  p = 3 mod 4, so -1 is a non-residue: with z a random bit, r and u random elements,
+    c = x r + (1 - 2 z) u^2 is a residue exactly when z = 0 if x = 0, and independently of z otherwise.
+
+    u2 = multiply(s, s) (one re-sharing round) -> iszero_mask per party (degree 2t) -> one opening from 2t+1 parties -> ONE
+    legendre_code on the public values -> iszero_finish per party -> prod_rows over the k rows: 2 + ceil(log2 k) rounds.
+    The arrays are row-major (k, n): row i holds the i-th masked copy.
+
+    rand_zero(count) supplies three sharings of count = k n entries: uniform bits z, uniform field elements r, uniform field
+    elements s.  The inputs are never written."""
+    m = len(xs)
+    if ctx.binary or ctx.modulus % 4 != 3:
+        raise ValueError('is_zero: a prime field with p = 3 mod 4')
+    if k < 1:
+        raise ValueError('is_zero: k >= 1')
+    senders = _parties('the zero test', t, m)                                      # 2t+1: the masked values have degree 2t
+    n = xs[0].n
+    z, r, s = rand_zero(k * n)
+    if not (len(z) == len(r) == len(s) == m) or any(v.n != k * n for w in (z, r, s) for v in w):
+        raise ValueError('is_zero: rand_zero(count) returns three sharings of count entries for every party')
+    u2 = multiply(ctx, field, s, s, t, rng)
+    c = open_(ctx, field, [ctx.iszero_mask(xs[i], r[i], z[i], u2[i], k) for i in range(senders)], t, degree=2 * t)
+    code = ctx.legendre_code(c)
+    return prod_rows(ctx, field, [ctx.iszero_finish(code, z[i]) for i in range(m)], k, t, rng)
+
+
+def equal(ctx: FieldContext, field, xs: Shares, ys: Shares, t: int, k: int, rand_zero, rng=None) -> Shares:
+    """runtime.np_equal on the Legendre route (runtime.py:3571, 3577): is_zero of the difference; shares of [x == y]."""
+    if len(xs) != len(ys):
+        raise ValueError('equal: both operands for every party')
+    return is_zero(ctx, field, [ctx.sub(x, y) for x, y in zip(xs, ys)], t, k, rand_zero, rng)
+
+
 # ---- sorting along one axis (runtime.np_sort, runtime.py:1738-1774) ---------------------------------------------
 def sort_stages(k: int):
     """The stages (p, d, r) of Batcher's merge-exchange network over k elements (Knuth 5.2.2M), in the order of the
