@@ -1,8 +1,9 @@
 /*
  * ffgpu_math.h -- second header of libffgpu.so: the local steps under the secure logarithm and exponential of fixed-point
- * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945) and under the probabilistic zero test over a
- * Blum prime (runtime._np_is_zero, runtime.py:3581-3620) that no entry of ffgpu.h serves.  Same library, same contexts
- * (ffgpu_ctx of ffgpu.h), same conventions:
+ * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945), under the probabilistic zero test over a
+ * Blum prime (runtime._np_is_zero, runtime.py:3581-3620) and under secure random bits (runtime.np_random_bits,
+ * runtime.py:4187-4273) that no entry of ffgpu.h serves.  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
+ * conventions:
  *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
  *   - array arguments are DEVICE pointers unless the name says host; elements are canonical little-endian limbs in the
  *     layouts ffgpu.h lists, host scalars little-endian 64-bit limbs, ffgpu_ctx_scalar_limbs() of them;
@@ -10,10 +11,10 @@
  *     can be captured in a HIP graph); inputs are never written, outputs are canonical;
  *   - n == 0 returns FFGPU_OK whatever the pointers (the counts are still checked); in every refused case nothing is
  *     written and nothing is launched;
- *   - an output that overlaps an input is FFGPU_EINVAL (the one exception is stated at ffgm_powers_prod);
+ *   - an output that overlaps an input is FFGPU_EINVAL (the exceptions are stated at ffgm_powers_prod and ffgm_rbits_finish);
  *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
- * log2(), log10(), pow_public_base(), exp2() and exp(), and into is_zero() and equal().
+ * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), and into random_bits().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -48,9 +49,26 @@
  * ffgm_iszero_finish: out[j] = z[j] if code[j] == 0, 1 - z[j] if code[j] == 1, 1 if code[j] == 2 (0 counts as a square).
  *   replaces: runtime.py:3614-3615 (`np.where(c == 0, 0, z)`, `np.where(is_sqr, 1 - z, z)` and the 1 of a zero).
  *
+ * The rows of the random-bit entries are SEPARATE arrays of n entries: host_r, host_z, host_b are host arrays of device
+ * pointers, one per row; at most 64 rows (the limit of ffgpu_recombine), whole packs in ffgm_rbits_open for up to 9.
+ *
+ * ffgm_rbits_open: out[h] = sum_{i<k} lambda[i] * (r_i[h]^2 + z_i[h]); *zeros += #{h : out[h] == 0}.  host_lambda: k host
+ *   scalars (the Lagrange vector of the k = 2t+1 senders).  The squares are reduced products, the sum is accumulated lazily
+ *   with one reduction per entry: 2k rows read, one written.  zeros: a device int32 that is ADDED to (one atomic per wave
+ *   that saw a zero), or NULL.
+ *   replaces: runtime.py:4251-4254 (`_r.value**2 + z.value`, its opening at threshold 2t, and the count of `_r2 != 0`).
+ * ffgm_rbits_finish: with s = c[h]^((3p-5)/4), the inverse square root of a square modulo p = 3 mod 4:
+ *   b_i[h] = r_i[h] * s * 2^f (is_signed: +-1 scaled) or (r_i[h] * s + 1) * (p+1)/2 * 2^f (0 or 1 scaled) for i < m, and 0 in
+ *   every row where c[h] == 0.  The exponentiation of the public c runs once for all m rows and is the one ffgpu_pow
+ *   launches for this exponent.  b_i may BE r_i (the same pointer); any other overlap of a b_i with c, an r_j or a b_j is
+ *   FFGPU_EINVAL.  c is never written.  0 <= f < 192.
+ *   replaces: runtime.py:4265-4272 (`r * field.array._sqrt(r2, INV=True)`, finfields.py:1424-1437, the `+ 1`, the halving
+ *   and the shift), once per party.
+ *
  * FFGPU_OK: n == 0 / count == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or
- * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; a size
- * overflowing; an output overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context; ffgm_legendre_code over p == 2.       */
+ * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; m < 1;
+ * f < 0 or f >= 192; a size overflowing; an output overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context;
+ * ffgm_legendre_code over p == 2; ffgm_rbits_finish unless p = 3 mod 4; more than 64 rows.                              */
 #ifndef FFGPU_MATH_H
 #define FFGPU_MATH_H
 
@@ -69,6 +87,10 @@ int ffgm_iszero_mask(ffgpu_ctx* ctx, const void* a, const void* r, const void* z
                      void* stream);
 int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t count, void* stream);
 int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void* out, size_t count, void* stream);
+int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const* host_z, const uint64_t* host_lambda, int k, void* out,
+                    int32_t* zeros, size_t n, void* stream);
+int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, void* const* host_b, int m, int is_signed, int f, size_t n,
+                      void* stream);
 
 #ifdef __cplusplus
 }

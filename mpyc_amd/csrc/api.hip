@@ -1801,6 +1801,91 @@ int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void*
     return status_of(ctx->ops->iszero_finish(ctx->policy, cs.lc, code, z, out, count, cs.st));
 }
 
+// ---- secure random bits over a prime field: the local steps of runtime.np_random_bits (rbits.hpp; include/ffgpu_math.h) ----
+// x = 2 x mod p on three limbs, x < p < 2^192
+static void dbl_mod3(uint64_t x[3], const uint64_t p[3]) {
+    const uint64_t top = x[2] >> 63;
+    x[2] = (x[2] << 1) | (x[1] >> 63);
+    x[1] = (x[1] << 1) | (x[0] >> 63);
+    x[0] <<= 1;
+    const bool ge = top || x[2] > p[2] || (x[2] == p[2] && (x[1] > p[1] || (x[1] == p[1] && x[0] >= p[0])));
+    if (ge) {
+        const uint64_t b0 = x[0] < p[0];
+        x[0] -= p[0];
+        const uint64_t b1 = x[1] < p[1] || (x[1] == p[1] && b0);
+        x[1] = x[1] - p[1] - b0;
+        x[2] = x[2] - p[2] - b1;
+    }
+}
+
+int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const* host_z, const uint64_t* host_lambda, int k, void* out,
+                    int32_t* zeros, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(k >= 1);
+    if (k > (int)RBITS_MAX_ROWS) return FFGPU_ENOTSUP;
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(rbits_open_plan(n, k, eb, false).ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(host_r && host_z && host_lambda && out);
+    ByteRange in[2 * RBITS_MAX_ROWS];
+    for (int j = 0; j < k; ++j) {
+        ARGCHK(host_r[j] && host_z[j]);
+        in[2 * j] = byte_range(host_r[j], n * eb);
+        in[2 * j + 1] = byte_range(host_z[j], n * eb);
+    }
+    const ByteRange o[2] = {byte_range(out, n * eb), byte_range(zeros, zeros ? sizeof(int32_t) : 0)};
+    ARGCHK(outputs_disjoint(in, 2 * k, o, 2));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->rbits_open(ctx->policy, cs.lc, host_r, host_z, host_lambda, k, out, zeros, n, cs.st));
+}
+
+int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, void* const* host_b, int m, int is_signed, int f, size_t n,
+                      void* stream) {
+    PRIME_CTX(ctx);
+    if ((ctx->modulus[0] & 3) != 3) return FFGPU_ENOTSUP;
+    ARGCHK(m >= 1 && f >= 0 && f < 192);
+    if (m > (int)RBITS_MAX_ROWS) return FFGPU_ENOTSUP;
+    const size_t eb = (size_t)ctx->elem_bytes;
+    ARGCHK(rbits_finish_plan(n, m, eb, false).ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(c && host_r && host_b);
+    const ByteRange cr = byte_range(c, n * eb);
+    for (int i = 0; i < m; ++i) {
+        ARGCHK(host_r[i] && host_b[i]);
+        const ByteRange bi = byte_range(host_b[i], n * eb);
+        ARGCHK(!overlaps(bi, cr));
+        for (int j = 0; j < m; ++j) {
+            if (j < i) ARGCHK(!overlaps(bi, byte_range(host_b[j], n * eb)));
+            if (j == i && host_b[i] == host_r[i]) continue;                     // (in place: the one overlap allowed)
+            ARGCHK(!overlaps(bi, byte_range(host_r[j], n * eb)));
+        }
+    }
+    // (3p - 5) / 4 = p - 2 - (p - 3) / 4, on three limbs; p >= 3
+    const uint64_t* p = ctx->modulus;
+    uint64_t q[3] = {(p[0] >> 2) | (p[1] << 62), (p[1] >> 2) | (p[2] << 62), p[2] >> 2}, e[3];
+    sub_small3(p, 2, e);
+    const uint64_t b0 = e[0] < q[0];
+    e[0] -= q[0];
+    const uint64_t b1 = e[1] < q[1] || (e[1] == q[1] && b0);
+    e[1] = e[1] - q[1] - b0;
+    e[2] = e[2] - q[2] - b1;
+    ExpArgs ex;
+    make_exp(e, 3, &ex);
+    exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
+    // A = 2^f, B = 0 (signed), or A = B = (p + 1) / 2 2^f
+    uint64_t A[3] = {1, 0, 0}, B[3] = {0, 0, 0};
+    if (!is_signed) {
+        A[0] = (p[0] >> 1) | (p[1] << 63);
+        A[1] = (p[1] >> 1) | (p[2] << 63);
+        A[2] = p[2] >> 1;
+        if (++A[0] == 0 && ++A[1] == 0) ++A[2];
+    }
+    for (int i = 0; i < f; ++i) dbl_mod3(A, p);
+    if (!is_signed) memcpy(B, A, sizeof(B));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A, B, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

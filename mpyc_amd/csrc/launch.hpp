@@ -194,6 +194,13 @@ struct FieldOps {
                          hipStream_t st);
     LaunchStatus (*iszero_finish)(const void* F, const LaunchCfg& lc, const uint8_t* code, const void* z, void* out, size_t count,
                          hipStream_t st);
+    // local steps of secure random bits (rbits.hpp), prime fields only; rows of n entries, one pointer each; lam2, A2, B2:
+    // host scalars; ex of rbits_finish: the exponent (3p - 5) / 4 as ffgpu_pow hands it to pow (L_PLAN_REFUSED:
+    // rbits_open_plan() / rbits_finish_plan() refuses the row count or the sizes)
+    LaunchStatus (*rbits_open)(const void* F, const LaunchCfg& lc, const void* const* r, const void* const* z, const uint64_t* lam2, int k,
+                      void* out, int* zeros, size_t n, hipStream_t st);
+    LaunchStatus (*rbits_finish)(const void* F, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* r, void* const* b,
+                        int m, const uint64_t* A2, const uint64_t* B2, size_t n, hipStream_t st);
 };
 
 // Host scalars (Lagrange coefficients, constants, matrix entries) cross the C ABI as little-endian 64-bit limbs:
@@ -1540,6 +1547,76 @@ struct Launchers {
             return launched();
         }
     }
+    // The local steps of secure random bits (rbits.hpp): the plan, grid and launch bounds of pow (rbits_open_plan /
+    // rbits_finish_plan restate plan(): tests/rbits_check.cpp).  The opening keeps whole packs for up to rbits_fused_rows()
+    // rows, with the row count a template parameter as in recombine; more rows (up to MAXK_ANY) go by elements.
+    template <int K>
+    static void go_rbits_open(const F& f, const LaunchCfg& lc, const void* const* r, const void* const* z, const uint64_t* lam2, E* out,
+                              int* zeros, size_t n, hipStream_t st) {
+        RbitsOpenArgs<F, K> ra;
+        bool vec = al(out);
+        for (int j = 0; j < K; ++j) {
+            ra.r[j] = (const E*)r[j];
+            ra.z[j] = (const E*)z[j];
+            ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
+            vec = vec && al(r[j]) && al(z[j]);
+        }
+        const RbitsPlan pl = rbits_open_plan(n, K, sizeof(E), vec);
+        hipLaunchKernelGGL((k_rbits_open<F, K>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, ra, out, zeros, pl.nvec, n);
+    }
+    static LaunchStatus rbits_open(const void* Fp, const LaunchCfg& lc, const void* const* r, const void* const* z, const uint64_t* lam2,
+                          int k, void* out, int* zeros, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            const RbitsPlan pl = rbits_open_plan(n, k, sizeof(E), false);
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (n == 0) return L_OK;
+            if (!pl.fused) {
+                static_assert(sizeof(RbitsOpenArgsAny<F>) + sizeof(F) + 64 <= 4096, "kernel arguments");
+                RbitsOpenArgsAny<F> ra;
+                for (int j = 0; j < MAXK_ANY; ++j) {
+                    const int s = j < k ? j : 0;
+                    ra.r[j] = (const E*)r[s];
+                    ra.z[j] = (const E*)z[s];
+                    ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)s));
+                }
+                hipLaunchKernelGGL((k_rbits_open_any<F>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, ra, k, (E*)out, zeros, n);
+                return launched();
+            }
+            if (!dispatch_int(IntRange<1, rbits_fused_rows(sizeof(E))>(), k,
+                              [&](auto k_) { go_rbits_open<decltype(k_)::value>(f, lc, r, z, lam2, (E*)out, zeros, n, st); }))
+                return L_BAD_ARG;
+            return launched();
+        }
+    }
+    static LaunchStatus rbits_finish(const void* Fp, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* r,
+                            void* const* b, int m, const uint64_t* A2, const uint64_t* B2, size_t n, hipStream_t st) {
+        if constexpr (F::BINARY) {
+            return L_NOT_SUPPORTED;
+        } else {
+            const F& f = policy(Fp);
+            static_assert(sizeof(RbitsFinishArgs<F>) + sizeof(F) + sizeof(ExpArgs) + 64 <= 4096, "kernel arguments");
+            if (!rbits_rows_valid(m)) return L_PLAN_REFUSED;
+            RbitsFinishArgs<F> fa;
+            bool vec = al(c);
+            for (int j = 0; j < MAXK_ANY; ++j) {
+                const int s = j < m ? j : 0;
+                fa.r[j] = (const E*)r[s];
+                fa.b[j] = (E*)b[s];
+                vec = vec && al(r[s]) && al(b[s]);
+            }
+            fa.A = word_at<F>(f, A2, 0);
+            fa.B = word_at<F>(f, B2, 0);
+            fa.m = m;
+            const RbitsPlan pl = rbits_finish_plan(n, m, sizeof(E), vec);
+            if (!pl.ok) return L_PLAN_REFUSED;
+            if (n == 0) return L_OK;
+            hipLaunchKernelGGL((k_rbits_finish<F>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, n);
+            return launched();
+        }
+    }
     static LaunchStatus dot(const void* Fp, const LaunchCfg& lc, const void* a, const void* b, void* out, void* workspace, size_t n,
                    hipStream_t st) {
         const F& f = policy(Fp);
@@ -1688,7 +1765,8 @@ struct Launchers {
             .find_leaf_prod = &find_leaf_prod, .find_leaf_apply = &find_leaf_apply, .find_prod = &find_prod,
             .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply,
             .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse,
-            .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish};
+            .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish,
+            .rbits_open = &rbits_open, .rbits_finish = &rbits_finish};
         return &ops;
     }
 };

@@ -1165,6 +1165,59 @@ class FieldContext:
         _ffi.check(self._L.ffgm_iszero_finish(self._h, code.data_ptr(), z.ptr, out.ptr, z.n, self._stream()), 'iszero_finish')
         return out
 
+    # ---- secure random bits over a prime field: the local steps of runtime.np_random_bits (runtime.py:4243-4272;
+    # include/ffgpu_math.h).  Rows are separate arrays of n entries, at most 64 of them ----
+    def zero_counter(self) -> torch.Tensor:
+        """A device int32 set to 0: what rbits_open adds its zeros to."""
+        return torch.zeros(1, dtype=torch.int32, device=self.torch_device)
+
+    def _counter(self, what: str, zeros: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        if zeros is not None and (not isinstance(zeros, torch.Tensor) or zeros.dtype != torch.int32 or zeros.numel() != 1
+                                  or zeros.device != torch.device(self.torch_device)):
+            raise ValueError(f'{what}: the counter is one torch.int32 on the context\'s device')
+        return zeros
+
+    def rbits_open(self, rs: Sequence[DevArray], zs: Sequence[DevArray], lambdas: Sequence[int], zeros: Optional[torch.Tensor] = None,
+                   out: Optional[DevArray] = None) -> DevArray:
+        """out[h] = sum_i lambdas[i] * (rs[i][h]^2 + zs[i][h]): the masked squares, opened (runtime.py:4251-4252); the number of
+        entries with out[h] == 0 is ADDED to zeros (a device int32, zero_counter()) when one is given."""
+        if self.binary:
+            raise NotImplementedError('rbits_open: prime fields only')
+        if len(zs) != len(rs):
+            raise ValueError('rbits_open: one row of z per row of r')
+        k, ptrs, lam = self._rec_args(rs, lambdas, 1)
+        n = rs[0].n
+        self._same(n, *zs, what='rbits_open operand')
+        self._counter('rbits_open', zeros)
+        out = self._out(n, out, 'rbits_open output')
+        zptrs = (ctypes.c_void_p * k)(*[z.ptr for z in zs])
+        _ffi.check(self._L.ffgm_rbits_open(self._h, ptrs, zptrs, lam, k, out.ptr, None if zeros is None else zeros.data_ptr(), n,
+                                           self._stream()), 'rbits_open')
+        return out
+
+    def rbits_finish(self, c: DevArray, rs: Sequence[DevArray], signed: bool = False, f: int = 0,
+                     outs: Optional[Sequence[DevArray]] = None) -> List[DevArray]:
+        """With s = c^((3p-5)/4) (p = 3 mod 4): outs[i] = rs[i] * s * 2^f when signed, else (rs[i] * s + 1) * (p+1)/2 * 2^f; 0 in
+        every row where c is 0 (runtime.py:4265-4272).  One exponentiation of the public c serves every row.  outs[i] may be
+        rs[i]."""
+        if self.binary:
+            raise NotImplementedError('rbits_finish: prime fields only')
+        if self.modulus % 4 != 3:
+            raise NotImplementedError('rbits_finish: p = 3 mod 4')
+        m = len(rs)
+        if not m or f < 0 or f >= 192:
+            raise ValueError('rbits_finish: at least one row, 0 <= f < 192')
+        self._same(c.n, c, *rs, what='rbits_finish operand')
+        if outs is None:
+            outs = [self.empty(c.n) for _ in range(m)]
+        if len(outs) != m:
+            raise ValueError('rbits_finish: one output per row')
+        self._same(c.n, *outs, what='rbits_finish output')
+        rp = (ctypes.c_void_p * m)(*[r.ptr for r in rs])
+        bp = (ctypes.c_void_p * m)(*[b.ptr for b in outs])
+        _ffi.check(self._L.ffgm_rbits_finish(self._h, c.ptr, rp, bp, m, int(bool(signed)), f, c.n, self._stream()), 'rbits_finish')
+        return list(outs)
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = self._out(a.n, out)

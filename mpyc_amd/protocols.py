@@ -1142,3 +1142,207 @@ def exp(ctx: FieldContext, field, xs: Shares, t: int, l: int, f: int, rand_trunc
     import math
     return exp2(ctx, field, _mul_public_float(ctx, field, xs, math.log2(math.e), t, f, l, rand_trunc), t, l, f, rand_trunc, rand_exp,
                 rng, sec_param)
+
+
+# ---- secure random bits over a prime field (runtime.np_random_bits, runtime.py:4187-4273, the PRSS branch :4243-4267) and
+# the supplier of the protocols' correlated randomness ------------------------------------------------------------------
+def _nonzero_mask(x: DevArray):
+    """entries of x that are not 0, as a torch mask over the elements"""
+    nz = x.t != 0
+    return nz if nz.dim() == 1 else nz.any(dim=1)
+
+
+def random_bits(ctx: FieldContext, field, count: int, t: int, draw, signed: bool = False, f: int = 0) -> Shares:
+    """runtime.np_random_bits over a prime field for all parties: shares of `count` uniform bits scaled by 2^f, in {0, 1}, or
+    in {-1, 1} when signed.  draw(h) returns (r, z): two sharings of h entries for all m >= 2t+1 parties, r uniform field
+    elements, z a sharing of zero of degree 2t.  The loop is the reference's (runtime.py:4246-4264):
+
+      draw h entries -> rbits_open on the first 2t+1 parties (ffgm_rbits_open: r^2 + z recombined in one pass, the zeros
+      counted on the device) -> read the counter (one 4-byte copy per round, the reference's own synchronisation point) ->
+      no zero and nothing kept: straight on; else keep the entries whose square is not 0 and draw as many again as were 0.
+
+    The entries kept from earlier draws come first, then the last draw whole (np.append, runtime.py:4256-4261).  Then
+    r (r^2)^(-1/2), a uniform +-1, and (bits + 1) / 2, shifted by f: one ffgm_rbits_finish for all parties when p = 3 mod 4
+    (the exponentiation of the public squares runs once), composed from sqrt_cl, inv, mul, add_scalar and mul_scalar when
+    p = 1 mod 4.  A compaction has probability count / p and uses torch indexing.  What draw() returns is never written."""
+    if ctx.binary:
+        raise ValueError('random_bits: a prime field (over GF(2^n) a random bit is one PRSS draw with mask_bits = 1)')
+    p = ctx.modulus
+    if count < 0 or f < 0 or t < 0:
+        raise ValueError('random_bits: count, t and f are not negative')
+    k = 2 * t + 1
+    lam = _lagrange(field, range(1, k + 1))
+    kept_r, kept_c, h, m = None, None, count, None
+    while True:
+        r, z = draw(h)
+        if m is None:
+            m = len(r)
+        _parties('random bits', t, m, len(r), len(z))
+        if any(x.n != h for w in (r, z) for x in w):
+            raise ValueError('random_bits: draw(h) returns two sharings of h entries for every party')
+        if count == 0:
+            return [ctx.empty(0) for _ in range(m)]
+        zeros = ctx.zero_counter()
+        c = ctx.rbits_open(r[:k], z[:k], lam, zeros=zeros)
+        h = int(zeros.item())
+        if h == 0:
+            break
+        keep = _nonzero_mask(c)
+        part_r, part_c = [x.t[keep] for x in r], c.t[keep]
+        kept_r = part_r if kept_r is None else [_torch().cat([a, b]) for a, b in zip(kept_r, part_r)]
+        kept_c = part_c if kept_c is None else _torch().cat([kept_c, part_c])
+    own = kept_r is not None and kept_c.shape[0] > 0
+    if own:                                                                         # the kept entries, then the last draw whole
+        r = [DevArray(ctx, _torch().cat([a, x.t]), count) for a, x in zip(kept_r, r)]
+        c = DevArray(ctx, _torch().cat([kept_c, c.t]), count)
+    if p % 4 == 3:
+        return ctx.rbits_finish(c, r, signed=signed, f=f, outs=r if own else None)
+    s = ctx.inv(ctx.sqrt_cl(c))                                                     # (c has no zero left)
+    bits = [ctx.mul(x, s) for x in r]
+    if not signed:
+        bits = [ctx.mul_scalar(ctx.add_scalar(b, 1), (p + 1) >> 1) for b in bits]
+    return [ctx.mul_scalar(b, (1 << f) % p) for b in bits] if f else bits
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class Randomness:
+    """The shipped supplier of the protocols' correlated randomness for all m parties on one GPU: pseudorandom secret
+    sharing (thresha.py:135-217) with one PRF key per subset of m - t parties, derived from `key`, and a counter as the
+    common input, so that no two calls see the same one.  The PRF is the device's (a ChaCha stream per subset key and common
+    input, thresha.prss_chacha_stream_key; ffgpu_prss_chacha with the weights f_S(i) of thresha._f_S_i, as
+    thresha._prss_device fills one party's row), so the values are pinned by (key, rounds) and the order of the calls.
+
+    elements / zeros / bits are the reference's _np_randoms, np_pseudorandom_share_0 and np_random_bits; rand_bits,
+    rand_trunc, rand_zero, rand_exp and rand_compare(l) are the callables the protocols of this module document."""
+
+    KEY_BYTES = 16                      # the reference's PRSS keys (runtime.py:130-140)
+    DOMAIN = b'mpyc_amd randomness v1\0'
+
+    def __init__(self, ctx: FieldContext, field, t: int, m: int, key: bytes, rounds: int = 20, sec_param: int = 30):
+        import itertools
+        from hashlib import shake_128
+        if ctx.binary:
+            raise ValueError('Randomness: a prime field')
+        if not 0 <= t or m < 2 * t + 1:
+            raise ValueError('Randomness: m >= 2t+1 parties')
+        self.ctx, self.field, self.t, self.m, self.rounds, self.sec_param = ctx, field, t, m, rounds, sec_param
+        key = bytes(key)
+        head = self.DOMAIN + len(key).to_bytes(2, 'little') + key
+        self._subsets = [tuple(S) for S in itertools.combinations(range(m), m - t)]
+        self._keys = {S: shake_128(head + b'S' + bytes(S)).digest(self.KEY_BYTES) for S in self._subsets}
+        self._own = [shake_128(head + b'P' + bytes([i])).digest(self.KEY_BYTES) for i in range(m)]     # a party's private draws
+        self._ncomb = len(self._subsets)
+        self.counter = 0                # common inputs handed out so far
+
+    def _uci(self) -> bytes:
+        """the next common input: every call takes one, none is used twice"""
+        c = self.counter
+        self.counter += 1
+        return c.to_bytes(8, 'little')
+
+    def _prss(self, count: int, bound: int, zero: bool) -> Shares:
+        """one PRSS call for all parties: thresha._prss_device (np convention) per party, the device PRF"""
+        ctx, m, t, p = self.ctx, self.m, self.t, self.ctx.modulus
+        uci = self._uci()
+        if bound & (bound - 1) == 0:
+            mask_bits, l = bound.bit_length() - 1, (bound.bit_length() - 1 + 7) // 8
+        elif bound == p:
+            mask_bits, l = 0, ((p - 1).bit_length() + 7) // 8 + self.KEY_BYTES
+        else:
+            raise ValueError('Randomness: the bound is the field order or a power of two')
+        d = t if zero else 1
+        if count == 0 or mask_bits == 0 and l == 0 or d == 0:                       # nothing, bound 1, or t = 0: zeros
+            out = [ctx.empty(count) for _ in range(m)]
+            for x in out:
+                x.t.zero_()
+            return out
+        if l > thresha.PRSS_MAX_DRAW_BYTES or d > 64:
+            raise NotImplementedError('Randomness: the draw is wider than ffgpu_prss_chacha takes')
+        per = max(1, min(32, 64 // d))
+        out = []
+        for i in range(m):
+            mine = [S for S in self._subsets if i in S]
+            weights = []
+            for S in mine:
+                fs = int(thresha._f_S_i(self.field, m, i, S))
+                weights += [fs * pow(i + 1, j + 1, p) % p if zero else fs for j in range(d)]
+            keys = [thresha.prss_chacha_stream_key(self._keys[S], uci) for S in mine]
+            x = ctx.empty(count)
+            for k0 in range(0, len(mine), per):
+                ctx.prss_chacha(keys[k0:k0 + per], d, l, weights[k0 * d:(k0 + per) * d], count, mask_bits=mask_bits, rounds=self.rounds,
+                                out=x, accumulate=k0 > 0)
+            out.append(x)
+        return out
+
+    def rounded_bound(self, bound: int) -> int:
+        """the power of two _np_randoms draws below per subset key (runtime.py:4074-4075): the sum stays below `bound`"""
+        return 1 << max(0, (bound // self._ncomb).bit_length() - 1)
+
+    def elements(self, count: int, bound: Optional[int] = None) -> Shares:
+        """runtime._np_randoms: a degree-t sharing of `count` random values, uniform field elements, or, with a bound, sums of
+        comb(m, t) draws below rounded_bound(bound) each."""
+        return self._prss(count, self.ctx.modulus if bound is None else self.rounded_bound(bound), False)
+
+    def zeros(self, count: int) -> Shares:
+        """thresha.np_pseudorandom_share_0: a random sharing of zero of degree 2t"""
+        return self._prss(count, self.ctx.modulus, True)
+
+    def _draw(self, h: int):
+        return self.elements(h), self.zeros(h)
+
+    def bits(self, count: int, signed: bool = False, f: int = 0) -> Shares:
+        """runtime.np_random_bits: `count` uniform bits (random_bits with this supplier's own draws)"""
+        return random_bits(self.ctx, self.field, count, self.t, self._draw, signed=signed, f=f)
+
+    # ---- the callables of the protocols ----
+    def rand_bits(self, count: int, l: int, bit_length: Optional[int] = None):
+        """(rbits, rdivl) of to_bits() / norm(): count * l bits and count values below 2^(bit_length + sec_param - l)
+        (runtime.py:4412, :4439; bit_length: of the secure type, l by default)."""
+        return self.bits(count * l), self.elements(count, 1 << ((l if bit_length is None else bit_length) + self.sec_param - l))
+
+    def rand_trunc(self, count: int, f: int, l: Optional[int] = None):
+        """(rbits, rdivf) of trunc() / fxp_multiply(): count * f bits and count values below 2^(sec_param + l - f)
+        (runtime.py:859-862), l the bit length np_trunc works with -- the L of trunc(), bit length plus f for a fixed-point
+        product.  By default the largest the field admits: the opened a + 2^(l-1) + r + 2^f R is below 2^l + 2^f +
+        2^(sec_param + l) < p for l = bit_length(p) - sec_param - 2."""
+        if l is None:
+            l = self.ctx.modulus.bit_length() - self.sec_param - 2
+        if l < f:
+            raise ValueError('rand_trunc: the field is too small for this truncation')
+        return self.bits(count * f), self.elements(count, 1 << (self.sec_param + l - f))
+
+    def rand_zero(self, count: int):
+        """(z, r, s) of is_zero(): bits, and two sharings of uniform elements (runtime.py:3594-3599)"""
+        z = self.bits(count)
+        s = self.elements(count)
+        return z, self.elements(count), s
+
+    def rand_compare(self, l: int):
+        """rand(count) of compare_zero() / sort() / amax() ...: (rbits, sbits, rdivl, rzero) for `count` comparisons of bit
+        length l -- count * l bits element-major, count bits, count values below 2^sec_param (runtime.py:3644-3645) and count
+        uniform elements, nonzero but for a probability of count / p (runtime.py:947)."""
+        def rand(count: int):
+            return self.bits(count * l), self.bits(count), self.elements(count, 1 << self.sec_param), self.elements(count)
+        return rand
+
+    def rand_exp(self, count: int, bound: int):
+        """the t+1 senders' plain draws of pow_public_base(): `count` values below bound (a power of two) each, from a stream
+        only that sender holds"""
+        if bound < 1 or bound & (bound - 1):
+            raise ValueError('rand_exp: the bound is a power of two')
+        ctx, uci = self.ctx, self._uci()
+        mask_bits = bound.bit_length() - 1
+        out = []
+        for i in range(self.t + 1):
+            x = ctx.empty(count)
+            if count and mask_bits:
+                ctx.prss_chacha([thresha.prss_chacha_stream_key(self._own[i], uci)], 1, (mask_bits + 7) // 8, [1], count,
+                                mask_bits=mask_bits, rounds=self.rounds, out=x)
+            else:
+                x.t.zero_()
+            out.append(x)
+        return out
