@@ -677,6 +677,14 @@ void ffgpu_shake128_close(void* handle);
  * range(bound): mask_bits == 0 -> bound is the field order (wide reduction, l = byte_length + 16),
  * mask_bits = b > 0 -> bound = 2^b (runtime.py:4062-4076 rounds bounds to powers of two).
  * host_weights: (ks, d) canonical 2-limb scalars f_S(i) * (i+1)^power from _f_S_i (thresha.py:135-141).
+ * Limits per call: ks <= 48 and ks * d <= 96 (FFGPU_ENOTSUP beyond them, as ffgpu_recombine answers for too many
+ * rows: split the subsets over several calls, the later ones with accumulate != 0); ks >= 1, d >= 1, 1 <= l <= 64 bytes
+ * per draw, 0 <= mask_bits <= 192 with 2^mask_bits <= order (a masked draw is used as the field element it is), and
+ * non-null host_streams, host_streams[s], host_weights and out (FFGPU_EINVAL otherwise).  A refused call launches nothing
+ * and writes nothing; n = 0 is FFGPU_OK and touches no pointer.
+ * Memory: the streams and the weights are never written; nothing outside the n elements of `out` is written; `out` may
+ * start at any multiple of the element size (no 16-byte alignment is needed); with accumulate != 0 every element of `out`
+ * is read exactly once, before it is stored, and out[h] depends on no other element of `out`; the n results are canonical.
  * replaces: thresha.py:163-173 np_pseudorandom_share (d = 1), :201-217 np_pseudorandom_share_0,
  * and the list versions :144-160, :176-198.                                                    */
 int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, int d, int l, int mask_bits,
@@ -692,8 +700,12 @@ int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, 
  * Layout of the keystream: ffgpu_prss_chacha_layout (tb blocks per tile of dpt draws, ceil(l/4) words per draw; draw j of
  * element h sits in tile h / dpt, slot h % dpt, block counters (tile * d + j) * tb + b).  Every party must use the same
  * mode; there is no reference counterpart for the PRF itself (pinned to RFC 8439 and to oracle/fforacle.c
- * orc_prss_chacha, not to reference outputs), the combination is the reference's.  Limits per call (FFGPU_EINVAL beyond
- * them): ks <= 32, ks * d <= 64, 1 <= l <= 64 bytes per draw (the mirror raises NotImplementedError for wider draws).
+ * orc_prss_chacha, not to reference outputs), the combination is the reference's.  Limits per call: ks <= 32 and
+ * ks * d <= 64 (FFGPU_ENOTSUP beyond them; the later calls of a split one accumulate); ks >= 1, d >= 1, 1 <= l <= 64 bytes
+ * per draw (the mirror raises NotImplementedError for wider draws), rounds in {20, 12, 8}, 0 <= mask_bits <= 192 with
+ * 2^mask_bits <= order, non-null host_keys, host_weights and out (FFGPU_EINVAL otherwise).  The memory contract is that of
+ * ffgpu_prss_combine: nothing but the n elements of `out` is written, at any element alignment, each read once before it
+ * is stored when accumulate != 0; results are canonical; a refused call writes nothing.
  * replaces: thresha.py:163-173, 201-217 (np_pseudorandom_share, np_pseudorandom_share_0) with PRF := ChaCha.      */
 int ffgpu_prss_chacha(ffgpu_ctx* ctx, const uint8_t* host_keys, int ks, int d, int l, int mask_bits, int rounds,
                       const uint64_t* host_weights, int accumulate, void* out, size_t n, void* stream);

@@ -1944,10 +1944,20 @@ int ffgpu_sum(ffgpu_ctx* ctx, const void* a, void* out, void* workspace, size_t 
     return do_dot(ctx, a, nullptr, out, workspace, n, stream);
 }
 
+// a masked draw is a field element as it stands only when 2^mask_bits <= order: the modulus (a prime, or the bit pattern
+// of a polynomial of degree n, order 2^n) has more than mask_bits bits
+static bool prss_mask_fits(const ffgpu_ctx* ctx, int mask_bits) {
+    const uint64_t* p = ctx->modulus;
+    const int top = p[2] ? 2 : p[1] ? 1 : 0;
+    const int bits = 64 * top + (64 - __builtin_clzll(p[top] | 1));
+    return mask_bits < bits;
+}
+
 int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, int d, int l, int mask_bits,
                        const uint64_t* host_weights, int accumulate, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
     ARGCHK(ks >= 1 && d >= 1 && l >= 1 && l <= 64 && mask_bits >= 0 && mask_bits <= 192);
+    ARGCHK(prss_mask_fits(ctx, mask_bits));
     if (n == 0) return FFGPU_OK;
     ARGCHK(host_streams && host_weights && out);
     for (int s = 0; s < ks; ++s) ARGCHK(host_streams[s]);
@@ -1963,6 +1973,7 @@ int ffgpu_prss_chacha(ffgpu_ctx* ctx, const uint8_t* host_keys, int ks, int d, i
     ARGCHK(ctx);
     ARGCHK(ks >= 1 && d >= 1 && l >= 1 && l <= 64 && mask_bits >= 0 && mask_bits <= 192);
     ARGCHK(rounds == 20 || rounds == 12 || rounds == 8);
+    ARGCHK(prss_mask_fits(ctx, mask_bits));
     if (n == 0) return FFGPU_OK;
     ARGCHK(host_keys && host_weights && out);
     uint64_t r2[2] = {ctx->rng_r[0], ctx->rng_r[1]};

@@ -389,6 +389,10 @@ def _prss_device(field, m, i, prfs, uci, n, zero: bool, np_convention: bool):
         mask_bits = 0
     else:
         raise NotImplementedError('PRF bound must be the field order or a power of two (runtime.py:4062-4076)')
+    if bound > ops.order:
+        # a masked draw goes into the combination as it stands: it must be a field element (ffgpu_prss_combine answers
+        # FFGPU_EINVAL for 2^mask_bits > order)
+        raise NotImplementedError(f'PRF bound 2^{mask_bits} exceeds the field order')
     out = ctx.empty(n)
     if n == 0:
         return out

@@ -236,7 +236,12 @@ class CpuFieldContext(engine.FieldContext):
         return [torch.frombuffer(bytearray(hashlib.shake_128(mg).digest(out_len)), dtype=torch.uint8) if out_len
                 else torch.empty(0, dtype=torch.uint8) for mg in msgs]
 
+    def _mask_fits(self, mask_bits, what):
+        if (1 << mask_bits) > self.order:             # FFGPU_EINVAL of the C entry points
+            raise ValueError(f'ffgpu {what}: 2^mask_bits exceeds the field order')
+
     def prss_combine(self, streams, d, l, weights, n, mask_bits=0, out=None, accumulate=False):
+        self._mask_fits(mask_bits, 'prss_combine')
         out = out or self.empty(n)
         acc = out.to_ints() if accumulate else [0] * n
         bound = (1 << mask_bits) if mask_bits else self.order
@@ -250,16 +255,21 @@ class CpuFieldContext(engine.FieldContext):
         return self._put(out, acc)
 
     def prss_chacha(self, keys40, d, l, weights, n, mask_bits=0, rounds=20, out=None, accumulate=False):
+        self._mask_fits(mask_bits, 'prss_chacha')
         out = out or self.empty(n)
         acc = out.to_ints() if accumulate else [0] * n
         bound = (1 << mask_bits) if mask_bits else self.order
         tb, dpt = po.prss_chacha_layout(l)
         lw = (l + 3) // 4
         for s, k40 in enumerate(keys40):
+            tiles = {}                                   # (tile, j) -> keystream: dpt elements share it
             for h in range(n):
                 tile, slot = divmod(h, dpt)
                 for j in range(d):
-                    ksb = b''.join(po.chacha_block(k40[:32], (tile * d + j) * tb + b, k40[32:], rounds) for b in range(tb))
+                    if (tile, j) not in tiles:
+                        tiles[tile, j] = b''.join(po.chacha_block(k40[:32], (tile * d + j) * tb + b, k40[32:], rounds)
+                                                  for b in range(tb))
+                    ksb = tiles[tile, j]
                     x = po.reduce(self.F, int.from_bytes(ksb[4 * slot * lw:4 * slot * lw + l], 'little') % bound)
                     acc[h] = po.add(self.F, acc[h], po.mul(self.F, x, weights[s * d + j]))
         return self._put(out, acc)

@@ -43,7 +43,7 @@ FRESH_AND_IN_PLACE = {1: ('fresh', 'o=a'), 2: ('fresh', 'o=a'), 3: ('fresh', 'o=
 class ContractViolation(AssertionError):
     """kinds: which of 'out' (wrong result), 'input' (an operand that is not the output changed), 'guard' (bytes outside
     every operand changed) were seen; tests/share_contract.py adds 'pad' (bytes between the n elements of a row and its
-    stride changed)"""
+    stride changed), tests/prss_contract.py 'canonical' (an output element that is not below the order)"""
 
     def __init__(self, kinds, message):
         super().__init__(message)
