@@ -340,10 +340,12 @@ int ffgpu_ctx_create(int kind, const uint64_t* modulus, int nlimbs, int device, 
         rc = FFGPU_EINVAL;
     }
     if (rc != FFGPU_OK) return rc;
-    if (!ops_for(pb.kind)) return FFGPU_ENOTSUP;
+    // (the secure steps' table goes with the kind: PRIME_CTX is then all an entry needs before it calls through ops->secure)
+    const FieldOps* ops = ops_for(pb.kind);
+    if (!ops || (ops->secure != nullptr) != (kind == FFGPU_PRIME)) return FFGPU_ENOTSUP;
     ffgpu_ctx* c = new (std::nothrow) ffgpu_ctx();
     if (!c) return FFGPU_ENOMEM;
-    c->ops = ops_for(pb.kind);
+    c->ops = ops;
     c->kind = kind;
     c->device = device;
     for (int i = 0; i < nlimbs; ++i) c->modulus[i] = modulus[i];
@@ -1220,13 +1222,17 @@ int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t o
 }
 
 // ---- secure comparison: the local steps of np_sgn (sgn.hpp) -------------------------------------------------------------
+// the bit length of the context's modulus
+static int modulus_bits(const ffgpu_ctx* ctx) {
+    const uint64_t* p = ctx->modulus;
+    const int top = p[2] ? 2 : p[1] ? 1 : 0;
+    return 64 * top + (64 - __builtin_clzll(p[top] | 1));
+}
 // 2^l, 2^(l-1) and 2^-l mod p as host scalars of the context's limb count; false unless 1 <= l <= 64 and
 // l <= bit_length(p) - 2 (the three constants are then field elements, 2^l < p / 2)
 static bool sgn_consts(const ffgpu_ctx* ctx, int l, uint64_t out[9]) {
     const uint64_t* p = ctx->modulus;
-    const int top = p[2] ? 2 : p[1] ? 1 : 0;
-    const int bits = 64 * top + (64 - __builtin_clzll(p[top] | 1));
-    if (l < 1 || l > SGN_MAX_L || l > bits - 2) return false;
+    if (l < 1 || l > SGN_MAX_L || l > modulus_bits(ctx) - 2) return false;
     const int sl = ffgpu_ctx_scalar_limbs(ctx);
     for (int i = 0; i < 9; ++i) out[i] = 0;
     out[0 * sl + l / 64] = 1ull << (l % 64);
@@ -1281,7 +1287,7 @@ int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void*
     const ByteRange o = byte_range(masked, n * eb);
     ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->sgn_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
+    return status_of(ctx->ops->secure->sgn_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
 
 int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* rbits, const void* sbit, int l, void* e_out,
@@ -1305,7 +1311,7 @@ int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* r
     if (z_out) o[no++] = byte_range(z_out, n * eb);
     ARGCHK(outputs_disjoint(in, 4, o, no));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->sgn_expand(ctx->policy, cs.lc, c, a, rbits, e_out ? sbit : nullptr, l, consts, e_out, nx_out, z_out,
+    return status_of(ctx->ops->secure->sgn_expand(ctx->policy, cs.lc, c, a, rbits, e_out ? sbit : nullptr, l, consts, e_out, nx_out, z_out,
                                           n, cs.st));
 }
 
@@ -1321,7 +1327,7 @@ int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void
     const ByteRange o = byte_range(lt_out, n * eb);
     ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
+    return status_of(ctx->ops->secure->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
 }
 
 // ---- sorting network: the two ends of a compare-exchange stage (sort.hpp) ------------------------------------------------
@@ -1347,7 +1353,7 @@ int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->cx_diff(ctx->policy, cs.lc, a, out, outer, k, inner, p, d, r, cs.st));
+    return status_of(ctx->ops->secure->cx_diff(ctx->policy, cs.lc, a, out, outer, k, inner, p, d, r, cs.st));
 }
 
 int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, size_t outer,
@@ -1361,7 +1367,7 @@ int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const 
     const ByteRange ar = byte_range(a, outer * k * inner * eb);
     ARGCHK(rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &ar, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
+    return status_of(ctx->ops->secure->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
 }
 
 // ---- tournament along an axis: the ends of a round (tour.hpp) -------------------------------------------------------------
@@ -1385,7 +1391,7 @@ int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->tour_diff(ctx->policy, cs.lc, a, out, outer, k, inner, mode, neg, cs.st));
+    return status_of(ctx->ops->secure->tour_diff(ctx->policy, cs.lc, a, out, outer, k, inner, mode, neg, cs.st));
 }
 
 int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_rows, const uint64_t* host_lambda, int nrows, void* out,
@@ -1399,7 +1405,7 @@ int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_row
     const ByteRange o = byte_range(out, outer * pl.next * inner * eb);
     ARGCHK(!overlaps(o, byte_range(a, outer * k * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->tour_select(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, out, outer, k, inner, mode, neg, cs.st));
+    return status_of(ctx->ops->secure->tour_select(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, out, outer, k, inner, mode, neg, cs.st));
 }
 
 int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out, size_t outer, size_t k, size_t inner, void* stream) {
@@ -1411,7 +1417,7 @@ int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out
     const ByteRange o = byte_range(out, outer * pl.row_elems * eb);
     ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && !overlaps(o, byte_range(c, outer * pl.row_elems * eb)));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->tour_unit_prod(ctx->policy, cs.lc, u, c, out, outer, k, inner, cs.st));
+    return status_of(ctx->ops->secure->tour_unit_prod(ctx->policy, cs.lc, u, c, out, outer, k, inner, cs.st));
 }
 
 int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* host_rows, const uint64_t* host_lambda, int nrows,
@@ -1425,7 +1431,7 @@ int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* hos
     const ByteRange o = byte_range(out, outer * k * inner * eb);
     ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
+    return status_of(ctx->ops->secure->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
 }
 
 // ---- first-occurrence search along an axis: the ends of a round (find.hpp) -------------------------------------------------
@@ -1454,7 +1460,7 @@ int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void
     const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb);
     ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->find_leaf_prod(ctx->policy, cs.lc, bits, tab, out, outer, k, inner, ncomp, flip, virt, cs.st));
+    return status_of(ctx->ops->secure->find_leaf_prod(ctx->policy, cs.lc, bits, tab, out, outer, k, inner, ncomp, flip, virt, cs.st));
 }
 
 int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, const void* const* host_rows, const uint64_t* host_lambda,
@@ -1469,7 +1475,7 @@ int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, con
     ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)) &&
            rows_clear_of(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->find_leaf_apply(ctx->policy, cs.lc, bits, tab, host_rows, host_lambda, nrows, out, outer, k, inner, ncomp,
+    return status_of(ctx->ops->secure->find_leaf_apply(ctx->policy, cs.lc, bits, tab, host_rows, host_lambda, nrows, out, outer, k, inner, ncomp,
                                                flip, virt, cs.st));
 }
 
@@ -1481,7 +1487,7 @@ int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, 
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(!overlaps(byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb), byte_range(level, (size_t)ncomp * outer * k * inner * eb)));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->find_prod(ctx->policy, cs.lc, level, out, outer, k, inner, ncomp, cs.st));
+    return status_of(ctx->ops->secure->find_prod(ctx->policy, cs.lc, level, out, outer, k, inner, ncomp, cs.st));
 }
 
 // ---- bit decomposition over a prime field: the local steps of np_to_bits (bits.hpp) --------------------------------------
@@ -1538,7 +1544,7 @@ int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void
     const ByteRange o = byte_range(masked, n * eb);
     ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->bits_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
+    return status_of(ctx->ops->secure->bits_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
 
 int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, void* g_out, void* p_out, size_t n, void* stream) {
@@ -1554,7 +1560,7 @@ int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, v
     const ByteRange o[2] = {byte_range(g_out, p.nl * eb), byte_range(p_out, p.nl * eb)};
     ARGCHK(outputs_disjoint(in, 2, o, 2));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->bits_expand(ctx->policy, cs.lc, c, rbits, l, g_out, p_out, n, cs.st));
+    return status_of(ctx->ops->secure->bits_expand(ctx->policy, cs.lc, c, rbits, l, g_out, p_out, n, cs.st));
 }
 
 int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const void* g, int l, void* out, size_t n, void* stream) {
@@ -1570,7 +1576,7 @@ int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const vo
     const ByteRange o = byte_range(out, p.nl * eb);
     ARGCHK(outputs_disjoint(in, 3, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->bits_finish(ctx->policy, cs.lc, c, rbits, g, l, out, n, cs.st));
+    return status_of(ctx->ops->secure->bits_finish(ctx->policy, cs.lc, c, rbits, g, l, out, n, cs.st));
 }
 
 // what both level entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
@@ -1594,7 +1600,7 @@ int ffgpu_carry_prod(ffgpu_ctx* ctx, const void* g, const void* p, int l, int ro
     const ByteRange o = byte_range(out, (size_t)(lv.rc + lv.rd) * n * eb);
     ARGCHK(outputs_disjoint(in, 2, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->carry_prod(ctx->policy, cs.lc, g, p, l, lv, out, n, cs.st));
+    return status_of(ctx->ops->secure->carry_prod(ctx->policy, cs.lc, g, p, l, lv, out, n, cs.st));
 }
 
 int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
@@ -1608,7 +1614,7 @@ int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_
     const ByteRange gp[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
     ARGCHK(!overlaps(gp[0], gp[1]) && rows_clear_of(host_rows, nrows, (size_t)(lv.rc + lv.rd) * n * eb, gp, 2));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
+    return status_of(ctx->ops->secure->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
 }
 
 // ---- fixed point over a prime field: the local steps of np_trunc and of _norm (fxp.hpp) -------------------------------------
@@ -1626,7 +1632,7 @@ int ffgpu_trunc_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const voi
     const ByteRange o[2] = {byte_range(ar_out, n * eb), byte_range(masked_out, n * eb)};
     ARGCHK(outputs_disjoint(in, 3, o, 2));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->trunc_mask(ctx->policy, cs.lc, a, rbits, rdivf, f, consts, ar_out, masked_out, n, cs.st));
+    return status_of(ctx->ops->secure->trunc_mask(ctx->policy, cs.lc, a, rbits, rdivf, f, consts, ar_out, masked_out, n, cs.st));
 }
 
 int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int nrows, const void* ar, int f,
@@ -1643,7 +1649,7 @@ int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint6
     const ByteRange o = byte_range(out, n * eb);
     ARGCHK(!overlaps(o, byte_range(ar, n * eb)) && rows_clear_of(host_rows, nrows, n * eb, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->trunc_finish(ctx->policy, cs.lc, host_rows, host_lambda, nrows, ar, f,
+    return status_of(ctx->ops->secure->trunc_finish(ctx->policy, cs.lc, host_rows, host_lambda, nrows, ar, f,
                                             consts + 2 * ffgpu_ctx_scalar_limbs(ctx), out, n, cs.st));
 }
 
@@ -1668,7 +1674,7 @@ int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* si
     const ByteRange o[2] = {byte_range(out, pl.elems * eb), byte_range(sign_out, sign_out ? n * eb : 0)};
     ARGCHK(outputs_disjoint(&in, 1, o, sign_out ? 2 : 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->norm_prod(ctx->policy, cs.lc, bits, l, out, sign_out, n, cs.st));
+    return status_of(ctx->ops->secure->norm_prod(ctx->policy, cs.lc, bits, l, out, sign_out, n, cs.st));
 }
 
 int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_rows, const uint64_t* host_lambda, int nrows, int l,
@@ -1683,17 +1689,11 @@ int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_r
     const ByteRange o = byte_range(out, pl.elems * eb);
     ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && rows_clear_of(host_rows, nrows, pl.elems * eb, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
+    return status_of(ctx->ops->secure->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
 }
 
 // ---- logarithm and exponential of fixed-point numbers over a prime field: the local steps no other entry serves (explog.hpp;
 // include/ffgpu_math.h) -------------------------------------------------------------------------------------------------------
-static int modulus_bits(const ffgpu_ctx* ctx) {
-    const uint64_t* p = ctx->modulus;
-    const int top = p[2] ? 2 : p[1] ? 1 : 0;
-    return 64 * top + (64 - __builtin_clzll(p[top] | 1));
-}
-
 int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w, void* out, size_t n, void* stream) {
     PRIME_CTX(ctx);
     ARGCHK(explog_prod_valid(h, w));
@@ -1705,7 +1705,7 @@ int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w,
     ARGCHK(pl.ok && cx_mul_ok((size_t)w, n, wn) && wn <= ((size_t)1 << 62) / eb);
     ARGCHK(!overlaps(byte_range(out, wn * eb), byte_range(P, pl.span * eb)));     // (rows h.. of P's allocation lie past the span)
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->powers_prod(ctx->policy, cs.lc, P, stride, h, w, out, n, cs.st));
+    return status_of(ctx->ops->secure->powers_prod(ctx->policy, cs.lc, P, stride, h, w, out, n, cs.st));
 }
 
 int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const void* tab, const uint64_t* host_c0, void* out, size_t n,
@@ -1721,7 +1721,7 @@ int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const
     const ByteRange o = byte_range(out, n * eb);
     ARGCHK(outputs_disjoint(in, 2, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->poly_dot(ctx->policy, cs.lc, P, stride, theta, tab, host_c0, out, n, cs.st));
+    return status_of(ctx->ops->secure->poly_dot(ctx->policy, cs.lc, P, stride, theta, tab, host_c0, out, n, cs.st));
 }
 
 int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const void* tab, void* out, size_t n, void* stream) {
@@ -1737,7 +1737,7 @@ int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const voi
     const ByteRange o = byte_range(out, n * eb);
     ARGCHK(outputs_disjoint(in, 2, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->pow_base(ctx->policy, cs.lc, x, shift, ebits, pbits, tab, out, n, cs.st));
+    return status_of(ctx->ops->secure->pow_base(ctx->policy, cs.lc, x, shift, ebits, pbits, tab, out, n, cs.st));
 }
 
 int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t n, void* stream) {
@@ -1752,7 +1752,7 @@ int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t
     const ByteRange o = byte_range(out, pl.elems * eb);
     ARGCHK(outputs_disjoint(&in, 1, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->bits_reverse(ctx->policy, cs.lc, bits, l, out, n, cs.st));
+    return status_of(ctx->ops->secure->bits_reverse(ctx->policy, cs.lc, bits, l, out, n, cs.st));
 }
 
 // ---- the Legendre zero test over a Blum prime: the local steps of runtime._np_is_zero (iszero.hpp; include/ffgpu_math.h) ----
@@ -1768,7 +1768,7 @@ int ffgm_iszero_mask(ffgpu_ctx* ctx, const void* a, const void* r, const void* z
     const ByteRange o = byte_range(out, kn);
     ARGCHK(outputs_disjoint(in, 4, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->iszero_mask(ctx->policy, cs.lc, a, r, z, u2, k, out, n, cs.st));
+    return status_of(ctx->ops->secure->iszero_mask(ctx->policy, cs.lc, a, r, z, u2, k, out, n, cs.st));
 }
 
 int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t count, void* stream) {
@@ -1785,7 +1785,7 @@ int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t coun
     legendre_exponent(ctx, &ex);
     exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->legendre_code(ctx->policy, cs.lc, c, &ex, code, count, cs.st));
+    return status_of(ctx->ops->secure->legendre_code(ctx->policy, cs.lc, c, &ex, code, count, cs.st));
 }
 
 int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void* out, size_t count, void* stream) {
@@ -1798,7 +1798,7 @@ int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void*
     const ByteRange o = byte_range(out, count * eb);
     ARGCHK(outputs_disjoint(in, 2, &o, 1));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->iszero_finish(ctx->policy, cs.lc, code, z, out, count, cs.st));
+    return status_of(ctx->ops->secure->iszero_finish(ctx->policy, cs.lc, code, z, out, count, cs.st));
 }
 
 // ---- secure random bits over a prime field: the local steps of runtime.np_random_bits (rbits.hpp; include/ffgpu_math.h) ----
@@ -1836,7 +1836,7 @@ int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const
     const ByteRange o[2] = {byte_range(out, n * eb), byte_range(zeros, zeros ? sizeof(int32_t) : 0)};
     ARGCHK(outputs_disjoint(in, 2 * k, o, 2));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->rbits_open(ctx->policy, cs.lc, host_r, host_z, host_lambda, k, out, zeros, n, cs.st));
+    return status_of(ctx->ops->secure->rbits_open(ctx->policy, cs.lc, host_r, host_z, host_lambda, k, out, zeros, n, cs.st));
 }
 
 int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, void* const* host_b, int m, int is_signed, int f, size_t n,
@@ -1883,7 +1883,7 @@ int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, 
     for (int i = 0; i < f; ++i) dbl_mod3(A, p);
     if (!is_signed) memcpy(B, A, sizeof(B));
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A, B, n, cs.st));
+    return status_of(ctx->ops->secure->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A, B, n, cs.st));
 }
 
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
