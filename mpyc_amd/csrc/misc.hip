@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include "kernels.hpp"
 #include "bitslice.hpp"
+#include "sbox_layer_geom.hpp"
 
 using namespace ffgpu;
 
@@ -522,87 +523,6 @@ struct Gf8SboxLayerArgs {
 };
 enum { SBL_TABLE_BYTES = 1536 + 2304 + 2304 };
 
-// The keystream of the layer, two ways (same words in the same order: block b of word i has counter i * NBLK + b):
-//   DR == 0  any round count: a block is computed when the previous one is used up -- a burst of ~1000 VALU
-//            instructions between phases that wait on LDS look-ups;
-//   DR  > 0  DR double rounds, known at compile time (10 = ChaCha20): block b + 1 advances by DR / 2 quarter rounds for
-//            every word taken from block b, i.e. its arithmetic sits BETWEEN the table look-ups of the gates that
-//            consume block b and fills their latency.  At 10^6 bytes every SIMD holds four waves that all start
-//            together: without this they run their ChaCha bursts and their look-up phases in step (43 us against
-//            24 us per 10^6 bytes in a long run, profiles/r04_sbox_layer.md).
-template <int DR>
-struct SblKeystream {
-    uint32_t ks[16];        // block being consumed
-    uint32_t x[16];         // DR > 0: the next block, in progress
-    int kpos, qpos;
-    uint64_t next_ctr;      // counter of the block in x (DR > 0) / of the next block to compute (DR == 0)
-    const RngKey* rk;
-
-    __device__ __forceinline__ void start_block(uint64_t ctr) {
-        x[0] = 0x61707865u; x[1] = 0x3320646eu; x[2] = 0x79622d32u; x[3] = 0x6b206574u;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) x[4 + q] = rk->key[q];
-        x[12] = (uint32_t)ctr; x[13] = (uint32_t)(ctr >> 32); x[14] = rk->nonce[0]; x[15] = rk->nonce[1];
-    }
-    __device__ __forceinline__ void finish_block(uint64_t ctr) {       // ks = x + the block's input words
-        ks[0] = x[0] + 0x61707865u; ks[1] = x[1] + 0x3320646eu; ks[2] = x[2] + 0x79622d32u; ks[3] = x[3] + 0x6b206574u;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) ks[4 + q] = x[4 + q] + rk->key[q];
-        ks[12] = x[12] + (uint32_t)ctr; ks[13] = x[13] + (uint32_t)(ctr >> 32);
-        ks[14] = x[14] + rk->nonce[0]; ks[15] = x[15] + rk->nonce[1];
-    }
-    __device__ __forceinline__ void quarter(int q) {                    // q = index within a double round (constant-folded)
-        switch (q & 7) {
-            case 0: { FF_QR(x[0], x[4], x[8], x[12]) } break;
-            case 1: { FF_QR(x[1], x[5], x[9], x[13]) } break;
-            case 2: { FF_QR(x[2], x[6], x[10], x[14]) } break;
-            case 3: { FF_QR(x[3], x[7], x[11], x[15]) } break;
-            case 4: { FF_QR(x[0], x[5], x[10], x[15]) } break;
-            case 5: { FF_QR(x[1], x[6], x[11], x[12]) } break;
-            case 6: { FF_QR(x[2], x[7], x[8], x[13]) } break;
-            default: { FF_QR(x[3], x[4], x[9], x[14]) } break;
-        }
-    }
-    // begin(): x holds block `first_ctr` complete (DR > 0) / nothing is computed yet (DR == 0); step_begin() marks the
-    // consumed block as used up.  All positions (kpos, qpos) are compile-time constants once the caller is unrolled:
-    // a step that takes a multiple of 16 words from the stream leaves it in the state step_begin() describes.
-    __device__ __forceinline__ void step_begin() {
-        kpos = 16;
-        qpos = 8 * DR;
-    }
-    __device__ __forceinline__ void begin(const RngKey* key, uint64_t first_ctr) {
-        rk = key;
-        next_ctr = first_ctr;
-        if (DR > 0) {
-            start_block(next_ctr);
-#pragma unroll
-            for (int q = 0; q < 8 * DR; ++q) quarter(q);
-        }
-        step_begin();
-    }
-    __device__ __forceinline__ uint32_t next_word() {
-        if (DR == 0) {
-            if (kpos == 16) {
-                chacha_block(rk->key, (uint32_t)next_ctr, (uint32_t)(next_ctr >> 32), rk->nonce[0], rk->nonce[1], (int)rk->rounds, ks);
-                ++next_ctr;
-                kpos = 0;
-            }
-            return ks[kpos++];
-        }
-        if (kpos == 16) {                      // the block in x has had its 16 x DR / 2 = 8 DR quarter rounds: it becomes ks
-            finish_block(next_ctr);
-            ++next_ctr;
-            start_block(next_ctr);
-            kpos = 0;
-            qpos = 0;
-        }
-        const uint32_t w = ks[kpos++];
-#pragma unroll
-        for (int q = 0; q < DR / 2; ++q) quarter(qpos++);
-        return w;
-    }
-};
-
 // W SWAR words (four secure bytes each) of one thread through the whole layer.  The words share ONE keystream: W x 33
 // coefficient words (m = 3, t = 1) are 4.125 ChaCha blocks for W = 2 -- five blocks for eight bytes instead of six --
 // and the 2 W K table products of a gate are independent of each other (twice the look-ups in flight per wave).
@@ -786,15 +706,16 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
     // steps; the launcher caps the grid at the resident workgroups, so at 10^8 bytes a thread walks through ~95 steps
     // on 2.06 blocks each.  Counters: thread g streams blocks [g * bpt, (g + 1) * bpt), its spare blocks are
     // 2^62 + g * spt + (step / 16), the ragged end of the rows draws from 2^61.
-    constexpr bool CAN_CONT = (T == 1 && W == 1);
-    constexpr int NBLK = (11 * (2 * T + 1) * T * W + 15) / 16;
-    const uint64_t steps = (nthreads_full + gsz - 1) / gsz;
-    const uint64_t bpt = 2 * steps + 2, spt = steps / 16 + 1;
+    // (sbox_layer_geom.hpp has the arithmetic; the launcher's plan holds the same numbers)
+    constexpr bool CAN_CONT = sbl_can_cont(T, W);
+    constexpr int NBLK = sbl_nblk(T, W);
+    const uint64_t steps = sbl_nsteps(nthreads_full, gsz);
+    const uint64_t bpt = sbl_bpt(steps), spt = sbl_spt(steps);
     auto run = [&](auto dr_, auto cont_) {
         constexpr int DRV = decltype(dr_)::value;
         constexpr bool CONT = decltype(cont_)::value;
         SblKeystream<DRV> stream;
-        if (CONT && gid < nthreads_full) stream.begin(&ra.rk, (uint64_t)gid * bpt);
+        if (CONT && gid < nthreads_full) stream.begin(&ra.rk, sbl_ctr_thread(gid, bpt));
         uint64_t j = 0;
         for (size_t i = gid; i < nthreads_full; i += gsz, ++j) {
             uint32_t sw = 0;
@@ -802,7 +723,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
                 // the spare block lives in LDS ([word][thread]: conflict-free), not in 16 registers: the kernel stays at
                 // four waves per SIMD
                 if ((j & 15) == 0) {
-                    const uint64_t c = (1ull << 62) + (uint64_t)gid * spt + (j >> 4);
+                    const uint64_t c = sbl_ctr_spare(gid, spt, j);
                     uint32_t blk[16];
                     chacha_block(ra.rk.key, (uint32_t)c, (uint32_t)(c >> 32), ra.rk.nonce[0], ra.rk.nonce[1], (int)ra.rk.rounds, blk);
 #pragma unroll
@@ -810,7 +731,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
                 }
                 sw = spare_lds[(int)(j & 15) * BLOCK + threadIdx.x];
             }
-            sbl_words<M, T, DRV, W, CONT>(f, a, ra, lg, ex, tbits, tfold, i, true, all4, stream, (uint64_t)i * NBLK, sw);
+            sbl_words<M, T, DRV, W, CONT>(f, a, ra, lg, ex, tbits, tfold, i, true, all4, stream, sbl_ctr_step(i, NBLK), sw);
         }
     };
     // (a thread with one or two steps gains nothing from the continued stream and would compute its spare block as a
@@ -819,7 +740,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
     const bool cont = CAN_CONT && (SBL_PROBE_PATH & 1);
     const bool dr10 = (SBL_PROBE_PATH & 2) != 0;
 #else
-    const bool cont = CAN_CONT && steps >= 4;
+    const bool cont = sbl_cont(T, W, steps);
     const bool dr10 = ra.rk.rounds == 20;
 #endif
     if constexpr (CAN_CONT) {
@@ -840,7 +761,7 @@ __global__ __launch_bounds__(BLOCK) void k_gf8_sbox_layer(GF2P8 f, Gf8SboxLayerA
             valid[w] = left >= 4 ? 4 : (left > 0 ? left : 0);
         }
         SblKeystream<0> stream;
-        sbl_words<M, T, 0, W, false>(f, a, ra, lg, ex, tbits, tfold, nthreads_full, false, valid, stream, 1ull << 61, 0u);
+        sbl_words<M, T, 0, W, false>(f, a, ra, lg, ex, tbits, tfold, nthreads_full, false, valid, stream, SBL_CTR_RAGGED, 0u);
     }
     rng_state_release(ra);
 }
@@ -864,24 +785,17 @@ LaunchStatus ffgpu_launch_gf8_sbox_layer(const void* policy, const LaunchCfg& lc
     // One word (four bytes) per thread.  (Two words per thread sharing a keystream -- five ChaCha blocks for eight bytes instead
     // of six, but 131 VGPRs and half the waves -- measured slower at 10^6 bytes in round 4 and was removed; the continued
     // keystream of the kernel gets the same saving without the registers: profiles/r04_sbox_layer.md.)
-    constexpr int W = 1;
-    const size_t nthreads_full = n / (4 * (size_t)W);
-    const int rest_bytes = (int)(n - nthreads_full * 4 * W);
-    size_t want = (nthreads_full + BLOCK - 1) / BLOCK;
-    if (want < 1) want = 1;
     // persistent above one round of resident workgroups (4 per CU at t = 1, m <= 4: 119-128 VGPRs; 3 for m >= 5; 2-3 per CU
     // for t >= 2): the threads of the t = 1 kernels then carry their keystream from step to step instead of discarding 15
-    // of every 48 words
-    const size_t resident = (size_t)lc.num_cu * (t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2));
-    if (want > resident) want = resident;
-    const unsigned grid = (unsigned)want;
-    {   // the keystream's counter ranges never meet: threads stream blocks [g * bpt, (g + 1) * bpt) (or step i its blocks
-        // i * NBLK ...), the ragged end draws from 2^61, the spare blocks of the continued stream from 2^62 + g * spt + j / 16,
-        // re-draws elsewhere in the library from 2^63 -- refuse shapes that would leave their range (n > ~10^17 bytes)
-        const uint64_t gsz = (uint64_t)grid * BLOCK;
-        const uint64_t steps = (nthreads_full + gsz - 1) / gsz;
-        if (gsz * (2 * steps + 2) >= (1ull << 61) || gsz * (steps / 16 + 1) >= (1ull << 61) || nthreads_full * 16ull >= (1ull << 61)) return L_NOT_SUPPORTED;
-    }
+    // of every 48 words.  The keystream's counter ranges never meet: threads stream blocks [g * bpt, (g + 1) * bpt) (or step i
+    // its blocks i * NBLK ...), the ragged end draws from 2^61, the spare blocks of the continued stream from
+    // 2^62 + g * spt + j / 16, re-draws elsewhere in the library from 2^63 -- the plan refuses shapes that would leave their
+    // range (n > ~10^17 bytes)
+    const SblPlan pl = sbl_plan(n, t, m, lc.num_cu);
+    if (!pl.ok) return L_NOT_SUPPORTED;
+    const size_t nthreads_full = pl.nthreads_full;
+    const int rest_bytes = pl.rest_bytes;
+    const unsigned grid = pl.grid;
     // (measured and NOT kept, round 4: letting up to 1024 workgroups advance the state themselves with a ticket drawn at
     // workgroup START -- the returning atomic sits in front of the wave's first loads in the in-order vmcnt queue, and 977
     // same-address atomics at ~25 ns each delay those waves: 43.7 us against 38.4 us with the one-thread kernel after it)

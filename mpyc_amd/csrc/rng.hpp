@@ -57,6 +57,87 @@ FF_HD void chacha_block(const uint32_t key[8], uint32_t w12, uint32_t w13, uint3
     out[12] = x12 + w12; out[13] = x13 + w13; out[14] = x14 + w14; out[15] = x15 + w15;
 }
 
+// The keystream of the fused GF(2^8) S-box layer (misc.hip, k_gf8_sbox_layer), two ways (same words in the same order: block b of word i has counter i * NBLK + b):
+//   DR == 0  any round count: a block is computed when the previous one is used up -- a burst of ~1000 VALU
+//            instructions between phases that wait on LDS look-ups;
+//   DR  > 0  DR double rounds, known at compile time (10 = ChaCha20): block b + 1 advances by DR / 2 quarter rounds for
+//            every word taken from block b, i.e. its arithmetic sits BETWEEN the table look-ups of the gates that
+//            consume block b and fills their latency.  At 10^6 bytes every SIMD holds four waves that all start
+//            together: without this they run their ChaCha bursts and their look-up phases in step (43 us against
+//            24 us per 10^6 bytes in a long run, profiles/r04_sbox_layer.md).
+template <int DR>
+struct SblKeystream {
+    uint32_t ks[16];        // block being consumed
+    uint32_t x[16];         // DR > 0: the next block, in progress
+    int kpos, qpos;
+    uint64_t next_ctr;      // counter of the block in x (DR > 0) / of the next block to compute (DR == 0)
+    const RngKey* rk;
+
+    FF_HD void start_block(uint64_t ctr) {
+        x[0] = 0x61707865u; x[1] = 0x3320646eu; x[2] = 0x79622d32u; x[3] = 0x6b206574u;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[4 + q] = rk->key[q];
+        x[12] = (uint32_t)ctr; x[13] = (uint32_t)(ctr >> 32); x[14] = rk->nonce[0]; x[15] = rk->nonce[1];
+    }
+    FF_HD void finish_block(uint64_t ctr) {       // ks = x + the block's input words
+        ks[0] = x[0] + 0x61707865u; ks[1] = x[1] + 0x3320646eu; ks[2] = x[2] + 0x79622d32u; ks[3] = x[3] + 0x6b206574u;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ks[4 + q] = x[4 + q] + rk->key[q];
+        ks[12] = x[12] + (uint32_t)ctr; ks[13] = x[13] + (uint32_t)(ctr >> 32);
+        ks[14] = x[14] + rk->nonce[0]; ks[15] = x[15] + rk->nonce[1];
+    }
+    FF_HD void quarter(int q) {                    // q = index within a double round (constant-folded)
+        switch (q & 7) {
+            case 0: { FF_QR(x[0], x[4], x[8], x[12]) } break;
+            case 1: { FF_QR(x[1], x[5], x[9], x[13]) } break;
+            case 2: { FF_QR(x[2], x[6], x[10], x[14]) } break;
+            case 3: { FF_QR(x[3], x[7], x[11], x[15]) } break;
+            case 4: { FF_QR(x[0], x[5], x[10], x[15]) } break;
+            case 5: { FF_QR(x[1], x[6], x[11], x[12]) } break;
+            case 6: { FF_QR(x[2], x[7], x[8], x[13]) } break;
+            default: { FF_QR(x[3], x[4], x[9], x[14]) } break;
+        }
+    }
+    // begin(): x holds block `first_ctr` complete (DR > 0) / nothing is computed yet (DR == 0); step_begin() marks the
+    // consumed block as used up.  All positions (kpos, qpos) are compile-time constants once the caller is unrolled:
+    // a step that takes a multiple of 16 words from the stream leaves it in the state step_begin() describes.
+    FF_HD void step_begin() {
+        kpos = 16;
+        qpos = 8 * DR;
+    }
+    FF_HD void begin(const RngKey* key, uint64_t first_ctr) {
+        rk = key;
+        next_ctr = first_ctr;
+        if (DR > 0) {
+            start_block(next_ctr);
+#pragma unroll
+            for (int q = 0; q < 8 * DR; ++q) quarter(q);
+        }
+        step_begin();
+    }
+    FF_HD uint32_t next_word() {
+        if (DR == 0) {
+            if (kpos == 16) {
+                chacha_block(rk->key, (uint32_t)next_ctr, (uint32_t)(next_ctr >> 32), rk->nonce[0], rk->nonce[1], (int)rk->rounds, ks);
+                ++next_ctr;
+                kpos = 0;
+            }
+            return ks[kpos++];
+        }
+        if (kpos == 16) {                      // the block in x has had its 16 x DR / 2 = 8 DR quarter rounds: it becomes ks
+            finish_block(next_ctr);
+            ++next_ctr;
+            start_block(next_ctr);
+            kpos = 0;
+            qpos = 0;
+        }
+        const uint32_t w = ks[kpos++];
+#pragma unroll
+        for (int q = 0; q < DR / 2; ++q) quarter(qpos++);
+        return w;
+    }
+};
+
 // Per-policy sampling.  S = bytes of keystream per sample.
 //   * pseudo-Mersenne primes p = 2^k - c (PM64 / PM128 / PM96, every default MPyC prime): rejection
 //     sampling, REJECT = 1.  A sample is k keystream bits; it is >= p with probability c/2^k (2^-56 for

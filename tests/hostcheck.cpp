@@ -259,6 +259,33 @@ extern "C" void hc_chacha_block(const uint32_t key[8], const uint32_t w[4], int 
     chacha_block(key, w[0], w[1], w[2], w[3], rounds, out);
 }
 
+// the keystream of the fused S-box layer (rng.hpp SblKeystream): begin(first_ctr), then `nsteps` steps of `nwords` words
+// each, every step after the first entered through step_begin() as the layer's continued stream enters it.  dr = 10: the
+// interleaved ChaCha20 (SblKeystream<10>); dr = 0: any round count (SblKeystream<0>).  out: nsteps * nwords words.
+template <int DR>
+static void sbl_stream_words(const RngKey& rk, uint64_t first_ctr, int nsteps, int nwords, uint32_t* out) {
+    SblKeystream<DR> s;
+    s.begin(&rk, first_ctr);
+    for (int j = 0; j < nsteps; ++j) {
+        if (j) s.step_begin();
+        for (int q = 0; q < nwords; ++q) *out++ = s.next_word();
+    }
+}
+extern "C" int hc_sbl_keystream(const unsigned char* key32, uint64_t nonce, int rounds, int dr, uint64_t first_ctr, int nsteps,
+                                int nwords, uint32_t* out) {
+    RngKey rk;
+    memset(&rk, 0, sizeof(rk));
+    memcpy(rk.key, key32, 32);
+    rk.nonce[0] = (uint32_t)nonce;
+    rk.nonce[1] = (uint32_t)(nonce >> 32);
+    rk.rounds = (uint32_t)rounds;
+    if (nsteps < 1 || nwords < 1 || (nsteps > 1 && nwords % 16)) return 1;    // step_begin(): after whole blocks only
+    if (dr == 10 && rounds == 20) sbl_stream_words<10>(rk, first_ctr, nsteps, nwords, out);
+    else if (dr == 0) sbl_stream_words<0>(rk, first_ctr, nsteps, nwords, out);
+    else return 1;
+    return 0;
+}
+
 template <class F, int T>
 static void draw_rows(const PolicyBlob& pb, const RngKey& rk, unsigned char* out, size_t cstride, size_t n, int row0) {
     F f;

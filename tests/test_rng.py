@@ -134,3 +134,56 @@ def test_uniformity_smoke(hostcheck):
     for bit in (0, 17, 40, 60):
         frac = float(((c >> np.uint64(bit)) & np.uint64(1)).mean())
         assert 0.48 < frac < 0.52, bit
+
+
+# ---- the keystream of the fused S-box layer (rng.hpp SblKeystream) ---------------------------------------------------------
+def sbl_words(hostcheck, nonce, rounds, dr, ctr, nsteps, nwords):
+    out = (ctypes.c_uint32 * (nsteps * nwords))()
+    rc = hostcheck.hc_sbl_keystream(KEY, ctypes.c_uint64(nonce), rounds, dr, ctypes.c_uint64(ctr), nsteps, nwords, out)
+    assert rc == 0
+    return list(out)
+
+
+def chacha_words(po, nonce, rounds, ctr, nblocks):
+    """words of the blocks ctr, ctr + 1, ... of ChaCha with a 64-bit block counter (words 12, 13) and a 64-bit nonce"""
+    out = []
+    for b in range(nblocks):
+        c = ctr + b
+        blk = po.chacha_block(KEY, c, nonce.to_bytes(8, 'little'), rounds)
+        out += [int.from_bytes(blk[4 * i:4 * i + 4], 'little') for i in range(16)]
+    return out
+
+
+SBL_COUNTERS = [0, 1, 3 * 4099, 2**32 - 1, 2**32, 2**32 + 5, 0x123456789a, 2**61, 2**61 - 2, 2**62 + 77, 2**63 - 3]
+
+
+def test_sbox_layer_keystream_is_chacha(hostcheck):
+    """SblKeystream<10> (ChaCha20 interleaved with its consumer: five quarter rounds of the next block per word taken) and SblKeystream<0>
+    (a block at a time, 20 / 12 / 8 rounds) hand out the words of the blocks ctr, ctr + 1, ... in order: 33 words of a step
+    that begins its own stream, and five steps of 32 words of a continued one, at 64-bit counters with a high word.  The
+    Python ChaCha it is held against is pinned to the RFC 8439 block vector first."""
+    from oracle import pyoracle as po
+    w, expect = rfc8439_block_vector()
+    blk = po.chacha_block(KEY, w[0] | (w[1] << 32), w[2].to_bytes(4, 'little') + w[3].to_bytes(4, 'little'), 20)
+    assert [int.from_bytes(blk[4 * i:4 * i + 4], 'little') for i in range(16)] == expect
+    nonce = 0x0000000500000007
+    ncases = 0
+    for ctr in SBL_COUNTERS:
+        for dr, rounds in ((10, 20), (0, 20), (0, 12), (0, 8)):
+            want = chacha_words(po, nonce, rounds, ctr, 10)
+            assert len(set(want)) > 150                                  # (a stream, not a constant)
+            # a step with a stream of its own: 11 K T = 33 words at t = 1 -- two blocks and the first word of the third
+            assert sbl_words(hostcheck, nonce, rounds, dr, ctr, 1, 33) == want[:33], (hex(ctr), dr, rounds)
+            # ... 110 and 231 words at t = 2, 3
+            assert sbl_words(hostcheck, nonce, rounds, dr, ctr, 1, 231) == chacha_words(po, nonce, rounds, ctr, 15)[:231]
+            # the continued stream: five steps of two whole blocks each, entered through step_begin()
+            assert sbl_words(hostcheck, nonce, rounds, dr, ctr, 5, 32) == want[:160], (hex(ctr), dr, rounds)
+            ncases += 3
+    # another nonce, another stream; the nonce's two words are words 14 and 15
+    other = sbl_words(hostcheck, 0x0000000700000005, 20, 10, 5, 1, 33)
+    assert other == chacha_words(po, 0x0000000700000005, 20, 5, 3)[:33] and other != sbl_words(hostcheck, nonce, 20, 10, 5, 1, 33)
+    # the harness refuses what the kernel never does: a second step after a part of a block
+    out = (ctypes.c_uint32 * 66)()
+    assert hostcheck.hc_sbl_keystream(KEY, ctypes.c_uint64(0), 20, 10, ctypes.c_uint64(0), 2, 33, out) == 1
+    assert hostcheck.hc_sbl_keystream(KEY, ctypes.c_uint64(0), 12, 10, ctypes.c_uint64(0), 1, 33, out) == 1
+    assert ncases == 3 * 4 * len(SBL_COUNTERS)
