@@ -1,8 +1,9 @@
 /*
  * ffgpu_math.h -- second header of libffgpu.so: the local steps under the secure logarithm and exponential of fixed-point
  * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945), under the probabilistic zero test over a
- * Blum prime (runtime._np_is_zero, runtime.py:3581-3620) and under secure random bits (runtime.np_random_bits,
- * runtime.py:4187-4273) that no entry of ffgpu.h serves.  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
+ * Blum prime (runtime._np_is_zero, runtime.py:3581-3620), under secure random bits (runtime.np_random_bits,
+ * runtime.py:4187-4273) and under the secure binary sign by Legendre symbols (demos/np_bnnmnist.py:44-156) that no entry of
+ * ffgpu.h serves.  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
  * conventions:
  *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
  *   - array arguments are DEVICE pointers unless the name says host; elements are canonical little-endian limbs in the
@@ -14,7 +15,7 @@
  *   - an output that overlaps an input is FFGPU_EINVAL (the exceptions are stated at ffgm_powers_prod and ffgm_rbits_finish);
  *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
- * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), and into random_bits().
+ * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), into random_bits() and into bsgn().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -65,10 +66,25 @@
  *   replaces: runtime.py:4265-4272 (`r * field.array._sqrt(r2, INV=True)`, finfields.py:1424-1437, the `+ 1`, the halving
  *   and the shift), once per party.
  *
+ * The arrays of the binary sign are ROW-MAJOR (w, n), rows n elements apart, 1 <= w <= 8: row i belongs to the i-th symbol.
+ *
+ * ffgm_bsgn_mask: out[i*n + e] = z[i*n + e] * (alpha*a[e] + beta[i]) for i < w.  host_alpha: one host scalar, host_beta: w of
+ *   them, canonical.  A thread forms alpha*a once and keeps it in registers across the w rows; per row one addition, one
+ *   lazy product, one reduction: (2w + 1)*n elements of traffic.
+ *   replaces: np_bnnmnist.py:72, :106-110 and :147-150 (`y * (2*a + 1)`, `y + [[-2], [0], [2]]` and its broadcast product).
+ * ffgm_bsgn_finish: c: the public opened (w, n) values; host_s, host_out: host arrays of m <= 64 device pointers, party q's
+ *   (w, n) shares of the signs and its output.  With h = (c[i*n + e] | p), which is 1, -1 or 0:
+ *     sum == 0: out_q[i*n + e] = h * s_q[i*n + e] (s, p - s or 0), w*n entries;
+ *     sum == 1: out_q[e] = sum_{i<w} h_i * s_q[i*n + e], n entries.
+ *   The exponentiation by (p-1)/2 is the one ffgpu_pow launches for this exponent and runs once per opened value for all m
+ *   parties; no codes are written.  p odd: FFGPU_ENOTSUP for p == 2.
+ *   replaces: np_bnnmnist.py:74, :113-114 and :154 (`s * legendre_p(y)`, gmpy2.legendre per entry, and the sum over the rows).
+ *
  * FFGPU_OK: n == 0 / count == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or
  * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; m < 1;
- * f < 0 or f >= 192; a size overflowing; an output overlapping an input.  FFGPU_ENOTSUP: a GF(2^n) context;
- * ffgm_legendre_code over p == 2; ffgm_rbits_finish unless p = 3 mod 4; more than 64 rows.                              */
+ * f < 0 or f >= 192; w < 1 or w > 8; sum not 0 or 1; a size overflowing; an output overlapping an input or another output.
+ * FFGPU_ENOTSUP: a GF(2^n) context; ffgm_legendre_code and ffgm_bsgn_finish over p == 2; ffgm_rbits_finish unless
+ * p = 3 mod 4; more than 64 rows or parties.                                                                             */
 #ifndef FFGPU_MATH_H
 #define FFGPU_MATH_H
 
@@ -91,6 +107,10 @@ int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const
                     int32_t* zeros, size_t n, void* stream);
 int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, void* const* host_b, int m, int is_signed, int f, size_t n,
                       void* stream);
+int ffgm_bsgn_mask(ffgpu_ctx* ctx, const void* a, const void* z, const uint64_t* host_alpha, const uint64_t* host_beta, int w, void* out,
+                   size_t n, void* stream);
+int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, void* const* host_out, int m, int w, int sum, size_t n,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -155,6 +155,8 @@ _SIGS_MATH = {
     'ffgm_iszero_finish': [_vp, _vp, _vp, _vp, _sz, _vp],
     'ffgm_rbits_open': [_vp, _vp, _vp, _u64p, _int, _vp, _vp, _sz, _vp],
     'ffgm_rbits_finish': [_vp, _vp, _vp, _vp, _int, _int, _int, _sz, _vp],
+    'ffgm_bsgn_mask': [_vp, _vp, _vp, _u64p, _u64p, _int, _vp, _sz, _vp],
+    'ffgm_bsgn_finish': [_vp, _vp, _vp, _vp, _int, _int, _int, _sz, _vp],
 }
 EXPORTED_MATH = tuple(_SIGS_MATH)
 

@@ -1886,6 +1886,53 @@ int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, 
     return status_of(ctx->ops->secure->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A, B, n, cs.st));
 }
 
+// ---- the secure binary sign by Legendre symbols: the local steps of the demo's bsgn (bsgn.hpp; include/ffgpu_math.h) ----
+int ffgm_bsgn_mask(ffgpu_ctx* ctx, const void* a, const void* z, const uint64_t* host_alpha, const uint64_t* host_beta, int w, void* out,
+                   size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(bsgn_w_valid(w));
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
+    ARGCHK(pl.ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(a && z && host_alpha && host_beta && out);
+    const size_t wn = pl.span * eb;
+    const ByteRange in[2] = {byte_range(a, n * eb), byte_range(z, wn)};
+    const ByteRange o = byte_range(out, wn);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->bsgn_mask(ctx->policy, cs.lc, a, z, host_alpha, host_beta, w, out, n, cs.st));
+}
+
+int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, void* const* host_out, int m, int w, int sum, size_t n,
+                     void* stream) {
+    PRIME_CTX(ctx);
+    if (!ctx->modulus[2] && !ctx->modulus[1] && ctx->modulus[0] == 2) return FFGPU_ENOTSUP;
+    ARGCHK(m >= 1 && bsgn_w_valid(w) && (sum == 0 || sum == 1));
+    if (m > (int)BSGN_MAX_PARTIES) return FFGPU_ENOTSUP;
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
+    ARGCHK(pl.ok && bsgn_flat_plan(n, w, eb, false).ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(c && host_s && host_out);
+    const size_t wn = pl.span * eb, on = sum ? n * eb : wn;
+    const ByteRange cr = byte_range(c, wn);
+    for (int i = 0; i < m; ++i) {
+        ARGCHK(host_s[i] && host_out[i]);
+        const ByteRange oi = byte_range(host_out[i], on);
+        ARGCHK(!overlaps(oi, cr));
+        for (int j = 0; j < m; ++j) {
+            if (j < i) ARGCHK(!overlaps(oi, byte_range(host_out[j], on)));
+            ARGCHK(!overlaps(oi, byte_range(host_s[j], wn)));
+        }
+    }
+    ExpArgs ex;
+    legendre_exponent(ctx, &ex);
+    exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->bsgn_finish(ctx->policy, cs.lc, c, &ex, host_s, host_out, m, w, sum, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

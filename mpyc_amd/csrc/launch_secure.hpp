@@ -90,6 +90,14 @@ struct SecureOps {
                       void* out, int* zeros, size_t n, hipStream_t st);
     LaunchStatus (*rbits_finish)(const void* F, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* r, void* const* b,
                         int m, const uint64_t* A2, const uint64_t* B2, size_t n, hipStream_t st);
+    // local steps of the secure binary sign by Legendre symbols (bsgn.hpp); the (w, n) arrays are row-major; alpha2, beta2:
+    // one and w host scalars; ex of bsgn_finish: the exponent (p - 1) / 2 as ffgpu_pow hands it to pow; s, out: m rows of
+    // shares and outputs, an output of n entries when sum (L_PLAN_REFUSED: bsgn_rows_plan() / bsgn_flat_plan() refuses the
+    // counts or the sizes)
+    LaunchStatus (*bsgn_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* z, const uint64_t* alpha2,
+                     const uint64_t* beta2, int w, void* out, size_t n, hipStream_t st);
+    LaunchStatus (*bsgn_finish)(const void* F, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* s, void* const* out,
+                       int m, int w, int sum, size_t n, hipStream_t st);
 };
 
 template <class F>
@@ -525,6 +533,46 @@ struct SecureLaunchers : Launchers<F> {
         hipLaunchKernelGGL((k_rbits_finish<F>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, n);
         return launched();
     }
+    // The local steps of the secure binary sign (bsgn.hpp).  mask: one flat streaming loop over the units of a row, the
+    // launch of iszero_mask.  finish in rows mode: the launch of pow over the w n opened values, as legendre_code and
+    // rbits_finish (bsgn_flat_plan is legendre_plan); in sum mode: a flat loop over the units of a row, bound by the w
+    // exponentiations of a unit.
+    static LaunchStatus bsgn_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* z, const uint64_t* alpha2,
+                         const uint64_t* beta2, int w, void* out, size_t n, hipStream_t st) {
+        const F& f = policy(Fp);
+        const ExplogRowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), al(a) && al(z) && al(out));
+        return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
+            BsgnMaskArgs<F> ma;
+            ma.alpha = word_at<F>(f, alpha2, 0);
+            for (int i = 0; i < BSGN_MAX_ROWS; ++i) ma.beta[i] = word_at<F>(f, beta2, (size_t)(i < w ? i : 0));
+            hipLaunchKernelGGL((k_bsgn_mask<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)z, ma, w, (E*)out, pl);
+        });
+    }
+    static LaunchStatus bsgn_finish(const void* Fp, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* s,
+                           void* const* out, int m, int w, int sum, size_t n, hipStream_t st) {
+        const F& f = policy(Fp);
+        static_assert(sizeof(BsgnFinishArgs<F>) + sizeof(F) + sizeof(ExpArgs) + sizeof(ExplogRowsPlan) + 64 <= 4096, "kernel arguments");
+        if (!bsgn_m_valid(m) || !bsgn_w_valid(w)) return L_PLAN_REFUSED;
+        BsgnFinishArgs<F> fa;
+        bool vec = al(c);
+        for (int j = 0; j < BSGN_MAX_PARTIES; ++j) {
+            const int q = j < m ? j : 0;
+            fa.s[j] = (const E*)s[q];
+            fa.out[j] = (E*)out[q];
+            vec = vec && al(s[q]) && al(out[q]);
+        }
+        fa.m = m;
+        if (sum) {
+            const ExplogRowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), vec);
+            return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
+                hipLaunchKernelGGL((k_bsgn_finish_sum<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, w, pl);
+            });
+        }
+        const LegendrePlan pl = bsgn_flat_plan(n, w, sizeof(E), vec);
+        return flat(pl.ok, pl.threads, lc, [&](unsigned grid) {
+            hipLaunchKernelGGL((k_bsgn_finish<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, (size_t)w * n);
+        });
+    }
 
     static const SecureOps* table() {
         static const SecureOps ops = {
@@ -538,7 +586,8 @@ struct SecureLaunchers : Launchers<F> {
             .trunc_mask = &trunc_mask, .trunc_finish = &trunc_finish, .norm_prod = &norm_prod, .norm_apply = &norm_apply,
             .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse,
             .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish,
-            .rbits_open = &rbits_open, .rbits_finish = &rbits_finish};
+            .rbits_open = &rbits_open, .rbits_finish = &rbits_finish,
+            .bsgn_mask = &bsgn_mask, .bsgn_finish = &bsgn_finish};
         return &ops;
     }
 };

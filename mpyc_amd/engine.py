@@ -1218,6 +1218,49 @@ class FieldContext:
         _ffi.check(self._L.ffgm_rbits_finish(self._h, c.ptr, rp, bp, m, int(bool(signed)), f, c.n, self._stream()), 'rbits_finish')
         return list(outs)
 
+    # ---- the secure binary sign by Legendre symbols: the local steps of the demo's bsgn (np_bnnmnist.py:44-156;
+    # include/ffgpu_math.h), prime fields.  The arrays are row-major (w, n), 1 <= w <= 8: row i belongs to the i-th symbol ----
+    def bsgn_mask(self, a: DevArray, z: DevArray, alpha: int, betas: Sequence[int], out: Optional[DevArray] = None) -> DevArray:
+        """out[i*n + e] = z[i*n + e] * (alpha*a[e] + betas[i]) for i < w = len(betas), n = a.n: the masked values that are
+        opened (np_bnnmnist.py:72, :106-110, :147-150)."""
+        if self.binary:
+            raise NotImplementedError('bsgn_mask: prime fields only')
+        w = len(betas)
+        if not 1 <= w <= 8:
+            raise ValueError('bsgn_mask: 1 to 8 rows')
+        p = self.modulus
+        self._same(a.n, a, what='bsgn_mask operand')
+        self._same(w * a.n, z, what='bsgn_mask operand')
+        out = self._out(w * a.n, out, 'bsgn_mask output')
+        _ffi.check(self._L.ffgm_bsgn_mask(self._h, a.ptr, z.ptr, self._scalars([int(alpha) % p]), self._scalars([int(b) % p for b in betas]),
+                                          w, out.ptr, a.n, self._stream()), 'bsgn_mask')
+        return out
+
+    def bsgn_finish(self, c: DevArray, ss: Sequence[DevArray], w: int, sum: bool = False,
+                    outs: Optional[Sequence[DevArray]] = None) -> List[DevArray]:
+        """With h = (c | p), the Legendre symbols (1, -1 or 0) of the public (w, n) array c: outs[q] = h * ss[q] entry by
+        entry, or, with sum, outs[q][e] = sum_i h[i*n + e] * ss[q][i*n + e] (np_bnnmnist.py:74, :113-114, :154).  One
+        exponentiation of each public value serves every party."""
+        if self.binary:
+            raise NotImplementedError('bsgn_finish: prime fields only')
+        if self.modulus == 2:
+            raise NotImplementedError('bsgn_finish: odd primes only')
+        m = len(ss)
+        if not m or not 1 <= w <= 8 or c.n % w:
+            raise ValueError('bsgn_finish: at least one party, 1 to 8 rows, a (w, n) array')
+        n = c.n // w
+        self._same(c.n, c, *ss, what='bsgn_finish operand')
+        on = n if sum else c.n
+        if outs is None:
+            outs = [self.empty(on) for _ in range(m)]
+        if len(outs) != m:
+            raise ValueError('bsgn_finish: one output per party')
+        self._same(on, *outs, what='bsgn_finish output')
+        sp = (ctypes.c_void_p * m)(*[s.ptr for s in ss])
+        op = (ctypes.c_void_p * m)(*[o.ptr for o in outs])
+        _ffi.check(self._L.ffgm_bsgn_finish(self._h, c.ptr, sp, op, m, w, int(bool(sum)), n, self._stream()), 'bsgn_finish')
+        return list(outs)
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = self._out(a.n, out)

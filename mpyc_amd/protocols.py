@@ -1204,6 +1204,98 @@ def random_bits(ctx: FieldContext, field, count: int, t: int, draw, signed: bool
     return [ctx.mul_scalar(b, (1 << f) % p) for b in bits] if f else bits
 
 
+# ---- the secure binary sign by Legendre symbols (the bsgn_0 / bsgn_1 / bsgn_2 of demos/np_bnnmnist.py:44-156) ------------
+def bsgn_rows(d: int) -> int:
+    """the symbols (2a + 1 + 2j | p), |j| <= (w - 1) / 2, variant d takes per element: w = 1, 3, 5"""
+    if d not in (0, 1, 2):
+        raise ValueError('bsgn: d is 0, 1 or 2')
+    return (1, 3, 5)[d]
+
+
+def bsgn_draws(d: int) -> int:
+    """the (sign, element) pairs variant d draws per input element: 1, 3, 6 (np_bnnmnist.py:62, :92, :135)"""
+    if d not in (0, 1, 2):
+        raise ValueError('bsgn: d is 0, 1 or 2')
+    return (1, 3, 6)[d]
+
+
+def _legendre(p: int, v: int) -> int:
+    v %= p
+    if v == 0:
+        return 0
+    return 1 if pow(v, (p - 1) >> 1, p) == 1 else -1
+
+
+def bsgn_value(p: int, d: int, a: int) -> int:
+    """What bsgn() opens to for the input a over the odd prime p, as a signed integer: d = 0: (2a + 1 | p); d = 1:
+    (u + v + w - u v w) / 2 over u, v, w = (2a - 1 | p), (2a + 1 | p), (2a + 3 | p), their majority; d = 2: (t | p) with t the
+    sum of the five symbols (2a + 1 + 2j | p), |j| <= 2.  (0 | p) = 0, as gmpy2.legendre has it."""
+    w = bsgn_rows(d)
+    h = [_legendre(p, 2 * a + 1 + 2 * j) for j in range(-(w // 2), w // 2 + 1)]
+    if d == 0:
+        return h[0]
+    if d == 2:
+        return _legendre(p, sum(h))
+    x = (h[0] + h[1] + h[2] - h[0] * h[1] * h[2]) * ((p + 1) >> 1) % p
+    return x if x <= p >> 1 else x - p
+
+
+def bsgn_range(p: int, d: int, limit: int = 4096) -> int:
+    """The largest B <= limit with bsgn_value(p, d, a) = (1 if a >= 0 else -1) for every |a| <= B; -1 if there is none."""
+    B = -1
+    while B < limit and bsgn_value(p, d, B + 1) == 1 and (B + 1 == 0 or bsgn_value(p, d, -B - 1) == -1):
+        B += 1
+    return B
+
+
+def bsgn(ctx: FieldContext, field, xs: Shares, t: int, d: int, rand_bsgn, rng=None) -> Shares:
+    """The binary sign of the demo (np_bnnmnist.py:44-156) for all parties: shares of bsgn_value(p, d, a), which is 1 for
+    a >= 0 and -1 otherwise for every |a| <= bsgn_range(p, d).  p = 3 mod 4, so (s | p) = s for a sign s: with z = s r^2, r a
+    random nonzero element, y = (2a + 1) z is uniform among the nonzero elements, and s (y | p) = (2a + 1 | p).
+
+    r2 = multiply(r, r) -> z = multiply(s, r2) (two re-sharing rounds) -> bsgn_mask per party (alpha = 2, beta = 1 + 2j:
+    degree 2t) -> one opening from 2t+1 parties -> bsgn_finish for all parties (ONE exponentiation per opened value), then
+      d = 0: the shares h s are the result;
+      d = 1: the three rows of shares go through prod_rows (two rounds); (t0 + t1 + t2 - prod) (p + 1) / 2;
+      d = 2: bsgn_finish in sum mode gives shares of T, the sum of the five symbols; bsgn_mask(T, z5, alpha = 1, beta = 0),
+             a second opening at degree 2t, bsgn_finish with s5.
+    Unlike the demo's d = 1 and d = 2 (which open s0 s1 s2 and s5 r5^2, and thereby the product of the three symbols and
+    T), nothing but uniformly masked values is opened.  The arrays are row-major (w, n).
+
+    rand_bsgn(count) supplies two sharings of count = bsgn_draws(d) n entries: uniform signs s in {1, -1} and uniform field
+    elements r.  A zero symbol (r = 0, or 2a + 1 + 2j = 0 mod p) gives 0 in its term.  The inputs are never written."""
+    w, draws = bsgn_rows(d), bsgn_draws(d)
+    if ctx.binary or ctx.modulus % 4 != 3:
+        raise ValueError('bsgn: a prime field with p = 3 mod 4')
+    m = len(xs)
+    senders = _parties('the binary sign', t, m)                                    # 2t+1: the masked values have degree 2t
+    n, p = xs[0].n, ctx.modulus
+    drawn = rand_bsgn(draws * n)
+    if (not isinstance(drawn, (tuple, list)) or len(drawn) != 2 or any(len(v) != m for v in drawn)
+            or any(x.n != draws * n for v in drawn for x in v)):
+        raise ValueError('bsgn: rand_bsgn(count) returns two sharings of count entries for every party')
+    s, r = drawn
+    r2 = multiply(ctx, field, r, r, t, rng)
+    z = multiply(ctx, field, s, r2, t, rng)
+    betas = [1 + 2 * j for j in range(-(w // 2), w // 2 + 1)]
+    zw, sw = [_rows(ctx, x, 0, w, n) for x in z], [_rows(ctx, x, 0, w, n) for x in s]
+    c = open_(ctx, field, [ctx.bsgn_mask(xs[i], zw[i], 2, betas) for i in range(senders)], t, degree=2 * t)
+    if d == 0:
+        return ctx.bsgn_finish(c, sw, w)
+    if d == 1:
+        ts = ctx.bsgn_finish(c, sw, w)
+        prod = prod_rows(ctx, field, ts, w, t, rng)
+        out = []
+        for x, q in zip(ts, prod):
+            acc = ctx.add(ctx.add(_rows(ctx, x, 0, 1, n), _rows(ctx, x, 1, 2, n)), _rows(ctx, x, 2, 3, n))
+            out.append(ctx.mul_scalar(ctx.sub(acc, q), (p + 1) >> 1))
+        return out
+    T = ctx.bsgn_finish(c, sw, w, sum=True)
+    z5, s5 = [_rows(ctx, x, w, w + 1, n) for x in z], [_rows(ctx, x, w, w + 1, n) for x in s]
+    c2 = open_(ctx, field, [ctx.bsgn_mask(T[i], z5[i], 1, [0]) for i in range(senders)], t, degree=2 * t)
+    return ctx.bsgn_finish(c2, s5, 1)
+
+
 def _torch():
     import torch
     return torch
@@ -1217,7 +1309,7 @@ class Randomness:
     thresha._prss_device fills one party's row), so the values are pinned by (key, rounds) and the order of the calls.
 
     elements / zeros / bits are the reference's _np_randoms, np_pseudorandom_share_0 and np_random_bits; rand_bits,
-    rand_trunc, rand_zero, rand_exp and rand_compare(l) are the callables the protocols of this module document."""
+    rand_trunc, rand_zero, rand_bsgn, rand_exp and rand_compare(l) are the callables the protocols of this module document."""
 
     KEY_BYTES = 16                      # the reference's PRSS keys (runtime.py:130-140)
     DOMAIN = b'mpyc_amd randomness v1\0'
@@ -1320,6 +1412,12 @@ class Randomness:
         z = self.bits(count)
         s = self.elements(count)
         return z, self.elements(count), s
+
+    def rand_bsgn(self, count: int):
+        """(s, r) of bsgn(): signs in {1, -1}, then uniform elements -- the draw order of the demo (np_random_bits, then
+        _np_randoms: np_bnnmnist.py:62-63)"""
+        s = self.bits(count, signed=True)
+        return s, self.elements(count)
 
     def rand_compare(self, l: int):
         """rand(count) of compare_zero() / sort() / amax() ...: (rbits, sbits, rdivl, rzero) for `count` comparisons of bit
