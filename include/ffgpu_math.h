@@ -2,7 +2,8 @@
  * ffgpu_math.h -- second header of libffgpu.so: the local steps under the secure logarithm and exponential of fixed-point
  * numbers (runtime.np_log, np_exp2 and their wrappers, runtime.py:4853-4945), under the probabilistic zero test over a
  * Blum prime (runtime._np_is_zero, runtime.py:3581-3620), under secure random bits (runtime.np_random_bits,
- * runtime.py:4187-4273) and under the secure binary sign by Legendre symbols (demos/np_bnnmnist.py:44-156) that no entry of
+ * runtime.py:4187-4273), under the secure binary sign by Legendre symbols (demos/np_bnnmnist.py:44-156) and under secure unit
+ * vectors and table lookup at secret indices (runtime.np_unit_vector, unit_vector, runtime.py:4979-5029) that no entry of
  * ffgpu.h serves.  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
  * conventions:
  *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
@@ -15,7 +16,8 @@
  *   - an output that overlaps an input is FFGPU_EINVAL (the exceptions are stated at ffgm_powers_prod and ffgm_rbits_finish);
  *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
- * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), into random_bits() and into bsgn().
+ * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), into random_bits(), into bsgn() and into
+ * demux(), random_unit_vectors(), unit_vectors(), unit_vectors_from_bits() and lookup().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -80,11 +82,33 @@
  *   parties; no codes are written.  p odd: FFGPU_ENOTSUP for p == 2.
  *   replaces: np_bnnmnist.py:74, :113-114 and :154 (`s * legendre_p(y)`, gmpy2.legendre per entry, and the sum over the rows).
  *
+ * Unit vectors are POSITION-MAJOR (rows, n): row j holds position j for the n secret indices, rows n elements apart -- the
+ * (outer = 1, k = rows, inner = n) layout ffgpu_tour_unit_expand and ffgpu_matmul take as it is.  K2 = 2^kbits.
+ *
+ * ffgm_unit_prod: out[j*n + e] = x[e*xstride] * U[j*n + e] for j < h, h >= 1 -- the broadcast product of a demultiplexer
+ *   round, dense (h, n): bit x of every index times the h rows so far (degree 2t, before its re-sharing;
+ *   ffgpu_tour_unit_expand interleaves (u - v, v) after it).  A thread keeps its x in registers across the h rows: h + 1 loads
+ *   per element.  xstride = 1 for a row of random bits, xstride = l for one bit position of the element-major (n, l) bits of
+ *   ffgpu_bits_finish (x then points at that position of element 0).
+ *   replaces: random.py:141-151 (`x[i] * u` and its broadcast) and runtime.py:4993-4996 (scalar_mul(x[i], u)).
+ * ffgm_unit_roll: out[j*n + e] = U[((j - c[e]) mod K2)*n + e] for j < K, 1 <= K <= K2, 0 <= kbits <= 30 -- the (K2, n) random
+ *   unit vectors rotated down by the opened public offsets, the first K rows kept.  c: canonical elements; c[e] mod K2 is
+ *   taken from the low kbits bits of the canonical integer.  A gather: U is read by element.
+ *   replaces: runtime.py:5026-5028 (`c.value % n` and np.roll(u, c)), per index.
+ * ffgm_unit_dot: out[e] = sum_{j<rows} tab[(j + c[e]) mod K2] * U[j*n + e] -- a table read through unit vectors that are never
+ *   rotated.  tab: a device table of tlen canonical elements (public values or a party's shares: the arithmetic is the same),
+ *   entries from tlen up count as 0.  With c: rows == K2 and 1 <= tlen <= K2.  c == NULL: no rotation, tab[j], any rows >= 1,
+ *   tlen == rows, kbits is not looked at.  The table is staged in LDS, one word per entry: at most 64 KiB, so with c
+ *   kbits <= 14, 13, 12, 12, 11 for elements of 4, 8, 12, 16, 24 bytes (without c: rows <= 2^that); beyond: FFGPU_ENOTSUP.
+ *   One lazy accumulation per element, reduced every 192 terms (32 for the multi-limb 2^k - c primes); one store per element.
+ *   replaces: runtime.py:5016 (`u @ np.arange(n)`, any public table in its place) and `T @ np_unit_vector(a, n)` of the callers.
+ *
  * FFGPU_OK: n == 0 / count == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or
  * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; m < 1;
- * f < 0 or f >= 192; w < 1 or w > 8; sum not 0 or 1; a size overflowing; an output overlapping an input or another output.
+ * f < 0 or f >= 192; w < 1 or w > 8; sum not 0 or 1; xstride < 1; kbits < 0 or kbits > 30; K < 1 or K > K2; rows != K2 with c,
+ * tlen != rows without, tlen < 1 or tlen > K2; a size overflowing (rows * n included); an output overlapping an input or another output.
  * FFGPU_ENOTSUP: a GF(2^n) context; ffgm_legendre_code and ffgm_bsgn_finish over p == 2; ffgm_rbits_finish unless
- * p = 3 mod 4; more than 64 rows or parties.                                                                             */
+ * p = 3 mod 4; more than 64 rows or parties; a table of ffgm_unit_dot beyond 64 KiB of LDS.                                                                             */
 #ifndef FFGPU_MATH_H
 #define FFGPU_MATH_H
 
@@ -111,6 +135,10 @@ int ffgm_bsgn_mask(ffgpu_ctx* ctx, const void* a, const void* z, const uint64_t*
                    size_t n, void* stream);
 int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, void* const* host_out, int m, int w, int sum, size_t n,
                      void* stream);
+int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U, size_t h, void* out, size_t n, void* stream);
+int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size_t K, void* out, size_t n, void* stream);
+int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int kbits, const void* tab, size_t tlen, void* out, size_t n,
+                  void* stream);
 
 #ifdef __cplusplus
 }

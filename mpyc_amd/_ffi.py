@@ -157,6 +157,9 @@ _SIGS_MATH = {
     'ffgm_rbits_finish': [_vp, _vp, _vp, _vp, _int, _int, _int, _sz, _vp],
     'ffgm_bsgn_mask': [_vp, _vp, _vp, _u64p, _u64p, _int, _vp, _sz, _vp],
     'ffgm_bsgn_finish': [_vp, _vp, _vp, _vp, _int, _int, _int, _sz, _vp],
+    'ffgm_unit_prod': [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
+    'ffgm_unit_roll': [_vp, _vp, _vp, _int, _sz, _vp, _sz, _vp],
+    'ffgm_unit_dot': [_vp, _vp, _sz, _vp, _int, _vp, _sz, _vp, _sz, _vp],
 }
 EXPORTED_MATH = tuple(_SIGS_MATH)
 

@@ -1933,6 +1933,57 @@ int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, v
     return status_of(ctx->ops->secure->bsgn_finish(ctx->policy, cs.lc, c, &ex, host_s, host_out, m, w, sum, n, cs.st));
 }
 
+// ---- secure unit vectors and table lookup at secret indices: the local steps under runtime.np_unit_vector and
+// runtime.unit_vector (unitvec.hpp; include/ffgpu_math.h) ----
+int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U, size_t h, void* out, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(h >= 1 && xstride >= 1);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = unit_rows_plan(n, h, eb, false);
+    size_t xspan;
+    ARGCHK(pl.ok && unit_x_span(n, xstride, eb, xspan));
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(x && U && out);
+    const ByteRange in[2] = {byte_range(x, xspan * eb), byte_range(U, pl.span * eb)};
+    const ByteRange o = byte_range(out, pl.span * eb);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->unit_prod(ctx->policy, cs.lc, x, xstride, U, h, out, n, cs.st));
+}
+
+int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size_t K, void* out, size_t n, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(unit_roll_valid(kbits, K));
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const ExplogRowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, eb, false);
+    ARGCHK(pl.ok);
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(U && c && out);
+    const ByteRange in[2] = {byte_range(U, pl.span * eb), byte_range(c, n * eb)};
+    const ByteRange o = byte_range(out, K * n * eb);
+    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->unit_roll(ctx->policy, cs.lc, U, c, kbits, K, out, n, cs.st));
+}
+
+int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int kbits, const void* tab, size_t tlen, void* out, size_t n,
+                  void* stream) {
+    PRIME_CTX(ctx);
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const UnitDotPlan dp = unit_dot_plan(rows, c != nullptr, kbits, tlen, eb);
+    ARGCHK(dp.ok);
+    const ExplogRowsPlan pl = unit_rows_plan(n, rows, eb, false);
+    ARGCHK(pl.ok);
+    if (!dp.fits) return FFGPU_ENOTSUP;
+    if (n == 0) return FFGPU_OK;
+    ARGCHK(U && tab && out);
+    const ByteRange in[3] = {byte_range(U, pl.span * eb), byte_range(tab, tlen * eb), byte_range(c, c ? n * eb : 0)};
+    const ByteRange o = byte_range(out, n * eb);
+    ARGCHK(outputs_disjoint(in, c ? 3 : 2, &o, 1));
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->unit_dot(ctx->policy, cs.lc, U, rows, c, kbits, tab, tlen, out, n, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

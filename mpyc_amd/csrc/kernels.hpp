@@ -2305,4 +2305,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "iszero.hpp"   // local steps of the Legendre zero test over a Blum prime (_np_is_zero)
 #include "rbits.hpp"    // local steps of secure random bits over a prime field (np_random_bits)
 #include "bsgn.hpp"     // local steps of the secure binary sign by Legendre symbols (the bsgn of np_bnnmnist)
+#include "unitvec.hpp"  // local steps under secure unit vectors and table lookup at secret indices (np_unit_vector)
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -98,6 +98,15 @@ struct SecureOps {
                      const uint64_t* beta2, int w, void* out, size_t n, hipStream_t st);
     LaunchStatus (*bsgn_finish)(const void* F, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* s, void* const* out,
                        int m, int w, int sum, size_t n, hipStream_t st);
+    // local steps under secure unit vectors and table lookup (unitvec.hpp); the arrays are position-major (rows, n); c of
+    // unit_dot may be null: no rotation (L_PLAN_REFUSED: unit_rows_plan() / unit_dot_plan() refuses the counts or the sizes;
+    // L_NOT_SUPPORTED: the table of unit_dot does not fit LDS)
+    LaunchStatus (*unit_prod)(const void* F, const LaunchCfg& lc, const void* x, size_t xstride, const void* U, size_t h, void* out,
+                     size_t n, hipStream_t st);
+    LaunchStatus (*unit_roll)(const void* F, const LaunchCfg& lc, const void* U, const void* c, int kbits, size_t K, void* out, size_t n,
+                     hipStream_t st);
+    LaunchStatus (*unit_dot)(const void* F, const LaunchCfg& lc, const void* U, size_t rows, const void* c, int kbits, const void* tab,
+                    size_t tlen, void* out, size_t n, hipStream_t st);
 };
 
 template <class F>
@@ -573,6 +582,45 @@ struct SecureLaunchers : Launchers<F> {
             hipLaunchKernelGGL((k_bsgn_finish<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, (size_t)w * n);
         });
     }
+    // The local steps under secure unit vectors and table lookup (unitvec.hpp): one flat streaming loop over the units of a
+    // row.  unit_roll reads U by element: only c and the output decide on packs.  unit_dot stages its table per workgroup, as
+    // pow_base does: eight workgroups per compute unit at the most, each over many elements; the table's bytes are the
+    // launch's dynamic LDS.
+    static LaunchStatus unit_prod(const void* Fp, const LaunchCfg& lc, const void* x, size_t xstride, const void* U, size_t h, void* out,
+                         size_t n, hipStream_t st) {
+        const F& f = policy(Fp);
+        size_t xspan;
+        if (h < 1 || !unit_x_span(n, xstride, sizeof(E), xspan)) return L_PLAN_REFUSED;
+        const ExplogRowsPlan pl = unit_rows_plan(n, h, sizeof(E), al(U) && al(out));
+        return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
+            hipLaunchKernelGGL((k_unit_prod<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)x, xstride, (const E*)U, h, (E*)out, pl,
+                               unit_x_packs(pl, xstride) && al(x) ? 1 : 0);
+        });
+    }
+    static LaunchStatus unit_roll(const void* Fp, const LaunchCfg& lc, const void* U, const void* c, int kbits, size_t K, void* out,
+                         size_t n, hipStream_t st) {
+        const F& f = policy(Fp);
+        if (!unit_roll_valid(kbits, K)) return L_PLAN_REFUSED;
+        const ExplogRowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, sizeof(E), al(c) && al(out));
+        return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
+            hipLaunchKernelGGL((k_unit_roll<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)U, (const E*)c, unit_mask(kbits), K, (E*)out,
+                               pl, n);
+        });
+    }
+    static_assert(unit_word_bytes(sizeof(E)) == sizeof(typename F::word), "unitvec_geom.hpp states this field's word");
+    static LaunchStatus unit_dot(const void* Fp, const LaunchCfg& lc, const void* U, size_t rows, const void* c, int kbits,
+                        const void* tab, size_t tlen, void* out, size_t n, hipStream_t st) {
+        const F& f = policy(Fp);
+        const UnitDotPlan dp = unit_dot_plan(rows, c != nullptr, kbits, tlen, sizeof(E));
+        if (!dp.ok) return L_PLAN_REFUSED;
+        if (!dp.fits) return L_NOT_SUPPORTED;
+        const ExplogRowsPlan pl = unit_rows_plan(n, rows, sizeof(E), al(U) && al(out) && (!c || al(c)));
+        return flat(pl.ok, pl.total, lc, [&](unsigned want) {
+            const unsigned cap = (unsigned)(lc.num_cu > 0 ? lc.num_cu : 1) * 8u;
+            hipLaunchKernelGGL((k_unit_dot<F>), dim3(want < cap ? want : cap), dim3(BLOCK), (unsigned)dp.lds_bytes, st, f, (const E*)U, rows,
+                               (const E*)c, dp.mask, (const E*)tab, tlen, dp.entries, (E*)out, pl);
+        });
+    }
 
     static const SecureOps* table() {
         static const SecureOps ops = {
@@ -587,7 +635,8 @@ struct SecureLaunchers : Launchers<F> {
             .powers_prod = &powers_prod, .poly_dot = &poly_dot, .pow_base = &pow_base, .bits_reverse = &bits_reverse,
             .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish,
             .rbits_open = &rbits_open, .rbits_finish = &rbits_finish,
-            .bsgn_mask = &bsgn_mask, .bsgn_finish = &bsgn_finish};
+            .bsgn_mask = &bsgn_mask, .bsgn_finish = &bsgn_finish,
+            .unit_prod = &unit_prod, .unit_roll = &unit_roll, .unit_dot = &unit_dot};
         return &ops;
     }
 };

@@ -1261,6 +1261,81 @@ class FieldContext:
         _ffi.check(self._L.ffgm_bsgn_finish(self._h, c.ptr, sp, op, m, w, int(bool(sum)), n, self._stream()), 'bsgn_finish')
         return list(outs)
 
+    # ---- secure unit vectors and table lookup at secret indices: the local steps under runtime.np_unit_vector / unit_vector
+    # (runtime.py:4979-5029; include/ffgpu_math.h), prime fields.  Unit vectors are position-major (rows, n): row j holds
+    # position j for the n indices; K2 = 2^kbits ----
+    UNIT_MAX_KBITS = 30
+
+    def unit_dot_max_kbits(self) -> int:
+        """the largest kbits whose 2^kbits-entry table unit_dot holds in LDS: 14, 13, 12, 12, 11 for 4, 8, 12, 16, 24 bytes --
+        unit_dot_max_kbits of csrc/unitvec_geom.hpp restated (tests/test_unitvec_host.py holds the two together, and the GPU
+        tests run the library at this value and are refused one above it)"""
+        word = {4: 4, 8: 8, 24: 24}.get(self.elem_bytes, 16)
+        return (65536 // word).bit_length() - 1
+
+    def unit_iota(self, count: int) -> DevArray:
+        """The table 0, 1, .., count - 1 on the device, uploaded once per context and count and kept: unit_dot on it without a
+        rotation gives the positions u @ arange(count) (runtime.py:5016), and a second call allocates and copies nothing.
+        Never written by the library (a table is an input); the caller must not write it either."""
+        cache = self.__dict__.setdefault('_unit_iota', {})
+        if count not in cache:
+            if not 1 <= count <= self.modulus:
+                raise ValueError('unit_iota: 1 <= count <= p')
+            cache[count] = self.from_ints(list(range(count)))
+        return cache[count]
+
+    def _unit_rows(self, what: str, U: DevArray, rows: int) -> int:
+        """n of the position-major (rows, n) array U"""
+        if self.binary:
+            raise NotImplementedError(f'{what}: prime fields only')
+        if rows < 1 or U.n % rows:
+            raise ValueError(f'{what}: the operand is not a (rows, n) array of {rows} rows')
+        self._same(U.n, U, what=f'{what} operand')
+        return U.n // rows
+
+    def unit_prod(self, x: DevArray, U: DevArray, h: int, xstride: int = 1, xoffset: int = 0, out: Optional[DevArray] = None) -> DevArray:
+        """out[j*n + e] = x[xoffset + e*xstride] * U[j*n + e] for j < h, n = U.n / h: one bit of every index times the h rows
+        of a demultiplexer round (random.py:141-151, runtime.py:4993-4996).  xstride = 1: a row of n bits starting at xoffset;
+        xstride = l, xoffset = i: bit i of the element-major (n, l) bits of bits_finish."""
+        n = self._unit_rows('unit_prod', U, h)
+        if xstride < 1 or xoffset < 0 or (n and xoffset + (n - 1) * xstride >= x.n):
+            raise ValueError('unit_prod: the factors x[xoffset + e*xstride], e < n, lie inside x')
+        self._same(x.n, x, what='unit_prod factor')
+        out = self._out(h * n, out, 'unit_prod output')
+        _ffi.check(self._L.ffgm_unit_prod(self._h, x.ptr + xoffset * self.elem_bytes, xstride, U.ptr, h, out.ptr, n, self._stream()),
+                   'unit_prod')
+        return out
+
+    def unit_roll(self, U: DevArray, c: DevArray, kbits: int, K: int, out: Optional[DevArray] = None) -> DevArray:
+        """out[j*n + e] = U[((j - c[e]) mod 2^kbits)*n + e] for j < K <= 2^kbits: the (2^kbits, n) unit vectors rotated by the
+        public canonical c (its low kbits bits), the first K rows kept (runtime.py:5026-5028)."""
+        if not 0 <= kbits <= self.UNIT_MAX_KBITS or not 1 <= K <= 1 << kbits:
+            raise ValueError('unit_roll: 0 <= kbits <= 30 and 1 <= K <= 2^kbits')
+        n = self._unit_rows('unit_roll', U, 1 << kbits)
+        self._same(n, c, what='unit_roll offsets')
+        out = self._out(K * n, out, 'unit_roll output')
+        _ffi.check(self._L.ffgm_unit_roll(self._h, U.ptr, c.ptr, kbits, K, out.ptr, n, self._stream()), 'unit_roll')
+        return out
+
+    def unit_dot(self, U: DevArray, tab: DevArray, rows: int, c: Optional[DevArray] = None, kbits: int = 0,
+                 out: Optional[DevArray] = None) -> DevArray:
+        """out[e] = sum_{j<rows} tab[(j + c[e]) mod 2^kbits] * U[j*n + e], tab zero from tab.n up: a table read through unit
+        vectors that are never rotated (runtime.py:5016 and `T @ np_unit_vector(a, n)`).  With c: rows == 2^kbits and
+        1 <= tab.n <= rows.  Without c: tab[j], any rows, tab.n == rows.  The table lives in LDS: NotImplementedError beyond
+        unit_dot_max_kbits()."""
+        n = self._unit_rows('unit_dot', U, rows)
+        if c is not None:
+            if not 0 <= kbits <= self.UNIT_MAX_KBITS or rows != 1 << kbits or not 1 <= tab.n <= rows:
+                raise ValueError('unit_dot: with offsets, rows == 2^kbits and a table of 1 to rows entries')
+            self._same(n, c, what='unit_dot offsets')
+        elif tab.n != rows:
+            raise ValueError('unit_dot: without offsets, a table of `rows` entries')
+        self._same(tab.n, tab, what='unit_dot table')
+        out = self._out(n, out, 'unit_dot output')
+        _ffi.check(self._L.ffgm_unit_dot(self._h, U.ptr, rows, None if c is None else c.ptr, kbits, tab.ptr, tab.n, out.ptr, n,
+                                         self._stream()), 'unit_dot')
+        return out
+
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""
         out = self._out(a.n, out)

@@ -1296,6 +1296,158 @@ def bsgn(ctx: FieldContext, field, xs: Shares, t: int, d: int, rand_bsgn, rng=No
     return ctx.bsgn_finish(c2, s5, 1)
 
 
+# ---- unit vectors of secret indices and table lookup at them (runtime.np_unit_vector, runtime.py:5002-5029; runtime.unit_vector,
+# runtime.py:4979-5000; mpyc.random.np_random_unit_vector, random.py:123-152), for a BATCH of n indices into one table --------
+def unit_rounds(K: int, full: bool = False):
+    """The plan of the demultiplexer for K positions, kbits = bit_length(K - 1) rounds: [(h, keep)] per round -- the round
+    multiplies the first h rows of its level by the next index bit (most significant first), expands them to 2h rows and
+    keeps the first `keep` of them as the next level.  Level s holds N_s = ceil(K / 2^(kbits-s)) rows (2^s when full: all
+    K2 = 2^kbits positions), h = ceil(N_(s+1) / 2) <= N_s.  The first round has h = 1 and its parent is the public 1: it costs
+    no multiplication.  About 2K rows are multiplied and written in all, not 2 K2."""
+    if K < 1:
+        raise ValueError('unit_rounds: at least one position')
+    kbits = (K - 1).bit_length()
+    plan = []
+    for s in range(kbits):
+        keep = 1 << (s + 1) if full else -(-K >> (kbits - s - 1))
+        plan.append(((keep + 1) // 2, keep))
+    return plan
+
+
+def _public_ones(ctx: FieldContext, n: int) -> DevArray:
+    one = ctx.empty(n)
+    one.t.zero_()
+    return ctx.add_scalar(one, 1)
+
+
+def demux(ctx: FieldContext, field, bits: Shares, n: int, kbits: int, K: int, t: int, xstride: int = 1, full: bool = False,
+          rng=None) -> Shares:
+    """Shares of the position-major (K, n) unit vectors ((2^kbits, n) when full) of the n indices whose bits are shared in
+    `bits`: row j is 1 where the index is j.  From the public 1, for the index bits most significant first (unit_rounds):
+      unit_prod on the first 2t+1 parties: v = x u for the h rows the round needs (ffgm_unit_prod, x kept in registers),
+      they re-share v (ffgpu_split_rng),
+      tour_unit_expand per party: the received sub-shares recombined to v, and (u - v, v) interleaved to rows 2j, 2j + 1
+      (ffgpu_tour_unit_expand as argmax uses it);
+    the first round has the 1 for a parent and needs no multiplication.  After kbits rounds the 1 sits at row
+    (x_(kbits-1) ... x_0)_2.
+
+    xstride == 1: bits is bit-major (>= kbits, n), row i the bit of weight 2^i.  xstride == l >= kbits: bits is the
+    element-major (n, l) output of to_bits(), bit i of element e at e*l + i.  Needs m >= 2t+1 parties; bits is not written."""
+    m = len(bits)
+    kk = _parties('the demultiplexer', t, m)
+    if n < 0 or kbits != (K - 1).bit_length() or xstride < 1:
+        raise ValueError('demux: K positions take kbits = bit_length(K - 1) bits')
+    need = kbits * n if xstride == 1 else (n * xstride if xstride >= kbits else -1)
+    if need < 0 or any(b.n < need for b in bits):
+        raise ValueError('demux: kbits bits per index, bit-major (xstride 1) or element-major (xstride l >= kbits)')
+    u = [_public_ones(ctx, n) for _ in range(m)]           # an array of its own per party: a caller may write one in place
+    for s, (h, keep) in enumerate(unit_rounds(K, full)):
+        i = kbits - 1 - s
+        xoff = i * n if xstride == 1 else i
+        if s == 0:                                      # the parent is the 1: (1 - x, x) without a multiplication
+            top = [_rows(ctx, b, i, i + 1, n) if xstride == 1 else ctx.unit_prod(b, x, 1, xstride, xoff) for b, x in zip(bits, u)]
+            u = [ctx.tour_unit_expand(u[j], [top[j]], [1], 1, 2, n) for j in range(m)]
+        else:
+            par = [_rows(ctx, x, 0, h, n) for x in u]
+            sub = reshare(ctx, field, [ctx.unit_prod(bits[q], par[q], h, xstride, xoff) for q in range(kk)], t, m, rng)
+            u = [ctx.tour_unit_expand(par[j], sub.rows[j], sub.lam, 1, 2 * h, n) for j in range(m)]
+        if keep < 2 * h:
+            u = [_rows(ctx, x, 0, keep, n) for x in u]
+    return u
+
+
+def random_unit_vectors(ctx: FieldContext, field, n: int, kbits: int, t: int, bits: Shares, rng=None) -> Shares:
+    """mpyc.random.np_random_unit_vector for n vectors at once: shares of the position-major (2^kbits, n) unit vectors at
+    uniformly random positions, from kbits*n shared random bits (bit-major).  The full demultiplexer: no position is left
+    out, so nothing is opened and nothing restarts (the reference rejects and redraws for lengths that are no power of two)."""
+    return demux(ctx, field, bits, n, kbits, 1 << kbits, t, full=True, rng=rng)
+
+
+def _unit_positions(ctx: FieldContext, u: Shares, kbits: int, n: int) -> Shares:
+    """u @ arange(K2) (runtime.py:5016), local: arg_index(u), through ffgm_unit_dot without a rotation on the table 0 .. K2 - 1
+    where that table fits its LDS (a sixth of the time of arg_index's one-row matmul_stack: profiles/unitvec_kernels.md)"""
+    K2 = 1 << kbits
+    if kbits > ctx.unit_dot_max_kbits():
+        return arg_index(ctx, u, 1, K2, n)
+    iv = ctx.unit_iota(K2)
+    return [ctx.unit_dot(x, iv, K2) for x in u]
+
+
+def _unit_offsets(what: str, ctx: FieldContext, field, idx: Shares, K: int, t: int, rand_unit, sec_param: int, rng):
+    """(u, c, kbits): shares of random (K2, n) unit vectors and the opened c = a - r + R K2, r their positions"""
+    m = len(idx)
+    _parties(what, t, m)
+    n, p = idx[0].n, ctx.modulus
+    kbits = (K - 1).bit_length()
+    if ctx.binary or K < 2 or any(x.n != n for x in idx):
+        raise ValueError(f'{what}: a prime field, at least two positions, shares of one length')
+    if p.bit_length() <= sec_param + kbits + 1:
+        raise ValueError(f'{what}: the field is too small: bit_length(p) > sec_param + kbits + 1')
+    drawn = rand_unit(n, kbits, sec_param)
+    if (not isinstance(drawn, (tuple, list)) or len(drawn) != 2 or any(len(v) != m for v in drawn)
+            or any(b.n != kbits * n for b in drawn[0]) or any(r.n != n for r in drawn[1])):
+        raise ValueError(f'{what}: rand_unit(count, kbits, sec_param) returns count*kbits bits and count values for every party')
+    bits, R = drawn
+    K2 = 1 << kbits
+    u = random_unit_vectors(ctx, field, n, kbits, t, bits, rng)
+    r = _unit_positions(ctx, u, kbits, n)
+    masked = [ctx.add(ctx.sub(idx[i], r[i]), ctx.mul_scalar(R[i], K2)) for i in range(t + 1)]
+    return u, open_(ctx, field, masked, t), kbits
+
+
+def unit_vectors(ctx: FieldContext, field, idx: Shares, K: int, t: int, rand_unit, sec_param: int = 30, rng=None) -> Shares:
+    """runtime.np_unit_vector for n secret indices at once, for all parties: shares of the position-major (K, n) unit vectors,
+    row j is 1 where the index is j.  With K2 = 2^kbits, kbits = bit_length(K - 1):
+      random_unit_vectors: u, (K2, n), from kbits*n random bits,
+      r = arg_index(u), local (as a unit_dot on the table 0 .. K2 - 1 where that fits),
+      c = a - r + R K2 is opened, R uniform in [1, 2^sec_param] per index (positive and below p: ValueError unless
+      bit_length(p) > sec_param + kbits + 1),
+      unit_roll per party: out[j] = u[(j - c) mod K2], j < K (ffgm_unit_roll).
+    The reference rotates modulo n; here the rotation is modulo K2 and the first K rows are kept: the same function of a for
+    0 <= a < K, which the caller guarantees -- otherwise the result is the unit vector of a mod K2 cut to K rows.  No bit
+    decomposition.  rand_unit(count, kbits, sec_param) returns (bits, R): count*kbits shared bits, bit-major, and count
+    shared values in [1, 2^sec_param] (Randomness.rand_unit).  K == 1 is the public 1.  idx is not written."""
+    if K == 1:
+        _parties('unit_vectors', t, len(idx))
+        return [_public_ones(ctx, idx[0].n) for _ in idx]
+    u, c, kbits = _unit_offsets('unit_vectors', ctx, field, idx, K, t, rand_unit, sec_param, rng)
+    return [ctx.unit_roll(x, c, kbits, K) for x in u]
+
+
+def unit_vectors_from_bits(ctx: FieldContext, field, bits: Shares, l: int, K: int, t: int, rng=None) -> Shares:
+    """runtime.unit_vector for n secret indices at once, for all parties, behind to_bits(): bits is its element-major (n, l)
+    output, l >= bit_length(K - 1).  The truncated demultiplexer on the low kbits bits, most significant first; nothing is
+    opened.  Returns shares of the position-major (K, n) unit vectors of a mod 2^kbits cut to K rows."""
+    kbits = (K - 1).bit_length() if K >= 1 else -1
+    if l < 1 or kbits < 0 or kbits > l or any(b.n % l for b in bits):
+        raise ValueError('unit_vectors_from_bits: (n, l) bits with l >= bit_length(K - 1)')
+    return demux(ctx, field, bits, bits[0].n // l, kbits, K, t, xstride=l, rng=rng)
+
+
+def lookup(ctx: FieldContext, field, idx: Shares, table, K: int, t: int, rand_unit, sec_param: int = 30, rng=None) -> Shares:
+    """table[a] for n secret indices a at once, for all parties: `T @ np_unit_vector(a, K)` without the rotated vectors ever
+    being stored.  table: a public DevArray of K entries, or Shares of one.  The steps of unit_vectors() up to the opening
+    of c, then T[a] = sum_{i < K2} T[(i + c) mod K2] u[i] with T zero beyond K (ffgm_unit_dot, the table in LDS):
+      public table: per party, local;
+      shared table: on the first 2t+1 parties (degree 2t), then one re-sharing of n elements.
+    Returns Shares of n entries.  0 <= a < K is the caller's guarantee; K == 1 is table[0].  2^kbits entries must fit the LDS
+    of ffgm_unit_dot (FieldContext.unit_dot_max_kbits)."""
+    m = len(idx)
+    public = isinstance(table, DevArray)
+    if (table.n if public else min((x.n for x in table), default=0)) != K or not public and len(table) != m:
+        raise ValueError('lookup: a table of K entries, public or shared among all parties')
+    if K == 1:
+        _parties('lookup', t, m)
+        one = _public_ones(ctx, idx[0].n)
+        return [ctx.unit_dot(one, table if public else table[j], 1) for j in range(m)]
+    u, c, kbits = _unit_offsets('lookup', ctx, field, idx, K, t, rand_unit, sec_param, rng)
+    K2 = 1 << kbits
+    if public:
+        return [ctx.unit_dot(x, table, K2, c=c, kbits=kbits) for x in u]
+    kk = 2 * t + 1
+    return materialize(ctx, reshare(ctx, field, [ctx.unit_dot(u[q], table[q], K2, c=c, kbits=kbits) for q in range(kk)], t, m, rng))
+
+
 def _torch():
     import torch
     return torch
@@ -1309,7 +1461,7 @@ class Randomness:
     thresha._prss_device fills one party's row), so the values are pinned by (key, rounds) and the order of the calls.
 
     elements / zeros / bits are the reference's _np_randoms, np_pseudorandom_share_0 and np_random_bits; rand_bits,
-    rand_trunc, rand_zero, rand_bsgn, rand_exp and rand_compare(l) are the callables the protocols of this module document."""
+    rand_trunc, rand_zero, rand_bsgn, rand_unit, rand_exp and rand_compare(l) are the callables the protocols of this module document."""
 
     KEY_BYTES = 16                      # the reference's PRSS keys (runtime.py:130-140)
     DOMAIN = b'mpyc_amd randomness v1\0'
@@ -1418,6 +1570,13 @@ class Randomness:
         _np_randoms: np_bnnmnist.py:62-63)"""
         s = self.bits(count, signed=True)
         return s, self.elements(count)
+
+    def rand_unit(self, count: int, kbits: int, sec_param: Optional[int] = None):
+        """(bits, R) of unit_vectors() / lookup(): count * kbits bits, bit-major, and count values in [1, 2^sec_param]
+        (runtime.py:5021-5024: `_random(type(a), 1 << sec_param)` plus 1)"""
+        sec = self.sec_param if sec_param is None else sec_param
+        bits = self.bits(count * kbits)
+        return bits, [self.ctx.add_scalar(x, 1) for x in self.elements(count, 1 << sec)]
 
     def rand_compare(self, l: int):
         """rand(count) of compare_zero() / sort() / amax() ...: (rbits, sbits, rdivl, rzero) for `count` comparisons of bit

@@ -42,6 +42,10 @@ def extract(obj, tmp, tag):
 
 
 def digest(buf):
+    # objdump's `...` at the END of a kernel is the zero padding up to the next one (a section's last kernel has none): not
+    # code.  Inside a body the mark stands for a run of zeros that is part of the kernel, and stays.
+    while buf and buf[-1] == '...':
+        buf = buf[:-1]
     """(exact, position-free, order-free, instructions): the second with the displacement of `s_getpc_b64; s_add_u32 lo,
     lo, DISP` masked -- the distance to a callee that was not inlined moves when code between the two is removed, the
     instructions do not; the third over the sorted lines of the second"""
@@ -59,7 +63,9 @@ def code(co):
                 out[name] = digest(buf)
             name, buf = m.group(1), []
         elif name:
-            buf.append(re.sub(r'//.*$', '', line).strip())
+            text = re.sub(r'//.*$', '', line).strip()
+            if text:
+                buf.append(text)
     if name:
         out[name] = digest(buf)
     return out
