@@ -14,10 +14,12 @@
  *   - n == 0 returns FFGPU_OK whatever the pointers (the counts are still checked); in every refused case nothing is
  *     written and nothing is launched;
  *   - an output that overlaps an input is FFGPU_EINVAL (the exceptions are stated at ffgm_powers_prod and ffgm_rbits_finish);
- *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes).
+ *   - prime fields only: FFGPU_ENOTSUP for a GF(2^n) context; every element size (4, 8, 12, 16, 24 bytes) -- but for the two
+ *     Keccak entries at the end, which serve GF(2^n <= 8) only.
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
  * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), into random_bits(), into bsgn() and into
- * demux(), random_unit_vectors(), unit_vectors(), unit_vectors_from_bits() and lookup().
+ * demux(), random_unit_vectors(), unit_vectors(), unit_vectors_from_bits() and lookup(), and into keccak_f1600(), sponge(),
+ * sha3() and shake().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -139,6 +141,34 @@ int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U,
 int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size_t K, void* out, size_t n, void* stream);
 int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int kbits, const void* tab, size_t tlen, void* out, size_t n,
                   void* stream);
+
+/* ---- threshold SHA-3: secure rounds of Keccak-f[1600] (demos/sha3.py:72-106) over GF(2^n), 1 <= n <= 8 ------------------
+ * The ONE exception to "prime fields only": these two entries serve GF(2^n <= 8) contexts and no other.
+ * Every bit of a 1600-bit Keccak state is shared as one element (one byte) of the context's field.  A party's share of a
+ * batch of `nstates` states is nstates x 1600 bytes, state-major: position i = 64 (5 y + x) + z of state b (S[i] of
+ * sha3.py:43, A[x, y, z]) is byte 1600 b + i.  One round for one sender's share a:
+ *   1. a = sum_{s<k} lambda_s rows[s] (k = 1, lambda = 1: a plain share); iota_round >= 0: the field's 1 is added at
+ *      z = 2^j - 1 of plane (0, 0) for the set bits j < 7 of that round's constant (sha3.py:31-33, 102-103);
+ *   2. theta, rho, pi (sha3.py:85-95);   3. chi's local product out = b + (b[x+1] + 1) b[x+2] (sha3.py:98): degree 2t.
+ * ffgm_gf2_keccak_local writes `out` of that map (apply_round = 1) or the state after step 1 only (apply_round = 0: the
+ *   tail after round 23, a plain recombination) for `nbatch` senders in one launch: sender y reads every row
+ *   batch_stride_in bytes x y further on and writes at out + y * batch_stride_out.  Deterministic.
+ * ffgm_gf2_keccak_round is the same map for the senders 1..2t+1 followed by the share generation of `_reshare`
+ *   (runtime.py:603-689, thresha.py:47-64) for each of the 1600 elements, coefficients from the device CSPRNG: the
+ *   share of party j+1 from sender y goes to shares + j * share_stride + y * batch_stride_out -- the [recipient][sender]
+ *   block of ffgpu_gate_rng_batch.  Randomness as ffgpu_gate_rng_batch (host key + nonce < 2^40 + rounds, or dev_state with
+ *   `nonce` as offset and defer_advance); the keystream a position receives depends on (key, nonce, sender, state index,
+ *   position) only, never on nstates.  (m, t) = (1, 0) writes the round's output as the one party's share.
+ * All strides in bytes.  FFGPU_ENOTSUP with nothing written: a context that is not GF(2^n <= 8), k > 7, (m, t) other than
+ * (1, 0) and the nine pairs of ffgpu_gf256_sbox_layer, 2^n <= m, row pointers or strides that are not multiples of 4,
+ * iota_round outside -1..23.  Scalars: canonical 2-limb host scalars.                                                   */
+int ffgm_gf2_keccak_local(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int k, size_t batch_stride_in,
+                           int nbatch, int iota_round, int apply_round, void* out, size_t batch_stride_out, size_t nstates,
+                           void* stream);
+int ffgm_gf2_keccak_round(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int k, size_t batch_stride_in,
+                           int iota_round, const uint8_t* host_key32, uint64_t nonce, int rounds, void* dev_state,
+                           int defer_advance, int t, int m, void* shares, size_t share_stride, size_t batch_stride_out,
+                           size_t nstates, void* stream);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,9 @@ _SIGS_MATH = {
     'ffgm_unit_prod': [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
     'ffgm_unit_roll': [_vp, _vp, _vp, _int, _sz, _vp, _sz, _vp],
     'ffgm_unit_dot': [_vp, _vp, _sz, _vp, _int, _vp, _sz, _vp, _sz, _vp],
+    'ffgm_gf2_keccak_local': [_vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _int, _int, _int, _vp, _sz, _sz, _vp],
+    'ffgm_gf2_keccak_round': [_vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _int, ctypes.c_char_p, ctypes.c_uint64, _int, _vp, _int,
+                               _int, _int, _vp, _sz, _sz, _sz, _vp],
 }
 EXPORTED_MATH = tuple(_SIGS_MATH)
 

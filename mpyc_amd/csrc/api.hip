@@ -16,6 +16,7 @@
 #include "handoff.hpp"
 #include "kernels.hpp"
 #include "policy_build.hpp"
+#include "keccak_geom.hpp"
 
 using namespace ffgpu;
 
@@ -2180,6 +2181,56 @@ int ffgpu_gf256_sbox_layer(ffgpu_ctx* ctx, const uint64_t* host_matrix, const ui
     CallScope cs(ctx, stream);
     return status_of(ffgpu_launch_gf8_sbox_layer(ctx->policy, cs.lc, x, x_stride, rbits, rbits_stride, out, out_stride,
                                                  ctx->sbl_tables_dev, host_lambda, host_mu, t, m, n, cs.st, &ra));
+}
+
+// what both Keccak entry points refuse before anything is launched
+static int keccak_args_ok(const ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int k, int iota_round) {
+    ARGCHK(ctx && host_rows && host_lambda && k >= 1);
+    if (ctx->kind != FFGPU_BINARY || ctx->elem_bytes != 1) return FFGPU_ENOTSUP;
+    if (k > 7 || iota_round < -1 || iota_round > 23) return FFGPU_ENOTSUP;
+    for (int s = 0; s < k; ++s) ARGCHK(host_rows[s]);
+    return FFGPU_OK;
+}
+
+int ffgm_gf2_keccak_local(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int k, size_t batch_stride_in,
+                           int nbatch, int iota_round, int apply_round, void* out, size_t batch_stride_out, size_t nstates,
+                           void* stream) {
+    const int rc = keccak_args_ok(ctx, host_rows, host_lambda, k, iota_round);
+    if (rc != FFGPU_OK) return rc;
+    ARGCHK(nbatch >= 1 && nbatch <= 255);
+    if (nstates == 0) return FFGPU_OK;
+    ARGCHK(out && (nbatch == 1 || (batch_stride_in >= 1600 * nstates && batch_stride_out >= 1600 * nstates)));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_keccak_local(ctx->policy, host_rows, host_lambda, k, batch_stride_in, nbatch, iota_round,
+                                               apply_round, out, batch_stride_out, nstates, cs.st));
+}
+
+int ffgm_gf2_keccak_round(ffgpu_ctx* ctx, const void* const* host_rows, const uint64_t* host_lambda, int k, size_t batch_stride_in,
+                           int iota_round, const uint8_t* host_key32, uint64_t nonce, int rounds, void* dev_state,
+                           int defer_advance, int t, int m, void* shares, size_t share_stride, size_t batch_stride_out,
+                           size_t nstates, void* stream) {
+    const int rc0 = keccak_args_ok(ctx, host_rows, host_lambda, k, iota_round);
+    if (rc0 != FFGPU_OK) return rc0;
+    ARGCHK(m >= 1 && t >= 0 && t < m);
+    if (!kk_pair_ok(m, t)) return FFGPU_ENOTSUP;
+    ARGCHK(!dev_state || nonce <= 0xffffffffull);
+    // host-key path: the sender goes into bits 40..47 of the 64-bit nonce, as the batch row of ffgpu_gate_rng_batch
+    ARGCHK(dev_state || t == 0 || nonce < (1ull << 40));
+    RngArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    if (t > 0) {
+        if (dev_state) {
+            ra = make_dev_rng(ctx, dev_state, nonce, defer_advance, false);
+        } else {
+            const int rc = make_rng(ctx, host_key32, nonce, rounds, &ra);
+            if (rc != FFGPU_OK) return rc;
+        }
+    }
+    if (nstates == 0) return FFGPU_OK;
+    ARGCHK(shares && (m == 1 || share_stride >= 1600 * nstates) && (t == 0 || (batch_stride_in >= 1600 * nstates && batch_stride_out >= 1600 * nstates)));
+    CallScope cs(ctx, stream);
+    return status_of(ffgpu_launch_keccak_round(ctx->policy, host_rows, host_lambda, k, batch_stride_in, iota_round, t, m, shares,
+                                               share_stride, batch_stride_out, nstates, cs.st, &ra));
 }
 
 int ffgpu_gf256_sbox(ffgpu_ctx* ctx, const void* in, const uint8_t* host_rows8, uint8_t b, void* out,

@@ -1163,6 +1163,12 @@ ffgpu::LaunchStatus ffgpu_launch_gf8_group8(const void* policy, const ffgpu::Lau
 ffgpu::LaunchStatus ffgpu_launch_gf8_sbox_layer(const void* policy, const ffgpu::LaunchCfg& lc, const void* x, size_t xs, const void* r, size_t rs,
                                                 void* out, size_t os, const void* tables_dev, const uint64_t* lam2, const uint64_t* mu2,
                                                 int t, int m, size_t n, hipStream_t st, const ffgpu::RngArgs* rng);
+ffgpu::LaunchStatus ffgpu_launch_keccak_local(const void* policy, const void* const* rows, const uint64_t* lam2, int k, size_t in_batch,
+                                              int nbatch, int iota_round, int apply_round, void* out, size_t out_batch, size_t nstates,
+                                              hipStream_t st);
+ffgpu::LaunchStatus ffgpu_launch_keccak_round(const void* policy, const void* const* rows, const uint64_t* lam2, int k, size_t in_batch,
+                                              int iota_round, int t, int m, void* shares, size_t share_stride, size_t out_batch,
+                                              size_t nstates, hipStream_t st, const ffgpu::RngArgs* rng);
 ffgpu::LaunchStatus ffgpu_launch_gf8_mul_tab(const void* tables, const ffgpu::LaunchCfg& lc, const void* a, const void* b, void* out, size_t n,
                                              hipStream_t st);
 ffgpu::LaunchStatus ffgpu_launch_gf2w_mul_win(const void* policy, int limbs, const void* rtable, const ffgpu::LaunchCfg& lc, const void* a,

@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "bitslice.hpp"
 #include "sbox_layer_geom.hpp"
+#include "keccak.hpp"
 
 using namespace ffgpu;
 
@@ -830,6 +831,17 @@ void ffgpu_gf8_sbox_layer_tables(const void* policy, const void* mul_tables, con
     memcpy(out + 1536, &tb, 2304);
     gf8_byte_tables(f, m2, bias2, tb);
     memcpy(out + 1536 + 2304, &tb, 2304);
+}
+
+// ---- GF(2^n <= 8): secure Keccak-f[1600] rounds (keccak.hpp) ------------------------------------------------------------
+LaunchStatus ffgpu_launch_keccak_local(const void* policy, const void* const* rows, const uint64_t* lam2, int k, size_t in_batch, int nbatch,
+                                       int iota_round, int apply_round, void* out, size_t out_batch, size_t nstates, hipStream_t st) {
+    return ffgpu_launch_keccak_local_impl(policy, rows, lam2, k, in_batch, nbatch, iota_round, apply_round, out, out_batch, nstates, st);
+}
+LaunchStatus ffgpu_launch_keccak_round(const void* policy, const void* const* rows, const uint64_t* lam2, int k, size_t in_batch,
+                                       int iota_round, int t, int m, void* shares, size_t share_stride, size_t out_batch, size_t nstates,
+                                       hipStream_t st, const RngArgs* rng) {
+    return ffgpu_launch_keccak_round_impl(policy, rows, lam2, k, in_batch, iota_round, t, m, shares, share_stride, out_batch, nstates, st, rng);
 }
 
 // ---- GF(2^64), x^64 + x^4 + x^3 + x + 1: element-wise product, BIT-SLICED ------------------------------------------

@@ -1620,6 +1620,49 @@ class FieldContext:
                    'gf256_sbox_layer')
         return out
 
+    # ---- threshold SHA-3: secure Keccak-f[1600] rounds over GF(2^n <= 8) (ffgpu_math.h; csrc/keccak.hpp) -------------------
+    KECCAK_STATE = 1600
+
+    def _keccak_rows(self, rows: Sequence[DevArray], lam: Sequence[int], nstates: int):
+        if nstates < 1:
+            raise ValueError('keccak: at least one state')
+        return self._rows(rows, lam, self.KECCAK_STATE * nstates, 'keccak share row')
+
+    def keccak_local(self, rows: Sequence[DevArray], lam: Sequence[int], nstates: int, iota_round: int = -1,
+                     apply_round: bool = True, nbatch: int = 1, stride_in: int = 0, out: Optional[DevMatrix] = None) -> DevMatrix:
+        """One Keccak-f[1600] round on shares, without the re-sharing (ffgm_gf2_keccak_local): a = sum lam[s] * rows[s]
+        (shares of `nstates` states, 1600 bytes each, state-major), plus iota of round `iota_round` (-1: none), then
+        theta, rho, pi and chi's local product -- or, with apply_round=False, only the recombined state plus iota.  For
+        `nbatch` senders in one launch, sender y reads every row y * stride_in bytes further on and writes row y of
+        `out` (the caller owns that layout, as for gate_batch).  Raises NotImplementedError where the kernels do not
+        apply (not GF(2^n <= 8), more than 7 rows, unaligned rows, iota_round outside -1..23)."""
+        k, ptrs, la = self._keccak_rows(rows, lam, nstates)
+        out = self._out_matrix(out, nbatch, self.KECCAK_STATE * nstates)
+        _ffi.check(self._L.ffgm_gf2_keccak_local(self._h, ptrs, la, k, stride_in, nbatch, iota_round, 1 if apply_round else 0,
+                                                  out.ptr, out.stride, nstates, self._stream()), 'gf2_keccak_local')
+        return out
+
+    def keccak_round(self, rows: Sequence[DevArray], lam: Sequence[int], nstates: int, t: int, m: int, iota_round: int = -1,
+                     stride_in: int = 0, out: Optional[DevMatrix] = None, key: Optional[bytes] = None, nonce: int = 0,
+                     rounds: int = 20, state: Optional['RngState'] = None) -> DevMatrix:
+        """keccak_local(apply_round=True) for the senders 1..2t+1 followed by the share generation of the re-sharing round
+        (ffgm_gf2_keccak_round): `out` is the [recipient][sender] block of gate_batch, m * (2t+1) rows -- row
+        j * (2t+1) + y = what sender y+1 deals to party j+1.  With `state` the launch is one of a sequence of deferred
+        launches: state.commit() follows.  (m, t) = (1, 0): one row, the round's output."""
+        import secrets as _secrets
+        k, ptrs, la = self._keccak_rows(rows, lam, nstates)
+        senders = 2 * t + 1
+        out = self._out_matrix(out, m * senders, self.KECCAK_STATE * nstates)
+        if state is None and key is None:
+            key = _secrets.token_bytes(32)
+        defer = 0
+        if state is not None:
+            nonce, defer = state.take_offset(), 1
+        _ffi.check(self._L.ffgm_gf2_keccak_round(self._h, ptrs, la, k, stride_in, iota_round, key, nonce, rounds,
+                                                  state.ptr if state is not None else None, defer, t, m, out.ptr,
+                                                  out.stride * senders, out.stride, nstates, self._stream()), 'gf2_keccak_round')
+        return out
+
     def to_bits(self, x: DevArray, addend: Optional[DevArray] = None, out: Optional[DevArray] = None) -> DevArray:
         """GF(2^n<=8): bits of PUBLIC bytes as field elements (8 per byte), plus `addend` (runtime.py:4418-4423)."""
         out = self._out(8 * x.n, out)

@@ -1603,3 +1603,122 @@ class Randomness:
                 x.t.zero_()
             out.append(x)
         return out
+
+
+# ---- threshold SHA-3: Keccak-f[1600] on secret-shared bits (demos/sha3.py) ---------------------------------------------
+# Every bit of a Keccak state is shared as one element of GF(2^e), 2^e > m (the reference's SecFld(2) does the same,
+# sha3.py:13-17): GF(4) for three parties, GF(8) for up to seven, one element per byte.  A party's share of a batch of
+# `nstates` states is one row of 1600 * nstates bytes, state-major, position i = 64 (5 y + x) + z of a state at byte i
+# (S[i] of sha3.py:43); all parties are the rows of one DevMatrix.  A round is ONE launch for all 2t+1 senders
+# (FieldContext.keccak_round): it recombines the previous round's [recipient][sender] block, adds that round's constants,
+# runs theta, rho, pi and chi's local product and re-shares the 1600 elements of every state.  Messages are bit shares too:
+# bit j of message byte B is (B >> j) & 1 (FIPS 202), a batch of `nstates` messages of one common length `nbits` is a
+# state-major (nstates, nbits) array per party.
+KECCAK_B = 1600
+
+
+def _state_view(mtx, nstates: int, width: int):
+    """(parties, nstates, width) view of a DevMatrix whose rows are state-major (nstates, width) arrays"""
+    return mtx.t[:, :nstates * width].unflatten(1, (nstates, width))
+
+
+def keccak_f1600(ctx: FieldContext, field, S, nstates: int, t: int, rng=None):
+    """keccak_f1600 (sha3.py:72-106) on a batch of states for all parties: S is a DevMatrix, row j = party j+1's share of
+    nstates x 1600 bits; returns a new DevMatrix of the same shape, S is not written.  24 launches of keccak_round -- launch
+    r recombines round r-1's sub-shares and adds the constants of round r-1 in its front -- and one keccak_local that
+    recombines the last block and adds the constants of round 23, for all parties at once.  t = 0 (nothing to re-share,
+    runtime.py:603-606): the same 25 launches of keccak_local on the parties' rows.  rng: an engine.RngState (one
+    rng.commit() follows the 24 rounds) or None (a fresh host key per launch)."""
+    m, n = S.rows, KECCAK_B * nstates
+    if S.n != n:
+        raise ValueError('keccak_f1600: rows of 1600 * nstates elements')
+    k = _parties('keccak_f1600', t, m)
+    if t == 0:
+        cur, spare = S, None
+        for r in range(24):
+            nxt = ctx.keccak_local([cur.row(0)], [1], nstates, iota_round=r - 1, nbatch=m, stride_in=cur.stride, out=spare)
+            cur, spare = nxt, (cur if r else None)
+        return ctx.keccak_local([cur.row(0)], [1], nstates, iota_round=23, apply_round=False, nbatch=m, stride_in=cur.stride,
+                                out=spare)
+    lam = _lagrange(field, range(1, k + 1))
+    rows, la, stride, spare = [S.row(0)], [1], S.stride, None
+    for r in range(24):
+        blk = ctx.keccak_round(rows, la, nstates, t, m, iota_round=r - 1, stride_in=stride, out=spare, state=rng)
+        spare = cur if r else None                   # two blocks take turns: a launch never writes what it reads
+        cur = blk
+        rows, la, stride = [blk.row(s) for s in range(k)], lam, k * blk.stride
+    if rng is not None:
+        rng.commit()                                 # one nonce update for the 24 rounds (deferred advance)
+    return ctx.keccak_local(rows, la, nstates, iota_round=23, apply_round=False, nbatch=m, stride_in=stride)
+
+
+def sponge(ctx: FieldContext, field, bits, nbits: int, nstates: int, t: int, r: int, d: int, suffix: Sequence[int] = (),
+           rng=None):
+    """sponge (sha3.py:109-128) with rate r and output length d over a batch: bits is a DevMatrix, row j = party j+1's
+    shares of the (nstates, nbits) message bits (nbits == 0: a matrix of empty rows, one per party); `suffix` the public
+    domain bits appended to every message.  Suffix, the 10*1 padding and the zero initial state are public: they are XORed as the field's 1 into every
+    party's row.  Returns a DevMatrix of (nstates, d) bit shares per party."""
+    import numpy as np
+    import torch
+    if not (0 < r < KECCAK_B) or d < 1 or nbits < 0 or nstates < 1:
+        raise ValueError('sponge: 0 < r < 1600, d >= 1, nstates >= 1')
+    if bits.n != nstates * nbits:
+        raise ValueError('sponge: the message is (nstates, nbits) bit shares per party')
+    npub = nbits + len(suffix)
+    public = np.zeros(npub + 2 + (-(npub + 2)) % r, dtype=np.uint8)          # P of sha3.py:112, message bits left zero
+    public[nbits:npub] = np.asarray(suffix, dtype=np.uint8)
+    public[npub] = 1
+    public[-1] ^= 1
+    m = bits.rows
+    _parties('sponge', t, m)
+    S = ctx.empty_matrix(m, KECCAK_B * nstates)
+    S.t.zero_()
+    pub = torch.from_numpy(public).to(S.t.device)
+    msg = _state_view(bits, nstates, nbits) if nbits else None
+    for i in range(len(public) // r):
+        sv = _state_view(S, nstates, KECCAK_B)
+        lo, hi = i * r, min((i + 1) * r, nbits)
+        if hi > lo:
+            sv[:, :, :hi - lo] ^= msg[:, :, lo:hi]
+        sv[:, :, :r] ^= pub[i * r:(i + 1) * r]
+        S = keccak_f1600(ctx, field, S, nstates, t, rng)
+    out = ctx.empty_matrix(m, nstates * d)
+    ov, got = _state_view(out, nstates, d), 0
+    while True:
+        take = min(r, d - got)
+        ov[:, :, got:got + take] = _state_view(S, nstates, KECCAK_B)[:, :, :take]
+        got += take
+        if got == d:
+            return out
+        S = keccak_f1600(ctx, field, S, nstates, t, rng)
+
+
+def sha3(ctx: FieldContext, field, bits, nbits: int, nstates: int, t: int, d: int = 256, rng=None):
+    """SHA3-d (sha3.py:137-141) of a batch of secret-shared messages: capacity 2d, domain bits 01."""
+    if d not in (224, 256, 384, 512):
+        raise ValueError('sha3: d is 224, 256, 384 or 512')
+    return sponge(ctx, field, bits, nbits, nstates, t, KECCAK_B - 2 * d, d, (0, 1), rng)
+
+
+def shake(ctx: FieldContext, field, bits, nbits: int, nstates: int, t: int, d: int, c: int = 256, rng=None):
+    """SHAKE[c/2] (sha3.py:144-148) with d output bits: domain bits 1111."""
+    if c not in (256, 512):
+        raise ValueError('shake: c is 256 (SHAKE128) or 512 (SHAKE256)')
+    return sponge(ctx, field, bits, nbits, nstates, t, KECCAK_B - c, d, (1, 1, 1, 1), rng)
+
+
+def message_bits(messages: Sequence[bytes]):
+    """The (nstates, 8 * len) bit array of a batch of equally long byte strings, bit j of byte B = (B >> j) & 1 (numpy uint8)."""
+    import numpy as np
+    a = np.frombuffer(b''.join(messages), dtype=np.uint8).reshape(len(messages), len(messages[0]))
+    return np.unpackbits(a, axis=1, bitorder='little')
+
+
+def digest_bytes(opened) -> List[bytes]:
+    """Opened digest bits, an (nstates, d) array of 0 / 1 with d a multiple of 8, packed into bytes LSB first (what
+    sha3.py:151-158 xprint undoes per byte): one bytes object per state."""
+    import numpy as np
+    a = np.asarray(opened, dtype=np.uint8)
+    if a.ndim != 2 or a.shape[1] % 8 or (a > 1).any():
+        raise ValueError('digest_bytes: (nstates, d) bits, d a multiple of 8')
+    return [bytes(row) for row in np.packbits(a, axis=1, bitorder='little')]
