@@ -4,7 +4,7 @@
  * Blum prime (runtime._np_is_zero, runtime.py:3581-3620), under secure random bits (runtime.np_random_bits,
  * runtime.py:4187-4273), under the secure binary sign by Legendre symbols (demos/np_bnnmnist.py:44-156) and under secure unit
  * vectors and table lookup at secret indices (runtime.np_unit_vector, unit_vector, runtime.py:4979-5029) that no entry of
- * ffgpu.h serves.  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
+ * ffgpu.h serves, and the local correlation of a secure 2-D convolution layer (demos/np_cnnmnist.py:53-85).  Same library, same contexts (ffgpu_ctx of ffgpu.h), same
  * conventions:
  *   - every entry returns an int status of ffgpu.h (FFGPU_OK == 0); nothing throws across the boundary;
  *   - array arguments are DEVICE pointers unless the name says host; elements are canonical little-endian limbs in the
@@ -19,7 +19,7 @@
  * The entries carry the prefix ffgm_ .  protocols.py composes them, with the entries of ffgpu.h, into powers(), log(),
  * log2(), log10(), pow_public_base(), exp2() and exp(), into is_zero() and equal(), into random_bits(), into bsgn() and into
  * demux(), random_unit_vectors(), unit_vectors(), unit_vectors_from_bits() and lookup(), and into keccak_f1600(), sponge(),
- * sha3() and shake().
+ * sha3() and shake(), and into conv2d() and conv_layer().
  *
  * A block of powers is POWER-MAJOR: row j holds y^(j+1) for the n elements, rows `stride` >= n elements apart.
  *
@@ -105,12 +105,30 @@
  *   One lazy accumulation per element, reduced every 192 terms (32 for the multi-limb 2^k - c primes); one store per element.
  *   replaces: runtime.py:5016 (`u @ np.arange(n)`, any public table in its place) and `T @ np_unit_vector(a, n)` of the callers.
  *
+ * The tensors of a convolution layer are dense and ROW-MAJOR: x (k, r, m, n) -- k images of r input channels, m rows, n
+ * columns --, W (v, r, s, s), b (v), out (k, v, m, n).  host_x, host_w, host_b, host_out are host arrays of nsend <= 64 device
+ * pointers, sender q's tensors; host_b == NULL: no bias (else every entry is set).
+ *
+ * ffgm_conv2d: out_q[i, j, I, J] = b_q[j] + sum_{l<r} sum_{di<s} sum_{dj<s} x_q[i, l, I + di - (s-1)/2, J + dj - s/2] * W_q[j, l, di, dj]
+ *   for q < nsend, terms whose x index falls outside [0, m) x [0, n) being 0; 1 <= s <= 16 and s <= n (m < s is fine).  The two
+ *   offsets differ for even s: the row offset is the demo's s2, the column offset np.correlate(mode='same')'s.  One launch
+ *   for all senders; a workgroup owns one image, one tile of output pixels and one block of output channels and keeps its
+ *   sums in registers, reduced every 192 terms (32 for the multi-limb 2^k - c primes) after whole filter rows.  Traffic: x
+ *   once per block of output channels, W once per tile, out once; no scratch: memory linear in the tensors.  Inputs may
+ *   alias each other (the same public W for every sender); an output overlapping any input or another output is
+ *   FFGPU_EINVAL.  k*v*m*n == 0 with valid counts: FFGPU_OK, nothing launched.
+ *   replaces: np_cnnmnist.py:69-80 (the four nested loops around np.correlate on object arrays, and the bias).
+ * ffgm_conv2d_plan: host-only, launches nothing: the shape ffgm_conv2d takes for these sizes on this context -- the tile,
+ *   the output channels per workgroup, the input channels per staging step, the grid, the LDS bytes, the filter rows
+ *   between two reductions, and whether it is the wide shape.  Refuses what ffgm_conv2d refuses for the same counts.
+ *
  * FFGPU_OK: n == 0 / count == 0.  FFGPU_EINVAL: a null context or required pointer; h < 1, w < 1 or w > h; theta < 1 or
  * theta > 64; ebits < 1 or ebits > bit_length(p), shift < 0 or shift >= 192; l < 1 or l > 64; stride < n; k < 1; m < 1;
  * f < 0 or f >= 192; w < 1 or w > 8; sum not 0 or 1; xstride < 1; kbits < 0 or kbits > 30; K < 1 or K > K2; rows != K2 with c,
- * tlen != rows without, tlen < 1 or tlen > K2; a size overflowing (rows * n included); an output overlapping an input or another output.
+ * tlen != rows without, tlen < 1 or tlen > K2; nsend < 1, s < 1, s > 16 or s > n, r, m, n or v < 1 with a non-empty output;
+ * a size overflowing (rows * n included); an output overlapping an input or another output.
  * FFGPU_ENOTSUP: a GF(2^n) context; ffgm_legendre_code and ffgm_bsgn_finish over p == 2; ffgm_rbits_finish unless
- * p = 3 mod 4; more than 64 rows or parties; a table of ffgm_unit_dot beyond 64 KiB of LDS.                                                                             */
+ * p = 3 mod 4; more than 64 rows or parties; a table of ffgm_unit_dot beyond 64 KiB of LDS; more than 64 senders or a grid beyond HIP's limit in ffgm_conv2d.        */
 #ifndef FFGPU_MATH_H
 #define FFGPU_MATH_H
 
@@ -141,6 +159,19 @@ int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U,
 int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size_t K, void* out, size_t n, void* stream);
 int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int kbits, const void* tab, size_t tlen, void* out, size_t n,
                   void* stream);
+
+typedef struct ffgm_conv2d_plan_t {
+    int tile_rows, tile_cols;   /* output pixels of a workgroup's tile */
+    int out_channels;           /* output channels of a workgroup */
+    int in_channels_step;       /* input channels staged in LDS per step */
+    int flush_rows;             /* filter rows between two reductions of an accumulator */
+    int wide;                   /* 1: the wide shape, 0: the narrow one */
+    size_t grid_x, grid_y;      /* workgroups: k * tiles * channel blocks, senders (0, 0 for an empty output) */
+    size_t lds_bytes;           /* dynamic LDS of a workgroup */
+} ffgm_conv2d_plan_t;
+int ffgm_conv2d(ffgpu_ctx* ctx, const void* const* host_x, const void* const* host_w, const void* const* host_b, void* const* host_out,
+                int nsend, size_t k, size_t r, size_t m, size_t n, size_t v, int s, void* stream);
+int ffgm_conv2d_plan(ffgpu_ctx* ctx, size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend, ffgm_conv2d_plan_t* host_plan);
 
 /* ---- threshold SHA-3: secure rounds of Keccak-f[1600] (demos/sha3.py:72-106) over GF(2^n), 1 <= n <= 8 ------------------
  * The ONE exception to "prime fields only": these two entries serve GF(2^n <= 8) contexts and no other.

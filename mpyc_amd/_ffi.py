@@ -160,11 +160,20 @@ _SIGS_MATH = {
     'ffgm_unit_prod': [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
     'ffgm_unit_roll': [_vp, _vp, _vp, _int, _sz, _vp, _sz, _vp],
     'ffgm_unit_dot': [_vp, _vp, _sz, _vp, _int, _vp, _sz, _vp, _sz, _vp],
+    'ffgm_conv2d': [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _int, _sz, _sz, _sz, _sz, _sz,
+                    _int, _vp],
+    'ffgm_conv2d_plan': [_vp, _sz, _sz, _sz, _sz, _sz, _int, _int, _vp],
     'ffgm_gf2_keccak_local': [_vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _int, _int, _int, _vp, _sz, _sz, _vp],
     'ffgm_gf2_keccak_round': [_vp, ctypes.POINTER(_vp), _u64p, _int, _sz, _int, ctypes.c_char_p, ctypes.c_uint64, _int, _vp, _int,
                                _int, _int, _vp, _sz, _sz, _sz, _vp],
 }
 EXPORTED_MATH = tuple(_SIGS_MATH)
+
+
+class Conv2dPlanStruct(ctypes.Structure):
+    """ffgm_conv2d_plan_t of include/ffgpu_math.h"""
+    _fields_ = [('tile_rows', _int), ('tile_cols', _int), ('out_channels', _int), ('in_channels_step', _int), ('flush_rows', _int),
+                ('wide', _int), ('grid_x', _sz), ('grid_y', _sz), ('lds_bytes', _sz)]
 
 
 def lib():

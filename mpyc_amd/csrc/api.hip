@@ -1985,6 +1985,53 @@ int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int
     return status_of(ctx->ops->secure->unit_dot(ctx->policy, cs.lc, U, rows, c, kbits, tab, tlen, out, n, cs.st));
 }
 
+// ---- secure 2-D convolution layers: the local correlation of the demo's convolvetensor for all senders (conv2d.hpp;
+// include/ffgpu_math.h) ----
+int ffgm_conv2d_plan(ffgpu_ctx* ctx, size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend, ffgm_conv2d_plan_t* host_plan) {
+    PRIME_CTX(ctx);
+    ARGCHK(host_plan && nsend >= 1);
+    if (nsend > (int)CONV2D_MAX_SENDERS) return FFGPU_ENOTSUP;
+    const Conv2dPlan pl = ctx->ops->secure->conv2d_plan(ctx->lc, k, r, m, n, v, s, nsend);
+    ARGCHK(pl.ok);
+    if (!pl.grid_ok) return FFGPU_ENOTSUP;
+    host_plan->tile_rows = pl.g.TH;
+    host_plan->tile_cols = pl.g.TW;
+    host_plan->out_channels = pl.g.VB;
+    host_plan->in_channels_step = pl.g.CH;
+    host_plan->flush_rows = pl.flush_rows;
+    host_plan->wide = pl.wide;
+    host_plan->grid_x = pl.empty ? 0 : (size_t)pl.grid_x;
+    host_plan->grid_y = pl.empty ? 0 : (size_t)pl.grid_y;
+    host_plan->lds_bytes = pl.lds_bytes;
+    return FFGPU_OK;
+}
+
+int ffgm_conv2d(ffgpu_ctx* ctx, const void* const* host_x, const void* const* host_w, const void* const* host_b, void* const* host_out,
+                int nsend, size_t k, size_t r, size_t m, size_t n, size_t v, int s, void* stream) {
+    PRIME_CTX(ctx);
+    ARGCHK(nsend >= 1);
+    if (nsend > (int)CONV2D_MAX_SENDERS) return FFGPU_ENOTSUP;
+    const size_t eb = (size_t)ctx->elem_bytes;
+    const Conv2dPlan pl = ctx->ops->secure->conv2d_plan(ctx->lc, k, r, m, n, v, s, nsend);
+    ARGCHK(pl.ok);
+    if (pl.empty) return FFGPU_OK;
+    if (!pl.grid_ok) return FFGPU_ENOTSUP;
+    ARGCHK(host_x && host_w && host_out);
+    size_t nx, nw, ny;
+    ARGCHK(conv2d_sizes(k, r, m, n, v, s, eb, &nx, &nw, &ny));
+    for (int i = 0; i < nsend; ++i) ARGCHK(host_x[i] && host_w[i] && host_out[i] && (!host_b || host_b[i]));
+    for (int i = 0; i < nsend; ++i) {                       // tiles read while others write: no output meets an input or another output
+        const ByteRange oi = byte_range(host_out[i], ny * eb);
+        for (int j = 0; j < nsend; ++j) {
+            if (j < i) ARGCHK(!overlaps(oi, byte_range(host_out[j], ny * eb)));
+            ARGCHK(!overlaps(oi, byte_range(host_x[j], nx * eb)) && !overlaps(oi, byte_range(host_w[j], nw * eb)));
+            if (host_b) ARGCHK(!overlaps(oi, byte_range(host_b[j], v * eb)));
+        }
+    }
+    CallScope cs(ctx, stream);
+    return status_of(ctx->ops->secure->conv2d(ctx->policy, cs.lc, host_x, host_w, host_b, host_out, nsend, k, r, m, n, v, s, cs.st));
+}
+
 int ffgpu_group_matvec(ffgpu_ctx* ctx, const uint64_t* host_matrix, const uint64_t* host_bias, int r, int g,
                        const void* in, void* out, size_t ngroups, void* stream) {
     ARGCHK(ctx && host_matrix && r >= 1 && g >= 1);

@@ -2306,4 +2306,5 @@ __global__ __launch_bounds__(BLOCK) void k_group8_bytes(F f, GroupMatArgs<F> ga,
 #include "rbits.hpp"    // local steps of secure random bits over a prime field (np_random_bits)
 #include "bsgn.hpp"     // local steps of the secure binary sign by Legendre symbols (the bsgn of np_bnnmnist)
 #include "unitvec.hpp"  // local steps under secure unit vectors and table lookup at secret indices (np_unit_vector)
+#include "conv2d.hpp"   // the 2-D correlation of a secure convolution layer (the convolvetensor of np_cnnmnist)
 #include "launch.hpp"   // host side: FieldOps table + launchers

@@ -107,6 +107,13 @@ struct SecureOps {
                      hipStream_t st);
     LaunchStatus (*unit_dot)(const void* F, const LaunchCfg& lc, const void* U, size_t rows, const void* c, int kbits, const void* tab,
                     size_t tlen, void* out, size_t n, hipStream_t st);
+    // the 2-D correlation of a secure convolution layer (conv2d.hpp): x, w, b (null: no bias; else nsend entries, all set)
+    // and out are HOST arrays of nsend device pointers, one launch for all senders.  conv2d_plan is host-only: the plan
+    // this policy's launcher takes for the sizes (conv2d_geom.hpp) (L_PLAN_REFUSED: conv2d_plan() refuses the sizes;
+    // L_NOT_SUPPORTED: more than CONV2D_MAX_SENDERS senders, or a grid beyond HIP's limits)
+    LaunchStatus (*conv2d)(const void* F, const LaunchCfg& lc, const void* const* x, const void* const* w, const void* const* b,
+                  void* const* out, int nsend, size_t k, size_t r, size_t m, size_t n, size_t v, int s, hipStream_t st);
+    Conv2dPlan (*conv2d_plan)(const LaunchCfg& lc, size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend);
 };
 
 template <class F>
@@ -621,6 +628,34 @@ struct SecureLaunchers : Launchers<F> {
                                (const E*)c, dp.mask, (const E*)tab, tlen, dp.entries, (E*)out, pl);
         });
     }
+    // The 2-D correlation (conv2d.hpp): grid (k tiles channel-blocks, senders), the shape by conv2d_plan(): wide once its
+    // workgroups give every compute unit lc.conv_wide_per_cu of them, as for ffgpu_convolve; the staged channels are the
+    // launch's dynamic LDS.
+    static Conv2dPlan conv2d_plan_of(const LaunchCfg& lc, size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend) {
+        return conv2d_plan(k, r, m, n, v, s, nsend, lc.num_cu, lc.conv_wide_per_cu, sizeof(E), conv2d_slot_bytes<F>(), DotAcc<F>::FLUSH);
+    }
+    static LaunchStatus conv2d(const void* Fp, const LaunchCfg& lc, const void* const* x, const void* const* w, const void* const* b,
+                      void* const* out, int nsend, size_t k, size_t r, size_t m, size_t n, size_t v, int s, hipStream_t st) {
+        const F& f = policy(Fp);
+        static_assert(sizeof(Conv2dArgs<F>) + sizeof(F) + sizeof(Conv2dGeom) + 64 <= 4096, "kernel arguments");
+        if (nsend > (int)CONV2D_MAX_SENDERS) return L_NOT_SUPPORTED;
+        const Conv2dPlan pl = conv2d_plan_of(lc, k, r, m, n, v, s, nsend);
+        if (!pl.ok) return L_PLAN_REFUSED;
+        if (pl.empty) return L_OK;
+        if (!pl.grid_ok) return L_NOT_SUPPORTED;
+        Conv2dArgs<F> ca;
+        for (int j = 0; j < (int)CONV2D_MAX_SENDERS; ++j) {
+            const int q = j < nsend ? j : 0;
+            ca.x[j] = (const E*)x[q];
+            ca.w[j] = (const E*)w[q];
+            ca.b[j] = b ? (const E*)b[q] : nullptr;
+            ca.out[j] = (E*)out[q];
+        }
+        const dim3 grid((unsigned)pl.grid_x, pl.grid_y);
+        if (pl.wide) hipLaunchKernelGGL((k_conv2d<F, Conv2dWide>), grid, dim3(BLOCK), (unsigned)pl.lds_bytes, st, f, ca, pl.g);
+        else hipLaunchKernelGGL((k_conv2d<F, Conv2dNarrow>), grid, dim3(BLOCK), (unsigned)pl.lds_bytes, st, f, ca, pl.g);
+        return launched();
+    }
 
     static const SecureOps* table() {
         static const SecureOps ops = {
@@ -636,7 +671,8 @@ struct SecureLaunchers : Launchers<F> {
             .iszero_mask = &iszero_mask, .legendre_code = &legendre_code, .iszero_finish = &iszero_finish,
             .rbits_open = &rbits_open, .rbits_finish = &rbits_finish,
             .bsgn_mask = &bsgn_mask, .bsgn_finish = &bsgn_finish,
-            .unit_prod = &unit_prod, .unit_roll = &unit_roll, .unit_dot = &unit_dot};
+            .unit_prod = &unit_prod, .unit_roll = &unit_roll, .unit_dot = &unit_dot,
+            .conv2d = &conv2d, .conv2d_plan = &conv2d_plan_of};
         return &ops;
     }
 };

@@ -8,6 +8,7 @@ streams, interop with torch.distributed); all arithmetic goes through libffgpu.s
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Iterable, List, Optional, Sequence
 
@@ -17,6 +18,9 @@ import torch
 from . import _ffi
 
 _MASK64 = (1 << 64) - 1
+
+# what FieldContext.conv2d_plan reports (ffgm_conv2d_plan_t of include/ffgpu_math.h); grid: (workgroups, senders)
+Conv2dPlan = collections.namedtuple('Conv2dPlan', 'tile_rows tile_cols out_channels in_channels_step flush_rows wide grid lds_bytes')
 
 
 def _np_dtype(eb: int):
@@ -1335,6 +1339,55 @@ class FieldContext:
         _ffi.check(self._L.ffgm_unit_dot(self._h, U.ptr, rows, None if c is None else c.ptr, kbits, tab.ptr, tab.n, out.ptr, n,
                                          self._stream()), 'unit_dot')
         return out
+
+    # ---- secure 2-D convolution layers: the local correlation of the demo's convolvetensor (np_cnnmnist.py:69-80;
+    # include/ffgpu_math.h), prime fields.  Dense row-major tensors: x (k, r, m, n), W (v, r, s, s), b (v), out (k, v, m, n) ----
+    CONV2D_MAX_S = 16
+    CONV2D_MAX_SENDERS = 64
+
+    def _conv2d_counts(self, what: str, k: int, r: int, m: int, n: int, v: int, s: int, nsend: int):
+        if self.binary:
+            raise NotImplementedError(f'{what}: prime fields only')
+        if nsend > self.CONV2D_MAX_SENDERS:
+            raise NotImplementedError(f'{what}: at most 64 senders')
+        if nsend < 1 or min(k, r, m, n, v) < 0 or not 1 <= s <= self.CONV2D_MAX_S:
+            raise ValueError(f'{what}: at least one sender, counts >= 0 and 1 <= s <= 16')
+        if k * v * m * n and (s > n or r < 1):
+            raise ValueError(f'{what}: s <= n and at least one input channel')
+        if not k * v * m * n and n and s > n:
+            raise ValueError(f'{what}: s <= n')
+
+    def conv2d_plan(self, k: int, r: int, m: int, n: int, v: int, s: int, nsend: int = 1) -> Conv2dPlan:
+        """The shape conv2d takes for these sizes on this context (ffgm_conv2d_plan): host-only, launches nothing."""
+        self._conv2d_counts('conv2d_plan', k, r, m, n, v, s, nsend)
+        pl = _ffi.Conv2dPlanStruct()
+        _ffi.check(self._L.ffgm_conv2d_plan(self._h, k, r, m, n, v, s, nsend, ctypes.byref(pl)), 'conv2d_plan')
+        return Conv2dPlan(pl.tile_rows, pl.tile_cols, pl.out_channels, pl.in_channels_step, pl.flush_rows, bool(pl.wide),
+                          (int(pl.grid_x), int(pl.grid_y)), int(pl.lds_bytes))
+
+    def conv2d(self, xs: Sequence[DevArray], ws: Sequence[DevArray], bs: Optional[Sequence[DevArray]], k: int, r: int, m: int,
+               n: int, v: int, s: int, outs: Optional[Sequence[DevArray]] = None) -> List[DevArray]:
+        """outs[q][i, j, I, J] = bs[q][j] + sum_{l, di, dj} xs[q][i, l, I + di - (s-1)//2, J + dj - s//2] * ws[q][j, l, di, dj]
+        for every sender q in ONE launch, x outside the image counting as 0 (np_cnnmnist.py:69-80).  bs None: no bias.  The
+        operands may be the same arrays for several senders (public weights); no output may overlap an operand."""
+        nsend = len(xs)
+        self._conv2d_counts('conv2d', k, r, m, n, v, s, nsend)
+        if len(ws) != nsend or (bs is not None and len(bs) != nsend):
+            raise ValueError('conv2d: one x, one W and one b per sender')
+        self._same(k * r * m * n, *xs, what='conv2d image tensor')
+        self._same(v * r * s * s, *ws, what='conv2d filter tensor')
+        if bs is not None:
+            self._same(v, *bs, what='conv2d bias')
+        on = k * v * m * n
+        if outs is None:
+            outs = [self.empty(on) for _ in range(nsend)]
+        if len(outs) != nsend:
+            raise ValueError('conv2d: one output per sender')
+        self._same(on, *outs, what='conv2d output')
+        ptrs = lambda arrs: (ctypes.c_void_p * nsend)(*[a.ptr for a in arrs])
+        _ffi.check(self._L.ffgm_conv2d(self._h, ptrs(xs), ptrs(ws), None if bs is None else ptrs(bs), ptrs(outs), nsend, k, r, m, n, v, s,
+                                       self._stream()), 'conv2d')
+        return list(outs)
 
     def sqrt_cl(self, a: DevArray, out: Optional[DevArray] = None) -> DevArray:
         """Square roots for p = 1 mod 4 (Cipolla-Lehmer, finfields.py:447-470)."""

@@ -1448,6 +1448,97 @@ def lookup(ctx: FieldContext, field, idx: Shares, table, K: int, t: int, rand_un
     return materialize(ctx, reshare(ctx, field, [ctx.unit_dot(u[q], table[q], K2, c=c, kbits=kbits) for q in range(kk)], t, m, rng))
 
 
+# ---- secure 2-D convolution layers (demos/np_cnnmnist.py:53-92, :133-172) ------------------------------------------------------
+# Dense row-major tensors on RAW integers, as for the fixed-point functions above: x (k, r, m, n) -- k images, r input
+# channels --, W (v, r, s, s), b (v), the result (k, v, m, n).
+def _per_sender(what: str, a, kk: int, m: int):
+    """a public DevArray for every sender, or the first kk of the m parties' shares"""
+    if isinstance(a, DevArray):
+        return [a] * kk
+    if len(a) != m:
+        raise ValueError(f'{what}: an operand is public or shared among all parties')
+    return list(a[:kk])
+
+
+def _trunc_by(ctx: FieldContext, field, ys: Shares, t: int, f: int, l: Optional[int], rand_trunc) -> Shares:
+    """trunc() by f bits with the draws of rand_trunc(count, f); L = l, by default the largest the field admits with the
+    default draws of Randomness.rand_trunc: bit_length(p) - 2"""
+    if rand_trunc is None:
+        raise ValueError('a truncation needs rand_trunc')
+    rbits, rdivf = rand_trunc(ys[0].n, f)
+    return trunc(ctx, field, ys, rbits, rdivf, t, f, ctx.modulus.bit_length() - 2 if l is None else l)
+
+
+def conv2d(ctx: FieldContext, field, xs: Shares, ws, bs, k: int, r: int, m: int, n: int, v: int, s: int, t: int, rng=None,
+           f: int = 0, l: Optional[int] = None, rand_trunc=None) -> Shares:
+    """The demo's convolvetensor (np_cnnmnist.py:53-85) for all parties:
+      Y[i, j, I, J] = b[j] + sum_{l, di, dj} x[i, l, I + di - (s-1)//2, J + dj - s//2] W[j, l, di, dj], x outside the image 0,
+    the local correlation of the first 2t+1 senders in ONE launch (ffgm_conv2d; degree 2t), the re-sharing round, and for
+    f > 0 trunc() by f bits (np_cnnmnist.py:83-84; rand_trunc(count, f) as for fxp_multiply, l: the L of trunc()).
+
+    ws: Shares of W, or one public DevArray for all parties (the result is then still re-shared, as the reference does).
+    bs: Shares of b scaled by the caller as the demo's load() does, one public DevArray, or None.  1 <= s <= 16, s <= n."""
+    M = len(xs)
+    kk = _parties('conv2d', t, M)
+    prod = ctx.conv2d(list(xs[:kk]), _per_sender('conv2d', ws, kk, M), None if bs is None else _per_sender('conv2d', bs, kk, M),
+                      k, r, m, n, v, s)
+    ys = materialize(ctx, reshare(ctx, field, prod, t, M, rng, what='conv2d'))
+    return _trunc_by(ctx, field, ys, t, f, l, rand_trunc) if f > 0 else ys
+
+
+def maxpool2x2(ctx: FieldContext, field, xs: Shares, planes: int, m: int, n: int, t: int, l: int, rand, rng=None) -> Shares:
+    """The demo's maxpool (np_cnnmnist.py:88-92) on `planes` = k v images of (m, n): the maxima of 2 x 2 squares with stride
+    2, as two amax() calls: rows in pairs, (planes m/2, 2, n), then columns in pairs, (planes m/2 n/2, 2, 1).  Returns shares
+    of the (planes, m/2, n/2) array.  rand, l and the assumptions: amax()'s."""
+    if m % 2 or n % 2:
+        raise ValueError('maxpool2x2: m and n must be even')
+    rows = amax(ctx, field, xs, planes * (m // 2), 2, n, t, l, rand, rng)
+    return amax(ctx, field, rows, planes * (m // 2) * (n // 2), 2, 1, t, l, rand, rng)
+
+
+def relu(ctx: FieldContext, field, xs: Shares, t: int, l: int, rand, rng=None) -> Shares:
+    """(x >= 0) * x (np_cnnmnist.py:142): compare_zero(mode='lt') for [x < 0], then one secure multiplication of 1 - [x < 0]
+    with x.  rand(count): (rbits, sbits, rdivl, rzero) as for amax() (Randomness.rand_compare(l)); -2^(l-1) <= x < 2^(l-1)."""
+    _parties('relu', t, len(xs))
+    rbits, sbits, rdivl, rzero = rand(xs[0].n)
+    lt = compare_zero(ctx, field, xs, rbits, sbits, rdivl, rzero, t, l, mode='lt', rng=rng)
+    return multiply(ctx, field, [ctx.rsub_scalar(b, 1) for b in lt], xs, t, rng)
+
+
+def conv_layer(ctx: FieldContext, field, xs: Shares, ws, bs, k: int, r: int, m: int, n: int, v: int, s: int, t: int, l: int, rand,
+               rng=None, f: int = 0, trunc_l: Optional[int] = None, rand_trunc=None) -> Shares:
+    """conv2d -> maxpool2x2 -> relu: layers 1 and 2 of the demo (np_cnnmnist.py:133-155).  Returns shares of the
+    (k, v, m/2, n/2) tensor.  l, rand: of the comparisons; f, trunc_l, rand_trunc: of conv2d's truncation."""
+    y = conv2d(ctx, field, xs, ws, bs, k, r, m, n, v, s, t, rng, f, trunc_l, rand_trunc)
+    y = maxpool2x2(ctx, field, y, k * v, m, n, t, l, rand, rng)
+    return relu(ctx, field, y, t, l, rand, rng)
+
+
+def dense(ctx: FieldContext, field, xs: Shares, ws, bs, M: int, K: int, N: int, t: int, rng=None, f: int = 0, l: Optional[int] = None,
+          rand_trunc=None) -> Shares:
+    """x @ W + b (np_cnnmnist.py:162, :172) for the (M, K) sharing xs: matmul() with shared W (K, N) -- a public DevArray W
+    is a local product --, for f > 0 trunc() by f bits, then the bias b (N), public or shared or None, added to every row
+    (its broadcast is the product of a column of ones with b, ffgpu_matmul)."""
+    m = len(xs)
+    if isinstance(ws, DevArray):
+        _parties('dense', t, m)
+        ys = [ctx.matmul(x, ws, M, K, N) for x in xs]
+    else:
+        ys = matmul(ctx, field, xs, ws, M, K, N, t, rng)
+    if f > 0:
+        ys = _trunc_by(ctx, field, ys, t, f, l, rand_trunc)
+    if bs is None:
+        return ys
+    ones = _public_ones(ctx, M)
+    rows = {}
+
+    def spread(b: DevArray) -> DevArray:
+        if id(b) not in rows:
+            rows[id(b)] = ctx.matmul(ones, b, M, 1, N)
+        return rows[id(b)]
+    return [ctx.add(y, spread(b)) for y, b in zip(ys, _per_sender('dense', bs, m, m))]
+
+
 def _torch():
     import torch
     return torch
