@@ -14,6 +14,8 @@
 #include "../../include/ffgpu.h"
 #include "../../include/ffgpu_math.h"
 #include "handoff.hpp"
+#include "hostint.hpp"
+#include "operands.hpp"
 #include "kernels.hpp"
 #include "policy_build.hpp"
 #include "keccak_geom.hpp"
@@ -658,19 +660,18 @@ int ffgpu_muladd(ffgpu_ctx* ctx, const void* a, const void* b, const void* c, vo
     return status_of(ctx->ops->muladd(ctx->policy, cs.lc, a, b, c, out, n, cs.st));
 }
 
+// the modulus of a context (its limbs are zero-padded to three) and its bit length
+static U192 modulus_of(const ffgpu_ctx* ctx) { return U192(ctx->modulus, 3); }
+static int modulus_bits(const ffgpu_ctx* ctx) { return modulus_of(ctx).bits(); }
+
+static void set_exp(const U192& e, ExpArgs* ex) {
+    ex->post = 0;
+    e.store(ex->e, 3);
+    ex->nbits = e.bits();
+}
 static int make_exp(const uint64_t* e, int limbs, ExpArgs* ex) {
     if (!e || limbs < 1 || limbs > 3) return FFGPU_EINVAL;
-    ex->post = 0;
-    ex->e[0] = e[0];
-    ex->e[1] = limbs > 1 ? e[1] : 0;
-    ex->e[2] = limbs > 2 ? e[2] : 0;
-    int nb = 0;
-    for (int i = 191; i >= 0; --i)
-        if ((ex->e[i >> 6] >> (i & 63)) & 1) {
-            nb = i + 1;
-            break;
-        }
-    ex->nbits = nb;
+    set_exp(U192(e, limbs), ex);
     return FFGPU_OK;
 }
 
@@ -713,16 +714,12 @@ static int exp_chain_cost(const ExpArgs& ex) {
 // e = 3 e' + 1 with a shorter chain for e' (+ 3 products for r^3 * a): hand over (e', post = 1)
 static void exp_try_cube_form(ExpArgs* ex) {
     if (ex->nbits < 16) return;
-    uint64_t q[3];
-    unsigned __int128 rem = 0;
-    for (int l = 2; l >= 0; --l) {
-        const unsigned __int128 cur = (rem << 64) | ex->e[l];
-        q[l] = (uint64_t)(cur / 3);
-        rem = cur % 3;
-    }
+    unsigned rem;
+    const U192 q = U192(ex->e, 3).div3(&rem);
     if (rem != 1) return;
     ExpArgs alt;
-    if (make_exp(q, 3, &alt) != FFGPU_OK || alt.nbits == 0) return;
+    set_exp(q, &alt);
+    if (alt.nbits == 0) return;
     if (exp_chain_cost(alt) + 3 < exp_chain_cost(*ex)) {
         alt.post = 1;
         *ex = alt;
@@ -749,61 +746,21 @@ int ffgpu_pow(ffgpu_ctx* ctx, const void* a, const uint64_t* host_exp, int exp_l
     return status_of(ctx->ops->pow(ctx->policy, cs.lc, a, &ex, out, n, cs.st));
 }
 
-// three-limb primes: exponents derived from p by limb arithmetic
-static void sub_small3(const uint64_t p[3], uint64_t d, uint64_t out[3]) {     // p - d, d small, p >= d
-    out[0] = p[0] - d;
-    const uint64_t b = p[0] < d;
-    out[1] = p[1] - b;
-    out[2] = p[2] - ((p[1] < b) ? 1 : 0);
-}
-static void shr1_3(uint64_t x[3]) {
-    x[0] = (x[0] >> 1) | (x[1] << 63);
-    x[1] = (x[1] >> 1) | (x[2] << 63);
-    x[2] >>= 1;
-}
-static bool three_limb_prime(const ffgpu_ctx* ctx) { return ctx->kind == FFGPU_PRIME && ctx->modulus[2] != 0; }
-
 // exponent q - 2 (order of the multiplicative group minus one) for x^-1 = x^(q-2); false for the two-element fields
 // GF(2) and GF(2^1), where q - 2 = 0 and x^-1 = x: exponent 1
 static bool inverse_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
-    if (three_limb_prime(ctx)) {
-        uint64_t e3[3];
-        sub_small3(ctx->modulus, 2, e3);
-        make_exp(e3, 3, ex);
-        return true;
-    }
-    ff_u128 q;
-    if (ctx->kind == FFGPU_PRIME) {
-        q = ff_make128(ctx->modulus[1], ctx->modulus[0]);
-    } else {
-        int deg = ctx->modulus[2] ? 128 : (ctx->modulus[1] ? 64 + (63 - __builtin_clzll(ctx->modulus[1]))
-                                                           : 63 - __builtin_clzll(ctx->modulus[0]));
-        q = deg == 128 ? (ff_u128)0 : ((ff_u128)1 << deg);   // 2^128 wraps to 0; q-2 below is still right
-    }
-    ff_u128 e = q - 2;
-    uint64_t el[2] = {ff_lo(e), ff_hi(e)};
-    make_exp(el, 2, ex);
+    // (a binary context's modulus is the bit pattern of a polynomial of degree bits - 1)
+    const U192 q = ctx->kind == FFGPU_PRIME ? modulus_of(ctx) : U192::pow2(modulus_bits(ctx) - 1);
+    set_exp(p_minus_2(q), ex);
     if (ex->nbits == 0) {
-        ex->e[0] = 1;
-        ex->nbits = 1;
+        set_exp(1, ex);
         return false;
     }
     return true;
 }
 
 // the Legendre exponent (p - 1) / 2 of an odd prime field
-static void legendre_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) {
-    if (three_limb_prime(ctx)) {
-        uint64_t l1[3];
-        sub_small3(ctx->modulus, 1, l1);
-        shr1_3(l1);
-        make_exp(l1, 3, ex);
-    } else {
-        const ff_u128 e1 = (ff_make128(ctx->modulus[1], ctx->modulus[0]) - 1) >> 1;
-        const uint64_t l1[2] = {ff_lo(e1), ff_hi(e1)};
-        make_exp(l1, 2, ex);
-    }
-}
+static void legendre_exponent(const ffgpu_ctx* ctx, ExpArgs* ex) { set_exp(half_below(modulus_of(ctx)), ex); }
 
 int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stream) {
     ARGCHK(ctx);
@@ -812,19 +769,7 @@ int ffgpu_sqrt_cl(ffgpu_ctx* ctx, const void* a, void* out, size_t n, void* stre
     ARGCHK(a && out);
     ExpArgs eleg, elad;
     legendre_exponent(ctx, &eleg);
-    if (three_limb_prime(ctx)) {
-        uint64_t l2[3];
-        sub_small3(ctx->modulus, 1, l2);                   // (p+1)/2 = (p-1)/2 + 1 (p odd: the low limb cannot wrap)
-        shr1_3(l2);
-        l2[0] += 1;
-        if (l2[0] == 0 && ++l2[1] == 0) ++l2[2];
-        make_exp(l2, 3, &elad);
-    } else {
-        ff_u128 p = ff_make128(ctx->modulus[1], ctx->modulus[0]);
-        ff_u128 e2 = (p >> 1) + 1;                         // (p+1)/2 (p odd; no overflow at 128 bits)
-        uint64_t l2[2] = {ff_lo(e2), ff_hi(e2)};
-        make_exp(l2, 2, &elad);
-    }
+    set_exp(half_above(modulus_of(ctx)), &elad);
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->sqrt_cl(ctx->policy, cs.lc, a, &eleg, &elad, out, n, cs.st));
 }
@@ -1223,56 +1168,17 @@ int ffgpu_axis_reduce(ffgpu_ctx* ctx, int op, const void* a, void* out, size_t o
 }
 
 // ---- secure comparison: the local steps of np_sgn (sgn.hpp) -------------------------------------------------------------
-// the bit length of the context's modulus
-static int modulus_bits(const ffgpu_ctx* ctx) {
-    const uint64_t* p = ctx->modulus;
-    const int top = p[2] ? 2 : p[1] ? 1 : 0;
-    return 64 * top + (64 - __builtin_clzll(p[top] | 1));
-}
 // 2^l, 2^(l-1) and 2^-l mod p as host scalars of the context's limb count; false unless 1 <= l <= 64 and
 // l <= bit_length(p) - 2 (the three constants are then field elements, 2^l < p / 2)
 static bool sgn_consts(const ffgpu_ctx* ctx, int l, uint64_t out[9]) {
-    const uint64_t* p = ctx->modulus;
-    if (l < 1 || l > SGN_MAX_L || l > modulus_bits(ctx) - 2) return false;
-    const int sl = ffgpu_ctx_scalar_limbs(ctx);
-    for (int i = 0; i < 9; ++i) out[i] = 0;
-    out[0 * sl + l / 64] = 1ull << (l % 64);
-    out[1 * sl + (l - 1) / 64] = 1ull << ((l - 1) % 64);
-    uint64_t x[4] = {1, 0, 0, 0};                       // halve l times: x <- x / 2 mod p (x + p when x is odd)
-    for (int i = 0; i < l; ++i) {
-        if (x[0] & 1) {
-            unsigned __int128 carry = 0;
-            for (int j = 0; j < 4; ++j) {
-                carry += (unsigned __int128)x[j] + (j < 3 ? p[j] : 0);
-                x[j] = (uint64_t)carry;
-                carry >>= 64;
-            }
-        }
-        for (int j = 0; j < 4; ++j) x[j] = (x[j] >> 1) | (j < 3 ? x[j + 1] << 63 : 0);
-    }
-    for (int j = 0; j < sl; ++j) out[2 * sl + j] = x[j];
-    return true;
+    return l <= SGN_MAX_L && pow2_consts(modulus_of(ctx), l, ffgpu_ctx_scalar_limbs(ctx), out);
 }
-// no output range may overlap an input or another output (comparison, bit decomposition, carry network, fixed point)
-static bool outputs_disjoint(const ByteRange* in, int nin, const ByteRange* out, int nout) {
-    for (int j = 0; j < nout; ++j) {
-        for (int i = 0; i < nin; ++i)
-            if (overlaps(out[j], in[i])) return false;
-        for (int i = 0; i < j; ++i)
-            if (overlaps(out[j], out[i])) return false;
-    }
-    return true;
-}
-// the sub-share rows of an apply entry, `bytes` each: none is null, none overlaps one of the ranges the call writes
-static bool rows_clear_of(const void* const* host_rows, int nrows, size_t bytes, const ByteRange* ranges, int nranges) {
-    const int nin = nrows < (int)MAXK ? nrows : (int)MAXK;     // (more rows than that: the launcher refuses them)
-    for (int s = 0; s < nin; ++s) {
-        if (!host_rows[s]) return false;
-        for (int i = 0; i < nranges; ++i)
-            if (overlaps(byte_range(host_rows[s], bytes), ranges[i])) return false;
-    }
-    return true;
-}
+// the first sub-share rows of an apply entry, which the entry looks at (more rows than MAXK: the entry itself or launch_rows
+// refuses them, so a call with that many still gets that answer whatever lies past row MAXK)
+static int rows_seen(int nrows) { return nrows < (int)MAXK ? nrows : (int)MAXK; }
+static_assert((int)Operands::MAX_IN >= 3 * (int)CONV2D_MAX_SENDERS + 2 && (int)Operands::MAX_IN >= 2 * (int)RBITS_MAX_ROWS + 2 &&
+              (int)Operands::MAX_OUT >= (int)CONV2D_MAX_SENDERS && (int)Operands::MAX_OUT >= (int)BSGN_MAX_PARTIES + 2 &&
+              (int)Operands::MAX_OUT >= (int)RBITS_MAX_ROWS + 2, "operands.hpp holds the arrays of the largest callers");
 
 int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void* rdivl, int l, void* masked, size_t n,
                    void* stream) {
@@ -1280,13 +1186,10 @@ int ffgpu_sgn_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void*
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, l, consts));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(a && rbits && rdivl && masked);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
-    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
-    const ByteRange o = byte_range(masked, n * eb);
-    ARGCHK(outputs_disjoint(in, 3, &o, 1));
+    ARGCHK(Operands().in(a, n * eb).in(rbits, p.nl * eb).in(rdivl, n * eb).out(masked, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->sgn_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
@@ -1299,18 +1202,13 @@ int ffgpu_sgn_expand(ffgpu_ctx* ctx, const void* c, const void* a, const void* r
     ARGCHK(e_out || nx_out || z_out);
     ARGCHK(sbit || !e_out);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(c && a && rbits);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
-    const ByteRange in[4] = {byte_range(c, n * eb), byte_range(a, n * eb), byte_range(rbits, p.nl * eb),
-                             byte_range(sbit, sbit ? n * eb : 0)};
-    ByteRange o[3];
-    int no = 0;
-    if (e_out) o[no++] = byte_range(e_out, (p.nl + n) * eb);
-    if (nx_out) o[no++] = byte_range(nx_out, p.nl * eb);
-    if (z_out) o[no++] = byte_range(z_out, n * eb);
-    ARGCHK(outputs_disjoint(in, 4, o, no));
+    Operands io;
+    io.in(c, n * eb).in(a, n * eb).in(rbits, p.nl * eb).in_opt(sbit, n * eb);
+    io.out_opt(e_out, (p.nl + n) * eb).out_opt(nx_out, p.nl * eb).out_opt(z_out, n * eb);
+    ARGCHK(io.ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->sgn_expand(ctx->policy, cs.lc, c, a, rbits, e_out ? sbit : nullptr, l, consts, e_out, nx_out, z_out,
                                           n, cs.st));
@@ -1321,12 +1219,9 @@ int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, l, consts));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(w && sbit && z && lt_out);
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(n <= ((size_t)1 << 62) / eb);                 // n * eb cannot overflow
-    const ByteRange in[3] = {byte_range(w, n * eb), byte_range(sbit, n * eb), byte_range(z, n * eb)};
-    const ByteRange o = byte_range(lt_out, n * eb);
-    ARGCHK(outputs_disjoint(in, 3, &o, 1));
+    ARGCHK(Operands().in(w, n * eb).in(sbit, n * eb).in(z, n * eb).out(lt_out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
 }
@@ -1350,9 +1245,8 @@ int ffgpu_cx_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size_t
     PRIME_CTX(ctx);
     CxPlan pl;
     ARGS_OR_RETURN(cx_args(ctx, outer, k, inner, p, d, r, &pl, &work));
-    ARGCHK(a && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
+    ARGCHK(Operands().in(a, outer * k * inner * eb).out(out, outer * pl.row_elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->cx_diff(ctx->policy, cs.lc, a, out, outer, k, inner, p, d, r, cs.st));
 }
@@ -1363,10 +1257,8 @@ int ffgpu_cx_apply(ffgpu_ctx* ctx, void* a, const void* const* host_rows, const 
     ARGCHK(nrows >= 1);
     CxPlan pl;
     ARGS_OR_RETURN(cx_args(ctx, outer, k, inner, p, d, r, &pl, &work));
-    ARGCHK(a && host_rows && host_lambda);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange ar = byte_range(a, outer * k * inner * eb);
-    ARGCHK(rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &ar, 1));
+    ARGCHK(Operands().inout(a, outer * k * inner * eb).in_rows(host_rows, rows_seen(nrows), outer * pl.row_elems * eb).host(host_lambda).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->cx_apply(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, outer, k, inner, p, d, r, cs.st));
 }
@@ -1388,9 +1280,8 @@ int ffgpu_tour_diff(ffgpu_ctx* ctx, const void* a, void* out, size_t outer, size
     PRIME_CTX(ctx);
     TourPlan pl;
     ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, mode, &pl, &work));
-    ARGCHK(a && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(!overlaps(byte_range(out, outer * pl.row_elems * eb), byte_range(a, outer * k * inner * eb)));
+    ARGCHK(Operands().in(a, outer * k * inner * eb).out(out, outer * pl.row_elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->tour_diff(ctx->policy, cs.lc, a, out, outer, k, inner, mode, neg, cs.st));
 }
@@ -1401,10 +1292,10 @@ int ffgpu_tour_select(ffgpu_ctx* ctx, const void* a, const void* const* host_row
     ARGCHK(nrows >= 1);
     TourPlan pl;
     ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, mode, &pl, &work));
-    ARGCHK(a && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, outer * pl.next * inner * eb);
-    ARGCHK(!overlaps(o, byte_range(a, outer * k * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
+    Operands io;
+    io.in(a, outer * k * inner * eb).in_rows(host_rows, rows_seen(nrows), outer * pl.row_elems * eb).host(host_lambda);
+    ARGCHK(io.out(out, outer * pl.next * inner * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->tour_select(ctx->policy, cs.lc, a, host_rows, host_lambda, nrows, out, outer, k, inner, mode, neg, cs.st));
 }
@@ -1413,10 +1304,8 @@ int ffgpu_tour_unit_prod(ffgpu_ctx* ctx, const void* u, const void* c, void* out
     PRIME_CTX(ctx);
     TourPlan pl;
     ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, TOUR_HALVES, &pl, &work));
-    ARGCHK(u && c && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, outer * pl.row_elems * eb);
-    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && !overlaps(o, byte_range(c, outer * pl.row_elems * eb)));
+    ARGCHK(Operands().in(u, outer * pl.next * inner * eb).in(c, outer * pl.row_elems * eb).out(out, outer * pl.row_elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->tour_unit_prod(ctx->policy, cs.lc, u, c, out, outer, k, inner, cs.st));
 }
@@ -1427,10 +1316,10 @@ int ffgpu_tour_unit_expand(ffgpu_ctx* ctx, const void* u, const void* const* hos
     ARGCHK(nrows >= 1);
     TourPlan pl;
     ARGS_OR_RETURN(tour_args(ctx, outer, k, inner, TOUR_ODD_EVEN, &pl, &work));
-    ARGCHK(u && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, outer * k * inner * eb);
-    ARGCHK(!overlaps(o, byte_range(u, outer * pl.next * inner * eb)) && rows_clear_of(host_rows, nrows, outer * pl.row_elems * eb, &o, 1));
+    Operands io;
+    io.in(u, outer * pl.next * inner * eb).in_rows(host_rows, rows_seen(nrows), outer * pl.row_elems * eb).host(host_lambda);
+    ARGCHK(io.out(out, outer * k * inner * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->tour_unit_expand(ctx->policy, cs.lc, u, host_rows, host_lambda, nrows, out, outer, k, inner, cs.st));
 }
@@ -1456,10 +1345,10 @@ int ffgpu_find_leaf_prod(ffgpu_ctx* ctx, const void* bits, const void* tab, void
     PRIME_CTX(ctx);
     FindPlan pl;
     ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work));
-    ARGCHK(bits && tab && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb);
-    ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)));
+    Operands io;
+    io.in(bits, outer * k * inner * eb).in(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb);
+    ARGCHK(io.out(out, (size_t)ncomp * outer * pl.t.row_elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->find_leaf_prod(ctx->policy, cs.lc, bits, tab, out, outer, k, inner, ncomp, flip, virt, cs.st));
 }
@@ -1470,11 +1359,11 @@ int ffgpu_find_leaf_apply(ffgpu_ctx* ctx, const void* bits, const void* tab, con
     if (nrows < 1 || nrows > (int)MAXK) return FFGPU_ENOTSUP;
     FindPlan pl;
     ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, true, flip, virt, &pl, &work));
-    ARGCHK(bits && tab && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, (size_t)ncomp * outer * pl.t.next * inner * eb);
-    ARGCHK(!overlaps(o, byte_range(bits, outer * k * inner * eb)) && !overlaps(o, byte_range(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb)) &&
-           rows_clear_of(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb, &o, 1));
+    Operands io;
+    io.in(bits, outer * k * inner * eb).in(tab, (size_t)(ncomp - 1) * 2 * pl.kv * eb);
+    io.in_rows(host_rows, nrows, (size_t)ncomp * outer * pl.t.row_elems * eb).host(host_lambda);
+    ARGCHK(io.out(out, (size_t)ncomp * outer * pl.t.next * inner * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->find_leaf_apply(ctx->policy, cs.lc, bits, tab, host_rows, host_lambda, nrows, out, outer, k, inner, ncomp,
                                                flip, virt, cs.st));
@@ -1484,9 +1373,8 @@ int ffgpu_find_prod(ffgpu_ctx* ctx, const void* level, void* out, size_t outer, 
     PRIME_CTX(ctx);
     FindPlan pl;
     ARGS_OR_RETURN(find_args(ctx, outer, k, inner, ncomp, false, 0, 0, &pl, &work));
-    ARGCHK(level && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(!overlaps(byte_range(out, (size_t)ncomp * outer * pl.t.row_elems * eb), byte_range(level, (size_t)ncomp * outer * k * inner * eb)));
+    ARGCHK(Operands().in(level, (size_t)ncomp * outer * k * inner * eb).out(out, (size_t)ncomp * outer * pl.t.row_elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->find_prod(ctx->policy, cs.lc, level, out, outer, k, inner, ncomp, cs.st));
 }
@@ -1514,8 +1402,7 @@ int ffgpu_carry_level(int l, int round, uint8_t* k_out, uint8_t* q_out) {
 static bool bits_two_l(const ffgpu_ctx* ctx, int l, uint64_t out[3]) {
     uint64_t consts[9];
     if (!sgn_consts(ctx, l, consts)) return false;
-    const int sl = ffgpu_ctx_scalar_limbs(ctx);
-    for (int j = 0; j < 3; ++j) out[j] = j < sl ? consts[j] : 0;       // (scalar 0 of sgn_consts)
+    U192::pow2(l).store(out, 3);
     return true;
 }
 // the two scalars of a mask entry, 2^l and the caller's offset, as the launcher reads them; false as bits_two_l, or without offset
@@ -1524,10 +1411,8 @@ static bool mask_consts(const ffgpu_ctx* ctx, int l, const uint64_t* host_offset
     if (!bits_two_l(ctx, l, two_l) || !host_offset) return false;
     const int sl = ffgpu_ctx_scalar_limbs(ctx);
     for (int j = 0; j < 6; ++j) consts[j] = 0;
-    for (int j = 0; j < sl; ++j) {
-        consts[j] = two_l[j];
-        consts[sl + j] = host_offset[j];
-    }
+    U192(two_l, 3).store(consts, sl);
+    U192(host_offset, sl).store(consts + sl, sl);
     return true;
 }
 
@@ -1537,13 +1422,10 @@ int ffgpu_bits_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const void
     uint64_t consts[6];
     ARGCHK(mask_consts(ctx, l, host_offset, consts));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(a && rbits && rdivl && masked);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
-    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivl, n * eb)};
-    const ByteRange o = byte_range(masked, n * eb);
-    ARGCHK(outputs_disjoint(in, 3, &o, 1));
+    ARGCHK(Operands().in(a, n * eb).in(rbits, p.nl * eb).in(rdivl, n * eb).out(masked, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->bits_mask(ctx->policy, cs.lc, a, rbits, rdivl, l, consts, masked, n, cs.st));
 }
@@ -1553,13 +1435,10 @@ int ffgpu_bits_expand(ffgpu_ctx* ctx, const void* c, const void* rbits, int l, v
     uint64_t two_l[3];
     ARGCHK(bits_two_l(ctx, l, two_l));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(c && rbits && g_out && p_out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
-    const ByteRange in[2] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb)};
-    const ByteRange o[2] = {byte_range(g_out, p.nl * eb), byte_range(p_out, p.nl * eb)};
-    ARGCHK(outputs_disjoint(in, 2, o, 2));
+    ARGCHK(Operands().in(c, n * eb).in(rbits, p.nl * eb).out(g_out, p.nl * eb).out(p_out, p.nl * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->bits_expand(ctx->policy, cs.lc, c, rbits, l, g_out, p_out, n, cs.st));
 }
@@ -1569,13 +1448,10 @@ int ffgpu_bits_finish(ffgpu_ctx* ctx, const void* c, const void* rbits, const vo
     uint64_t two_l[3];
     ARGCHK(bits_two_l(ctx, l, two_l));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(c && rbits && g && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, l, eb);
     ARGCHK(p.ok);
-    const ByteRange in[3] = {byte_range(c, n * eb), byte_range(rbits, p.nl * eb), byte_range(g, p.nl * eb)};
-    const ByteRange o = byte_range(out, p.nl * eb);
-    ARGCHK(outputs_disjoint(in, 3, &o, 1));
+    ARGCHK(Operands().in(c, n * eb).in(rbits, p.nl * eb).in(g, p.nl * eb).out(out, p.nl * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->bits_finish(ctx->policy, cs.lc, c, rbits, g, l, out, n, cs.st));
 }
@@ -1595,11 +1471,8 @@ int ffgpu_carry_prod(ffgpu_ctx* ctx, const void* g, const void* p, int l, int ro
     PRIME_CTX(ctx);
     BitsLevel lv;
     ARGS_OR_RETURN(carry_args(ctx, l, round, n, &lv, &work));
-    ARGCHK(g && p && out);
     const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
-    const ByteRange in[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
-    const ByteRange o = byte_range(out, (size_t)(lv.rc + lv.rd) * n * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(g, nl * eb).in(p, nl * eb).out(out, (size_t)(lv.rc + lv.rd) * n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->carry_prod(ctx->policy, cs.lc, g, p, l, lv, out, n, cs.st));
 }
@@ -1610,10 +1483,10 @@ int ffgpu_carry_apply(ffgpu_ctx* ctx, void* g, void* p, const void* const* host_
     ARGCHK(nrows >= 1);
     BitsLevel lv;
     ARGS_OR_RETURN(carry_args(ctx, l, round, n, &lv, &work));
-    ARGCHK(g && p && host_rows && host_lambda);
     const size_t eb = (size_t)ctx->elem_bytes, nl = n * (size_t)l;
-    const ByteRange gp[2] = {byte_range(g, nl * eb), byte_range(p, nl * eb)};
-    ARGCHK(!overlaps(gp[0], gp[1]) && rows_clear_of(host_rows, nrows, (size_t)(lv.rc + lv.rd) * n * eb, gp, 2));
+    Operands io;
+    io.inout(g, nl * eb).inout(p, nl * eb).in_rows(host_rows, rows_seen(nrows), (size_t)(lv.rc + lv.rd) * n * eb).host(host_lambda);
+    ARGCHK(io.ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->carry_apply(ctx->policy, cs.lc, g, p, host_rows, host_lambda, nrows, l, lv, n, cs.st));
 }
@@ -1625,13 +1498,10 @@ int ffgpu_trunc_mask(ffgpu_ctx* ctx, const void* a, const void* rbits, const voi
     uint64_t consts[6];
     ARGCHK(mask_consts(ctx, f, host_offset, consts));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(a && rbits && rdivf && ar_out && masked_out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const SgnPlan p = sgn_plan(n, f, eb);
     ARGCHK(p.ok);
-    const ByteRange in[3] = {byte_range(a, n * eb), byte_range(rbits, p.nl * eb), byte_range(rdivf, n * eb)};
-    const ByteRange o[2] = {byte_range(ar_out, n * eb), byte_range(masked_out, n * eb)};
-    ARGCHK(outputs_disjoint(in, 3, o, 2));
+    ARGCHK(Operands().in(a, n * eb).in(rbits, p.nl * eb).in(rdivf, n * eb).out(ar_out, n * eb).out(masked_out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->trunc_mask(ctx->policy, cs.lc, a, rbits, rdivf, f, consts, ar_out, masked_out, n, cs.st));
 }
@@ -1644,11 +1514,9 @@ int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint6
     uint64_t consts[9];
     ARGCHK(sgn_consts(ctx, f, consts));                  // 1 <= f <= 64, f <= bit_length(p) - 2; scalar 2: 2^-f
     if (n == 0) return FFGPU_OK;
-    ARGCHK(host_rows && host_lambda && ar && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(sgn_plan(n, f, eb).ok);
-    const ByteRange o = byte_range(out, n * eb);
-    ARGCHK(!overlaps(o, byte_range(ar, n * eb)) && rows_clear_of(host_rows, nrows, n * eb, &o, 1));
+    ARGCHK(Operands().in_rows(host_rows, nrows, n * eb).host(host_lambda).in(ar, n * eb).out(out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->trunc_finish(ctx->policy, cs.lc, host_rows, host_lambda, nrows, ar, f,
                                             consts + 2 * ffgpu_ctx_scalar_limbs(ctx), out, n, cs.st));
@@ -1669,11 +1537,8 @@ int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* si
     PRIME_CTX(ctx);
     FxpNormPlan pl;
     ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
-    ARGCHK(bits && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange in = byte_range(bits, n * pl.l * eb);
-    const ByteRange o[2] = {byte_range(out, pl.elems * eb), byte_range(sign_out, sign_out ? n * eb : 0)};
-    ARGCHK(outputs_disjoint(&in, 1, o, sign_out ? 2 : 1));
+    ARGCHK(Operands().in(bits, n * pl.l * eb).out(out, pl.elems * eb).out_opt(sign_out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->norm_prod(ctx->policy, cs.lc, bits, l, out, sign_out, n, cs.st));
 }
@@ -1685,10 +1550,8 @@ int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_r
     if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
     FxpNormPlan pl;
     ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
-    ARGCHK(bits && host_rows && host_lambda && out);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ByteRange o = byte_range(out, pl.elems * eb);
-    ARGCHK(!overlaps(o, byte_range(bits, n * pl.l * eb)) && rows_clear_of(host_rows, nrows, pl.elems * eb, &o, 1));
+    ARGCHK(Operands().in(bits, n * pl.l * eb).in_rows(host_rows, nrows, pl.elems * eb).host(host_lambda).out(out, pl.elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->norm_apply(ctx->policy, cs.lc, bits, host_rows, host_lambda, nrows, l, out, n, cs.st));
 }
@@ -1699,12 +1562,11 @@ int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w,
     PRIME_CTX(ctx);
     ARGCHK(explog_prod_valid(h, w));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(P && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)h, stride, eb, false);
     size_t wn;
     ARGCHK(pl.ok && cx_mul_ok((size_t)w, n, wn) && wn <= ((size_t)1 << 62) / eb);
-    ARGCHK(!overlaps(byte_range(out, wn * eb), byte_range(P, pl.span * eb)));     // (rows h.. of P's allocation lie past the span)
+    ARGCHK(Operands().in(P, pl.span * eb).out(out, wn * eb).ok());                // (rows h.. of P's allocation lie past the span)
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->powers_prod(ctx->policy, cs.lc, P, stride, h, w, out, n, cs.st));
 }
@@ -1714,13 +1576,10 @@ int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const
     PRIME_CTX(ctx);
     ARGCHK(explog_poly_valid(theta) && host_c0);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(P && tab && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)theta, stride, eb, false);
     ARGCHK(pl.ok);
-    const ByteRange in[2] = {byte_range(P, pl.span * eb), byte_range(tab, (size_t)theta * eb)};
-    const ByteRange o = byte_range(out, n * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(P, pl.span * eb).in(tab, (size_t)theta * eb).out(out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->poly_dot(ctx->policy, cs.lc, P, stride, theta, tab, host_c0, out, n, cs.st));
 }
@@ -1731,12 +1590,9 @@ int ffgm_pow_base(ffgpu_ctx* ctx, const void* x, int shift, int ebits, const voi
     const int pbits = modulus_bits(ctx);
     ARGCHK(pow_base_plan(0, shift, ebits, pbits, eb).ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(x && tab && out);
     const PowBasePlan pl = pow_base_plan(n, shift, ebits, pbits, eb);
     ARGCHK(pl.ok);
-    const ByteRange in[2] = {byte_range(x, n * eb), byte_range(tab, (size_t)pl.tab_elems * eb)};
-    const ByteRange o = byte_range(out, n * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(x, n * eb).in(tab, (size_t)pl.tab_elems * eb).out(out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->pow_base(ctx->policy, cs.lc, x, shift, ebits, pbits, tab, out, n, cs.st));
 }
@@ -1745,13 +1601,10 @@ int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t
     PRIME_CTX(ctx);
     ARGCHK(explog_rev_l_valid(l));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(bits && out);
     const size_t eb = (size_t)ctx->elem_bytes;
     const FxpNormPlan pl = explog_rev_plan(n, l, eb, false);
     ARGCHK(pl.ok);
-    const ByteRange in = byte_range(bits, pl.elems * eb);
-    const ByteRange o = byte_range(out, pl.elems * eb);
-    ARGCHK(outputs_disjoint(&in, 1, &o, 1));
+    ARGCHK(Operands().in(bits, pl.elems * eb).out(out, pl.elems * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->bits_reverse(ctx->policy, cs.lc, bits, l, out, n, cs.st));
 }
@@ -1763,11 +1616,8 @@ int ffgm_iszero_mask(ffgpu_ctx* ctx, const void* a, const void* r, const void* z
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(iszero_mask_plan(n, k, eb, false).ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(a && r && z && u2 && out);
     const size_t kn = iszero_mask_plan(n, k, eb, false).span * eb;
-    const ByteRange in[4] = {byte_range(a, n * eb), byte_range(r, kn), byte_range(z, kn), byte_range(u2, kn)};
-    const ByteRange o = byte_range(out, kn);
-    ARGCHK(outputs_disjoint(in, 4, &o, 1));
+    ARGCHK(Operands().in(a, n * eb).in(r, kn).in(z, kn).in(u2, kn).out(out, kn).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->iszero_mask(ctx->policy, cs.lc, a, r, z, u2, k, out, n, cs.st));
 }
@@ -1778,10 +1628,7 @@ int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t coun
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(legendre_plan(count, eb, false).ok);
     if (count == 0) return FFGPU_OK;
-    ARGCHK(c && code);
-    const ByteRange in = byte_range(c, count * eb);
-    const ByteRange o = byte_range(code, count);
-    ARGCHK(outputs_disjoint(&in, 1, &o, 1));
+    ARGCHK(Operands().in(c, count * eb).out(code, count).ok());
     ExpArgs ex;
     legendre_exponent(ctx, &ex);
     exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
@@ -1794,31 +1641,12 @@ int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void*
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(iszero_flat_plan(count, eb, false).ok);
     if (count == 0) return FFGPU_OK;
-    ARGCHK(code && z && out);
-    const ByteRange in[2] = {byte_range(code, count), byte_range(z, count * eb)};
-    const ByteRange o = byte_range(out, count * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(code, count).in(z, count * eb).out(out, count * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->iszero_finish(ctx->policy, cs.lc, code, z, out, count, cs.st));
 }
 
 // ---- secure random bits over a prime field: the local steps of runtime.np_random_bits (rbits.hpp; include/ffgpu_math.h) ----
-// x = 2 x mod p on three limbs, x < p < 2^192
-static void dbl_mod3(uint64_t x[3], const uint64_t p[3]) {
-    const uint64_t top = x[2] >> 63;
-    x[2] = (x[2] << 1) | (x[1] >> 63);
-    x[1] = (x[1] << 1) | (x[0] >> 63);
-    x[0] <<= 1;
-    const bool ge = top || x[2] > p[2] || (x[2] == p[2] && (x[1] > p[1] || (x[1] == p[1] && x[0] >= p[0])));
-    if (ge) {
-        const uint64_t b0 = x[0] < p[0];
-        x[0] -= p[0];
-        const uint64_t b1 = x[1] < p[1] || (x[1] == p[1] && b0);
-        x[1] = x[1] - p[1] - b0;
-        x[2] = x[2] - p[2] - b1;
-    }
-}
-
 int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const* host_z, const uint64_t* host_lambda, int k, void* out,
                     int32_t* zeros, size_t n, void* stream) {
     PRIME_CTX(ctx);
@@ -1827,15 +1655,9 @@ int ffgm_rbits_open(ffgpu_ctx* ctx, const void* const* host_r, const void* const
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(rbits_open_plan(n, k, eb, false).ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(host_r && host_z && host_lambda && out);
-    ByteRange in[2 * RBITS_MAX_ROWS];
-    for (int j = 0; j < k; ++j) {
-        ARGCHK(host_r[j] && host_z[j]);
-        in[2 * j] = byte_range(host_r[j], n * eb);
-        in[2 * j + 1] = byte_range(host_z[j], n * eb);
-    }
-    const ByteRange o[2] = {byte_range(out, n * eb), byte_range(zeros, zeros ? sizeof(int32_t) : 0)};
-    ARGCHK(outputs_disjoint(in, 2 * k, o, 2));
+    Operands io;
+    io.in_rows(host_r, k, n * eb).in_rows(host_z, k, n * eb).host(host_lambda);
+    ARGCHK(io.out(out, n * eb).out_opt(zeros, sizeof(int32_t)).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->rbits_open(ctx->policy, cs.lc, host_r, host_z, host_lambda, k, out, zeros, n, cs.st));
 }
@@ -1849,42 +1671,18 @@ int ffgm_rbits_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_r, 
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(rbits_finish_plan(n, m, eb, false).ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(c && host_r && host_b);
-    const ByteRange cr = byte_range(c, n * eb);
-    for (int i = 0; i < m; ++i) {
-        ARGCHK(host_r[i] && host_b[i]);
-        const ByteRange bi = byte_range(host_b[i], n * eb);
-        ARGCHK(!overlaps(bi, cr));
-        for (int j = 0; j < m; ++j) {
-            if (j < i) ARGCHK(!overlaps(bi, byte_range(host_b[j], n * eb)));
-            if (j == i && host_b[i] == host_r[i]) continue;                     // (in place: the one overlap allowed)
-            ARGCHK(!overlaps(bi, byte_range(host_r[j], n * eb)));
-        }
-    }
-    // (3p - 5) / 4 = p - 2 - (p - 3) / 4, on three limbs; p >= 3
-    const uint64_t* p = ctx->modulus;
-    uint64_t q[3] = {(p[0] >> 2) | (p[1] << 62), (p[1] >> 2) | (p[2] << 62), p[2] >> 2}, e[3];
-    sub_small3(p, 2, e);
-    const uint64_t b0 = e[0] < q[0];
-    e[0] -= q[0];
-    const uint64_t b1 = e[1] < q[1] || (e[1] == q[1] && b0);
-    e[1] = e[1] - q[1] - b0;
-    e[2] = e[2] - q[2] - b1;
+    Operands io;
+    int r0;
+    io.in(c, n * eb).in_rows(host_r, m, n * eb, &r0);
+    ARGCHK(io.out_rows(host_b, m, n * eb, r0).ok());       // (in place, host_b[i] == host_r[i]: the one overlap allowed)
+    const U192 p = modulus_of(ctx);
     ExpArgs ex;
-    make_exp(e, 3, &ex);
+    set_exp(three_p_minus_5_over_4(p), &ex);
     exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
     // A = 2^f, B = 0 (signed), or A = B = (p + 1) / 2 2^f
-    uint64_t A[3] = {1, 0, 0}, B[3] = {0, 0, 0};
-    if (!is_signed) {
-        A[0] = (p[0] >> 1) | (p[1] << 63);
-        A[1] = (p[1] >> 1) | (p[2] << 63);
-        A[2] = p[2] >> 1;
-        if (++A[0] == 0 && ++A[1] == 0) ++A[2];
-    }
-    for (int i = 0; i < f; ++i) dbl_mod3(A, p);
-    if (!is_signed) memcpy(B, A, sizeof(B));
+    const U192 A = (is_signed ? U192(1) : half_above(p)).times_pow2_mod(f, p), B = is_signed ? U192(0) : A;
     CallScope cs(ctx, stream);
-    return status_of(ctx->ops->secure->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A, B, n, cs.st));
+    return status_of(ctx->ops->secure->rbits_finish(ctx->policy, cs.lc, c, &ex, host_r, host_b, m, A.w, B.w, n, cs.st));
 }
 
 // ---- the secure binary sign by Legendre symbols: the local steps of the demo's bsgn (bsgn.hpp; include/ffgpu_math.h) ----
@@ -1896,11 +1694,8 @@ int ffgm_bsgn_mask(ffgpu_ctx* ctx, const void* a, const void* z, const uint64_t*
     const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
     ARGCHK(pl.ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(a && z && host_alpha && host_beta && out);
     const size_t wn = pl.span * eb;
-    const ByteRange in[2] = {byte_range(a, n * eb), byte_range(z, wn)};
-    const ByteRange o = byte_range(out, wn);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(a, n * eb).in(z, wn).host(host_alpha).host(host_beta).out(out, wn).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->bsgn_mask(ctx->policy, cs.lc, a, z, host_alpha, host_beta, w, out, n, cs.st));
 }
@@ -1915,18 +1710,8 @@ int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, v
     const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
     ARGCHK(pl.ok && bsgn_flat_plan(n, w, eb, false).ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(c && host_s && host_out);
     const size_t wn = pl.span * eb, on = sum ? n * eb : wn;
-    const ByteRange cr = byte_range(c, wn);
-    for (int i = 0; i < m; ++i) {
-        ARGCHK(host_s[i] && host_out[i]);
-        const ByteRange oi = byte_range(host_out[i], on);
-        ARGCHK(!overlaps(oi, cr));
-        for (int j = 0; j < m; ++j) {
-            if (j < i) ARGCHK(!overlaps(oi, byte_range(host_out[j], on)));
-            ARGCHK(!overlaps(oi, byte_range(host_s[j], wn)));
-        }
-    }
+    ARGCHK(Operands().in(c, wn).in_rows(host_s, m, wn).out_rows(host_out, m, on).ok());
     ExpArgs ex;
     legendre_exponent(ctx, &ex);
     exp_try_cube_form(&ex);                                // (the choices of ffgpu_pow for this exponent)
@@ -1944,10 +1729,7 @@ int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U,
     size_t xspan;
     ARGCHK(pl.ok && unit_x_span(n, xstride, eb, xspan));
     if (n == 0) return FFGPU_OK;
-    ARGCHK(x && U && out);
-    const ByteRange in[2] = {byte_range(x, xspan * eb), byte_range(U, pl.span * eb)};
-    const ByteRange o = byte_range(out, pl.span * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(x, xspan * eb).in(U, pl.span * eb).out(out, pl.span * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->unit_prod(ctx->policy, cs.lc, x, xstride, U, h, out, n, cs.st));
 }
@@ -1959,10 +1741,7 @@ int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size
     const ExplogRowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, eb, false);
     ARGCHK(pl.ok);
     if (n == 0) return FFGPU_OK;
-    ARGCHK(U && c && out);
-    const ByteRange in[2] = {byte_range(U, pl.span * eb), byte_range(c, n * eb)};
-    const ByteRange o = byte_range(out, K * n * eb);
-    ARGCHK(outputs_disjoint(in, 2, &o, 1));
+    ARGCHK(Operands().in(U, pl.span * eb).in(c, n * eb).out(out, K * n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->unit_roll(ctx->policy, cs.lc, U, c, kbits, K, out, n, cs.st));
 }
@@ -1977,10 +1756,7 @@ int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int
     ARGCHK(pl.ok);
     if (!dp.fits) return FFGPU_ENOTSUP;
     if (n == 0) return FFGPU_OK;
-    ARGCHK(U && tab && out);
-    const ByteRange in[3] = {byte_range(U, pl.span * eb), byte_range(tab, tlen * eb), byte_range(c, c ? n * eb : 0)};
-    const ByteRange o = byte_range(out, n * eb);
-    ARGCHK(outputs_disjoint(in, c ? 3 : 2, &o, 1));
+    ARGCHK(Operands().in(U, pl.span * eb).in(tab, tlen * eb).in_opt(c, n * eb).out(out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->unit_dot(ctx->policy, cs.lc, U, rows, c, kbits, tab, tlen, out, n, cs.st));
 }
@@ -2016,18 +1792,12 @@ int ffgm_conv2d(ffgpu_ctx* ctx, const void* const* host_x, const void* const* ho
     ARGCHK(pl.ok);
     if (pl.empty) return FFGPU_OK;
     if (!pl.grid_ok) return FFGPU_ENOTSUP;
-    ARGCHK(host_x && host_w && host_out);
     size_t nx, nw, ny;
     ARGCHK(conv2d_sizes(k, r, m, n, v, s, eb, &nx, &nw, &ny));
-    for (int i = 0; i < nsend; ++i) ARGCHK(host_x[i] && host_w[i] && host_out[i] && (!host_b || host_b[i]));
-    for (int i = 0; i < nsend; ++i) {                       // tiles read while others write: no output meets an input or another output
-        const ByteRange oi = byte_range(host_out[i], ny * eb);
-        for (int j = 0; j < nsend; ++j) {
-            if (j < i) ARGCHK(!overlaps(oi, byte_range(host_out[j], ny * eb)));
-            ARGCHK(!overlaps(oi, byte_range(host_x[j], nx * eb)) && !overlaps(oi, byte_range(host_w[j], nw * eb)));
-            if (host_b) ARGCHK(!overlaps(oi, byte_range(host_b[j], v * eb)));
-        }
-    }
+    Operands io;                                            // tiles read while others write: no output meets an input or another output
+    io.in_rows(host_x, nsend, nx * eb).in_rows(host_w, nsend, nw * eb);
+    if (host_b) io.in_rows(host_b, nsend, v * eb);
+    ARGCHK(io.out_rows(host_out, nsend, ny * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->conv2d(ctx->policy, cs.lc, host_x, host_w, host_b, host_out, nsend, k, r, m, n, v, s, cs.st));
 }
@@ -2093,10 +1863,7 @@ int ffgpu_sum(ffgpu_ctx* ctx, const void* a, void* out, void* workspace, size_t 
 // a masked draw is a field element as it stands only when 2^mask_bits <= order: the modulus (a prime, or the bit pattern
 // of a polynomial of degree n, order 2^n) has more than mask_bits bits
 static bool prss_mask_fits(const ffgpu_ctx* ctx, int mask_bits) {
-    const uint64_t* p = ctx->modulus;
-    const int top = p[2] ? 2 : p[1] ? 1 : 0;
-    const int bits = 64 * top + (64 - __builtin_clzll(p[top] | 1));
-    return mask_bits < bits;
+    return mask_bits < modulus_bits(ctx);
 }
 
 int ffgpu_prss_combine(ffgpu_ctx* ctx, const void* const* host_streams, int ks, int d, int l, int mask_bits,
