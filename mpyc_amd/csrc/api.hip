@@ -1064,7 +1064,8 @@ static bool stack_span(size_t batch, size_t stride, size_t rows, size_t ld, size
     size_t m, t;
     if (__builtin_mul_overflow(rows - 1, ld, &m) || __builtin_add_overflow(m, cols, &m)) return false;
     if (__builtin_mul_overflow(batch - 1, stride, &t) || __builtin_add_overflow(t, m, &t)) return false;
-    if (__builtin_mul_overflow(t, eb, bytes) || *bytes > (size_t)1 << 62) return false;
+    if (!geom_bytes_ok(t, eb)) return false;
+    *bytes = t * eb;
     *matrix = m;
     return true;
 }
@@ -1220,7 +1221,7 @@ int ffgpu_sgn_finish(ffgpu_ctx* ctx, const void* w, const void* sbit, const void
     ARGCHK(sgn_consts(ctx, l, consts));
     if (n == 0) return FFGPU_OK;
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(n <= ((size_t)1 << 62) / eb);                 // n * eb cannot overflow
+    ARGCHK(geom_bytes_ok(n, eb));                        // n * eb cannot overflow
     ARGCHK(Operands().in(w, n * eb).in(sbit, n * eb).in(z, n * eb).out(lt_out, n * eb).ok());
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->sgn_finish(ctx->policy, cs.lc, w, sbit, z, l, consts, lt_out, n, cs.st));
@@ -1523,7 +1524,7 @@ int ffgpu_trunc_finish(ffgpu_ctx* ctx, const void* const* host_rows, const uint6
 }
 
 // what both norm entries check before they look at a pointer: FFGPU_OK with *work == false when there is nothing to do
-static int norm_args(const ffgpu_ctx* ctx, int l, size_t n, FxpNormPlan* pl, bool* work) {
+static int norm_args(const ffgpu_ctx* ctx, int l, size_t n, RevPlan* pl, bool* work) {
     ARGCHK(fxp_norm_l_valid(l));
     *work = false;
     if (n == 0) return FFGPU_OK;
@@ -1535,7 +1536,7 @@ static int norm_args(const ffgpu_ctx* ctx, int l, size_t n, FxpNormPlan* pl, boo
 
 int ffgpu_norm_prod(ffgpu_ctx* ctx, const void* bits, int l, void* out, void* sign_out, size_t n, void* stream) {
     PRIME_CTX(ctx);
-    FxpNormPlan pl;
+    RevPlan pl;
     ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(Operands().in(bits, n * pl.l * eb).out(out, pl.elems * eb).out_opt(sign_out, n * eb).ok());
@@ -1548,7 +1549,7 @@ int ffgpu_norm_apply(ffgpu_ctx* ctx, const void* bits, const void* const* host_r
     PRIME_CTX(ctx);
     ARGCHK(nrows >= 1);
     if (nrows > (int)MAXK) return FFGPU_ENOTSUP;
-    FxpNormPlan pl;
+    RevPlan pl;
     ARGS_OR_RETURN(norm_args(ctx, l, n, &pl, &work));
     const size_t eb = (size_t)ctx->elem_bytes;
     ARGCHK(Operands().in(bits, n * pl.l * eb).in_rows(host_rows, nrows, pl.elems * eb).host(host_lambda).out(out, pl.elems * eb).ok());
@@ -1563,9 +1564,9 @@ int ffgm_powers_prod(ffgpu_ctx* ctx, const void* P, size_t stride, int h, int w,
     ARGCHK(explog_prod_valid(h, w));
     if (n == 0) return FFGPU_OK;
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)h, stride, eb, false);
+    const RowsPlan pl = rows_plan(n, (size_t)h, stride, eb, false);
     size_t wn;
-    ARGCHK(pl.ok && cx_mul_ok((size_t)w, n, wn) && wn <= ((size_t)1 << 62) / eb);
+    ARGCHK(pl.ok && geom_mul_ok((size_t)w, n, wn) && geom_bytes_ok(wn, eb));
     ARGCHK(Operands().in(P, pl.span * eb).out(out, wn * eb).ok());                // (rows h.. of P's allocation lie past the span)
     CallScope cs(ctx, stream);
     return status_of(ctx->ops->secure->powers_prod(ctx->policy, cs.lc, P, stride, h, w, out, n, cs.st));
@@ -1577,7 +1578,7 @@ int ffgm_poly_dot(ffgpu_ctx* ctx, const void* P, size_t stride, int theta, const
     ARGCHK(explog_poly_valid(theta) && host_c0);
     if (n == 0) return FFGPU_OK;
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)theta, stride, eb, false);
+    const RowsPlan pl = rows_plan(n, (size_t)theta, stride, eb, false);
     ARGCHK(pl.ok);
     ARGCHK(Operands().in(P, pl.span * eb).in(tab, (size_t)theta * eb).out(out, n * eb).ok());
     CallScope cs(ctx, stream);
@@ -1602,7 +1603,7 @@ int ffgm_bits_reverse(ffgpu_ctx* ctx, const void* bits, int l, void* out, size_t
     ARGCHK(explog_rev_l_valid(l));
     if (n == 0) return FFGPU_OK;
     const size_t eb = (size_t)ctx->elem_bytes;
-    const FxpNormPlan pl = explog_rev_plan(n, l, eb, false);
+    const RevPlan pl = explog_rev_plan(n, l, eb, false);
     ARGCHK(pl.ok);
     ARGCHK(Operands().in(bits, pl.elems * eb).out(out, pl.elems * eb).ok());
     CallScope cs(ctx, stream);
@@ -1626,7 +1627,7 @@ int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t coun
     PRIME_CTX(ctx);
     if (!ctx->modulus[2] && !ctx->modulus[1] && ctx->modulus[0] == 2) return FFGPU_ENOTSUP;
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(legendre_plan(count, eb, false).ok);
+    ARGCHK(stream_plan(count, eb, false).ok);
     if (count == 0) return FFGPU_OK;
     ARGCHK(Operands().in(c, count * eb).out(code, count).ok());
     ExpArgs ex;
@@ -1639,7 +1640,7 @@ int ffgm_legendre_code(ffgpu_ctx* ctx, const void* c, uint8_t* code, size_t coun
 int ffgm_iszero_finish(ffgpu_ctx* ctx, const uint8_t* code, const void* z, void* out, size_t count, void* stream) {
     PRIME_CTX(ctx);
     const size_t eb = (size_t)ctx->elem_bytes;
-    ARGCHK(iszero_flat_plan(count, eb, false).ok);
+    ARGCHK(flat_plan(count, eb, false).ok);
     if (count == 0) return FFGPU_OK;
     ARGCHK(Operands().in(code, count).in(z, count * eb).out(out, count * eb).ok());
     CallScope cs(ctx, stream);
@@ -1691,7 +1692,7 @@ int ffgm_bsgn_mask(ffgpu_ctx* ctx, const void* a, const void* z, const uint64_t*
     PRIME_CTX(ctx);
     ARGCHK(bsgn_w_valid(w));
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
+    const RowsPlan pl = bsgn_rows_plan(n, w, eb, false);
     ARGCHK(pl.ok);
     if (n == 0) return FFGPU_OK;
     const size_t wn = pl.span * eb;
@@ -1707,7 +1708,7 @@ int ffgm_bsgn_finish(ffgpu_ctx* ctx, const void* c, const void* const* host_s, v
     ARGCHK(m >= 1 && bsgn_w_valid(w) && (sum == 0 || sum == 1));
     if (m > (int)BSGN_MAX_PARTIES) return FFGPU_ENOTSUP;
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, false);
+    const RowsPlan pl = bsgn_rows_plan(n, w, eb, false);
     ARGCHK(pl.ok && bsgn_flat_plan(n, w, eb, false).ok);
     if (n == 0) return FFGPU_OK;
     const size_t wn = pl.span * eb, on = sum ? n * eb : wn;
@@ -1725,7 +1726,7 @@ int ffgm_unit_prod(ffgpu_ctx* ctx, const void* x, size_t xstride, const void* U,
     PRIME_CTX(ctx);
     ARGCHK(h >= 1 && xstride >= 1);
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = unit_rows_plan(n, h, eb, false);
+    const RowsPlan pl = unit_rows_plan(n, h, eb, false);
     size_t xspan;
     ARGCHK(pl.ok && unit_x_span(n, xstride, eb, xspan));
     if (n == 0) return FFGPU_OK;
@@ -1738,7 +1739,7 @@ int ffgm_unit_roll(ffgpu_ctx* ctx, const void* U, const void* c, int kbits, size
     PRIME_CTX(ctx);
     ARGCHK(unit_roll_valid(kbits, K));
     const size_t eb = (size_t)ctx->elem_bytes;
-    const ExplogRowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, eb, false);
+    const RowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, eb, false);
     ARGCHK(pl.ok);
     if (n == 0) return FFGPU_OK;
     ARGCHK(Operands().in(U, pl.span * eb).in(c, n * eb).out(out, K * n * eb).ok());
@@ -1752,7 +1753,7 @@ int ffgm_unit_dot(ffgpu_ctx* ctx, const void* U, size_t rows, const void* c, int
     const size_t eb = (size_t)ctx->elem_bytes;
     const UnitDotPlan dp = unit_dot_plan(rows, c != nullptr, kbits, tlen, eb);
     ARGCHK(dp.ok);
-    const ExplogRowsPlan pl = unit_rows_plan(n, rows, eb, false);
+    const RowsPlan pl = unit_rows_plan(n, rows, eb, false);
     ARGCHK(pl.ok);
     if (!dp.fits) return FFGPU_ENOTSUP;
     if (n == 0) return FFGPU_OK;

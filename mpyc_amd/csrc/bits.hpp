@@ -20,6 +20,7 @@
 // products feed the re-sharing at once: default policy.  The sub-share rows of k_carry_apply: share_rows.hpp.
 #pragma once
 #include "bits_geom.hpp"
+#include "sgn_geom.hpp"
 
 namespace ffgpu {
 

@@ -17,7 +17,7 @@
 // R = Rc + Rd product rows, at most 63 for l <= 64 (l = 64, round 1: 32 + 31; R may reach or pass l, as for l = 6, round 2:
 // 4 + 2).  G, P and the compact products are bit-major: row k is n contiguous elements at k * n.
 #pragma once
-#include "sort_geom.hpp"
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -25,14 +25,14 @@ enum { BITS_MAX_L = 64 };
 enum { BITS_MAX_ROWS = 63 };                // the widest round of any l <= 64 (tests/bits_check.cpp walks them all)
 
 // rounds of the network: ceil(log2 l); 0 for l == 1, -1 for an l out of range
-FFCX_HD int bits_rounds(int l) {
+FFG_HD int bits_rounds(int l) {
     if (l < 1 || l > BITS_MAX_L) return -1;
     int r = 0;
     while (((size_t)1 << r) < (size_t)l) ++r;
     return r;
 }
 // ceil(log2 n), n >= 1
-FFCX_HD int bits_height(int n) {
+FFG_HD int bits_height(int n) {
     int r = 0;
     while ((1 << r) < n) ++r;
     return r;
@@ -85,9 +85,9 @@ inline bool bits_level(int l, int round, BitsLevel& lv) {
 
 // ---- the plan of a level launch -------------------------------------------------------------------------------------------
 // Both level kernels run grid (gx, R): workgroup row y serves product row y (the table entry is then uniform over the
-// workgroup), and the gx workgroups of a row stream its n elements in UNITS: packs of cx_pack(eb) elements when vec, single
-// elements otherwise.  Whole packs apply when every row starts aligned: n a multiple of cx_gran(eb) (24-byte elements:
-// whole waves, kernels.hpp ldgw / stgw), the byte pitch n * eb of a row a multiple of cx_align(eb), and aligned pointers.
+// workgroup), and the gx workgroups of a row stream its n elements in UNITS: packs of geom_pack(eb) elements when vec, single
+// elements otherwise.  Whole packs apply when every row starts aligned: n a multiple of geom_gran(eb) (24-byte elements:
+// whole waves, kernels.hpp ldgw / stgw), the byte pitch n * eb of a row a multiple of geom_align(eb), and aligned pointers.
 // Unit u of product row y: the compact arrays at unit y * row_units + u, G / P row r at unit r * row_units + u.
 struct BitsPlan {
     int ok;                 // 0: l or round out of range, sizes overflow -- nothing may be launched
@@ -96,24 +96,24 @@ struct BitsPlan {
     size_t row_units;       // units of a row
     unsigned gx;            // workgroups per product row
 };
-FFCX_HD BitsPlan bits_plan(size_t n, int l, int rows, size_t eb, bool aligned, size_t max_blocks) {
+FFG_HD BitsPlan bits_plan(size_t n, int l, int rows, size_t eb, bool aligned, size_t max_blocks) {
     BitsPlan pl = BitsPlan();
-    size_t nl, bytes;
-    if (l < 1 || l > BITS_MAX_L || rows < 0 || rows > BITS_MAX_ROWS || eb < 4 || eb % 4) return pl;
-    if (!cx_mul_ok(n, (size_t)l, nl) || !cx_mul_ok(nl, eb, bytes) || bytes > ((size_t)1 << 62)) return pl;
+    size_t nl;
+    if (l < 1 || l > BITS_MAX_L || rows < 0 || rows > BITS_MAX_ROWS) return pl;
+    if (!geom_mul_ok(n, (size_t)l, nl) || !geom_size_ok(nl, eb)) return pl;
     pl.ok = 1;
     pl.rows = rows;
     if (rows == 0 || n == 0) return pl;
-    pl.vec = aligned && n % cx_gran(eb) == 0 && (n * eb) % cx_align(eb) == 0;
-    pl.row_units = pl.vec ? n / cx_pack(eb) : n;
-    size_t want = (pl.row_units + CX_THREADS - 1) / CX_THREADS;
+    pl.vec = aligned && n % geom_gran(eb) == 0 && (n * eb) % geom_align(eb) == 0;
+    pl.row_units = pl.vec ? n / geom_pack(eb) : n;
+    size_t want = (pl.row_units + GEOM_THREADS - 1) / GEOM_THREADS;
     size_t cap = max_blocks / (size_t)rows;
     if (cap < 1) cap = 1;
-    if (cap > (size_t)CX_MAX_GRID) cap = (size_t)CX_MAX_GRID;
+    if (cap > (size_t)GEOM_MAX_GRID) cap = (size_t)GEOM_MAX_GRID;
     pl.gx = (unsigned)(want < cap ? want : cap);
     return pl;
 }
 // the unit of row r that belongs with unit u of a row
-FFCX_HD size_t bits_unit(const BitsPlan& pl, int r, size_t u) { return (size_t)r * pl.row_units + u; }
+FFG_HD size_t bits_unit(const BitsPlan& pl, int r, size_t u) { return (size_t)r * pl.row_units + u; }
 
 }  // namespace ffgpu

@@ -49,7 +49,7 @@ __device__ __forceinline__ typename F::word bsgn_mask_value(const F& f, const ty
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_bsgn_mask(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ z,
-                                                      BsgnMaskArgs<F> ma, int w, typename F::elem* __restrict__ out, ExplogRowsPlan pl) {
+                                                      BsgnMaskArgs<F> ma, int w, typename F::elem* __restrict__ out, RowsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(BLOCK) void k_bsgn_mask(F f, const typename F::elem
 #pragma unroll
             for (int i = 0; i < BSGN_MAX_ROWS; ++i) {
                 if (i >= w) break;
-                const size_t u = bsgn_row_unit(pl, (size_t)i, g);
+                const size_t u = rows_unit(pl, (size_t)i, g);
                 const PK xz = ldgw_finish(ldgw_issue<false>(zv + u));
                 PK y;
 #pragma unroll
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(BLOCK) void k_bsgn_mask(F f, const typename F::elem
 #pragma unroll
             for (int i = 0; i < BSGN_MAX_ROWS; ++i) {
                 if (i >= w) break;
-                const size_t u = bsgn_row_unit(pl, (size_t)i, g);
+                const size_t u = rows_unit(pl, (size_t)i, g);
                 st_elem<F>(out, u, bsgn_mask_value<F>(f, ap, ma.beta[i], ld_elem<F>(z, u)));
             }
         }
@@ -141,7 +141,7 @@ __device__ __forceinline__ typename F::word bsgn_accumulate(const F& f, unsigned
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_bsgn_finish_sum(F f, const typename F::elem* __restrict__ c, ExpArgs ex, BsgnFinishArgs<F> fa,
-                                                            int w, ExplogRowsPlan pl) {
+                                                            int w, RowsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
     typedef typename MemPack<F>::type MP;
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(BLOCK) void k_bsgn_finish_sum(F f, const typename F
         for (size_t g = gid; g < pl.total; g += gsz) {
             uint64_t codes = 0;
             for (int i = 0; i < w; ++i) {
-                const P x = ldg<false>(cv + bsgn_row_unit(pl, (size_t)i, g));
+                const P x = ldg<false>(cv + rows_unit(pl, (size_t)i, g));
 #pragma unroll
                 for (int q = 0; q < P::N; ++q) codes = bsgn_sym_put(codes, i, q, legendre_code_of(x.w[q], ff_pow_digits(f, x.w[q], ex)));
             }
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(BLOCK) void k_bsgn_finish_sum(F f, const typename F
 #pragma unroll
                 for (int q = 0; q < P::N; ++q) y.w[q] = W();
                 for (int i = 0; i < w; ++i) {
-                    const P s = ldg<true>(sv + bsgn_row_unit(pl, (size_t)i, g));
+                    const P s = ldg<true>(sv + rows_unit(pl, (size_t)i, g));
 #pragma unroll
                     for (int q = 0; q < P::N; ++q) y.w[q] = bsgn_accumulate<F>(f, bsgn_sym_of(codes, i, q), y.w[q], s.w[q]);
                 }
@@ -173,13 +173,13 @@ __global__ __launch_bounds__(BLOCK) void k_bsgn_finish_sum(F f, const typename F
         for (size_t g = gid; g < pl.total; g += gsz) {
             uint64_t codes = 0;
             for (int i = 0; i < w; ++i) {
-                const W x = ld_elem<F>(c, bsgn_row_unit(pl, (size_t)i, g));
+                const W x = ld_elem<F>(c, rows_unit(pl, (size_t)i, g));
                 codes = bsgn_sym_put(codes, i, 0, legendre_code_of(x, ff_pow(f, x, ex)));
             }
             for (int j = 0; j < fa.m; ++j) {
                 W y = W();
                 for (int i = 0; i < w; ++i)
-                    y = bsgn_accumulate<F>(f, bsgn_sym_of(codes, i, 0), y, ld_elem<F>(fa.s[j], bsgn_row_unit(pl, (size_t)i, g)));
+                    y = bsgn_accumulate<F>(f, bsgn_sym_of(codes, i, 0), y, ld_elem<F>(fa.s[j], rows_unit(pl, (size_t)i, g)));
                 st_elem<F>(fa.out[j], g, y);
             }
         }

@@ -23,14 +23,7 @@
 // Flush schedule: an accumulator takes s terms per filter row and holds `flush` of them, so it is reduced after every
 // flush / s filter rows, counted on across the input channels: inside a channel once s^2 > flush (s >= 6 at 32 terms).
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFC2D_HD __host__ __device__ __forceinline__
-#else
-#define FFC2D_HD inline
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -58,11 +51,11 @@ struct Conv2dShape {
 typedef Conv2dShape<16, 16, 4> Conv2dWide;
 typedef Conv2dShape<8, 16, 1> Conv2dNarrow;
 
-FFC2D_HD int conv2d_row_off(int s) { return (s - 1) / 2; }
-FFC2D_HD int conv2d_col_off(int s) { return s / 2; }
+FFG_HD int conv2d_row_off(int s) { return (s - 1) / 2; }
+FFG_HD int conv2d_col_off(int s) { return s / 2; }
 
 // filter rows between two reductions of an accumulator that holds `flush` terms: at least 2 for s <= CONV2D_MAX_S
-FFC2D_HD int conv2d_flush_rows(int s, int flush) { return flush / s; }
+FFG_HD int conv2d_flush_rows(int s, int flush) { return flush / s; }
 
 // the launch: everything the kernel needs beside the pointers.  Filled by conv2d_plan().
 struct Conv2dGeom {
@@ -85,33 +78,25 @@ struct Conv2dPlan {
     Conv2dGeom g;
 };
 
-FFC2D_HD bool conv2d_mul_ok(size_t a, size_t b, size_t* out) {
-    if (a != 0 && b > (~(size_t)0) / a) return false;
-    *out = a * b;
-    return true;
-}
-
 // elements of the three tensors; false when one of them, times elem_bytes, overflows size_t (or passes 2^62)
-FFC2D_HD bool conv2d_sizes(size_t k, size_t r, size_t m, size_t n, size_t v, int s, size_t elem_bytes, size_t* nx, size_t* nw,
+FFG_HD bool conv2d_sizes(size_t k, size_t r, size_t m, size_t n, size_t v, int s, size_t elem_bytes, size_t* nx, size_t* nw,
                            size_t* ny) {
-    size_t t, b;
-    if (!conv2d_mul_ok(k, r, &t) || !conv2d_mul_ok(t, m, &t) || !conv2d_mul_ok(t, n, nx)) return false;
-    if (!conv2d_mul_ok(v, r, &t) || !conv2d_mul_ok(t, (size_t)s * (size_t)s, nw)) return false;
-    if (!conv2d_mul_ok(k, v, &t) || !conv2d_mul_ok(t, m, &t) || !conv2d_mul_ok(t, n, ny)) return false;
-    const size_t cap = (size_t)1 << 62;
-    return conv2d_mul_ok(*nx, elem_bytes, &b) && b <= cap && conv2d_mul_ok(*nw, elem_bytes, &b) && b <= cap &&
-           conv2d_mul_ok(*ny, elem_bytes, &b) && b <= cap;
+    size_t t;
+    if (!geom_mul_ok(k, r, t) || !geom_mul_ok(t, m, t) || !geom_mul_ok(t, n, *nx)) return false;
+    if (!geom_mul_ok(v, r, t) || !geom_mul_ok(t, (size_t)s * (size_t)s, *nw)) return false;
+    if (!geom_mul_ok(k, v, t) || !geom_mul_ok(t, m, t) || !geom_mul_ok(t, n, *ny)) return false;
+    return geom_bytes_ok(*nx, elem_bytes) && geom_bytes_ok(*nw, elem_bytes) && geom_bytes_ok(*ny, elem_bytes);
 }
 
 // window and tap slots of one input channel
-FFC2D_HD int conv2d_win_slots(int TH, int TW, int s) { return (TH + s - 1) * (TW + s - 1); }
-FFC2D_HD int conv2d_tap_slots(int VB, int s) { return VB * s * s; }
+FFG_HD int conv2d_win_slots(int TH, int TW, int s) { return (TH + s - 1) * (TW + s - 1); }
+FFG_HD int conv2d_tap_slots(int VB, int s) { return VB * s * s; }
 // LDS bytes of a staging step of CH channels; slot_bytes: a staged operand (a word, or its 28-bit digits)
-FFC2D_HD size_t conv2d_lds_bytes(int TH, int TW, int VB, int s, int CH, size_t slot_bytes) {
+FFG_HD size_t conv2d_lds_bytes(int TH, int TW, int VB, int s, int CH, size_t slot_bytes) {
     return (size_t)CH * (size_t)(conv2d_win_slots(TH, TW, s) + conv2d_tap_slots(VB, s)) * slot_bytes;
 }
 // input channels per step: as many as CONV2D_LDS_STEP holds, at most CONV2D_MAX_CH and r, at least one
-FFC2D_HD int conv2d_channels_per_step(int TH, int TW, int VB, int s, size_t r, size_t slot_bytes) {
+FFG_HD int conv2d_channels_per_step(int TH, int TW, int VB, int s, size_t r, size_t slot_bytes) {
     const size_t one = conv2d_lds_bytes(TH, TW, VB, s, 1, slot_bytes);
     size_t ch = (size_t)CONV2D_LDS_STEP / one;
     if (ch > (size_t)CONV2D_MAX_CH) ch = CONV2D_MAX_CH;
@@ -119,25 +104,28 @@ FFC2D_HD int conv2d_channels_per_step(int TH, int TW, int VB, int s, size_t r, s
     return ch < 1 ? 1 : (int)ch;
 }
 
-FFC2D_HD size_t conv2d_ceil_div(size_t a, size_t b) { return a / b + (a % b != 0); }
+FFG_HD size_t conv2d_ceil_div(size_t a, size_t b) { return a / b + (a % b != 0); }
 
 // workgroups of a shape for the whole call; false on overflow
-FFC2D_HD bool conv2d_blocks(size_t k, size_t m, size_t n, size_t v, int TH, int TW, int VB, size_t* blocks) {
-    size_t t;
-    return conv2d_mul_ok(k, conv2d_ceil_div(m, (size_t)TH), &t) && conv2d_mul_ok(t, conv2d_ceil_div(n, (size_t)TW), &t) &&
-           conv2d_mul_ok(t, conv2d_ceil_div(v, (size_t)VB), blocks);
+FFG_HD bool conv2d_blocks(size_t k, size_t m, size_t n, size_t v, int TH, int TW, int VB, size_t* blocks) {
+    size_t t, all;
+    if (!geom_mul_ok(k, conv2d_ceil_div(m, (size_t)TH), t) || !geom_mul_ok(t, conv2d_ceil_div(n, (size_t)TW), t) ||
+        !geom_mul_ok(t, conv2d_ceil_div(v, (size_t)VB), all))
+        return false;
+    *blocks = all;                  // (untouched on overflow)
+    return true;
 }
 
 // the wide shape once its workgroups, over all senders, give every compute unit `per_cu` of them, the narrow one below
-FFC2D_HD bool conv2d_use_wide(size_t wide_blocks, int nsend, int num_cu, int per_cu) {
+FFG_HD bool conv2d_use_wide(size_t wide_blocks, int nsend, int num_cu, int per_cu) {
     size_t all;
-    if (!conv2d_mul_ok(wide_blocks, (size_t)nsend, &all)) return true;
+    if (!geom_mul_ok(wide_blocks, (size_t)nsend, all)) return true;
     return all >= (size_t)(num_cu > 0 ? num_cu : 1) * (size_t)per_cu;
 }
 
 // The launch plan.  ok: 1 <= s <= CONV2D_MAX_S, s <= n, nsend >= 1, no size overflowing, and r, m, n, v >= 1 unless
 // k v m n == 0 (empty: nothing is launched).  slot_bytes, flush: of the field policy (conv2d.hpp).
-FFC2D_HD Conv2dPlan conv2d_plan(size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend, int num_cu, int wide_per_cu,
+FFG_HD Conv2dPlan conv2d_plan(size_t k, size_t r, size_t m, size_t n, size_t v, int s, int nsend, int num_cu, int wide_per_cu,
                                 size_t elem_bytes, size_t slot_bytes, int flush) {
     Conv2dPlan p = Conv2dPlan();
     size_t nx, nw, ny;
@@ -181,7 +169,7 @@ struct Conv2dBlock {
     size_t I0, J0;                  // first output row and column of the tile
     size_t j0;                      // first output channel of the block
 };
-FFC2D_HD Conv2dBlock conv2d_block(const Conv2dGeom& g, unsigned b) {
+FFG_HD Conv2dBlock conv2d_block(const Conv2dGeom& g, unsigned b) {
     Conv2dBlock o;
     o.j0 = (size_t)(b % g.vblocks) * (size_t)g.VB;
     b /= g.vblocks;
@@ -196,7 +184,7 @@ FFC2D_HD Conv2dBlock conv2d_block(const Conv2dGeom& g, unsigned b) {
 struct Conv2dLane {
     int py, px, c0;
 };
-FFC2D_HD Conv2dLane conv2d_lane(const Conv2dGeom& g, int tid) {
+FFG_HD Conv2dLane conv2d_lane(const Conv2dGeom& g, int tid) {
     const int pl = g.TH * g.TW, p = tid % pl;
     Conv2dLane o;
     o.py = p / g.TW;
@@ -206,24 +194,24 @@ FFC2D_HD Conv2dLane conv2d_lane(const Conv2dGeom& g, int tid) {
 }
 
 // image row / column that window slot row wy / column wx holds for the tile at I0 / J0 (negative or past the image: zero)
-FFC2D_HD int64_t conv2d_win_row(size_t I0, int wy, int s) { return (int64_t)I0 + wy - conv2d_row_off(s); }
-FFC2D_HD int64_t conv2d_win_col(size_t J0, int wx, int s) { return (int64_t)J0 + wx - conv2d_col_off(s); }
+FFG_HD int64_t conv2d_win_row(size_t I0, int wy, int s) { return (int64_t)I0 + wy - conv2d_row_off(s); }
+FFG_HD int64_t conv2d_win_col(size_t J0, int wx, int s) { return (int64_t)J0 + wx - conv2d_col_off(s); }
 // the halo test
-FFC2D_HD bool conv2d_in_image(int64_t row, int64_t col, size_t m, size_t n) {
+FFG_HD bool conv2d_in_image(int64_t row, int64_t col, size_t m, size_t n) {
     return row >= 0 && col >= 0 && (uint64_t)row < (uint64_t)m && (uint64_t)col < (uint64_t)n;
 }
 // staged slot of window element (wy, wx) of the step's channel cl, and of tap (di, dj) of channel cl for channel c of the block
-FFC2D_HD int conv2d_win_slot(const Conv2dGeom& g, int cl, int wy, int wx) { return (cl * g.WH + wy) * g.WW + wx; }
-FFC2D_HD int conv2d_tap_slot(const Conv2dGeom& g, int cl, int c, int di, int dj) { return ((cl * g.VB + c) * g.s + di) * g.s + dj; }
+FFG_HD int conv2d_win_slot(const Conv2dGeom& g, int cl, int wy, int wx) { return (cl * g.WH + wy) * g.WW + wx; }
+FFG_HD int conv2d_tap_slot(const Conv2dGeom& g, int cl, int c, int di, int dj) { return ((cl * g.VB + c) * g.s + di) * g.s + dj; }
 // the inverse maps the staging loops use: slot -> (cl, wy, wx) and slot -> (cl, c, di * s + dj)
-FFC2D_HD void conv2d_win_of(const Conv2dGeom& g, int slot, int& cl, int& wy, int& wx) {
+FFG_HD void conv2d_win_of(const Conv2dGeom& g, int slot, int& cl, int& wy, int& wx) {
     const int per = g.WH * g.WW;
     cl = slot / per;
     const int rem = slot - cl * per;
     wy = rem / g.WW;
     wx = rem - wy * g.WW;
 }
-FFC2D_HD void conv2d_tap_of(const Conv2dGeom& g, int slot, int& cl, int& c, int& tap) {
+FFG_HD void conv2d_tap_of(const Conv2dGeom& g, int slot, int& cl, int& c, int& tap) {
     const int ss = g.s * g.s, per = g.VB * ss;
     cl = slot / per;
     const int rem = slot - cl * per;
@@ -231,13 +219,13 @@ FFC2D_HD void conv2d_tap_of(const Conv2dGeom& g, int slot, int& cl, int& c, int&
     tap = rem - c * ss;
 }
 // indices into the row-major tensors
-FFC2D_HD size_t conv2d_x_index(const Conv2dGeom& g, size_t img, size_t l, size_t row, size_t col) {
+FFG_HD size_t conv2d_x_index(const Conv2dGeom& g, size_t img, size_t l, size_t row, size_t col) {
     return ((img * g.r + l) * g.m + row) * g.n + col;
 }
-FFC2D_HD size_t conv2d_w_index(const Conv2dGeom& g, size_t j, size_t l, int tap) {
+FFG_HD size_t conv2d_w_index(const Conv2dGeom& g, size_t j, size_t l, int tap) {
     return (j * g.r + l) * (size_t)(g.s * g.s) + (size_t)tap;
 }
-FFC2D_HD size_t conv2d_y_index(const Conv2dGeom& g, size_t img, size_t j, size_t row, size_t col) {
+FFG_HD size_t conv2d_y_index(const Conv2dGeom& g, size_t img, size_t j, size_t row, size_t col) {
     return ((img * g.v + j) * g.m + row) * g.n + col;
 }
 

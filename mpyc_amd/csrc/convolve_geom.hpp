@@ -14,14 +14,7 @@
 // Per chunk the workgroup stages the TV taps and the WIN = TO + TV - 1 elements of `a` they meet, one element per thread
 // (WIN + TV <= BLOCK): window slot i holds a[k0 - j0 - (TV - 1) + i], zero outside [0, na).
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFCONV_HD __host__ __device__ __forceinline__
-#else
-#define FFCONV_HD inline
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -45,28 +38,28 @@ typedef ConvShape<CONV_R, 64> ConvWide;
 typedef ConvShape<CONV_R, 16> ConvNarrow;
 
 // the wide shape once it gives every compute unit `per_cu` tiles, the narrow one below that
-FFCONV_HD bool conv_use_wide(size_t nout, int num_cu, int per_cu) {
+FFG_HD bool conv_use_wide(size_t nout, int num_cu, int per_cu) {
     return (nout + ConvWide::TO - 1) / ConvWide::TO >= (size_t)num_cu * (size_t)per_cu;
 }
 
-FFCONV_HD size_t conv_tiles(size_t nout, int TO) { return (nout + (size_t)TO - 1) / (size_t)TO; }
+FFG_HD size_t conv_tiles(size_t nout, int TO) { return (nout + (size_t)TO - 1) / (size_t)TO; }
 
 // taps that reach the outputs [k0, k0 + TO): lo <= j < hi needs 0 <= k - j < na for some k of the tile.  Never empty for
 // k0 < na + nv - 1.
-FFCONV_HD void conv_tap_range(size_t k0, int TO, size_t na, size_t nv, size_t& lo, size_t& hi) {
+FFG_HD void conv_tap_range(size_t k0, int TO, size_t na, size_t nv, size_t& lo, size_t& hi) {
     lo = k0 + 1 > na ? k0 + 1 - na : 0;
     hi = k0 + (size_t)TO < nv ? k0 + (size_t)TO : nv;
 }
 
 // index into `a` of window slot i for the chunk of taps starting at j0 (negative or >= na: the slot holds zero)
-FFCONV_HD int64_t conv_win_index(size_t k0, size_t j0, int TV, int slot) {
+FFG_HD int64_t conv_win_index(size_t k0, size_t j0, int TV, int slot) {
     return (int64_t)k0 - (int64_t)j0 - (int64_t)(TV - 1) + (int64_t)slot;
 }
 // window slot that tap jj of the chunk (0 <= jj < TV) meets at local output o (0 <= o < TO)
-FFCONV_HD int conv_win_slot(int o, int jj, int TV) { return o - jj + (TV - 1); }
+FFG_HD int conv_win_slot(int o, int jj, int TV) { return o - jj + (TV - 1); }
 
 // unreduced accumulation: `since` terms (at most) sit in an accumulator that holds `flush` of them; after a chunk added up to
 // PER more, reduce before the next chunk could pass the bound
-FFCONV_HD bool conv_flush_due(int since, int PER, int flush) { return since + PER > flush; }
+FFG_HD bool conv_flush_due(int since, int PER, int flush) { return since + PER > flush; }
 
 }  // namespace ffgpu

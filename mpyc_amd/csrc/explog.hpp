@@ -7,7 +7,7 @@
 //   k_powers_prod   out[j n + e] = P[(h-1) stride + e] * P[j stride + e], j < w      the top power times the w lowest: dense (w, n)
 //   k_poly_dot      out[e] = c0 + sum_{j<theta} tab[j] P[j stride + e]               one lazy accumulator, one reduction
 //   k_pow_base      out[e] = prod_i T[15 i + d_i(e) - 1] over the windows d_i != 0   T = g^(d 16^i) staged in LDS
-//   k_bits_reverse  out[h l + j] = bits[h l + l-1-j]                                 the reversed index of fxp_geom.hpp
+//   k_bits_reverse  out[h l + j] = bits[h l + l-1-j]                                 the reversed-row walk of geom.hpp
 //
 // The first two and the last are streaming kernels as the fixed-point kernels are: one flat grid-stride loop, a unit a pack
 // (16 bytes; one 12- or 24-byte element) when the plan's vec, a single element otherwise, the 24-byte pack path
@@ -31,7 +31,7 @@ namespace ffgpu {
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_powers_prod(F f, const typename F::elem* P, int h, int w, typename F::elem* out,
-                                                        ExplogRowsPlan pl, size_t n) {
+                                                        RowsPlan pl, size_t n) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -41,9 +41,9 @@ __global__ __launch_bounds__(BLOCK) void k_powers_prod(F f, const typename F::el
         const MP* pv = reinterpret_cast<const MP*>(P);
         MP* ov = reinterpret_cast<MP*>(out);
         for (size_t g = gid; g < pl.total; g += gsz) {
-            const PK top = ldgw_finish(ldgw_issue<false>(pv + explog_row_unit(pl, (size_t)h - 1, g)));
+            const PK top = ldgw_finish(ldgw_issue<false>(pv + rows_unit(pl, (size_t)h - 1, g)));
             for (int j = 0; j < w; ++j) {
-                const PK x = ldgw_finish(ldgw_issue<false>(pv + explog_row_unit(pl, (size_t)j, g)));
+                const PK x = ldgw_finish(ldgw_issue<false>(pv + rows_unit(pl, (size_t)j, g)));
                 PK y;
 #pragma unroll
                 for (int q = 0; q < PK::N; ++q) y.w[q] = f.mul(top.w[q], x.w[q]);
@@ -52,9 +52,9 @@ __global__ __launch_bounds__(BLOCK) void k_powers_prod(F f, const typename F::el
         }
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
-            const W top = ld_elem<F>(P, explog_row_unit(pl, (size_t)h - 1, g));
+            const W top = ld_elem<F>(P, rows_unit(pl, (size_t)h - 1, g));
             for (int j = 0; j < w; ++j)
-                st_elem<F>(out, (size_t)j * n + g, f.mul(top, ld_elem<F>(P, explog_row_unit(pl, (size_t)j, g))));
+                st_elem<F>(out, (size_t)j * n + g, f.mul(top, ld_elem<F>(P, rows_unit(pl, (size_t)j, g))));
         }
     }
 }
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(BLOCK) void k_powers_prod(F f, const typename F::el
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_poly_dot(F f, const typename F::elem* __restrict__ P, int theta,
                                                      const typename F::elem* __restrict__ tab, typename F::word c0,
-                                                     typename F::elem* __restrict__ out, ExplogRowsPlan pl) {
+                                                     typename F::elem* __restrict__ out, RowsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(BLOCK) void k_poly_dot(F f, const typename F::elem*
 #pragma unroll
             for (int q = 0; q < PK::N; ++q) f.acc_zero(s[q]);
             for (int j = 0; j < theta; ++j) {
-                const PK x = ldgw_finish(ldgw_issue<false>(pv + explog_row_unit(pl, (size_t)j, g)));
+                const PK x = ldgw_finish(ldgw_issue<false>(pv + rows_unit(pl, (size_t)j, g)));
                 const W c = coef[j];
 #pragma unroll
                 for (int q = 0; q < PK::N; ++q) f.acc_mac(s[q], c, x.w[q]);
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(BLOCK) void k_poly_dot(F f, const typename F::elem*
         for (size_t g = gid; g < pl.total; g += gsz) {
             typename F::acc s;
             f.acc_zero(s);
-            for (int j = 0; j < theta; ++j) f.acc_mac(s, coef[j], ld_elem<F>(P, explog_row_unit(pl, (size_t)j, g)));
+            for (int j = 0; j < theta; ++j) f.acc_mac(s, coef[j], ld_elem<F>(P, rows_unit(pl, (size_t)j, g)));
             st_elem<F>(out, g, f.add(f.acc_reduce(s), c0));
         }
     }
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(BLOCK) void k_pow_base(F f, const typename F::elem*
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_bits_reverse(F f, const typename F::elem* __restrict__ bits, typename F::elem* __restrict__ out,
-                                                         FxpNormPlan pl) {
+                                                         RevPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -145,17 +145,17 @@ __global__ __launch_bounds__(BLOCK) void k_bits_reverse(F f, const typename F::e
     if (pl.vec) {
         MP* ov = reinterpret_cast<MP*>(out);
         for (size_t g = gid; g < pl.total; g += gsz) {
-            FxpNormAt at = fxp_norm_at(pl, g * PK::N);
+            RevAt at = rev_at(pl, g * PK::N);
             PK y;
 #pragma unroll
             for (int q = 0; q < PK::N; ++q) {
                 y.w[q] = ld_elem<F>(bits, at.src);
-                fxp_norm_next(pl, at);
+                rev_next(pl, at);
             }
             stgw<false>(ov + g, y);
         }
     } else {
-        for (size_t g = gid; g < pl.total; g += gsz) st_elem<F>(out, g, ld_elem<F>(bits, fxp_norm_at(pl, g).src));
+        for (size_t g = gid; g < pl.total; g += gsz) st_elem<F>(out, g, ld_elem<F>(bits, rev_at(pl, g).src));
     }
 }
 

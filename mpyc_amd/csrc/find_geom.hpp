@@ -23,11 +23,11 @@ namespace ffgpu {
 
 enum { FIND_MIN_COMP = 2, FIND_MAX_COMP = 5 };      // C = 1 + F, 1 <= F <= 4
 
-FFCX_HD bool find_comp_valid(int ncomp) { return ncomp >= FIND_MIN_COMP && ncomp <= FIND_MAX_COMP; }
+FFG_HD bool find_comp_valid(int ncomp) { return ncomp >= FIND_MIN_COMP && ncomp <= FIND_MAX_COMP; }
 
 // ---- the plan of a launch -----------------------------------------------------------------------------------------------------
 // t counts units as TourPlan does (packs when t.vec, else elements); so do the three plane distances.  Whole packs need what
-// tour_plan() needs; `inner` a multiple of cx_gran(eb) then makes every component plane, every row of the bits and the
+// tour_plan() needs; `inner` a multiple of geom_gran(eb) then makes every component plane, every row of the bits and the
 // position of a unit whole as well (a pack never straddles two positions).
 struct FindPlan {
     TourPlan t;             // the ODD_EVEN round over kk (a stored level) or kv (the leaf round, pitch_full = k * inner)
@@ -39,19 +39,19 @@ struct FindPlan {
 };
 
 // a stored level (C, outer, k, inner), k >= 2
-FFCX_HD FindPlan find_plan(size_t outer, size_t k, size_t inner, int ncomp, size_t eb, bool aligned) {
+FFG_HD FindPlan find_plan(size_t outer, size_t k, size_t inner, int ncomp, size_t eb, bool aligned) {
     FindPlan pl = FindPlan();
-    size_t n, all, bytes;
+    size_t n, all;
     if (!find_comp_valid(ncomp)) return pl;
     pl.t = tour_plan(outer, k, inner, TOUR_ODD_EVEN, eb, aligned);
     if (!pl.t.ok) return pl;
     n = outer * k * inner;                      // (tour_plan() has checked this product)
-    if (!cx_mul_ok(n, (size_t)ncomp, all) || !cx_mul_ok(all, eb, bytes) || bytes > ((size_t)1 << 62)) {
+    if (!geom_mul_ok(n, (size_t)ncomp, all) || !geom_size_ok(all, eb)) {
         pl.t.ok = 0;
         return pl;
     }
     pl.kv = k;
-    const size_t u = pl.t.vec ? cx_pack(eb) : 1;
+    const size_t u = pl.t.vec ? geom_pack(eb) : 1;
     pl.plane_full = n / u;
     pl.plane_half = outer * pl.t.next * inner / u;
     pl.plane_c = outer * pl.t.row_elems / u;
@@ -59,7 +59,7 @@ FFCX_HD FindPlan find_plan(size_t outer, size_t k, size_t inner, int ncomp, size
 }
 
 // the leaf round: bits (outer, k, inner), k >= 1, kv = k + virt >= 2 positions
-FFCX_HD FindPlan find_leaf_plan(size_t outer, size_t k, size_t inner, int ncomp, int virt, size_t eb, bool aligned) {
+FFG_HD FindPlan find_leaf_plan(size_t outer, size_t k, size_t inner, int ncomp, int virt, size_t eb, bool aligned) {
     FindPlan pl = FindPlan();
     if (k < 1 || (virt != 0 && virt != 1)) return pl;
     pl = find_plan(outer, k + (size_t)virt, inner, ncomp, eb, aligned);
@@ -67,7 +67,7 @@ FFCX_HD FindPlan find_leaf_plan(size_t outer, size_t k, size_t inner, int ncomp,
     pl.virt = virt;
     pl.plane_full = 0;                          // (no stored full level)
     if (outer == 0 || inner == 0) return pl;
-    pl.t.pitch_full = k * inner / (pl.t.vec ? cx_pack(eb) : 1);
+    pl.t.pitch_full = k * inner / (pl.t.vec ? geom_pack(eb) : 1);
     return pl;
 }
 
@@ -81,21 +81,19 @@ struct FindAt {
     int bye;                // this unit also carries a unit of the bye (position 0):
     size_t bye_full, bye_half;      // where it lies in the bits and in a component of the next level
 };
-FFCX_HD FindAt find_leaf_at(const FindPlan& pl, size_t g) {
+FFG_HD FindAt find_leaf_at(const FindPlan& pl, size_t g) {
     const TourPlan& t = pl.t;
-    const size_t o = cx_div(g, t.row_units, t.row_shift, t.narrow);
-    const size_t c = g - o * t.row_units;
-    const size_t b = cx_div(c, t.run, t.run_shift, t.narrow);
+    const PairAt w = pair_split(t, g);
     FindAt at;
     at.c = g;
-    at.first = o * t.pitch_full + t.bye + b * t.run + c;            // b * 2 run + (c - b * run)
-    at.virt2 = pl.virt && b + 1 == t.pairs;
+    at.first = w.o * t.pitch_full + t.bye + w.b * t.run + w.c;      // b * 2 run + (c - b * run)
+    at.virt2 = pl.virt && w.b + 1 == t.pairs;
     at.second = at.virt2 ? at.first : at.first + t.run;
-    at.pos = (pl.kv & 1) + 2 * b;
-    at.half = o * t.pitch_half + t.bye + c;
-    at.bye = c < t.bye;
-    at.bye_full = o * t.pitch_full + c;
-    at.bye_half = o * t.pitch_half + c;
+    at.pos = (pl.kv & 1) + 2 * w.b;
+    at.half = w.o * t.pitch_half + t.bye + w.c;
+    at.bye = w.c < t.bye;
+    at.bye_full = w.o * t.pitch_full + w.c;
+    at.bye_half = w.o * t.pitch_half + w.c;
     return at;
 }
 

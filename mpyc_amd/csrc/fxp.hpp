@@ -26,6 +26,7 @@
 // default policy.  The sub-share rows of the finish and of the apply: share_rows.hpp.
 #pragma once
 #include "fxp_geom.hpp"
+#include "sgn_geom.hpp"
 
 namespace ffgpu {
 
@@ -52,7 +53,7 @@ __device__ __forceinline__ typename F::word trunc_value(const F& f, const typena
 
 template <class F, int K>
 __global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ ar, uint64_t cmask,
-                                                         typename F::word inv, typename F::elem* __restrict__ out, FxpFlatPlan pl) {
+                                                         typename F::word inv, typename F::elem* __restrict__ out, FlatPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
     typedef typename MemPack<F>::type MP;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_trunc_finish(F f, ShareRows<F, K> ra,
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem* __restrict__ bits, typename F::elem* __restrict__ out,
-                                                      typename F::elem* __restrict__ sign_out, FxpNormPlan pl) {
+                                                      typename F::elem* __restrict__ sign_out, RevPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
     typedef typename MemPack<F>::type MP;
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem
     if (pl.vec) {
         MP* ov = reinterpret_cast<MP*>(out);
         for (size_t g = gid; g < pl.total; g += gsz) {
-            FxpNormAt at = fxp_norm_at(pl, g * P::N);
+            RevAt at = rev_at(pl, g * P::N);
             W xb[P::N], xt[P::N];
             size_t sg_at[P::N];
 #pragma unroll
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem
                 xb[q] = ld_elem<F>(bits, at.src);
                 xt[q] = ld_elem<F>(bits, at.top);
                 sg_at[q] = at.j == 0 ? at.h : (size_t)-1;
-                fxp_norm_next(pl, at);
+                rev_next(pl, at);
             }
             P y;
 #pragma unroll
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem
         }
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
-            const FxpNormAt at = fxp_norm_at(pl, g);
+            const RevAt at = rev_at(pl, g);
             const W xb = ld_elem<F>(bits, at.src), xt = ld_elem<F>(bits, at.top);
             const W s = f.sub(f.add(xt, xt), one);
             st_elem<F>(out, g, f.mul(s, xb));
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_prod(F f, const typename F::elem
 
 template <class F, int K>
 __global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, ShareRows<F, K> ra, const typename F::elem* __restrict__ bits,
-                                                       typename F::elem* __restrict__ out, FxpNormPlan pl) {
+                                                       typename F::elem* __restrict__ out, RevPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> P;
     typedef typename MemPack<F>::type MP;
@@ -146,11 +147,11 @@ __global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, ShareRows<F, K> ra, c
                 decltype(ldgw_issue<true>(reinterpret_cast<const MP*>(ra.rows[0]))) rx[K];
 #pragma unroll
                 for (int j = 0; j < K; ++j) rx[j] = ldgw_issue<true>(reinterpret_cast<const MP*>(ra.rows[j]) + g);
-                FxpNormAt at = fxp_norm_at(pl, g * P::N);
+                RevAt at = rev_at(pl, g * P::N);
 #pragma unroll
                 for (int q = 0; q < P::N; ++q) {
                     xt[q] = ld_elem<F>(bits, at.top);
-                    fxp_norm_next(pl, at);
+                    rev_next(pl, at);
                 }
 #pragma unroll
                 for (int j = 0; j < K; ++j) x[j] = ldgw_finish(rx[j]);
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_apply(F f, ShareRows<F, K> ra, c
         }
     } else {
         for (size_t g = gid; g < pl.total; g += gsz) {
-            const FxpNormAt at = fxp_norm_at(pl, g);
+            const RevAt at = rev_at(pl, g);
             const W v = share_rows_elem<F, K>(f, ra, g);
             st_elem<F>(out, g, f.add(f.sub(one, ld_elem<F>(bits, at.top)), v));
         }

@@ -56,7 +56,7 @@ __device__ __forceinline__ typename F::word iszero_mask_value(const F& f, const 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_iszero_mask(F f, const typename F::elem* __restrict__ a, const typename F::elem* __restrict__ r,
                                                         const typename F::elem* __restrict__ z, const typename F::elem* __restrict__ u2, int k,
-                                                        typename F::elem* __restrict__ out, ExplogRowsPlan pl) {
+                                                        typename F::elem* __restrict__ out, RowsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(BLOCK) void k_iszero_mask(F f, const typename F::el
 #pragma unroll
             for (int q = 0; q < PK::N; ++q) ap.w[q] = f.prep(ap.w[q]);
             for (int i = 0; i < k; ++i) {
-                const size_t u = iszero_mask_unit(pl, (size_t)i, g);
+                const size_t u = rows_unit(pl, (size_t)i, g);
                 const auto r0 = ldgw_issue<false>(rv + u), r1 = ldgw_issue<false>(zv + u), r2 = ldgw_issue<false>(uv + u);
                 const PK xr = ldgw_finish(r0), xz = ldgw_finish(r1), xu = ldgw_finish(r2);
                 PK y;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(BLOCK) void k_iszero_mask(F f, const typename F::el
         for (size_t g = gid; g < pl.total; g += gsz) {
             const W ap = f.prep(ld_elem<F>(a, g));
             for (int i = 0; i < k; ++i) {
-                const size_t u = iszero_mask_unit(pl, (size_t)i, g);
+                const size_t u = rows_unit(pl, (size_t)i, g);
                 st_elem<F>(out, u, iszero_mask_value<F>(f, ap, ld_elem<F>(r, u), ld_elem<F>(z, u), ld_elem<F>(u2, u), one));
             }
         }
@@ -130,7 +130,7 @@ __device__ __forceinline__ typename F::word iszero_finish_value(const F& f, unsi
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_iszero_finish(F f, const uint8_t* __restrict__ code, const typename F::elem* __restrict__ z,
-                                                          typename F::elem* __restrict__ out, IszeroFlatPlan pl) {
+                                                          typename F::elem* __restrict__ out, FlatPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;

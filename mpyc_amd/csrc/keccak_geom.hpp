@@ -19,16 +19,7 @@
 // receives depends on (key, nonce, sender, b, position) only.  The counters stay below 2^61 (the ranges above it belong to
 // other kernels, sbox_layer_geom.hpp and rng.hpp), which every nstates that a grid admits does.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFKK_HD __host__ __device__ __forceinline__
-#define FFKK_CX __host__ __device__ constexpr
-#else
-#define FFKK_HD inline
-#define FFKK_CX constexpr
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -41,27 +32,27 @@ enum { KK_MAX_K = 7, KK_MAX_M = 7, KK_MAX_T = 3 };
 // ---- rho, pi ----------------------------------------------------------------------------------------------------
 // rho offset of plane (x, y): the triangular numbers (t + 1)(t + 2) / 2 mod 64 along the walk (x, y) <- (y, 2x + 3y) from
 // (1, 0) (FIPS 202 section 3.2.2; demos/sha3.py:29, 91-95), 0 for (0, 0) -- as the published table, index 5 y + x
-FFKK_CX int kk_rho(int x, int y) {
+FFG_CX int kk_rho(int x, int y) {
     constexpr int R[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
     return R[5 * y + x];
 }
 // pi: plane (x, y) moves to (y, 2x + 3y)
-FFKK_CX int kk_pi_x(int, int y) { return y; }
-FFKK_CX int kk_pi_y(int x, int y) { return (2 * x + 3 * y) % 5; }
+FFG_CX int kk_pi_x(int, int y) { return y; }
+FFG_CX int kk_pi_y(int x, int y) { return (2 * x + 3 * y) % 5; }
 // the inverse, per OUTPUT plane (X, Y) of rho-pi: b[X, Y, z] = a[x, y, z - rho(x, y)] with y = X, x = (X + 3 Y) mod 5
 // (2 x = Y - 3 X, 1 / 2 = 3 mod 5)
-FFKK_CX int kk_src_x(int X, int Y) { return (X + 3 * Y) % 5; }
-FFKK_CX int kk_src_y(int X, int) { return X; }
-FFKK_CX int kk_src_plane(int P) { return 5 * kk_src_y(P % 5, P / 5) + kk_src_x(P % 5, P / 5); }
-FFKK_CX int kk_src_rot(int P) { return kk_rho(kk_src_x(P % 5, P / 5), kk_src_y(P % 5, P / 5)); }
+FFG_CX int kk_src_x(int X, int Y) { return (X + 3 * Y) % 5; }
+FFG_CX int kk_src_y(int X, int) { return X; }
+FFG_CX int kk_src_plane(int P) { return 5 * kk_src_y(P % 5, P / 5) + kk_src_x(P % 5, P / 5); }
+FFG_CX int kk_src_rot(int P) { return kk_rho(kk_src_x(P % 5, P / 5), kk_src_y(P % 5, P / 5)); }
 // a rotation along z by r on the words of a 16-lane group: out(g) = (w(g - q) << 8 c) | (w(g - q - 1) >> 8 (4 - c))
-FFKK_CX int kk_rot_lanes(int r) { return r >> 2; }
-FFKK_CX int kk_rot_bytes(int r) { return r & 3; }
+FFG_CX int kk_rot_lanes(int r) { return r >> 2; }
+FFG_CX int kk_rot_bytes(int r) { return r & 3; }
 
 // ---- iota ---------------------------------------------------------------------------------------------------------
 // bit j of round r: the coefficient of x^0 of x^(7 r + j) mod x^8 + x^6 + x^5 + x^4 + 1 (FIPS 202 algorithm 5;
 // demos/sha3.py:31-33), added at z = 2^j - 1 of plane (0, 0)
-FFKK_CX int kk_rc_bit(int t) {
+FFG_CX int kk_rc_bit(int t) {
     unsigned v = 1;                               // x^0
     for (int i = 0; i < t % 255; ++i) {
         v <<= 1;
@@ -69,9 +60,9 @@ FFKK_CX int kk_rc_bit(int t) {
     }
     return (int)(v & 1u);
 }
-FFKK_CX int kk_iota_bit(int round, int j) { return kk_rc_bit(7 * round + j); }
+FFG_CX int kk_iota_bit(int round, int j) { return kk_rc_bit(7 * round + j); }
 // the round constant as the 64-bit lane word of the standard
-FFKK_CX uint64_t kk_round_constant(int round) {
+FFG_CX uint64_t kk_round_constant(int round) {
     uint64_t rc = 0;
     for (int j = 0; j < 7; ++j)
         if (kk_iota_bit(round, j)) rc |= 1ull << ((1 << j) - 1);
@@ -80,25 +71,25 @@ FFKK_CX uint64_t kk_round_constant(int round) {
 struct KkRoundConstants {
     uint64_t rc[KK_ROUNDS];
 };
-FFKK_CX KkRoundConstants kk_round_constants() {
+FFG_CX KkRoundConstants kk_round_constants() {
     KkRoundConstants t = KkRoundConstants();
     for (int r = 0; r < KK_ROUNDS; ++r) t.rc[r] = kk_round_constant(r);
     return t;
 }
 // the SWAR word lane group g adds to plane 0: the field's 1 in byte i where bit 4 g + i of the round constant is set
-FFKK_HD uint32_t kk_iota_word(uint64_t rc, int g) {
+FFG_HD uint32_t kk_iota_word(uint64_t rc, int g) {
     const uint32_t nib = (uint32_t)(rc >> (4 * g)) & 0xfu;
     return (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
 }
 
 // ---- threads and keystream ---------------------------------------------------------------------------------------
-FFKK_CX int kk_nblk(int t) { return (KK_PLANES * t + 15) / 16; }              // keystream blocks of a thread: 2, 4, 5
-FFKK_HD uint64_t kk_state_of(uint64_t block, int thread) { return block * KK_STATES_PER_WG + (uint64_t)(thread / KK_LANES_PER_STATE); }
-FFKK_HD int kk_group_of(int thread) { return thread % KK_LANES_PER_STATE; }
+FFG_CX int kk_nblk(int t) { return (KK_PLANES * t + 15) / 16; }              // keystream blocks of a thread: 2, 4, 5
+FFG_HD uint64_t kk_state_of(uint64_t block, int thread) { return block * KK_STATES_PER_WG + (uint64_t)(thread / KK_LANES_PER_STATE); }
+FFG_HD int kk_group_of(int thread) { return thread % KK_LANES_PER_STATE; }
 // first keystream block of the thread of (state, lane group)
-FFKK_HD uint64_t kk_ctr(uint64_t state, int group, int nblk) { return (state * KK_LANES_PER_STATE + (uint64_t)group) * (uint64_t)nblk; }
+FFG_HD uint64_t kk_ctr(uint64_t state, int group, int nblk) { return (state * KK_LANES_PER_STATE + (uint64_t)group) * (uint64_t)nblk; }
 // byte offset of the thread's word of plane p within a row
-FFKK_HD size_t kk_offset(uint64_t state, int plane, int group) {
+FFG_HD size_t kk_offset(uint64_t state, int plane, int group) {
     return (size_t)state * KK_STATE_BYTES + (size_t)(64 * plane + 4 * group);
 }
 
@@ -110,7 +101,7 @@ struct KkPlan {
     unsigned grid;       // workgroups per sender
     int tail_states;     // states of the last workgroup (1..16)
 };
-FFKK_HD KkPlan kk_plan(size_t nstates) {
+FFG_HD KkPlan kk_plan(size_t nstates) {
     KkPlan pl = KkPlan();
     const uint64_t want = ((uint64_t)nstates + KK_STATES_PER_WG - 1) / KK_STATES_PER_WG;
     pl.ok = nstates >= 1 && want <= KK_MAX_GRID &&
@@ -120,7 +111,7 @@ FFKK_HD KkPlan kk_plan(size_t nstates) {
     return pl;
 }
 // the (m, t) the round kernel is built for: no re-sharing for one party, and the pairs of the S-box layer
-FFKK_CX bool kk_pair_ok(int m, int t) {
+FFG_CX bool kk_pair_ok(int m, int t) {
     return (m == 1 && t == 0) || (t >= 1 && t <= KK_MAX_T && m >= 2 * t + 1 && m <= KK_MAX_M);
 }
 

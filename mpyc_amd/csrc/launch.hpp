@@ -203,13 +203,11 @@ struct Launchers {
     // dwordx3 needs dword alignment only; three-limb (24-byte) elements are moved by the WAVE as dwordx4 (kernels.hpp, ldgw)
     enum { PACK_ALIGN = sizeof(E) == 12 ? 4 : 16 };
     static bool al(const void* p) { return ((uintptr_t)p & (PACK_ALIGN - 1)) == 0; }
-    // packs that go through the vector loop of a kernel (the rest: its scalar tail).  24-byte elements: whole waves only --
-    // in `for (i = gid; i < nvec; i += gsz)` every wave is then entirely in or entirely out, which ldgw / stgw rely on
-    static size_t nvec_of(size_t n, bool vec) {
-        if (!vec) return 0;
-        if (sizeof(E) == 24) return n & ~(size_t)63;
-        return n / EPV;
-    }
+    static_assert(geom_pack(sizeof(E)) == (unsigned)EPV, "geom.hpp counts this field's pack");
+    static_assert(geom_align(sizeof(E)) == (unsigned)PACK_ALIGN, "geom.hpp states this field's pack alignment");
+    // packs that go through the vector loop of a kernel (the rest: its scalar tail): the rule of geom.hpp, 24-byte elements in
+    // whole waves only
+    static size_t nvec_of(size_t n, bool vec) { return stream_nvec(n, sizeof(E), vec); }
     // The streaming plan of a launch: nvec packs through the vector loop, one pack per thread up to the grid cap (one element
     // per thread when the operands do not allow packs).  The one place where nvec_of and grid_for meet: every launcher takes
     // its nvec from here, so 24-byte fields get whole waves whatever grid it then picks.

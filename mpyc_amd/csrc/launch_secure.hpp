@@ -54,7 +54,7 @@ struct SecureOps {
     LaunchStatus (*find_prod)(const void* F, const LaunchCfg& lc, const void* level, void* out, size_t outer, size_t k, size_t inner,
                      int ncomp, hipStream_t st);
     // local steps of fixed-point truncation and normalisation (fxp.hpp); consts of trunc_mask: the host scalars 2^f and
-    // offset, of trunc_finish: 2^-f (L_PLAN_REFUSED: sgn_plan() / fxp_flat_plan() / fxp_norm_plan() refuses the sizes;
+    // offset, of trunc_finish: 2^-f (L_PLAN_REFUSED: sgn_plan() / flat_plan() / fxp_norm_plan() refuses the sizes;
     // L_NOT_SUPPORTED: fewer than one or more than MAXK rows)
     LaunchStatus (*trunc_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* rbits, const void* rdivf, int f,
                       const uint64_t* consts, void* ar, void* masked, size_t n, hipStream_t st);
@@ -65,7 +65,7 @@ struct SecureOps {
     LaunchStatus (*norm_apply)(const void* F, const LaunchCfg& lc, const void* bits, const void* const* rows, const uint64_t* lam2,
                       int nrows, int l, void* out, size_t n, hipStream_t st);
     // local steps under the secure logarithm and exponential (explog.hpp); c0 of poly_dot: one host scalar; pbits of
-    // pow_base: the bit length of the modulus (L_PLAN_REFUSED: explog_rows_plan() / pow_base_plan() / explog_rev_plan()
+    // pow_base: the bit length of the modulus (L_PLAN_REFUSED: rows_plan() / pow_base_plan() / explog_rev_plan()
     // refuses the sizes or the counts)
     LaunchStatus (*powers_prod)(const void* F, const LaunchCfg& lc, const void* P, size_t stride, int h, int w, void* out, size_t n,
                        hipStream_t st);
@@ -75,7 +75,7 @@ struct SecureOps {
                     size_t n, hipStream_t st);
     LaunchStatus (*bits_reverse)(const void* F, const LaunchCfg& lc, const void* bits, int l, void* out, size_t n, hipStream_t st);
     // local steps of the Legendre zero test (iszero.hpp); the (k, n) arrays are row-major; ex of legendre_code: the exponent
-    // (p - 1) / 2 as ffgpu_pow hands it to pow (L_PLAN_REFUSED: iszero_mask_plan() / legendre_plan() / iszero_flat_plan()
+    // (p - 1) / 2 as ffgpu_pow hands it to pow (L_PLAN_REFUSED: iszero_mask_plan() / stream_plan() / flat_plan()
     // refuses the sizes or the count)
     LaunchStatus (*iszero_mask)(const void* F, const LaunchCfg& lc, const void* a, const void* r, const void* z, const void* u2, int k,
                        void* out, size_t n, hipStream_t st);
@@ -201,8 +201,6 @@ struct SecureLaunchers : Launchers<F> {
         return launched();
     }
     // The two ends of a compare-exchange stage (sort.hpp): one flat streaming loop over the compact pair array.
-    static_assert(cx_pack(sizeof(E)) == (unsigned)EPV, "sort_geom.hpp counts this field's pack");
-    static_assert(cx_align(sizeof(E)) == (unsigned)PACK_ALIGN, "sort_geom.hpp states this field's pack alignment");
     static LaunchStatus cx_diff(const void* Fp, const LaunchCfg& lc, const void* a, void* out, size_t outer, size_t k, size_t inner,
                        size_t p, size_t d, size_t r, hipStream_t st) {
         const F& f = policy(Fp);
@@ -255,7 +253,7 @@ struct SecureLaunchers : Launchers<F> {
         });
     }
     static size_t bits_max_blocks(const LaunchCfg& lc) {
-        return lc.blocks_per_cu > 0 ? (size_t)lc.blocks_per_cu * (size_t)lc.num_cu : (size_t)CX_MAX_GRID;
+        return lc.blocks_per_cu > 0 ? (size_t)lc.blocks_per_cu * (size_t)lc.num_cu : (size_t)GEOM_MAX_GRID;
     }
     static LaunchStatus carry_prod(const void* Fp, const LaunchCfg& lc, const void* g, const void* p, int l, const BitsLevel& lv,
                           void* out, size_t n, hipStream_t st) {
@@ -382,7 +380,7 @@ struct SecureLaunchers : Launchers<F> {
                                 const uint64_t* consts, E* out, size_t n, hipStream_t st) {
         bool vec = al(ar) && al(out);
         const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
-        const FxpFlatPlan pl = fxp_flat_plan(n, sizeof(E), vec);
+        const FlatPlan pl = flat_plan(n, sizeof(E), vec);
         const uint64_t cmask = fb >= 64 ? ~0ull : (1ull << fb) - 1;         // (no shift by 64)
         hipLaunchKernelGGL((k_trunc_finish<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, ar, cmask,
                            word_at<F>(f, consts, 0), out, pl);
@@ -390,7 +388,7 @@ struct SecureLaunchers : Launchers<F> {
     static LaunchStatus trunc_finish(const void* Fp, const LaunchCfg& lc, const void* const* rows, const uint64_t* lam2, int nrows,
                             const void* ar, int fb, const uint64_t* consts, void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const bool plan_ok = fb >= 1 && fb <= FXP_MAX_BITS && fxp_flat_plan(n, sizeof(E), false).ok;
+        const bool plan_ok = fb >= 1 && fb <= FXP_MAX_BITS && flat_plan(n, sizeof(E), false).ok;
         return launch_rows(nrows, BELOW_ONE_NOT_SUPPORTED, plan_ok, n == 0, [&](auto k_) {
             go_trunc_finish<decltype(k_)::value>(f, lc, rows, lam2, (const E*)ar, fb, consts, (E*)out, n, st);
         });
@@ -398,7 +396,7 @@ struct SecureLaunchers : Launchers<F> {
     static LaunchStatus norm_prod(const void* Fp, const LaunchCfg& lc, const void* bits, int l, void* out, void* sign_out, size_t n,
                          hipStream_t st) {
         const F& f = policy(Fp);
-        const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), al(out));
+        const RevPlan pl = fxp_norm_plan(n, l, sizeof(E), al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_norm_prod<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)bits, (E*)out, (E*)sign_out, pl);
         });
@@ -408,13 +406,13 @@ struct SecureLaunchers : Launchers<F> {
                               E* out, size_t n, hipStream_t st) {
         bool vec = al(out);
         const ShareRows<F, K> ra = stage_rows<K>(f, rows, lam2, &vec);
-        const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), vec);
+        const RevPlan pl = fxp_norm_plan(n, l, sizeof(E), vec);
         hipLaunchKernelGGL((k_norm_apply<F, K>), dim3(grid_for(pl.total, lc)), dim3(BLOCK), 0, st, f, ra, bits, out, pl);
     }
     static LaunchStatus norm_apply(const void* Fp, const LaunchCfg& lc, const void* bits, const void* const* rows, const uint64_t* lam2,
                           int nrows, int l, void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const FxpNormPlan pl = fxp_norm_plan(n, l, sizeof(E), false);
+        const RevPlan pl = fxp_norm_plan(n, l, sizeof(E), false);
         return launch_rows(nrows, BELOW_ONE_NOT_SUPPORTED, pl.ok, pl.total == 0, [&](auto k_) {
             go_norm_apply<decltype(k_)::value>(f, lc, (const E*)bits, rows, lam2, l, (E*)out, n, st);
         });
@@ -425,7 +423,7 @@ struct SecureLaunchers : Launchers<F> {
                            hipStream_t st) {
         const F& f = policy(Fp);
         if (!explog_prod_valid(h, w)) return L_PLAN_REFUSED;
-        const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)h, stride, sizeof(E), al(P) && al(out));
+        const RowsPlan pl = rows_plan(n, (size_t)h, stride, sizeof(E), al(P) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_powers_prod<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)P, h, w, (E*)out, pl, n);
         });
@@ -434,7 +432,7 @@ struct SecureLaunchers : Launchers<F> {
                         const uint64_t* c0, void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
         if (!explog_poly_valid(theta)) return L_PLAN_REFUSED;
-        const ExplogRowsPlan pl = explog_rows_plan(n, (size_t)theta, stride, sizeof(E), al(P) && al(out));
+        const RowsPlan pl = rows_plan(n, (size_t)theta, stride, sizeof(E), al(P) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_poly_dot<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)P, theta, (const E*)tab,
                                word_at<F>(f, c0, 0), (E*)out, pl);
@@ -452,20 +450,20 @@ struct SecureLaunchers : Launchers<F> {
     }
     static LaunchStatus bits_reverse(const void* Fp, const LaunchCfg& lc, const void* bits, int l, void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const FxpNormPlan pl = explog_rev_plan(n, l, sizeof(E), al(out));
+        const RevPlan pl = explog_rev_plan(n, l, sizeof(E), al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_bits_reverse<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)bits, (E*)out, pl);
         });
     }
     // The local steps of the Legendre zero test (iszero.hpp).  mask and finish: one flat streaming loop; whole packs also need
     // the code bytes aligned to the one access that moves a pack's codes.  legendre_code is the launch of pow with a byte
-    // array for an output: the same packs through the vector loop and the same grid (legendre_plan restates plan():
-    // tests/iszero_check.cpp); its pl.threads is 0 for count == 0 only.
+    // array for an output: the same packs through the vector loop and the same grid (stream_plan takes its nvec where plan()
+    // does: stream_nvec, geom.hpp); its pl.threads is 0 for count == 0 only.
     static bool codes_al(const void* code) { return iszero_codes_aligned((uintptr_t)code, sizeof(E)); }
     static LaunchStatus iszero_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* r, const void* z, const void* u2, int k,
                            void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const ExplogRowsPlan pl = iszero_mask_plan(n, k, sizeof(E), al(a) && al(r) && al(z) && al(u2) && al(out));
+        const RowsPlan pl = iszero_mask_plan(n, k, sizeof(E), al(a) && al(r) && al(z) && al(u2) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_iszero_mask<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)a, (const E*)r, (const E*)z,
                                (const E*)u2, k, (E*)out, pl);
@@ -474,7 +472,7 @@ struct SecureLaunchers : Launchers<F> {
     static LaunchStatus legendre_code(const void* Fp, const LaunchCfg& lc, const void* c, const ExpArgs* ex, uint8_t* code, size_t count,
                              hipStream_t st) {
         const F& f = policy(Fp);
-        const LegendrePlan pl = legendre_plan(count, sizeof(E), al(c) && codes_al(code));
+        const StreamPlan pl = stream_plan(count, sizeof(E), al(c) && codes_al(code));
         return flat(pl.ok, pl.threads, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_legendre_code<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, code, pl.nvec, count);
         });
@@ -482,13 +480,13 @@ struct SecureLaunchers : Launchers<F> {
     static LaunchStatus iszero_finish(const void* Fp, const LaunchCfg& lc, const uint8_t* code, const void* z, void* out, size_t count,
                              hipStream_t st) {
         const F& f = policy(Fp);
-        const IszeroFlatPlan pl = iszero_flat_plan(count, sizeof(E), al(z) && al(out) && codes_al(code));
+        const FlatPlan pl = flat_plan(count, sizeof(E), al(z) && al(out) && codes_al(code));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_iszero_finish<F>), dim3(grid), dim3(BLOCK), 0, st, f, code, (const E*)z, (E*)out, pl);
         });
     }
     // The local steps of secure random bits (rbits.hpp): the plan, grid and launch bounds of pow (rbits_open_plan /
-    // rbits_finish_plan restate plan(): tests/rbits_check.cpp).  The opening keeps whole packs for up to rbits_fused_rows()
+    // rbits_finish_plan are stream_plan: tests/rbits_check.cpp).  The opening keeps whole packs for up to rbits_fused_rows()
     // rows, with the row count a template parameter as in recombine; more rows (up to MAXK_ANY) go by elements.
     template <int K>
     static void go_rbits_open(const F& f, const LaunchCfg& lc, const void* const* r, const void* const* z, const uint64_t* lam2, E* out,
@@ -501,16 +499,16 @@ struct SecureLaunchers : Launchers<F> {
             ra.lam[j] = f.prep(word_at<F>(f, lam2, (size_t)j));
             vec = vec && al(r[j]) && al(z[j]);
         }
-        const RbitsPlan pl = rbits_open_plan(n, K, sizeof(E), vec);
+        const StreamPlan pl = rbits_open_plan(n, K, sizeof(E), vec);
         hipLaunchKernelGGL((k_rbits_open<F, K>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, ra, out, zeros, pl.nvec, n);
     }
     static LaunchStatus rbits_open(const void* Fp, const LaunchCfg& lc, const void* const* r, const void* const* z, const uint64_t* lam2,
                           int k, void* out, int* zeros, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const RbitsPlan pl = rbits_open_plan(n, k, sizeof(E), false);
+        const StreamPlan pl = rbits_open_plan(n, k, sizeof(E), false);
         if (!pl.ok) return L_PLAN_REFUSED;
         if (n == 0) return L_OK;
-        if (!pl.fused) {
+        if (k > rbits_fused_rows(sizeof(E))) {
             static_assert(sizeof(RbitsOpenArgsAny<F>) + sizeof(F) + 64 <= 4096, "kernel arguments");
             RbitsOpenArgsAny<F> ra;
             for (int j = 0; j < MAXK_ANY; ++j) {
@@ -543,7 +541,7 @@ struct SecureLaunchers : Launchers<F> {
         fa.A = word_at<F>(f, A2, 0);
         fa.B = word_at<F>(f, B2, 0);
         fa.m = m;
-        const RbitsPlan pl = rbits_finish_plan(n, m, sizeof(E), vec);
+        const StreamPlan pl = rbits_finish_plan(n, m, sizeof(E), vec);
         if (!pl.ok) return L_PLAN_REFUSED;
         if (n == 0) return L_OK;
         hipLaunchKernelGGL((k_rbits_finish<F>), dim3(grid_for(pl.threads, lc)), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, n);
@@ -551,12 +549,12 @@ struct SecureLaunchers : Launchers<F> {
     }
     // The local steps of the secure binary sign (bsgn.hpp).  mask: one flat streaming loop over the units of a row, the
     // launch of iszero_mask.  finish in rows mode: the launch of pow over the w n opened values, as legendre_code and
-    // rbits_finish (bsgn_flat_plan is legendre_plan); in sum mode: a flat loop over the units of a row, bound by the w
+    // rbits_finish (bsgn_flat_plan is stream_plan over w n); in sum mode: a flat loop over the units of a row, bound by the w
     // exponentiations of a unit.
     static LaunchStatus bsgn_mask(const void* Fp, const LaunchCfg& lc, const void* a, const void* z, const uint64_t* alpha2,
                          const uint64_t* beta2, int w, void* out, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        const ExplogRowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), al(a) && al(z) && al(out));
+        const RowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), al(a) && al(z) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             BsgnMaskArgs<F> ma;
             ma.alpha = word_at<F>(f, alpha2, 0);
@@ -567,7 +565,7 @@ struct SecureLaunchers : Launchers<F> {
     static LaunchStatus bsgn_finish(const void* Fp, const LaunchCfg& lc, const void* c, const ExpArgs* ex, const void* const* s,
                            void* const* out, int m, int w, int sum, size_t n, hipStream_t st) {
         const F& f = policy(Fp);
-        static_assert(sizeof(BsgnFinishArgs<F>) + sizeof(F) + sizeof(ExpArgs) + sizeof(ExplogRowsPlan) + 64 <= 4096, "kernel arguments");
+        static_assert(sizeof(BsgnFinishArgs<F>) + sizeof(F) + sizeof(ExpArgs) + sizeof(RowsPlan) + 64 <= 4096, "kernel arguments");
         if (!bsgn_m_valid(m) || !bsgn_w_valid(w)) return L_PLAN_REFUSED;
         BsgnFinishArgs<F> fa;
         bool vec = al(c);
@@ -579,12 +577,12 @@ struct SecureLaunchers : Launchers<F> {
         }
         fa.m = m;
         if (sum) {
-            const ExplogRowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), vec);
+            const RowsPlan pl = bsgn_rows_plan(n, w, sizeof(E), vec);
             return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
                 hipLaunchKernelGGL((k_bsgn_finish_sum<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, w, pl);
             });
         }
-        const LegendrePlan pl = bsgn_flat_plan(n, w, sizeof(E), vec);
+        const StreamPlan pl = bsgn_flat_plan(n, w, sizeof(E), vec);
         return flat(pl.ok, pl.threads, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_bsgn_finish<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)c, *ex, fa, pl.nvec, (size_t)w * n);
         });
@@ -598,7 +596,7 @@ struct SecureLaunchers : Launchers<F> {
         const F& f = policy(Fp);
         size_t xspan;
         if (h < 1 || !unit_x_span(n, xstride, sizeof(E), xspan)) return L_PLAN_REFUSED;
-        const ExplogRowsPlan pl = unit_rows_plan(n, h, sizeof(E), al(U) && al(out));
+        const RowsPlan pl = unit_rows_plan(n, h, sizeof(E), al(U) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_unit_prod<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)x, xstride, (const E*)U, h, (E*)out, pl,
                                unit_x_packs(pl, xstride) && al(x) ? 1 : 0);
@@ -608,7 +606,7 @@ struct SecureLaunchers : Launchers<F> {
                          size_t n, hipStream_t st) {
         const F& f = policy(Fp);
         if (!unit_roll_valid(kbits, K)) return L_PLAN_REFUSED;
-        const ExplogRowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, sizeof(E), al(c) && al(out));
+        const RowsPlan pl = unit_rows_plan(n, (size_t)1 << kbits, sizeof(E), al(c) && al(out));
         return flat(pl.ok, pl.total, lc, [&](unsigned grid) {
             hipLaunchKernelGGL((k_unit_roll<F>), dim3(grid), dim3(BLOCK), 0, st, f, (const E*)U, (const E*)c, unit_mask(kbits), K, (E*)out,
                                pl, n);
@@ -621,7 +619,7 @@ struct SecureLaunchers : Launchers<F> {
         const UnitDotPlan dp = unit_dot_plan(rows, c != nullptr, kbits, tlen, sizeof(E));
         if (!dp.ok) return L_PLAN_REFUSED;
         if (!dp.fits) return L_NOT_SUPPORTED;
-        const ExplogRowsPlan pl = unit_rows_plan(n, rows, sizeof(E), al(U) && al(out) && (!c || al(c)));
+        const RowsPlan pl = unit_rows_plan(n, rows, sizeof(E), al(U) && al(out) && (!c || al(c)));
         return flat(pl.ok, pl.total, lc, [&](unsigned want) {
             const unsigned cap = (unsigned)(lc.num_cu > 0 ? lc.num_cu : 1) * 8u;
             hipLaunchKernelGGL((k_unit_dot<F>), dim3(want < cap ? want : cap), dim3(BLOCK), (unsigned)dp.lds_bytes, st, f, (const E*)U, rows,

@@ -11,14 +11,7 @@
 //           (blockIdx.x: grid.z stops at 65 535 and the batch must not).
 // Neither shape needs scratch memory or a workspace, and any batch is one launch.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFSTACK_HD __host__ __device__ __forceinline__
-#else
-#define FFSTACK_HD inline
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -43,11 +36,11 @@ struct StackPlan {
 };
 
 // LDS bytes of one staged element: its word, or 4 bytes per 28-bit digit for the digit-column policies (lazy_nl > 0)
-FFSTACK_HD int stack_slot_bytes(int word_bytes, int lazy_nl) { return lazy_nl > 0 ? 4 * lazy_nl : word_bytes; }
+FFG_HD int stack_slot_bytes(int word_bytes, int lazy_nl) { return lazy_nl > 0 ? 4 * lazy_nl : word_bytes; }
 
 // elem_bytes: storage of an element (1: the packed-byte fields, >= 12: words of two or three limbs); slot_bytes:
 // stack_slot_bytes of the policy; shared_a / shared_b: the operand has batch stride 0.
-FFSTACK_HD StackPlan stack_plan(size_t M, size_t K, size_t N, size_t batch, int elem_bytes, int num_cu, int slot_bytes,
+FFG_HD StackPlan stack_plan(size_t M, size_t K, size_t N, size_t batch, int elem_bytes, int num_cu, int slot_bytes,
                                 bool shared_a, bool shared_b) {
     StackPlan p = {};
     if (M == 0 || N == 0 || batch == 0 || M >= ((size_t)1 << 30) || N >= ((size_t)1 << 30) || K >= ((size_t)1 << 30) ||
@@ -91,7 +84,7 @@ FFSTACK_HD StackPlan stack_plan(size_t M, size_t K, size_t N, size_t batch, int 
 }
 
 // packed: the output thread t of workgroup wg owns; false: the thread owns none (past the P matrices or the batch)
-FFSTACK_HD bool stack_packed_owner(int P, int M, int N, size_t batch, size_t wg, int t, size_t& b, int& pl, int& i, int& j) {
+FFG_HD bool stack_packed_owner(int P, int M, int N, size_t batch, size_t wg, int t, size_t& b, int& pl, int& i, int& j) {
     const int mn = M * N;
     pl = t / mn;
     const int rem = t - pl * mn;
@@ -102,7 +95,7 @@ FFSTACK_HD bool stack_packed_owner(int P, int M, int N, size_t batch, size_t wg,
 }
 
 // tiled: flat tile index -> matrix and tile origin
-FFSTACK_HD void stack_tile_of(size_t flat, size_t tiles_m, size_t tiles_n, int bm, int bn, size_t& b, int& m0, int& n0) {
+FFG_HD void stack_tile_of(size_t flat, size_t tiles_m, size_t tiles_n, int bm, int bn, size_t& b, int& m0, int& n0) {
     const size_t per = tiles_m * tiles_n;
     b = flat / per;
     const size_t r = flat - b * per;
@@ -112,7 +105,7 @@ FFSTACK_HD void stack_tile_of(size_t flat, size_t tiles_m, size_t tiles_n, int b
 // tiled: thread t of a tile owns rows m0 + t / 16 + 16 u (u < bm / 16) and columns n0 + t % 16 + 16 v (v < bn / 16).
 // A RESTATEMENT for the host walk of what the tile body (matmul_tile_body.hpp) computes inline as ty + 16 i, tx + 16 j: the kernel
 // does not call these two.
-FFSTACK_HD int stack_tile_row(int m0, int t, int u) { return m0 + (t >> 4) + 16 * u; }
-FFSTACK_HD int stack_tile_col(int n0, int t, int v) { return n0 + (t & 15) + 16 * v; }
+FFG_HD int stack_tile_row(int m0, int t, int u) { return m0 + (t >> 4) + 16 * u; }
+FFG_HD int stack_tile_col(int n0, int t, int v) { return n0 + (t & 15) + 16 * v; }
 
 }  // namespace ffgpu

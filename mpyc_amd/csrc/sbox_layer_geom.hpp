@@ -18,16 +18,7 @@
 // The first two lie below 2^61, everything below 2^63 (from where the re-draws of the samplers count, rng.hpp): a shape
 // that would leave a range is refused (ok = 0).
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFSBL_HD __host__ __device__ __forceinline__
-#define FFSBL_CX __host__ __device__ constexpr
-#else
-#define FFSBL_HD inline
-#define FFSBL_CX constexpr
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -40,25 +31,25 @@ static constexpr uint64_t SBL_CTR_RAGGED = 1ull << 61;       // first block of t
 static constexpr uint64_t SBL_CTR_SPARE = 1ull << 62;        // first spare block
 
 // keystream words of a step, and the blocks that hold them
-FFSBL_CX int sbl_step_words(int t, int w) { return 11 * (2 * t + 1) * t * w; }
-FFSBL_CX int sbl_nblk(int t, int w) { return (sbl_step_words(t, w) + 15) / 16; }
+FFG_CX int sbl_step_words(int t, int w) { return 11 * (2 * t + 1) * t * w; }
+FFG_CX int sbl_nblk(int t, int w) { return (sbl_step_words(t, w) + 15) / 16; }
 // the continued stream exists for one word per thread at t = 1: 33 = 2 x 16 + 1 words per step
-FFSBL_CX bool sbl_can_cont(int t, int w) { return t == 1 && w == 1; }
+FFG_CX bool sbl_can_cont(int t, int w) { return t == 1 && w == 1; }
 
 // resident workgroups per compute unit (4 per CU at t = 1, m <= 4: 119-128 VGPRs; 3 for m >= 5; 2-3 per CU for t >= 2)
-FFSBL_CX int sbl_resident_per_cu(int t, int m) { return t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2); }
+FFG_CX int sbl_resident_per_cu(int t, int m) { return t == 1 ? (m <= 4 ? 4 : 3) : (t == 2 ? 3 : 2); }
 
 // what a thread of a grid of gsz threads does with nthreads_full words
-FFSBL_HD uint64_t sbl_nsteps(size_t nthreads_full, size_t gsz) { return (nthreads_full + gsz - 1) / gsz; }   // words of thread 0
-FFSBL_HD uint64_t sbl_bpt(uint64_t steps) { return 2 * steps + 2; }         // blocks of a thread's continued stream
-FFSBL_HD uint64_t sbl_spt(uint64_t steps) { return steps / 16 + 1; }        // its spare blocks
+FFG_HD uint64_t sbl_nsteps(size_t nthreads_full, size_t gsz) { return (nthreads_full + gsz - 1) / gsz; }   // words of thread 0
+FFG_HD uint64_t sbl_bpt(uint64_t steps) { return 2 * steps + 2; }         // blocks of a thread's continued stream
+FFG_HD uint64_t sbl_spt(uint64_t steps) { return steps / 16 + 1; }        // its spare blocks
 // the keystream continues from step to step
-FFSBL_HD bool sbl_cont(int t, int w, uint64_t steps) { return sbl_can_cont(t, w) && steps >= 4; }
+FFG_HD bool sbl_cont(int t, int w, uint64_t steps) { return sbl_can_cont(t, w) && steps >= 4; }
 
 // block counters
-FFSBL_HD uint64_t sbl_ctr_step(size_t i, int nblk) { return (uint64_t)i * nblk; }                  // fresh stream of word i
-FFSBL_HD uint64_t sbl_ctr_thread(size_t g, uint64_t bpt) { return (uint64_t)g * bpt; }             // continued stream of thread g
-FFSBL_HD uint64_t sbl_ctr_spare(size_t g, uint64_t spt, uint64_t j) {                              // spare block of step j
+FFG_HD uint64_t sbl_ctr_step(size_t i, int nblk) { return (uint64_t)i * nblk; }                  // fresh stream of word i
+FFG_HD uint64_t sbl_ctr_thread(size_t g, uint64_t bpt) { return (uint64_t)g * bpt; }             // continued stream of thread g
+FFG_HD uint64_t sbl_ctr_spare(size_t g, uint64_t spt, uint64_t j) {                              // spare block of step j
     return SBL_CTR_SPARE + (uint64_t)g * spt + (j >> 4);
 }
 
@@ -73,7 +64,7 @@ struct SblPlan {
     uint64_t bpt, spt;
 };
 // (m, t) as the launcher dispatches them: 2t + 1 <= m <= 7, 1 <= t <= 3
-FFSBL_HD SblPlan sbl_plan(size_t n, int t, int m, int num_cu) {
+FFG_HD SblPlan sbl_plan(size_t n, int t, int m, int num_cu) {
     SblPlan pl = SblPlan();
     constexpr int W = SBL_W;
     pl.nthreads_full = n / (4 * (size_t)W);

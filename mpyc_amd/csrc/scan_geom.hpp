@@ -16,14 +16,7 @@
 //            apart in memory (strided, uncoalesced: the geometry of few long lines only).
 // The launcher chooses by line count, line length and stride (scan_choose).
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFSCAN_HD __host__ __device__ __forceinline__
-#else
-#define FFSCAN_HD inline
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
@@ -33,15 +26,9 @@ enum { SCAN_MAX_GRID = 0x7fffffff };
 
 // elements a thread of the row geometry holds (by element size in bytes: the arithmetic word is 4 or 8 bytes up to 8-byte
 // elements, 16 or 24 bytes above)
-FFSCAN_HD int scan_items(size_t eb) { return eb <= 8 ? 16 : 8; }
+FFG_HD int scan_items(size_t eb) { return eb <= 8 ? 16 : 8; }
 // elements of one 16-byte pack (one lane's access) in the column geometry; 12-, 16- and 24-byte elements go one per lane
-FFSCAN_HD int scan_epv(size_t eb) { return eb <= 8 ? (int)(16 / eb) : 1; }
-
-// a * b, false on overflow
-FFSCAN_HD bool scan_mul_ok(size_t a, size_t b, size_t& r) {
-    r = a * b;
-    return a == 0 || r / a == b;
-}
+FFG_HD int scan_epv(size_t eb) { return eb <= 8 ? (int)(16 / eb) : 1; }
 
 struct ScanPlan {
     int ok;             // 0: sizes overflow or the grid would be too large -- nothing may be launched
@@ -64,7 +51,7 @@ struct ScanPlan {
 // measured nine times slower than even a thin column walk ((64, 65536) bytes of GF(2^8), profiles/r09_scan.md); row tiles
 // only for few long strided lines.  Contiguous lines (inner == 1): row tiles, except many short lines (a quarter tile at
 // most), which take one thread per line.
-FFSCAN_HD int scan_choose(size_t units, size_t k, size_t inner, size_t tile, int num_cu, int geom_cfg) {
+FFG_HD int scan_choose(size_t units, size_t k, size_t inner, size_t tile, int num_cu, int geom_cfg) {
     if (geom_cfg == SCAN_COLS || geom_cfg == SCAN_ROWS) return geom_cfg;
     const bool fills = units >= (size_t)num_cu * 64;
     if (inner > 1) return fills || k < tile ? SCAN_COLS : SCAN_ROWS;
@@ -73,14 +60,13 @@ FFSCAN_HD int scan_choose(size_t units, size_t k, size_t inner, size_t tile, int
 
 // aligned: every pointer of the call is 16-byte aligned (4-byte for 12-byte elements).  with_initial counts for the
 // output size check only.
-FFSCAN_HD ScanPlan scan_plan(size_t outer, size_t k, size_t inner, size_t eb, bool aligned, int num_cu, int geom_cfg,
+FFG_HD ScanPlan scan_plan(size_t outer, size_t k, size_t inner, size_t eb, bool aligned, int num_cu, int geom_cfg,
                              int tile_threads, int with_initial = 0) {
     ScanPlan p = ScanPlan();
-    size_t n, nout, bytes;
+    size_t n, nout;
     if (k == 0 || outer == 0 || inner == 0 || eb == 0) return p;
-    if (!scan_mul_ok(outer, inner, p.lines) || !scan_mul_ok(p.lines, k, n)) return p;
-    if (k + 1 == 0 || !scan_mul_ok(p.lines, k + (with_initial ? 1 : 0), nout) || !scan_mul_ok(nout, eb, bytes)) return p;
-    if (bytes > ((size_t)1 << 62)) return p;
+    if (!geom_mul_ok(outer, inner, p.lines) || !geom_mul_ok(p.lines, k, n)) return p;
+    if (k + 1 == 0 || !geom_mul_ok(p.lines, k + (with_initial ? 1 : 0), nout) || !geom_bytes_ok(nout, eb)) return p;
     const int epv = scan_epv(eb);
     p.vec = aligned && inner % (size_t)epv == 0;
     p.per = p.vec ? inner / (size_t)epv : inner;
@@ -91,7 +77,7 @@ FFSCAN_HD ScanPlan scan_plan(size_t outer, size_t k, size_t inner, size_t eb, bo
     p.geom = scan_choose(p.units, k, inner, p.tile, num_cu, geom_cfg);
     size_t blocks;
     if (p.geom == SCAN_ROWS) {
-        if (!scan_mul_ok(p.lines, p.ntiles, blocks) || blocks > (size_t)SCAN_MAX_GRID) return p;
+        if (!geom_mul_ok(p.lines, p.ntiles, blocks) || blocks > (size_t)SCAN_MAX_GRID) return p;
         p.ws_elems = p.ntiles > 1 ? blocks : 0;
     } else {
         if ((p.units + SCAN_THREADS - 1) / SCAN_THREADS > (size_t)SCAN_MAX_GRID) return p;
@@ -103,26 +89,26 @@ FFSCAN_HD ScanPlan scan_plan(size_t outer, size_t k, size_t inner, size_t eb, bo
 
 // ---- columns -----------------------------------------------------------------------------------------------------------
 // thread `u` of p.units: its o and its column c (pack or element) within o
-FFSCAN_HD void scan_col_of(size_t u, size_t per, size_t& o, size_t& c) {
+FFG_HD void scan_col_of(size_t u, size_t per, size_t& o, size_t& c) {
     o = u / per;
     c = u % per;
 }
 // index (in packs or elements, whichever `per` counts) of step j of that column in an array with kk entries along the axis
-FFSCAN_HD size_t scan_col_index(size_t o, size_t c, size_t j, size_t kk, size_t per) { return (o * kk + j) * per + c; }
+FFG_HD size_t scan_col_index(size_t o, size_t c, size_t j, size_t kk, size_t per) { return (o * kk + j) * per + c; }
 
 // ---- rows --------------------------------------------------------------------------------------------------------------
 // workgroup b: its line and its tile
-FFSCAN_HD void scan_tile_of(size_t b, size_t ntiles, size_t& line, size_t& t) {
+FFG_HD void scan_tile_of(size_t b, size_t ntiles, size_t& line, size_t& t) {
     line = b / ntiles;
     t = b % ntiles;
 }
 // first element (j = 0) of a line in an array with kk entries along the axis
-FFSCAN_HD size_t scan_line_base(size_t line, size_t kk, size_t inner) { return (line / inner) * kk * inner + line % inner; }
+FFG_HD size_t scan_line_base(size_t line, size_t kk, size_t inner) { return (line / inner) * kk * inner + line % inner; }
 // axis position of item q of thread `tid` in tile t (valid when tid < tt and the result is < k)
-FFSCAN_HD size_t scan_item_j(size_t t, size_t tile, int tid, int items, int q) {
+FFG_HD size_t scan_item_j(size_t t, size_t tile, int tid, int items, int q) {
     return t * tile + (size_t)tid * (size_t)items + (size_t)q;
 }
 // workspace slot of a tile's aggregate / carry-in
-FFSCAN_HD size_t scan_ws_index(size_t line, size_t t, size_t ntiles) { return line * ntiles + t; }
+FFG_HD size_t scan_ws_index(size_t line, size_t t, size_t ntiles) { return line * ntiles + t; }
 
 }  // namespace ffgpu

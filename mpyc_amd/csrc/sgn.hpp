@@ -15,7 +15,7 @@
 
 namespace ffgpu {
 
-static_assert((int)SGN_THREADS == (int)BLOCK && (int)SGN_TILE == (int)BLOCK, "sgn_geom.hpp is laid out for the library's workgroup");
+static_assert((int)GEOM_THREADS == (int)BLOCK && (int)SGN_TILE == (int)BLOCK, "sgn_geom.hpp is laid out for the library's workgroup");
 static_assert((int)SGN_X24_BYTES == (BLOCK / 64) * 96 * 16, "sgn_geom.hpp counts the staging region of ldgw / stgw");
 
 template <class W>

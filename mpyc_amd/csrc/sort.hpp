@@ -21,7 +21,7 @@
 
 namespace ffgpu {
 
-static_assert((int)CX_THREADS == (int)BLOCK, "sort_geom.hpp is laid out for the library's workgroup");
+static_assert((int)GEOM_THREADS == (int)BLOCK && (int)CX_THREADS == (int)BLOCK, "geom.hpp is laid out for the library's workgroup");
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_cx_diff(F f, const typename F::elem* __restrict__ a, typename F::elem* __restrict__ out,

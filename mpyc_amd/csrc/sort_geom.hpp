@@ -12,33 +12,12 @@
 // p * inner contiguous elements.  With c the index of an element of a compact row (c < P * inner), b = c / run and
 // w = c % run, the pair's members are at  b * 2 run + w + r * inner  and  d * inner  further on in the row of `a`.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define FFCX_HD __host__ __device__ __forceinline__
-#define FFCX_CX __host__ __device__ constexpr
-#else
-#define FFCX_HD inline
-#define FFCX_CX constexpr
-#endif
+#include "geom.hpp"
 
 namespace ffgpu {
 
-enum { CX_THREADS = 256 };                  // = BLOCK (kernels.hpp)
-enum { CX_MAX_GRID = 0x7fffffff };
-
-FFCX_HD bool cx_pow2(size_t x) { return x != 0 && (x & (x - 1)) == 0; }
-FFCX_HD int cx_log2(size_t x) {             // x a power of two
-    int s = 0;
-    while ((x >> s) > 1) ++s;
-    return s;
-}
-// a * b, false on overflow
-FFCX_HD bool cx_mul_ok(size_t a, size_t b, size_t& r) {
-    r = a * b;
-    return a == 0 || r / a == b;
-}
+enum { CX_THREADS = 256 };                  // = GEOM_THREADS; tests/test_gpu_rbits.py reads the workgroup size off this line
+static_assert((int)CX_THREADS == (int)GEOM_THREADS, "the compare-exchange kernels run the library's workgroup");
 
 // ---- the stage list: the reference's loop over (p, d, q, r) ------------------------------------------------------------------
 //   t = (k-1).bit_length(); p = 1 << t-1
@@ -48,7 +27,7 @@ FFCX_HD bool cx_mul_ok(size_t a, size_t b, size_t& r) {
 struct CxStageIter {
     size_t p, d, q, r, top;                 // top = 1 << t-1; p == 0: past the last stage
 };
-FFCX_HD CxStageIter cx_stages_begin(size_t k) {
+FFG_HD CxStageIter cx_stages_begin(size_t k) {
     CxStageIter it = CxStageIter();
     if (k < 2) return it;
     size_t top = 1;
@@ -56,8 +35,8 @@ FFCX_HD CxStageIter cx_stages_begin(size_t k) {
     it.p = it.d = it.q = it.top = top;
     return it;
 }
-FFCX_HD bool cx_stages_done(const CxStageIter& it) { return it.p == 0; }
-FFCX_HD void cx_stages_next(CxStageIter& it) {
+FFG_HD bool cx_stages_done(const CxStageIter& it) { return it.p == 0; }
+FFG_HD void cx_stages_next(CxStageIter& it) {
     it.d = it.q - it.p;
     it.q >>= 1;
     it.r = it.p;
@@ -70,17 +49,17 @@ FFCX_HD void cx_stages_next(CxStageIter& it) {
 }
 
 // ---- one stage ---------------------------------------------------------------------------------------------------------------
-FFCX_HD bool cx_stage_valid(size_t k, size_t p, size_t d, size_t r) {
-    if (k < 2 || !cx_pow2(p)) return false;
+FFG_HD bool cx_stage_valid(size_t k, size_t p, size_t d, size_t r) {
+    if (k < 2 || !geom_pow2(p)) return false;
     if (r == 0) return d == p;
     if (r != p) return false;
     const size_t q = d + p;
-    return q > d && q > p && cx_pow2(q);    // (q > d: no wrap-around)
+    return q > d && q > p && geom_pow2(q);    // (q > d: no wrap-around)
 }
 // pairs of the stage; 0 for an invalid stage
-FFCX_HD size_t cx_pairs(size_t k, size_t p, size_t d, size_t r) {
+FFG_HD size_t cx_pairs(size_t k, size_t p, size_t d, size_t r) {
     if (!cx_stage_valid(k, p, d, r) || d >= k || p >= k) return 0;
-    const int lg = cx_log2(p);
+    const int lg = geom_log2(p);
     const size_t m = k - d;
     const size_t full = (m >> lg) >> 1;                      // m / 2p
     const size_t rem = m - ((full << lg) << 1);              // m % 2p
@@ -88,21 +67,13 @@ FFCX_HD size_t cx_pairs(size_t k, size_t p, size_t d, size_t r) {
     return (full << lg) + tail;
 }
 // the j-th member of I (lg = log2 p)
-FFCX_HD size_t cx_index_lg(size_t j, int lg, size_t r) { return ((j >> lg) << (lg + 1)) + (j & (((size_t)1 << lg) - 1)) + r; }
-FFCX_HD size_t cx_index(size_t j, size_t p, size_t r) { return cx_index_lg(j, cx_log2(p), r); }
+FFG_HD size_t cx_index_lg(size_t j, int lg, size_t r) { return ((j >> lg) << (lg + 1)) + (j & (((size_t)1 << lg) - 1)) + r; }
+FFG_HD size_t cx_index(size_t j, size_t p, size_t r) { return cx_index_lg(j, geom_log2(p), r); }
 
 // ---- the plan of a launch ------------------------------------------------------------------------------------------------------
-// What one lane moves per access (elements), what a run, a compact row and the byte pitch of a row of `a` must be multiples
-// of for whole packs to apply, per element size (bytes): 4 -> four elements in 16 bytes, 8 -> two, 12 -> one (dwordx3,
-// dword aligned), 16 -> one, 24 -> one per lane, but the WAVE moves its 64 elements as one 16-byte aligned span
-// (kernels.hpp, ldgw / stgw): runs and compact rows of whole waves.
-FFCX_CX unsigned cx_pack(size_t eb) { return eb == 4 ? 4u : eb == 8 ? 2u : 1u; }
-FFCX_CX unsigned cx_gran(size_t eb) { return eb == 24 ? 64u : cx_pack(eb); }
-FFCX_CX unsigned cx_align(size_t eb) { return eb == 12 ? 4u : 16u; }
-
-// Everything below `vec` counts UNITS: packs of cx_pack(eb) elements when vec, single elements otherwise.  The kernels run
-// one flat loop over outer * row_units units, g -> (o, c) = (g / row_units, g % row_units), c -> (b, w) = (c / run, c % run);
-// a shift replaces a division wherever the divisor is a power of two (always, for run, when inner is one).
+// Everything below `vec` counts UNITS: packs of geom_pack(eb) elements when vec, single elements otherwise.  Whole packs apply
+// when a run, a compact row and the byte pitch of a row of `a` are whole numbers of geom_gran(eb) elements / geom_align(eb)
+// bytes and the pointers are aligned.  The flat loop is the pair walk of geom.hpp (always a shift, for run, when inner is one).
 struct CxPlan {
     int ok;                 // 0: invalid stage, sizes overflow -- nothing may be launched
     size_t pairs;           // P
@@ -116,46 +87,34 @@ struct CxPlan {
     int run_shift, row_shift;   // log2 of run / row_units when a power of two, else -1
     int narrow;             // every flat index and divisor fits 32 bits
 };
-FFCX_HD CxPlan cx_plan(size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, size_t eb, bool aligned) {
+FFG_HD CxPlan cx_plan(size_t outer, size_t k, size_t inner, size_t p, size_t d, size_t r, size_t eb, bool aligned) {
     CxPlan pl = CxPlan();
-    size_t rowa, n, bytes;
-    if (!cx_stage_valid(k, p, d, r) || eb < 4 || eb % 4) return pl;
-    if (!cx_mul_ok(k, inner, rowa) || !cx_mul_ok(outer, rowa, n) || !cx_mul_ok(n, eb, bytes) || bytes > ((size_t)1 << 62)) return pl;
+    size_t rowa, n;
+    if (!cx_stage_valid(k, p, d, r)) return pl;
+    if (!geom_mul_ok(k, inner, rowa) || !geom_mul_ok(outer, rowa, n) || !geom_size_ok(n, eb)) return pl;
     pl.ok = 1;
     pl.pairs = cx_pairs(k, p, d, r);
     pl.row_elems = pl.pairs * inner;        // (P <= k / 2 and d < k when P > 0: the products below stay under n)
     if (pl.pairs == 0 || outer == 0 || inner == 0) return pl;
     const size_t run = p * inner;
-    const unsigned g = cx_gran(eb);
-    pl.vec = aligned && run % g == 0 && pl.row_elems % g == 0 && (rowa * eb) % cx_align(eb) == 0;
-    const size_t u = pl.vec ? cx_pack(eb) : 1;
-    pl.row_units = pl.row_elems / u;
-    pl.run = run / u;
+    const unsigned g = geom_gran(eb);
+    pl.vec = aligned && run % g == 0 && pl.row_elems % g == 0 && (rowa * eb) % geom_align(eb) == 0;
+    const size_t u = pl.vec ? geom_pack(eb) : 1;
+    pair_fill(pl, outer, pl.row_elems, run, u);
     pl.pitch = rowa / u;
     pl.off_r = r * inner / u;
     pl.off_d = d * inner / u;
-    pl.total = outer * pl.row_units;
-    pl.run_shift = cx_pow2(pl.run) ? cx_log2(pl.run) : -1;
-    pl.row_shift = cx_pow2(pl.row_units) ? cx_log2(pl.row_units) : -1;
-    pl.narrow = pl.total <= 0xffffffffu && pl.run <= 0xffffffffu;
     return pl;
 }
 
-// ---- what a lane does with flat unit g (the kernels call exactly these) ------------------------------------------------------------
-FFCX_HD size_t cx_div(size_t x, size_t y, int shift, int narrow) {
-    if (shift >= 0) return x >> shift;
-    if (narrow) return (size_t)((uint32_t)x / (uint32_t)y);
-    return x / y;
-}
+// ---- what a lane does with flat unit g (the kernels call exactly this) ---------------------------------------------------------------
 struct CxAt {
     size_t lo, hi, c;       // units: first and second member in `a`, and the unit of the compact array
 };
-FFCX_HD CxAt cx_at(const CxPlan& pl, size_t g) {
-    const size_t o = cx_div(g, pl.row_units, pl.row_shift, pl.narrow);
-    const size_t c = g - o * pl.row_units;
-    const size_t b = cx_div(c, pl.run, pl.run_shift, pl.narrow);
+FFG_HD CxAt cx_at(const CxPlan& pl, size_t g) {
+    const PairAt w = pair_split(pl, g);
     CxAt at;
-    at.lo = o * pl.pitch + b * pl.run + c + pl.off_r;      // b * 2 run + (c - b * run)
+    at.lo = w.o * pl.pitch + w.b * pl.run + w.c + pl.off_r;        // b * 2 run + (c - b * run)
     at.hi = at.lo + pl.off_d;
     at.c = g;
     return at;

@@ -17,23 +17,23 @@
 //   half level     o * kc * inner + n0 * inner + c
 // and the bye's `inner` elements at the start of a row go with the first `inner` compact elements of that row.
 #pragma once
-#include "sort_geom.hpp"
+#include "geom.hpp"
 
 namespace ffgpu {
 
 enum { TOUR_HALVES = 0, TOUR_ODD_EVEN = 1 };        // = FFGPU_TOUR_HALVES / FFGPU_TOUR_ODD_EVEN (include/ffgpu.h)
 
-FFCX_HD bool tour_mode_valid(int mode) { return mode == TOUR_HALVES || mode == TOUR_ODD_EVEN; }
-FFCX_HD size_t tour_pairs(size_t k) { return k / 2; }
-FFCX_HD size_t tour_next(size_t k) { return k / 2 + k % 2; }
-FFCX_HD size_t tour_first(size_t k, int mode, size_t j) { return mode == TOUR_HALVES ? k % 2 + j : k % 2 + 2 * j; }
-FFCX_HD size_t tour_second(size_t k, int mode, size_t j) { return mode == TOUR_HALVES ? tour_next(k) + j : k % 2 + 2 * j + 1; }
+FFG_HD bool tour_mode_valid(int mode) { return mode == TOUR_HALVES || mode == TOUR_ODD_EVEN; }
+FFG_HD size_t tour_pairs(size_t k) { return k / 2; }
+FFG_HD size_t tour_next(size_t k) { return k / 2 + k % 2; }
+FFG_HD size_t tour_first(size_t k, int mode, size_t j) { return mode == TOUR_HALVES ? k % 2 + j : k % 2 + 2 * j; }
+FFG_HD size_t tour_second(size_t k, int mode, size_t j) { return mode == TOUR_HALVES ? tour_next(k) + j : k % 2 + 2 * j + 1; }
 
 // ---- the plan of a launch ------------------------------------------------------------------------------------------------------
-// Everything below `vec` counts UNITS: packs of cx_pack(eb) elements when vec, single elements otherwise (sort_geom.hpp).
-// Whole packs apply when a run, a compact row and the bye are multiples of cx_gran(eb) elements (24-byte elements: whole
+// Everything below `vec` counts UNITS: packs of geom_pack(eb) elements when vec, single elements otherwise (geom.hpp).
+// Whole packs apply when a run, a compact row and the bye are multiples of geom_gran(eb) elements (24-byte elements: whole
 // waves) and the pointers are aligned; every row of the three arrays then starts on a pack, and a wave on a wave.  The
-// kernels run one flat loop over outer * row_units units, g -> (o, c) = (g / row_units, g % row_units), c -> b = c / run.
+// flat loop is the pair walk of geom.hpp.
 struct TourPlan {
     int ok;                 // 0: k < 2, unknown mode, sizes overflow -- nothing may be launched
     size_t pairs, next;     // h, kc
@@ -48,11 +48,11 @@ struct TourPlan {
     int run_shift, row_shift;   // log2 of run / row_units when a power of two, else -1
     int narrow;             // every flat index and divisor fits 32 bits
 };
-FFCX_HD TourPlan tour_plan(size_t outer, size_t k, size_t inner, int mode, size_t eb, bool aligned) {
+FFG_HD TourPlan tour_plan(size_t outer, size_t k, size_t inner, int mode, size_t eb, bool aligned) {
     TourPlan pl = TourPlan();
-    size_t rowa, n, bytes;
-    if (k < 2 || !tour_mode_valid(mode) || eb < 4 || eb % 4) return pl;
-    if (!cx_mul_ok(k, inner, rowa) || !cx_mul_ok(outer, rowa, n) || !cx_mul_ok(n, eb, bytes) || bytes > ((size_t)1 << 62)) return pl;
+    size_t rowa, n;
+    if (k < 2 || !tour_mode_valid(mode)) return pl;
+    if (!geom_mul_ok(k, inner, rowa) || !geom_mul_ok(outer, rowa, n) || !geom_size_ok(n, eb)) return pl;
     pl.ok = 1;
     pl.pairs = tour_pairs(k);
     pl.next = tour_next(k);
@@ -60,18 +60,13 @@ FFCX_HD TourPlan tour_plan(size_t outer, size_t k, size_t inner, int mode, size_
     if (outer == 0 || inner == 0) return pl;
     const size_t run = mode == TOUR_HALVES ? pl.row_elems : inner;
     const size_t bye = (k % 2) * inner;
-    const unsigned g = cx_gran(eb);
-    pl.vec = aligned && run % g == 0 && pl.row_elems % g == 0 && bye % g == 0;     // (g * eb is a multiple of cx_align(eb))
-    const size_t u = pl.vec ? cx_pack(eb) : 1;
-    pl.row_units = pl.row_elems / u;
-    pl.run = run / u;
+    const unsigned g = geom_gran(eb);
+    pl.vec = aligned && run % g == 0 && pl.row_elems % g == 0 && bye % g == 0;     // (g * eb is a multiple of geom_align(eb))
+    const size_t u = pl.vec ? geom_pack(eb) : 1;
+    pair_fill(pl, outer, pl.row_elems, run, u);
     pl.pitch_full = rowa / u;
     pl.pitch_half = pl.next * inner / u;
     pl.bye = bye / u;
-    pl.total = outer * pl.row_units;
-    pl.run_shift = cx_pow2(pl.run) ? cx_log2(pl.run) : -1;
-    pl.row_shift = cx_pow2(pl.row_units) ? cx_log2(pl.row_units) : -1;
-    pl.narrow = pl.total <= 0xffffffffu && pl.run <= 0xffffffffu;
     return pl;
 }
 
@@ -83,18 +78,16 @@ struct TourAt {
     int bye;                // this unit also carries a unit of the bye:
     size_t bye_full, bye_half;      // where it lies in the full and in the half level
 };
-FFCX_HD TourAt tour_at(const TourPlan& pl, size_t g) {
-    const size_t o = cx_div(g, pl.row_units, pl.row_shift, pl.narrow);
-    const size_t c = g - o * pl.row_units;
-    const size_t b = cx_div(c, pl.run, pl.run_shift, pl.narrow);
+FFG_HD TourAt tour_at(const TourPlan& pl, size_t g) {
+    const PairAt w = pair_split(pl, g);
     TourAt at;
     at.c = g;
-    at.first = o * pl.pitch_full + pl.bye + b * pl.run + c;         // b * 2 run + (c - b * run)
+    at.first = w.o * pl.pitch_full + pl.bye + w.b * pl.run + w.c;   // b * 2 run + (c - b * run)
     at.second = at.first + pl.run;
-    at.half = o * pl.pitch_half + pl.bye + c;
-    at.bye = c < pl.bye;
-    at.bye_full = o * pl.pitch_full + c;
-    at.bye_half = o * pl.pitch_half + c;
+    at.half = w.o * pl.pitch_half + pl.bye + w.c;
+    at.bye = w.c < pl.bye;
+    at.bye_full = w.o * pl.pitch_full + w.c;
+    at.bye_half = w.o * pl.pitch_half + w.c;
     return at;
 }
 

@@ -47,7 +47,7 @@ enum { UNIT_GROUP = 4 };            // row loads a thread of k_unit_prod / k_uni
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_unit_prod(F f, const typename F::elem* __restrict__ x, size_t xstride,
                                                       const typename F::elem* __restrict__ U, size_t h,
-                                                      typename F::elem* __restrict__ out, ExplogRowsPlan pl, int xvec) {
+                                                      typename F::elem* __restrict__ out, RowsPlan pl, int xvec) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_prod(F f, const typename F::elem
                 decltype(ldgw_issue<false>(uv)) raw[UNIT_GROUP];
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
-                    if (j0 + r < h) raw[r] = ldgw_issue<false>(uv + unit_row_unit(pl, j0 + r, g));
+                    if (j0 + r < h) raw[r] = ldgw_issue<false>(uv + rows_unit(pl, j0 + r, g));
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
                     if (j0 + r < h) {
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_prod(F f, const typename F::elem
                         PK y;
 #pragma unroll
                         for (int q = 0; q < PK::N; ++q) y.w[q] = f.mul(xs.w[q], uj.w[q]);
-                        stgw<false>(ov + unit_row_unit(pl, j0 + r, g), y);
+                        stgw<false>(ov + rows_unit(pl, j0 + r, g), y);
                     }
             }
         }
@@ -90,10 +90,10 @@ __global__ __launch_bounds__(BLOCK) void k_unit_prod(F f, const typename F::elem
                 W uj[UNIT_GROUP];
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
-                    if (j0 + r < h) uj[r] = ld_elem<F>(U, unit_row_unit(pl, j0 + r, g));
+                    if (j0 + r < h) uj[r] = ld_elem<F>(U, rows_unit(pl, j0 + r, g));
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
-                    if (j0 + r < h) st_elem<F>(out, unit_row_unit(pl, j0 + r, g), f.mul(xs, uj[r]));
+                    if (j0 + r < h) st_elem<F>(out, rows_unit(pl, j0 + r, g), f.mul(xs, uj[r]));
             }
         }
     }
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_prod(F f, const typename F::elem
 
 template <class F>
 __global__ __launch_bounds__(BLOCK) void k_unit_roll(F f, const typename F::elem* __restrict__ U, const typename F::elem* __restrict__ c,
-                                                      uint64_t cmask, size_t K, typename F::elem* __restrict__ out, ExplogRowsPlan pl,
+                                                      uint64_t cmask, size_t K, typename F::elem* __restrict__ out, RowsPlan pl,
                                                       size_t n) {
     typedef typename F::word W;
     typedef Pack<W> PK;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_roll(F f, const typename F::elem
                 PK y;
 #pragma unroll
                 for (int q = 0; q < PK::N; ++q) y.w[q] = ld_elem<F>(U, unit_roll_src(j, off[q], cmask) * n + unit_elem(pl, g, (unsigned)q));
-                stgw<false>(ov + unit_row_unit(pl, j, g), y);
+                stgw<false>(ov + rows_unit(pl, j, g), y);
             }
         }
     } else {
@@ -138,7 +138,7 @@ template <class F>
 __global__ __launch_bounds__(BLOCK) void k_unit_dot(F f, const typename F::elem* __restrict__ U, size_t rows,
                                                      const typename F::elem* __restrict__ c, uint64_t cmask,
                                                      const typename F::elem* __restrict__ tab, size_t tlen, size_t entries,
-                                                     typename F::elem* __restrict__ out, ExplogRowsPlan pl) {
+                                                     typename F::elem* __restrict__ out, RowsPlan pl) {
     typedef typename F::word W;
     typedef Pack<W> PK;
     typedef typename MemPack<F>::type MP;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_dot(F f, const typename F::elem*
                 decltype(ldgw_issue<false>(uv)) raw[UNIT_GROUP];
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
-                    if (j0 + r < rows) raw[r] = ldgw_issue<false>(uv + unit_row_unit(pl, j0 + r, g));
+                    if (j0 + r < rows) raw[r] = ldgw_issue<false>(uv + rows_unit(pl, j0 + r, g));
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
                     if (j0 + r < rows) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(BLOCK) void k_unit_dot(F f, const typename F::elem*
                 W uj[UNIT_GROUP];
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
-                    if (j0 + r < rows) uj[r] = ld_elem<F>(U, unit_row_unit(pl, j0 + r, g));
+                    if (j0 + r < rows) uj[r] = ld_elem<F>(U, rows_unit(pl, j0 + r, g));
 #pragma unroll
                 for (int r = 0; r < UNIT_GROUP; ++r)
                     if (j0 + r < rows) {

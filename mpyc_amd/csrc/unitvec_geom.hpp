@@ -4,66 +4,62 @@
 // Plain C++ (no HIP): the kernels, their launcher and the C ABI take every index from here, and tests/unitvec_check.cpp walks
 // the same functions with g++.
 //
-// Unit vectors are POSITION-MAJOR (rows, n): row j holds position j for the n indices, rows n elements apart -- the
-// (outer = 1, k = rows, inner = n) convention of tour_geom.hpp.  All three kernels are flat over the n elements of a row: a
-// thread owns a unit of every row it touches -- a pack of cx_pack(eb) consecutive elements where whole packs apply
-// (explog_rows_plan with stride n: pointers aligned, n a whole number of cx_gran(eb) elements, whole waves for 24-byte
-// elements), a single element otherwise.  Unit g of row j is unit  j * total + g  of the array.
+// Unit vectors are POSITION-MAJOR (rows, n): row j holds position j for the n indices, rows n elements apart.  All three
+// kernels are flat over the n elements of a row: a thread owns a unit of every row it touches, which is the rows plan of
+// geom.hpp with stride n.  Unit g of row j is unit  rows_unit(pl, j, g)  of the array.
 //   * unit_prod: element q of unit g takes x[(g pack + q) xstride]: a pack of x itself when xstride == 1, gathered by
 //     element otherwise (the element-major (n, l) bits of bits_finish: xstride = l);
 //   * unit_roll: out row j < K of element e is source row  (j - c[e]) mod K2,  K2 = 2^kbits;
 //   * unit_dot:  term j < rows of element e takes table entry  (j + c[e]) mod K2;  without c the entry j.
 // c[e] mod K2 is the low kbits bits of the canonical integer: the low limb under the mask K2 - 1 (the high limbs are
-// arbitrary), as the masked opening of fxp_geom.hpp is cut.
+// arbitrary), as the masked opening of the truncation (fxp.hpp) is cut.
 //
 // The table of unit_dot lives in dynamically sized LDS, one prepared WORD per entry (4, 8, 16, 16, 24 bytes for elements of
 // 4, 8, 12, 16, 24 bytes), zero from tlen up; 64 KiB at the most: kbits <= 14, 13, 12, 12, 11.
 #pragma once
-#include "bsgn_geom.hpp"
+#include "geom.hpp"
 
 namespace ffgpu {
 
 enum { UNIT_MAX_KBITS = 30 };               // of a rotation: K2 = 2^kbits rows
 enum { UNIT_LDS_BYTES = 65536 };            // the table of unit_dot
 
-FFCX_HD bool unit_kbits_valid(int kbits) { return kbits >= 0 && kbits <= UNIT_MAX_KBITS; }
-FFCX_HD uint64_t unit_mask(int kbits) { return ((uint64_t)1 << kbits) - 1; }
+FFG_HD bool unit_kbits_valid(int kbits) { return kbits >= 0 && kbits <= UNIT_MAX_KBITS; }
+FFG_HD uint64_t unit_mask(int kbits) { return ((uint64_t)1 << kbits) - 1; }
 
 // ---- the rows plan of all three: `rows` dense rows of n elements; pl.span == rows * n --------------------------------------
-FFCX_HD ExplogRowsPlan unit_rows_plan(size_t n, size_t rows, size_t eb, bool aligned) {
-    return explog_rows_plan(n, rows, n, eb, aligned);
+FFG_HD RowsPlan unit_rows_plan(size_t n, size_t rows, size_t eb, bool aligned) {
+    return rows_plan(n, rows, n, eb, aligned);
 }
-// unit g of row j, in units of a (rows, n) array
-FFCX_HD size_t unit_row_unit(const ExplogRowsPlan& pl, size_t j, size_t g) { return explog_row_unit(pl, j, g); }
 // element q of unit g, as an element of its row
-FFCX_HD size_t unit_elem(const ExplogRowsPlan& pl, size_t g, unsigned q) { return g * pl.pack + q; }
+FFG_HD size_t unit_elem(const RowsPlan& pl, size_t g, unsigned q) { return g * pl.pack + q; }
 
 // ---- unit_prod: where the factor of element e sits in x; the elements x spans ----------------------------------------------
-FFCX_HD size_t unit_x_at(size_t e, size_t xstride) { return e * xstride; }
-FFCX_HD bool unit_x_span(size_t n, size_t xstride, size_t eb, size_t& span) {
-    size_t above, bytes;
+FFG_HD size_t unit_x_at(size_t e, size_t xstride) { return e * xstride; }
+FFG_HD bool unit_x_span(size_t n, size_t xstride, size_t eb, size_t& span) {
+    size_t above;
     span = 0;
     if (xstride < 1) return false;
     if (n == 0) return true;
-    if (!cx_mul_ok(n - 1, xstride, above) || above + 1 < above) return false;
+    if (!geom_mul_ok(n - 1, xstride, above) || above + 1 < above) return false;
     span = above + 1;
-    return cx_mul_ok(span, eb, bytes) && bytes <= ((size_t)1 << 62);
+    return geom_bytes_ok(span, eb);
 }
 // a pack of x serves a unit as it is: consecutive factors (and x aligned, which the launcher knows)
-FFCX_HD bool unit_x_packs(const ExplogRowsPlan& pl, size_t xstride) { return pl.vec && xstride == 1; }
+FFG_HD bool unit_x_packs(const RowsPlan& pl, size_t xstride) { return pl.vec && xstride == 1; }
 
 // ---- unit_roll / unit_dot: the rotation ---------------------------------------------------------------------------------------
 // the offset of an element from the low limb of its canonical opened value
-FFCX_HD size_t unit_offset(uint64_t low_limb, uint64_t mask) { return (size_t)(low_limb & mask); }
+FFG_HD size_t unit_offset(uint64_t low_limb, uint64_t mask) { return (size_t)(low_limb & mask); }
 // source row of out row j:  (j - off) mod K2,  off <= mask = K2 - 1
-FFCX_HD size_t unit_roll_src(size_t j, size_t off, uint64_t mask) { return (j + ((size_t)mask + 1 - off)) & (size_t)mask; }
+FFG_HD size_t unit_roll_src(size_t j, size_t off, uint64_t mask) { return (j + ((size_t)mask + 1 - off)) & (size_t)mask; }
 // table entry of term j:  (j + off) mod K2;  without a rotation off == 0 and mask == ~0
-FFCX_HD size_t unit_dot_tab(size_t j, size_t off, uint64_t mask) { return (j + off) & (size_t)mask; }
-FFCX_HD bool unit_roll_valid(int kbits, size_t K) { return unit_kbits_valid(kbits) && K >= 1 && K <= ((size_t)1 << kbits); }
+FFG_HD size_t unit_dot_tab(size_t j, size_t off, uint64_t mask) { return (j + off) & (size_t)mask; }
+FFG_HD bool unit_roll_valid(int kbits, size_t K) { return unit_kbits_valid(kbits) && K >= 1 && K <= ((size_t)1 << kbits); }
 
 // ---- unit_dot: the table in LDS ---------------------------------------------------------------------------------------------------
-FFCX_CX size_t unit_word_bytes(size_t eb) { return eb == 4 ? 4u : eb == 8 ? 8u : eb == 24 ? 24u : 16u; }
-FFCX_CX int unit_dot_max_kbits(size_t eb) {
+FFG_CX size_t unit_word_bytes(size_t eb) { return eb == 4 ? 4u : eb == 8 ? 8u : eb == 24 ? 24u : 16u; }
+FFG_CX int unit_dot_max_kbits(size_t eb) {
     int k = 0;
     while (((size_t)2 << k) * unit_word_bytes(eb) <= (size_t)UNIT_LDS_BYTES) ++k;
     return k;
@@ -75,7 +71,7 @@ struct UnitDotPlan {
     size_t lds_bytes;
     uint64_t mask;          // K2 - 1 with a rotation, all ones without
 };
-FFCX_HD UnitDotPlan unit_dot_plan(size_t rows, bool rotated, int kbits, size_t tlen, size_t eb) {
+FFG_HD UnitDotPlan unit_dot_plan(size_t rows, bool rotated, int kbits, size_t tlen, size_t eb) {
     UnitDotPlan pl = UnitDotPlan();
     if (rows < 1 || tlen < 1) return pl;
     if (rotated) {

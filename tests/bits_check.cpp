@@ -132,10 +132,10 @@ static void check_plan(size_t n, int l, const BitsLevel& lv, size_t eb, bool ali
     const BitsPlan pl = bits_plan(n, l, R, eb, aligned, max_blocks);
     CHECK(pl.ok && pl.rows == R);
     if (R == 0 || n == 0) return;
-    const size_t u = pl.vec ? cx_pack(eb) : 1;
+    const size_t u = pl.vec ? geom_pack(eb) : 1;
     CHECK(pl.gx >= 1 && (size_t)pl.gx * (size_t)R <= (max_blocks > (size_t)R ? max_blocks : (size_t)R));
     if (pl.vec) {
-        CHECK(aligned && n % cx_gran(eb) == 0 && (n * eb) % cx_align(eb) == 0 && pl.row_units * u == n);
+        CHECK(aligned && n % geom_gran(eb) == 0 && (n * eb) % geom_align(eb) == 0 && pl.row_units * u == n);
         if (eb == 24) CHECK(pl.row_units % 64 == 0);      // every wave of the loop entirely in or out
     } else {
         CHECK(pl.row_units == n);
@@ -143,11 +143,11 @@ static void check_plan(size_t n, int l, const BitsLevel& lv, size_t eb, bool ali
     std::vector<int> compact((size_t)R * n, 0), g((size_t)l * n, 0), p((size_t)l * n, 0), rdg((size_t)l * n, 0), rdp((size_t)l * n, 0);
     for (int y = 0; y < R; ++y)
         for (unsigned bx = 0; bx < pl.gx; ++bx)
-            for (unsigned t = 0; t < (unsigned)CX_THREADS; ++t)
-                for (size_t x = (size_t)bx * CX_THREADS + t; x < pl.row_units; x += (size_t)pl.gx * CX_THREADS) {
+            for (unsigned t = 0; t < (unsigned)GEOM_THREADS; ++t)
+                for (size_t x = (size_t)bx * GEOM_THREADS + t; x < pl.row_units; x += (size_t)pl.gx * GEOM_THREADS) {
                     const size_t c = bits_unit(pl, y, x), at = bits_unit(pl, lv.k[y], x), qa = bits_unit(pl, lv.q[y], x);
                     if (pl.vec && (eb != 24 || x % 64 == 0))      // (24 bytes: the wave's 64 elements start aligned)
-                        CHECK((c * u * eb) % cx_align(eb) == 0 && (at * u * eb) % cx_align(eb) == 0 && (qa * u * eb) % cx_align(eb) == 0);
+                        CHECK((c * u * eb) % geom_align(eb) == 0 && (at * u * eb) % geom_align(eb) == 0 && (qa * u * eb) % geom_align(eb) == 0);
                     for (size_t e = 0; e < u; ++e) {
                         CHECK(c * u + e < (size_t)R * n && at * u + e < (size_t)l * n && qa * u + e < (size_t)l * n);
                         ++compact[c * u + e];
@@ -190,8 +190,8 @@ int main() {
                 BitsLevel lv;
                 CHECK(bits_level(l, rho, lv));
                 for (size_t n : ns) {
-                    check_plan(n, l, lv, eb, true, (size_t)CX_MAX_GRID);
-                    check_plan(n, l, lv, eb, false, (size_t)CX_MAX_GRID);
+                    check_plan(n, l, lv, eb, true, (size_t)GEOM_MAX_GRID);
+                    check_plan(n, l, lv, eb, false, (size_t)GEOM_MAX_GRID);
                     check_plan(n, l, lv, eb, true, 70);                    // a capped grid: threads take several units
                     check_plan(n, l, lv, eb, true, 1);
                 }

@@ -1,6 +1,6 @@
 // bsgn_check.cpp -- walks mpyc_amd/csrc/bsgn_geom.hpp on the host (g++, no HIP) against brute-force enumeration, for five
 // element sizes and both alignments:
-//   * the rows plan of the mask and of the finish in sum mode (bsgn_rows_plan / bsgn_row_unit): for n in {1, 2, 63, 64, 65,
+//   * the rows plan of the mask and of the finish in sum mode (bsgn_rows_plan / rows_unit): for n in {1, 2, 63, 64, 65,
 //     128, 255, 256, 257, 5003} and w in 1..8, the units of every row cover its n elements once, every element a unit touches
 //     lies inside row i of the (w, n) array, unit g of row i and unit g of `a` (of a sum-mode output) are the same elements of
 //     their rows; packs only on aligned pointers, whole waves for 24-byte elements;
@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "../mpyc_amd/csrc/bsgn_geom.hpp"
+#include "../mpyc_amd/csrc/rbits_geom.hpp"     // RBITS_MAX_ROWS: the row limit the parties are held to
 
 using namespace ffgpu;
 
@@ -29,19 +30,19 @@ using namespace ffgpu;
 static size_t nplans = 0;
 
 static void check_rows(size_t n, int w, size_t eb, bool aligned) {
-    const ExplogRowsPlan pl = bsgn_rows_plan(n, w, eb, aligned);
-    const size_t W = (size_t)w, gran = cx_gran(eb);
+    const RowsPlan pl = bsgn_rows_plan(n, w, eb, aligned);
+    const size_t W = (size_t)w, gran = geom_gran(eb);
     CHECK(pl.ok && pl.span == W * n, "n=%zu w=%d", n, w);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
     else CHECK(pl.vec == (n % gran == 0), "pack decision n=%zu w=%d eb=%zu", n, w, eb);
-    CHECK(pl.pack == (pl.vec ? cx_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
+    CHECK(pl.pack == (pl.vec ? geom_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
     CHECK(pl.pack <= 4, "the codes of a unit: four elements at the most");
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
-    if (pl.vec) CHECK((n * eb) % cx_align(eb) == 0, "rows of packs start aligned");
+    if (pl.vec) CHECK((n * eb) % geom_align(eb) == 0, "rows of packs start aligned");
     std::vector<int> seen(W * n, 0);
     for (size_t i = 0; i < W; ++i)
         for (size_t g = 0; g < pl.total; ++g) {
-            const size_t u = bsgn_row_unit(pl, i, g);
+            const size_t u = rows_unit(pl, i, g);
             for (unsigned q = 0; q < pl.pack; ++q) {
                 const size_t e = u * pl.pack + q, ea = g * pl.pack + q;      // entry of the (w, n) array, element of `a`
                 CHECK(e < W * n && ea < n && e == i * n + ea, "unit (%zu, %zu) is not its element of row %zu", i, g, i);
@@ -53,7 +54,7 @@ static void check_rows(size_t n, int w, size_t eb, bool aligned) {
 }
 
 static void check_flat(size_t n, int w, size_t eb, bool aligned) {
-    const LegendrePlan pl = bsgn_flat_plan(n, w, eb, aligned), want = legendre_plan((size_t)w * n, eb, aligned);
+    const StreamPlan pl = bsgn_flat_plan(n, w, eb, aligned), want = stream_plan((size_t)w * n, eb, aligned);
     const size_t count = (size_t)w * n;
     CHECK(pl.ok && want.ok, "n=%zu w=%d eb=%zu", n, w, eb);
     CHECK(pl.pack == want.pack && pl.nvec == want.nvec && pl.tail == want.tail && pl.threads == want.threads,

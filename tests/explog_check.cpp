@@ -1,10 +1,10 @@
 // explog_check.cpp -- walks mpyc_amd/csrc/explog_geom.hpp on the host (g++, no HIP) against brute-force enumeration, for five
 // element sizes and both alignments:
-//   * the row plan of powers_prod / poly_dot (explog_rows_plan / explog_row_unit): for n in {1, 2, 63, 64, 65, 257, 5003}, rows
+//   * the row plan of powers_prod / poly_dot (rows_plan / rows_unit): for n in {1, 2, 63, 64, 65, 257, 5003}, rows
 //     in {1, 2, 3, 21, 64} and strides n, n + 3 and n + 64, the units of every row cover its n elements once, every element a
 //     unit touches lies inside row j of the block, and (row, element) pairs are hit exactly once; packs only on aligned
 //     pointers with an aligned pitch, whole waves for 24-byte elements;
-//   * the reversed index of bits_reverse (explog_rev_plan with fxp_norm_at / fxp_norm_next): l in 1..64, every (h, j) is owned
+//   * the reversed index of bits_reverse (explog_rev_plan with rev_at / rev_next): l in 1..64, every (h, j) is owned
 //     once and reads bits[h l + l-1-j], no source falls outside n * l;
 //   * the windows of pow_base (pow_base_plan / pow_base_digit / pow_base_slot): for random three-limb integers, shifts and bit
 //     counts, the digits are those of ((x >> shift) mod 2^ebits) in base 16, every window index and every table slot is in
@@ -31,19 +31,19 @@ using namespace ffgpu;
 static size_t nplans = 0;
 
 static void check_rows(size_t n, size_t rows, size_t stride, size_t eb, bool aligned) {
-    const ExplogRowsPlan pl = explog_rows_plan(n, rows, stride, eb, aligned);
-    const size_t gran = cx_gran(eb);
+    const RowsPlan pl = rows_plan(n, rows, stride, eb, aligned);
+    const size_t gran = geom_gran(eb);
     CHECK(pl.ok && pl.span == (rows - 1) * stride + n, "n=%zu rows=%zu stride=%zu", n, rows, stride);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
-    const bool pitch_ok = rows == 1 || ((stride * eb) % cx_align(eb) == 0 && stride % cx_pack(eb) == 0);
+    const bool pitch_ok = rows == 1 || ((stride * eb) % geom_align(eb) == 0 && stride % geom_pack(eb) == 0);
     if (aligned) CHECK(pl.vec == (n % gran == 0 && pitch_ok), "pack decision n=%zu stride=%zu eb=%zu", n, stride, eb);
-    CHECK(pl.pack == (pl.vec ? cx_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
+    CHECK(pl.pack == (pl.vec ? geom_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
     if (pl.vec && rows > 1) CHECK(pl.pitch * pl.pack == stride, "the pitch is the stride in units");
     std::vector<int> seen(rows * n, 0);
     for (size_t j = 0; j < rows; ++j)
         for (size_t g = 0; g < pl.total; ++g) {
-            const size_t u = explog_row_unit(pl, j, g);
+            const size_t u = rows_unit(pl, j, g);
             for (unsigned q = 0; q < pl.pack; ++q) {
                 const size_t e = u * pl.pack + q;                          // element of the block
                 CHECK(e >= j * stride && e < j * stride + n && e < pl.span, "unit (%zu, %zu) leaves its row", j, g);
@@ -55,8 +55,8 @@ static void check_rows(size_t n, size_t rows, size_t stride, size_t eb, bool ali
 }
 
 static void check_rev(size_t n, int l, size_t eb, bool aligned) {
-    const FxpNormPlan pl = explog_rev_plan(n, l, eb, aligned);
-    const size_t L = (size_t)l, elems = n * L, gran = cx_gran(eb);
+    const RevPlan pl = explog_rev_plan(n, l, eb, aligned);
+    const size_t L = (size_t)l, elems = n * L, gran = geom_gran(eb);
     CHECK(pl.ok && pl.l == L && pl.l1 == L && pl.elems == elems, "n=%zu l=%d", n, l);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
     else CHECK(pl.vec == (elems % gran == 0), "pack decision n=%zu l=%d eb=%zu", n, l, eb);
@@ -64,14 +64,14 @@ static void check_rev(size_t n, int l, size_t eb, bool aligned) {
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
     std::vector<int> seen_c(elems, 0), seen_src(elems, 0);
     for (size_t g = 0; g < pl.total; ++g) {
-        FxpNormAt at = fxp_norm_at(pl, g * pl.pack);
+        RevAt at = rev_at(pl, g * pl.pack);
         for (unsigned q = 0; q < pl.pack; ++q) {
             const size_t c = g * pl.pack + q;
             CHECK(at.h == c / L && at.j == c % L && at.h < n, "c=%zu -> (h, j)", c);
             CHECK(at.src == at.h * L + (L - 1 - at.j) && at.src < elems, "source of c=%zu", c);
             ++seen_c[c];
             ++seen_src[at.src];
-            fxp_norm_next(pl, at);
+            rev_next(pl, at);
         }
     }
     for (size_t c = 0; c < elems; ++c) CHECK(seen_c[c] == 1 && seen_src[c] == 1, "element %zu written %d, read %d times", c, seen_c[c], seen_src[c]);
@@ -135,11 +135,11 @@ int main() {
     // refused
     CHECK(!explog_prod_valid(0, 1) && !explog_prod_valid(3, 0) && !explog_prod_valid(3, 4) && explog_prod_valid(3, 3), "h, w");
     CHECK(!explog_poly_valid(0) && !explog_poly_valid(65) && explog_poly_valid(1) && explog_poly_valid(64), "theta");
-    CHECK(!explog_rows_plan(5, 0, 5, 8, true).ok && !explog_rows_plan(5, 2, 4, 8, true).ok && !explog_rows_plan(5, 2, 5, 6, true).ok, "rows, stride, element size");
-    CHECK(!explog_rows_plan((size_t)1 << 60, 64, (size_t)1 << 60, 8, true).ok && !explog_rows_plan((size_t)1 << 61, 1, (size_t)1 << 61, 24, true).ok, "sizes overflow");
+    CHECK(!rows_plan(5, 0, 5, 8, true).ok && !rows_plan(5, 2, 4, 8, true).ok && !rows_plan(5, 2, 5, 6, true).ok, "rows, stride, element size");
+    CHECK(!rows_plan((size_t)1 << 60, 64, (size_t)1 << 60, 8, true).ok && !rows_plan((size_t)1 << 61, 1, (size_t)1 << 61, 24, true).ok, "sizes overflow");
     CHECK(!explog_rev_plan(5, 0, 8, true).ok && !explog_rev_plan(5, 65, 8, true).ok && !explog_rev_plan((size_t)1 << 58, 64, 8, true).ok, "l, n * l");
     CHECK(!pow_base_plan((size_t)1 << 61, 0, 4, 61, 8).ok && !pow_base_plan(5, 0, 4, 65, 8).ok, "n * eb, modulus wider than the element");
-    CHECK(explog_rows_plan(0, 3, 0, 8, true).ok && explog_rows_plan(0, 3, 0, 8, true).total == 0 && explog_rev_plan(0, 7, 8, true).total == 0, "empty");
+    CHECK(rows_plan(0, 3, 0, 8, true).ok && rows_plan(0, 3, 0, 8, true).total == 0 && explog_rev_plan(0, 7, 8, true).total == 0, "empty");
     printf("explog ok %zu\n", nplans);
     return 0;
 }

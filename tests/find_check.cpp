@@ -38,13 +38,13 @@ static void check_leaf(size_t outer, size_t k, size_t inner, int virt, int ncomp
     }
     const size_t n0 = kv % 2, h = kv / 2, kc = h + n0;
     CHECK(pl.t.ok && pl.t.pairs == h && pl.t.next == kc && pl.t.row_elems == h * inner && pl.kv == kv && pl.virt == virt, "k=%zu virt=%d", k, virt);
-    const size_t u = pl.t.vec ? cx_pack(eb) : 1, gran = cx_gran(eb);
+    const size_t u = pl.t.vec ? geom_pack(eb) : 1, gran = geom_gran(eb);
     if (!aligned) CHECK(!pl.t.vec, "packs on unaligned pointers");
     if (pl.t.vec) CHECK(inner % gran == 0, "pack conditions");
     else if (aligned) CHECK(inner % gran != 0, "packs apply and are not taken");
     CHECK(pl.t.total == outer * h * inner / u && pl.t.pitch_full == k * inner / u && pl.t.pitch_half == kc * inner / u, "loop length and pitches");
     CHECK(pl.plane_c == outer * h * inner / u && pl.plane_half == outer * kc * inner / u, "plane distances");
-    if (pl.t.vec) CHECK((pl.plane_c * u * eb) % cx_align(eb) == 0 && (pl.plane_half * u * eb) % cx_align(eb) == 0 && pl.plane_c % (gran / u) == 0 && pl.plane_half % (gran / u) == 0, "planes stay aligned");
+    if (pl.t.vec) CHECK((pl.plane_c * u * eb) % geom_align(eb) == 0 && (pl.plane_half * u * eb) % geom_align(eb) == 0 && pl.plane_c % (gran / u) == 0 && pl.plane_half % (gran / u) == 0, "planes stay aligned");
     const size_t nbits = outer * k * inner, nhalf = outer * kc * inner, nc = outer * h * inner;
     std::vector<int> seen_bits(nbits, 0), seen_half(nhalf, 0), seen_c(nc, 0), bye_bits(nbits, 0), bye_half(nhalf, 0);
     size_t virtual_pairs = 0;
@@ -57,7 +57,7 @@ static void check_leaf(size_t outer, size_t k, size_t inner, int virt, int ncomp
             CHECK(at.bye == prev.bye && (!at.bye || (at.bye_full == prev.bye_full + 1 && at.bye_half == prev.bye_half + 1)), "bye splits a wave at g=%zu", g);
         }
         if (pl.t.vec && (eb != 24 || g % 64 == 0)) {
-            const size_t al = cx_align(eb), ub = u * eb;
+            const size_t al = geom_align(eb), ub = u * eb;
             CHECK((at.first * ub) % al == 0 && (at.second * ub) % al == 0 && (at.c * ub) % al == 0 && (at.half * ub) % al == 0, "alignment");
             if (at.bye) CHECK((at.bye_full * ub) % al == 0 && (at.bye_half * ub) % al == 0, "alignment of the bye");
         }
@@ -106,10 +106,10 @@ static void check_level(size_t outer, size_t k, size_t inner, int ncomp, size_t 
     const TourPlan t = tour_plan(outer, k, inner, TOUR_ODD_EVEN, eb, aligned);
     CHECK(pl.t.ok && t.ok && pl.t.vec == t.vec && pl.t.total == t.total && pl.t.pitch_full == t.pitch_full && pl.t.pitch_half == t.pitch_half &&
               pl.t.run == t.run && pl.t.bye == t.bye && pl.t.row_units == t.row_units, "a stored level is a tournament round per component");
-    const size_t u = pl.t.vec ? cx_pack(eb) : 1, h = k / 2, kc = h + k % 2;
+    const size_t u = pl.t.vec ? geom_pack(eb) : 1, h = k / 2, kc = h + k % 2;
     CHECK(pl.plane_full * u == outer * k * inner && pl.plane_half * u == outer * kc * inner && pl.plane_c * u == outer * h * inner && pl.kv == k && !pl.virt, "plane distances");
     if (pl.t.vec)
-        CHECK((pl.plane_full * u * eb) % cx_align(eb) == 0 && pl.plane_full % (cx_gran(eb) / u) == 0 && pl.plane_c % (cx_gran(eb) / u) == 0, "planes stay aligned");
+        CHECK((pl.plane_full * u * eb) % geom_align(eb) == 0 && pl.plane_full % (geom_gran(eb) / u) == 0 && pl.plane_c % (geom_gran(eb) / u) == 0, "planes stay aligned");
     // the last unit of the last component stays inside (C, outer, k, inner) and (C, outer, h, inner)
     if (pl.t.total) {
         const TourAt at = tour_at(pl.t, pl.t.total - 1);

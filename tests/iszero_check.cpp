@@ -1,13 +1,13 @@
 // iszero_check.cpp -- walks mpyc_amd/csrc/iszero_geom.hpp on the host (g++, no HIP) against brute-force enumeration, for five
 // element sizes and both alignments:
-//   * the mask (iszero_mask_plan / iszero_mask_unit): for n in {1, 2, 63, 64, 65, 128, 255, 256, 257, 5003} and k in
+//   * the mask (iszero_mask_plan / rows_unit): for n in {1, 2, 63, 64, 65, 128, 255, 256, 257, 5003} and k in
 //     {1, 2, 8, 9, 30}, the units of every row cover its n elements once, every element a unit touches lies inside row i of
 //     the (k, n) array and below k n, unit g of row i and unit g of `a` are the same elements of their rows, and (row,
 //     element) pairs are hit exactly once; packs only on aligned pointers, whole waves for 24-byte elements;
-//   * the symbols (legendre_plan): the packs of the vector loop and the element tail cover the count entries once, the code
+//   * the symbols (stream_plan): the packs of the vector loop and the element tail cover the count entries once, the code
 //     bytes of pack i are bytes i pack .. i pack + pack - 1, whole waves for 24-byte elements, the grid is sized for the packs
 //     (or for the entries when there are none) -- the plan of the exponentiation restated;
-//   * the finish (iszero_flat_plan / iszero_code_at): every entry and every code byte is owned once;
+//   * the finish (flat_plan / iszero_code_at): every entry and every code byte is owned once;
 //   * the code word of a pack (iszero_code_put / iszero_code_of) and the alignment rule of the byte array;
 //   * k < 1 and overflowing sizes are refused.
 // Prints "iszero ok <plans>" and exits 0, or the first failure and exits 1.
@@ -31,18 +31,18 @@ using namespace ffgpu;
 static size_t nplans = 0;
 
 static void check_mask(size_t n, int k, size_t eb, bool aligned) {
-    const ExplogRowsPlan pl = iszero_mask_plan(n, k, eb, aligned);
-    const size_t K = (size_t)k, gran = cx_gran(eb);
+    const RowsPlan pl = iszero_mask_plan(n, k, eb, aligned);
+    const size_t K = (size_t)k, gran = geom_gran(eb);
     CHECK(pl.ok && pl.span == K * n, "n=%zu k=%d", n, k);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
     else CHECK(pl.vec == (n % gran == 0), "pack decision n=%zu k=%d eb=%zu", n, k, eb);
-    CHECK(pl.pack == (pl.vec ? cx_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
+    CHECK(pl.pack == (pl.vec ? geom_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
-    if (pl.vec) CHECK((n * eb) % cx_align(eb) == 0, "rows of packs start aligned");
+    if (pl.vec) CHECK((n * eb) % geom_align(eb) == 0, "rows of packs start aligned");
     std::vector<int> seen(K * n, 0);
     for (size_t i = 0; i < K; ++i)
         for (size_t g = 0; g < pl.total; ++g) {
-            const size_t u = iszero_mask_unit(pl, i, g);
+            const size_t u = rows_unit(pl, i, g);
             for (unsigned q = 0; q < pl.pack; ++q) {
                 const size_t e = u * pl.pack + q, ea = g * pl.pack + q;      // entry of the (k, n) array, element of `a`
                 CHECK(e < K * n && ea < n && e == i * n + ea, "unit (%zu, %zu) is not its element of row %zu", i, g, i);
@@ -54,8 +54,8 @@ static void check_mask(size_t n, int k, size_t eb, bool aligned) {
 }
 
 static void check_legendre(size_t count, size_t eb, bool aligned) {
-    const LegendrePlan pl = legendre_plan(count, eb, aligned);
-    CHECK(pl.ok && pl.pack == cx_pack(eb), "count=%zu eb=%zu", count, eb);
+    const StreamPlan pl = stream_plan(count, eb, aligned);
+    CHECK(pl.ok && pl.pack == geom_pack(eb), "count=%zu eb=%zu", count, eb);
     if (!aligned) CHECK(pl.nvec == 0, "packs on unaligned pointers");
     else if (eb == 24) CHECK(pl.nvec % 64 == 0 && count - pl.nvec < 64, "24-byte packs: whole waves, a tail below one");
     else CHECK(pl.nvec == count / pl.pack, "every whole pack goes through the vector loop");
@@ -74,11 +74,11 @@ static void check_legendre(size_t count, size_t eb, bool aligned) {
 }
 
 static void check_finish(size_t count, size_t eb, bool aligned) {
-    const IszeroFlatPlan pl = iszero_flat_plan(count, eb, aligned);
+    const FlatPlan pl = flat_plan(count, eb, aligned);
     CHECK(pl.ok, "count=%zu eb=%zu", count, eb);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
-    else CHECK(pl.vec == (count != 0 && count % cx_gran(eb) == 0), "pack decision count=%zu eb=%zu", count, eb);
-    CHECK(pl.pack == (pl.vec ? cx_pack(eb) : 1u) && pl.total * pl.pack == count, "loop length");
+    else CHECK(pl.vec == (count != 0 && count % geom_gran(eb) == 0), "pack decision count=%zu eb=%zu", count, eb);
+    CHECK(pl.pack == (pl.vec ? geom_pack(eb) : 1u) && pl.total * pl.pack == count, "loop length");
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
     std::vector<int> seen(count, 0);
     for (size_t g = 0; g < pl.total; ++g) {
@@ -112,9 +112,9 @@ int main() {
             CHECK(!iszero_mask_plan(5, 0, eb, al != 0).ok && !iszero_mask_plan(5, -1, eb, al != 0).ok, "k < 1");
             CHECK(!iszero_mask_plan((size_t)1 << 62, 8, eb, al != 0).ok, "k n overflows");
             CHECK(!iszero_mask_plan(((size_t)1 << 61) / eb, 30, eb, al != 0).ok, "k n eb overflows");
-            CHECK(!legendre_plan((size_t)1 << 62, eb, al != 0).ok && !iszero_flat_plan((size_t)1 << 62, eb, al != 0).ok, "count eb overflows");
+            CHECK(!stream_plan((size_t)1 << 62, eb, al != 0).ok && !flat_plan((size_t)1 << 62, eb, al != 0).ok, "count eb overflows");
         }
-    CHECK(!iszero_mask_plan(4, 2, 6, true).ok && !legendre_plan(4, 2, true).ok && !iszero_flat_plan(4, 0, true).ok, "element size");
+    CHECK(!iszero_mask_plan(4, 2, 6, true).ok && !stream_plan(4, 2, true).ok && !flat_plan(4, 0, true).ok, "element size");
     // the code word of a pack, and the alignment of the byte array for the one access that moves it
     for (unsigned c0 = 0; c0 < 3; ++c0)
         for (unsigned c1 = 0; c1 < 3; ++c1)

@@ -5,7 +5,7 @@
 //     (rbits_grid_entries) -- and every row count in {1, 3, 5, 7, 9, 10, 64}, the packs of the vector loop and the element
 //     tail cover the n entries of a row once; pack i is elements i pack .. i pack + pack - 1; whole waves for 24-byte
 //     elements; the grid is sized for the packs (or for the entries when there are none): the plan of the exponentiation
-//     (legendre_plan) restated;
+//     (stream_plan) restated;
 //   * the opening keeps packs only for up to rbits_fused_rows(eb) rows (9; 5 for 24-byte elements), the finish for every row
 //     count; no packs on unaligned pointers;
 //   * row counts below 1 and above RBITS_MAX_ROWS and overflowing sizes are refused; n = 0 is a plan of nothing.
@@ -29,16 +29,16 @@ using namespace ffgpu;
 
 static size_t nplans = 0;
 
-static void check_plan(const RbitsPlan& pl, size_t n, int rows, size_t eb, bool packs, bool open) {
-    CHECK(pl.ok && pl.pack == cx_pack(eb), "n=%zu rows=%d eb=%zu", n, rows, eb);
-    const LegendrePlan lp = legendre_plan(n, eb, packs);
+static void check_plan(const StreamPlan& pl, size_t n, int rows, size_t eb, bool packs, bool open) {
+    CHECK(pl.ok && pl.pack == geom_pack(eb), "n=%zu rows=%d eb=%zu", n, rows, eb);
+    const StreamPlan lp = stream_plan(n, eb, packs);
     CHECK(pl.nvec == lp.nvec && pl.tail == lp.tail && pl.threads == lp.threads, "the plan of the exponentiation");
     if (!packs) CHECK(pl.nvec == 0, "packs where none apply");
     else if (eb == 24) CHECK(pl.nvec % 64 == 0 && n - pl.nvec < 64, "24-byte packs: whole waves, a tail below one");
     else CHECK(pl.nvec == n / pl.pack, "every whole pack goes through the vector loop");
     CHECK(pl.tail == pl.nvec * pl.pack && pl.tail <= n, "the tail starts after the packs");
     CHECK(pl.threads == (pl.nvec ? pl.nvec : n), "the grid is sized for the packs");
-    if (open) CHECK(pl.fused == (rows <= rbits_fused_rows(eb)), "fused rows");
+    if (open && rows > rbits_fused_rows(eb)) CHECK(pl.nvec == 0, "packs beyond the fused rows");
     std::vector<int> seen(n, 0);
     for (size_t i = 0; i < pl.nvec; ++i)
         for (unsigned q = 0; q < pl.pack; ++q) {
@@ -56,8 +56,8 @@ int main() {
     const int rows[7] = {1, 3, 5, 7, 9, 10, 64};
     CHECK(RBITS_FUSED_ROWS == 9 && RBITS_FUSED_ROWS_24 == 5 && RBITS_MAX_ROWS == 64, "the row limits of the header");
     for (size_t eb : ebs) {
-        const size_t pack = cx_pack(eb), wave = 64 * pack, block = rbits_grid_entries(1, eb), grid = rbits_grid_entries(3, eb);
-        CHECK(block == (size_t)CX_THREADS * pack && grid == 3 * block, "entries of a grid");
+        const size_t pack = geom_pack(eb), wave = 64 * pack, block = rbits_grid_entries(1, eb), grid = rbits_grid_entries(3, eb);
+        CHECK(block == (size_t)GEOM_THREADS * pack && grid == 3 * block, "entries of a grid");
         const size_t ns[] = {1, pack - 1, pack, pack + 1, wave - 1, wave, wave + 1, block - 1, block, block + 1, grid, grid + 1, 5003};
         CHECK(rbits_fused_rows(eb) == (eb == 24 ? 5 : 9), "fused rows per element size");
         for (int al = 0; al < 2; ++al) {

@@ -63,9 +63,9 @@ int main() {
                     ncols += cols;
                     const unsigned upr = sgn_units_per_row(cols, eb);
                     if (upr * (unsigned)uw != (unsigned)(cols * ew)) return fail("units per row", eb, l, n);
-                    for (unsigned tid = 0; tid < (unsigned)SGN_THREADS; ++tid) {
+                    for (unsigned tid = 0; tid < (unsigned)GEOM_THREADS; ++tid) {
                         unsigned q = tid;
-                        for (SgnCursor c = sgn_cursor(tid, upr); c.row < rows; sgn_cursor_next(c), q += SGN_THREADS) {
+                        for (SgnCursor c = sgn_cursor(tid, upr); c.row < rows; sgn_cursor_next(c), q += GEOM_THREADS) {
                             if (c.row != q / upr || c.u != q % upr) return fail("cursor", eb, l, n);
                             const size_t src = sgn_unit_src_word(h0, c.row, l, i0, c.u, eb);
                             const unsigned at = sgn_unit_lds_word(c.row, c.u, eb);
@@ -87,11 +87,11 @@ int main() {
                         const unsigned wpr = (unsigned)(cols * ew), span = (32 * (unsigned)uw + wpr - 1) / wpr + 1;
                         const unsigned shortmax = wpr < span ? wpr : span;
                         for (unsigned k = 0; k < upr; ++k)
-                            for (unsigned g = 0; g < (unsigned)SGN_THREADS; g += 32)
+                            for (unsigned g = 0; g < (unsigned)GEOM_THREADS; g += 32)
                                 for (int w = 0; w < uw; ++w) {
                                     unsigned char cnt[32] = {0};
                                     for (unsigned t = g; t < g + 32; ++t) {
-                                        const unsigned q = t + k * (unsigned)SGN_THREADS;
+                                        const unsigned q = t + k * (unsigned)GEOM_THREADS;
                                         if (++cnt[(sgn_unit_lds_word(q / upr, q % upr, eb) + (unsigned)w) % 32] > (cols == ch ? 2u : shortmax))
                                             return fail("staging store: more than two lanes on a bank", eb, l, n);
                                     }

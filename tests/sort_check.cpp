@@ -61,11 +61,11 @@ static void check_plan(size_t outer, size_t k, size_t inner, const Stage& s, siz
         CHECK(pl.total == 0, "empty stage with work");
         return;
     }
-    const size_t u = pl.vec ? cx_pack(eb) : 1;
+    const size_t u = pl.vec ? geom_pack(eb) : 1;
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
     if (pl.vec) {
-        CHECK((s.p * inner) % cx_gran(eb) == 0 && pl.row_elems % cx_gran(eb) == 0 && (k * inner * eb) % cx_align(eb) == 0, "pack conditions");
-        CHECK(pl.total % (cx_gran(eb) / u) == 0, "whole waves");
+        CHECK((s.p * inner) % geom_gran(eb) == 0 && pl.row_elems % geom_gran(eb) == 0 && (k * inner * eb) % geom_align(eb) == 0, "pack conditions");
+        CHECK(pl.total % (geom_gran(eb) / u) == 0, "whole waves");
     }
     CHECK(pl.total == outer * pl.row_elems / u, "loop length");
     std::vector<int> seen_a(outer * k * inner, 0), seen_c(outer * pl.row_elems, 0);
@@ -75,7 +75,7 @@ static void check_plan(size_t outer, size_t k, size_t inner, const Stage& s, siz
             const CxAt prev = cx_at(pl, g - 1);
             CHECK(at.lo == prev.lo + 1 && at.hi == prev.hi + 1 && at.c == prev.c + 1, "wave not contiguous at g=%zu", g);
         }
-        if (pl.vec && (eb != 24 || g % 64 == 0)) CHECK((at.lo * u * eb) % cx_align(eb) == 0 && (at.hi * u * eb) % cx_align(eb) == 0 && (at.c * u * eb) % cx_align(eb) == 0, "alignment");
+        if (pl.vec && (eb != 24 || g % 64 == 0)) CHECK((at.lo * u * eb) % geom_align(eb) == 0 && (at.hi * u * eb) % geom_align(eb) == 0 && (at.c * u * eb) % geom_align(eb) == 0, "alignment");
         for (size_t e = 0; e < u; ++e) {
             const size_t c = at.c * u + e, lo = at.lo * u + e, hi = at.hi * u + e;
             CHECK(c < seen_c.size() && hi < seen_a.size() && lo < hi, "out of range: k=%zu inner=%zu g=%zu", k, inner, g);

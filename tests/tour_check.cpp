@@ -47,14 +47,14 @@ static void check_plan(size_t outer, size_t k, size_t inner, int mode, size_t eb
     brute(k, mode, a1, a2);
     const size_t n0 = k % 2, h = k / 2, kc = h + n0;
     CHECK(pl.ok && pl.pairs == h && pl.next == kc && pl.row_elems == h * inner, "k=%zu mode=%d", k, mode);
-    const size_t u = pl.vec ? cx_pack(eb) : 1;
+    const size_t u = pl.vec ? geom_pack(eb) : 1;
     const size_t run = mode == TOUR_HALVES ? h * inner : inner;
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
     if (pl.vec) {
-        CHECK(run % cx_gran(eb) == 0 && pl.row_elems % cx_gran(eb) == 0 && (n0 * inner) % cx_gran(eb) == 0, "pack conditions");
-        CHECK(pl.total % (cx_gran(eb) / u) == 0 && pl.bye % (cx_gran(eb) / u) == 0, "whole waves");
+        CHECK(run % geom_gran(eb) == 0 && pl.row_elems % geom_gran(eb) == 0 && (n0 * inner) % geom_gran(eb) == 0, "pack conditions");
+        CHECK(pl.total % (geom_gran(eb) / u) == 0 && pl.bye % (geom_gran(eb) / u) == 0, "whole waves");
     } else if (aligned) {
-        CHECK(run % cx_gran(eb) != 0 || pl.row_elems % cx_gran(eb) != 0 || (n0 * inner) % cx_gran(eb) != 0, "packs apply and are not taken");
+        CHECK(run % geom_gran(eb) != 0 || pl.row_elems % geom_gran(eb) != 0 || (n0 * inner) % geom_gran(eb) != 0, "packs apply and are not taken");
     }
     CHECK(pl.total == outer * pl.row_elems / u, "loop length");
     const size_t nfull = outer * k * inner, nhalf = outer * kc * inner, ncomp = outer * h * inner;
@@ -69,7 +69,7 @@ static void check_plan(size_t outer, size_t k, size_t inner, int mode, size_t eb
                   "bye splits a wave at g=%zu", g);
         }
         if (pl.vec && (eb != 24 || g % 64 == 0)) {
-            const size_t al = cx_align(eb), ub = u * eb;
+            const size_t al = geom_align(eb), ub = u * eb;
             CHECK((at.first * ub) % al == 0 && (at.second * ub) % al == 0 && (at.c * ub) % al == 0 && (at.half * ub) % al == 0, "alignment");
             if (at.bye) CHECK((at.bye_full * ub) % al == 0 && (at.bye_half * ub) % al == 0, "alignment of the bye");
         }

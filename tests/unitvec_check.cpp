@@ -1,6 +1,6 @@
 // unitvec_check.cpp -- walks mpyc_amd/csrc/unitvec_geom.hpp on the host (g++, no HIP) against brute-force enumeration, for five
 // element sizes and both alignments:
-//   * the rows plan of the three kernels (unit_rows_plan / unit_row_unit / unit_elem): for n in {1, 2, 63, 64, 65, 128, 255,
+//   * the rows plan of the three kernels (unit_rows_plan / rows_unit / unit_elem): for n in {1, 2, 63, 64, 65, 128, 255,
 //     256, 257, 5003} and rows in {1, 2, 3, 5, 8, 64}, the units of every row cover its n elements once and lie inside the row;
 //     packs only on aligned pointers, whole waves for 24-byte elements; the factor of unit_prod for xstride in {1, 3, 16} is
 //     the element's own (unit_x_at), its span (unit_x_span) the last factor plus one, a pack of x only for xstride 1;
@@ -30,17 +30,17 @@ using namespace ffgpu;
 static size_t nplans = 0;
 
 static void check_rows(size_t n, size_t rows, size_t eb, bool aligned) {
-    const ExplogRowsPlan pl = unit_rows_plan(n, rows, eb, aligned);
-    const size_t gran = cx_gran(eb);
+    const RowsPlan pl = unit_rows_plan(n, rows, eb, aligned);
+    const size_t gran = geom_gran(eb);
     CHECK(pl.ok && pl.span == rows * n, "n=%zu rows=%zu", n, rows);
     if (!aligned) CHECK(!pl.vec, "packs on unaligned pointers");
-    else CHECK(pl.vec == (n % gran == 0 && (rows == 1 || (n * eb) % cx_align(eb) == 0)), "pack decision n=%zu rows=%zu eb=%zu", n, rows, eb);
-    CHECK(pl.pack == (pl.vec ? cx_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
+    else CHECK(pl.vec == (n % gran == 0 && (rows == 1 || (n * eb) % geom_align(eb) == 0)), "pack decision n=%zu rows=%zu eb=%zu", n, rows, eb);
+    CHECK(pl.pack == (pl.vec ? geom_pack(eb) : 1u) && pl.total * pl.pack == n, "loop length");
     if (pl.vec && eb == 24) CHECK(pl.total % 64 == 0, "24-byte packs: whole waves");
     std::vector<int> seen(rows * n, 0);
     for (size_t j = 0; j < rows; ++j)
         for (size_t g = 0; g < pl.total; ++g) {
-            const size_t u = unit_row_unit(pl, j, g);
+            const size_t u = rows_unit(pl, j, g);
             for (unsigned q = 0; q < pl.pack; ++q) {
                 const size_t e = u * pl.pack + q, er = unit_elem(pl, g, q);
                 CHECK(e < rows * n && er < n && e == j * n + er, "unit (%zu, %zu) is not its element of row %zu", j, g, j);
