@@ -12,7 +12,9 @@ the host: the output slot holds the reference result, every other byte -- operan
 Expected values never come from the code under test: fields of up to 128 bits take the C oracle's element-wise ADD / SUB /
 MUL / NEG / REDUCE (OracleRef; scalars as broadcast arrays, muladd and beaver_combine composed, pow by square-and-multiply over
 whole arrays), 24-byte fields Python integers (IntRef).  An inverse is checked by what defines it: canonical, zero exactly
-where the input is zero, a * r == 1 elsewhere -- the inverse is unique, so this is an exact comparison.
+where the input is zero, a * r == 1 elsewhere -- the inverse is unique, so this is an exact comparison.  A square root
+(sqrt_cl, primes = 1 mod 4: sqrt_fields()) is not unique: the expectation is oracle.pyoracle.sqrt_prime on Python integers,
+element by element, for every width -- the root the reference returns and its value for a non-residue (tests/golden/sqrt.json).
 
 Nothing here imports the GPU at module level: tests/test_elementwise_contract_host.py drives the same code against
 tests/cpuctx.CpuFieldContext and against deliberately wrong contexts."""
@@ -27,7 +29,7 @@ BIG_EXP_MAX_N = 129                 # the exponents q - 2 and 3e' + 1 stop here
 BIG_EXPS = ('q-2', '3e+1')
 
 OPERANDS = {'add': 'ab', 'sub': 'ab', 'mul': 'ab', 'neg': 'a', 'reduce': 'a', 'add_scalar': 'a', 'mul_scalar': 'a',
-            'rsub_scalar': 'a', 'muladd': 'abc', 'pow': 'a', 'inv': 'a', 'beaver_combine': 'zxyde'}
+            'rsub_scalar': 'a', 'muladd': 'abc', 'pow': 'a', 'inv': 'a', 'beaver_combine': 'zxyde', 'sqrt_cl': 'a'}
 
 # alias patterns per number of array operands: name -> (slot of every operand, slot of the output); 'o' is a fresh slot
 PATTERNS = {
@@ -67,6 +69,63 @@ def nonzero_elems(raw, eb):
     return raw.reshape(-1, eb).any(axis=1)
 
 
+# ---- square roots: the reference, element by element --------------------------------------------------------------------
+SQRT_POOL = 1024                    # distinct random operands of sqrt_cl per field: the integer reference runs once per value
+DEEP_WALK_BOUND = 50000
+_sqrt_memo = {}
+_deep_memo = {}
+_pool_memo = {}
+
+
+def sqrt_ints(p, vals):
+    """oracle.pyoracle.sqrt_prime on Python integers, every distinct (p, value) computed once per process"""
+    from oracle import pyoracle as po
+    F = po.Field(p, False)
+    memo = _sqrt_memo.setdefault(p, {})
+    out = []
+    for v in vals:
+        r = memo.get(v)
+        if r is None:
+            r = memo[v] = po.sqrt_prime(F, v)
+        out.append(r)
+    return out
+
+
+def sqrt_depth(p, a):
+    """how many candidates b = 1, 2, ... the reference tries for a != 0 until b^2 - 4a is a non-residue"""
+    b = 1
+    while pow((b * b - 4 * a) % p, (p - 1) >> 1, p) != p - 1:
+        b += 1
+    return b
+
+
+def deep_elements(p):
+    """{6: the first 64 squares i^2, i = 1, 2, ..., of depth >= 6, 8: the first 8 of depth >= 8, 11: the first 2 of depth >= 11};
+    the walk stops at DEEP_WALK_BOUND candidates (or at p), so a list may come back short: the callers assert"""
+    if p not in _deep_memo:
+        need = {6: 64, 8: 8, 11: 2}
+        found = {d: [] for d in need}
+        for i in range(1, min(p, DEEP_WALK_BOUND + 1)):
+            a = i * i % p
+            d = sqrt_depth(p, a)
+            for lvl, k in need.items():
+                if d >= lvl and len(found[lvl]) < k and a not in found[lvl]:
+                    found[lvl].append(a)
+            if all(len(found[lvl]) == k for lvl, k in need.items()):
+                break
+        _deep_memo[p] = found
+    return _deep_memo[p]
+
+
+def sqrt_specials(p):
+    """0, 1, p - 1, 4^-1 and 9 * 4^-1 (b^2 - 4a = 0 at b = 1 and at b = 3: a candidate to pass over), and the deepest element
+    the walk found (none for a field as small as GF(13))"""
+    inv4 = pow(4, -1, p)
+    deep = deep_elements(p)
+    deepest = next((deep[lvl][0] for lvl in (11, 8, 6) if deep[lvl]), None)
+    return [0, 1, p - 1, inv4, 9 * inv4 % p] + ([deepest] if deepest is not None else [])
+
+
 # ---- references ---------------------------------------------------------------------------------------------------------
 class OracleRef:
     """fields of at most 128 bits: oracle/fforacle.c through coracle.CField.ew; arrays are flat uint8 limb images"""
@@ -102,6 +161,9 @@ class OracleRef:
             if bit == '1':
                 r = self.mul(r, a)
         return r
+
+    def sqrt_cl(self, a):
+        return ints_to_bytes(sqrt_ints(self.modulus, bytes_to_ints(a, self.eb)), self.eb)
 
     def check_inv(self, a, r):
         """None if r is the element-wise inverse of a (zero for zero), else what is wrong at the first bad element"""
@@ -177,6 +239,9 @@ class IntRef:
     def pow(self, a, e):
         return self._raw(np.array([pow(x, e, self.q) for x in self._obj(a)], dtype=object))
 
+    def sqrt_cl(self, a):
+        return ints_to_bytes(sqrt_ints(self.q, bytes_to_ints(a, 24)), 24)
+
     def check_inv(self, a, r):
         A, R = self._obj(a), self._obj(r)
         for what, bad in (('not canonical', R >= self.q), ('zero pattern differs', (A == 0) != (R == 0)),
@@ -212,6 +277,8 @@ def apply_ref(ref, entry, args):
         return ref.add(ref.mul(args[0], args[1]), args[2])
     if name == 'pow':
         return ref.pow(args[0], par)
+    if name == 'sqrt_cl':
+        return ref.sqrt_cl(args[0])
     if name == 'beaver_combine':                      # z + d*y + e*x (+ d*e)
         z, x, y, d, e = args
         r = ref.add(ref.add(z, ref.mul(d, y)), ref.mul(e, x))
@@ -231,6 +298,8 @@ def invoke(ctx, entry, ops, out):
         ctx.muladd(ops[0], ops[1], ops[2], out=out)
     elif name == 'inv':
         ctx.inv(ops[0], out=out, check_zero=False)
+    elif name == 'sqrt_cl':
+        ctx.sqrt_cl(ops[0], out=out)
     elif name == 'beaver_combine':
         ctx.beaver_combine(ops[0], ops[1], ops[2], ops[3], ops[4], par, out=out)
     else:
@@ -238,7 +307,8 @@ def invoke(ctx, entry, ops, out):
 
 
 def all_entries(q, rnd):
-    """(entry point, label, parameter) of every call the contract covers; rnd: one random canonical scalar"""
+    """(entry point, label, parameter) of every call the contract covers; rnd: one random canonical scalar.  sqrt_cl, which
+    serves the primes = 1 mod 4 only, comes last and only for those (the order of a binary field is even)"""
     ent = [(name, '', None) for name in ('add', 'sub', 'mul', 'neg', 'reduce')]
     for name in ('add_scalar', 'mul_scalar', 'rsub_scalar'):
         ent += [(name, label, s) for label, s in (('0', 0), ('1', 1), ('q-1', q - 1), ('rnd', rnd))]
@@ -247,7 +317,14 @@ def all_entries(q, rnd):
                                                ('3e+1', 3 * (2**20 - 1) + 1))]
     ent.append(('inv', '', None))
     ent += [('beaver_combine', 'add_de=%d' % v, bool(v)) for v in (0, 1)]
+    if q % 4 == 1:
+        ent.append(('sqrt_cl', '', None))
     return ent
+
+
+def sqrt_cases_of(q):
+    """(pairs, matrix cases, alignment cases) that sqrt_cl adds to run_matrix / run_alignment on a field of order q"""
+    return (2, 2 * len(SMALL_SIZES) + 2 * len(LARGE_SIZES), 2 * 2 * len(ALIGN_SIZES)) if q % 4 == 1 else (0, 0, 0)
 
 
 def layout(eb, n, slots, one_in):
@@ -274,15 +351,18 @@ class Driver:
         self.seen = set()          # (entry point, label, pattern, n, alignment class) of every case that was checked
         self.steps = 0             # calls compared with the reference (two per case)
         self._mixed = 0
+        self._rot = 0
         self._prev = None
 
     def entry(self, name, label=''):
         return next(e for e in self.entries if e[0] == name and e[1] == label)
 
     def draw(self, entry, n):
-        """canonical random elements with 0, 1 and q - 1 planted; raw limbs for reduce"""
+        """canonical random elements with 0, 1 and q - 1 planted; raw limbs for reduce; for sqrt_cl see draw_sqrt"""
         if entry[0] == 'reduce':
             return self.rng.integers(0, 256, size=n * self.eb, dtype=np.uint8)
+        if entry[0] == 'sqrt_cl':
+            return self.draw_sqrt(n)
         v = self.ref.random(self.rng, n).reshape(n, self.eb)
         if n >= 3:
             pos = self.rng.choice(n, size=3, replace=False)
@@ -290,6 +370,25 @@ class Driver:
                 v[p] = self.ref.const(s, 1)
         elif n == 2:
             v[int(self.rng.integers(2))] = 0
+        return v.reshape(-1)
+
+    def sqrt_pool(self):
+        """SQRT_POOL canonical random elements, the same for every driver of a field, as an (., eb) byte matrix"""
+        if self.q not in _pool_memo:
+            _pool_memo[self.q] = self.ref.random(np.random.default_rng(self.q % 1009 + 4), SQRT_POOL).reshape(SQRT_POOL, self.eb)
+        return _pool_memo[self.q]
+
+    def draw_sqrt(self, n):
+        """operands of sqrt_cl: elements of the pool (about half of them non-residues) at random, with sqrt_specials planted at
+        random places -- all of them from n = 6 on; below, as many as fit, starting with another one at every draw"""
+        pool = self.sqrt_pool()
+        v = pool[self.rng.integers(0, len(pool), size=n)].copy()
+        sp = sqrt_specials(self.q)
+        k = min(n, len(sp))
+        pos = self.rng.choice(n, size=k, replace=False) if n else ()
+        for i, p in enumerate(pos):
+            v[p] = self.ref.const(sp[(self._rot + i) % len(sp)], 1)
+        self._rot += k
         return v.reshape(-1)
 
     def _view(self, base, off, n):
@@ -397,14 +496,14 @@ class Driver:
                 for pat in self.in_place_pair(e):
                     self.run(e, pat, n)
 
-    def run_alignment(self, sizes=ALIGN_SIZES):
+    def run_alignment(self, sizes=ALIGN_SIZES, entries=None, aligns=('one-in', 'mixed')):
         """every entry point, fresh and in place, with all operands one element in and with one operand one element in"""
-        for e in self.entries:
+        for e in entries or self.entries:
             for n in sizes:
                 if e[1] in BIG_EXPS and n > BIG_EXP_MAX_N:
                     continue
                 for pat in self.in_place_pair(e):
-                    for align in ('one-in', 'mixed'):
+                    for align in aligns:
                         self.run(e, pat, n, align)
 
     def run_reduced(self, small=SMALL_SIZES, large=LARGE_SIZES):
@@ -455,6 +554,28 @@ def run_noncanonical_reduce(drv, clmod, n=257):
     for pat in ('fresh', 'o=a'):
         drv.run(drv.entry('reduce'), pat, n, inputs={'a': img})
     return len(vals)
+
+
+# PolicyKind of mpyc_amd/csrc/policy_build.hpp (what tests/hostcheck.cpp reports) and the name engine.FieldContext.reduction has
+POLICY_KINDS = {'PM64_MERSENNE': 1, 'PM64_K64': 2, 'PM64_GEN': 3, 'RC64': 4, 'RC32': 5, 'PM128_K128': 6, 'PM128_GEN': 7, 'PM96': 8,
+                'MONT128': 9, 'PM192': 13, 'MONT192': 14}
+REDUCTION_OF = {'PM': 'pseudo-mersenne', 'RC': 'reciprocal', 'MO': 'montgomery'}
+SQRT_ROWS = ('RC32', 'PM64_GEN', 'PM64_K64', 'RC64', 'PM96', 'PM128_GEN', 'PM128_K128', 'MONT128', 'PM192', 'MONT192')
+
+
+def sqrt_fields():
+    """(modulus, policy, element bytes) of the fields sqrt_cl is tested on: primes = 1 mod 4, at least one per prime policy and
+    storage size.  The Mersenne policy has none: 2^k - 1 = 3 mod 4 for every k >= 2."""
+    return [(13, 'RC32', 4), (2**31 - 19, 'RC32', 4),
+            (2**33 - 79, 'PM64_GEN', 8), (2**40 - 87, 'PM64_GEN', 8), (2**63 - 259, 'PM64_GEN', 8),
+            (2**64 - 59, 'PM64_K64', 8),
+            (0x5bd1e995c6a4a715, 'RC64', 8),
+            (2**80 - 143, 'PM96', 12), (2**96 - 87, 'PM96', 12),
+            (2**100 - 15, 'PM128_GEN', 16), (2**127 - 39, 'PM128_GEN', 16),
+            (2**128 - 159, 'PM128_K128', 16),
+            (2**127 + 2**100 + 0x101, 'MONT128', 16), (0xc2b2ae3d27d4eb4f165667b19e377991, 'MONT128', 16),
+            (2**136 - 243, 'PM192', 24), (2**192 - 399, 'PM192', 24),
+            (2**135 + 33, 'MONT192', 24), (2**192 - 2**40 + 341, 'MONT192', 24)]
 
 
 def contract_fields():

@@ -388,18 +388,30 @@ def sqrt_cases():
             x -= 1
         return x
 
-    for name, start in (('p5', 6), ('p13', 14), ('p17', 18), ('P31', 2**31), ('P40', 2**40), ('P61', 2**61),
-                        ('P64', 2**64), ('P63G', 6616326157076047771), ('P96', 2**96), ('P128', 2**128),
-                        ('P128G', 258797994007609146293811961253269568351)):
-        p = prime_1mod4_below(start)
+    moduli = [(name, prime_1mod4_below(start)) for name, start in (
+        ('p5', 6), ('p13', 14), ('p17', 18), ('P31', 2**31), ('P40', 2**40), ('P61', 2**61), ('P64', 2**64),
+        ('P63G', 6616326157076047771), ('P96', 2**96), ('P128', 2**128), ('P128G', 258797994007609146293811961253269568351))]
+    # one p = 1 mod 4 prime per prime policy and storage size (sqrt_fields() of tests/ew_contract.py), as far as the
+    # search above did not find it already; they come last, so the entries before them keep their random draws
+    have = {p for _, p in moduli}
+    for name, p in (('P31S', 2**31 - 19), ('P33', 2**33 - 79), ('P63', 2**63 - 259), ('RC64', 0x5bd1e995c6a4a715),
+                    ('P80S', 2**80 - 143), ('P100', 2**100 - 15), ('P127S', 2**127 - 39), ('M127', 2**127 + 2**100 + 0x101),
+                    ('M128', 0xc2b2ae3d27d4eb4f165667b19e377991), ('P136S', 2**136 - 243), ('P192S', 2**192 - 399),
+                    ('M135', 2**135 + 33), ('M192', 2**192 - 2**40 + 341)):
+        assert p % 4 == 1 and g.is_prime(p), name
+        if p not in have:
+            moduli.append((name, p))
+    for name, p in moduli:
         F = finfields.GF(p)
         vals = [0, 1, 4 % p, p - 1, 2 % p, 3 % p] + [r.randrange(p) for _ in range(10)]
         sq = [pow(r.randrange(1, p), 2, p) for _ in range(8)]
-        a = F.array(vals + sq)
+        inv4 = pow(4, -1, p)
+        zero_disc = [inv4, 9 * inv4 % p]          # b^2 - 4a = 0 at b = 1 and b = 3: a candidate the search must pass over
+        a = F.array(vals + sq + zero_disc)
         roots = a.sqrt()
-        inv_roots = F.array(sq + [1]).sqrt(INV=True)
-        out[name] = {'modulus': hx(p), 'a': hxl(vals + sq), 'sqrt': hxl(int(v) % p for v in roots.value),
-                     'sq': hxl(sq + [1]), 'inv_sqrt': hxl(int(v) % p for v in inv_roots.value),
+        inv_roots = F.array(sq + [1] + zero_disc).sqrt(INV=True)
+        out[name] = {'modulus': hx(p), 'a': hxl(vals + sq + zero_disc), 'sqrt': hxl(int(v) % p for v in roots.value),
+                     'sq': hxl(sq + [1] + zero_disc), 'inv_sqrt': hxl(int(v) % p for v in inv_roots.value),
                      'is_sqr': [bool(b) for b in a.is_sqr()]}
     with open(os.path.join(OUT, 'sqrt.json'), 'w') as fh:
         json.dump(out, fh, separators=(',', ':'))

@@ -567,6 +567,49 @@ def test_sqrt_p_1_mod_4_golden(api):
             F.array([1, 0]).sqrt(INV=True)
 
 
+@pytest.mark.parametrize('p', [2**31 - 19, 2**64 - 59, 2**80 - 143, 2**100 - 15, 2**136 - 243], ids=hex)
+def test_sqrt_p_1_mod_4_shapes_against_integers(api, p):
+    """a.sqrt(), np.sqrt(a), a.sqrt(INV=True) and a.is_sqr() through k_sqrt_cl on one field per storage size (4, 8, 12, 16 and
+    24 bytes): a (3, 5) array, an empty one and a single element, against oracle.pyoracle.sqrt_prime (the root the reference
+    returns, and its value for a non-residue), its modular inverse, and Euler's criterion on Python integers"""
+    import ew_contract as ew
+    from oracle import pyoracle as po
+    finfields, _, _ = api
+    eb = {m: b for m, _, b in ew.sqrt_fields()}[p]
+    assert eb == {2**31 - 19: 4, 2**64 - 59: 8, 2**80 - 143: 12, 2**100 - 15: 16, 2**136 - 243: 24}[p]
+    F, G = finfields.GF(p), po.Field(p, False)
+    rng = random.Random(p % 997)
+    inv4 = pow(4, -1, p)
+    vals = [0, 1, p - 1, inv4, 9 * inv4 % p, 4, 2, 3] + [rng.randrange(1, p) for _ in range(7)]
+    root = lambda vs: [po.sqrt_prime(G, v) for v in vs]
+    euler = lambda vs: [v == 0 or pow(v, (p - 1) >> 1, p) == 1 for v in vs]
+    assert True in euler(vals[5:]) and False in euler(vals[5:])
+    a = F.array(vals).reshape(3, 5)
+    for r in (a.sqrt(), np.sqrt(a)):
+        assert r.shape == (3, 5) and ints(r) == root(vals)
+    assert a.is_sqr().shape == (3, 5) and [bool(b) for b in a.is_sqr().reshape(-1)] == euler(vals)
+    assert ints(a) == vals, 'sqrt wrote its operand'
+    with pytest.raises(ZeroDivisionError):
+        a.sqrt(INV=True)
+    nz = vals[1:] + [5]
+    b = F.array(nz).reshape(3, 5)
+    r = b.sqrt(INV=True)
+    assert r.shape == (3, 5) and ints(r) == [pow(v, -1, p) for v in root(nz)]
+    empty = F.array([])
+    for r in (empty.sqrt(), np.sqrt(empty), empty.sqrt(INV=True)):
+        assert r.shape == (0,) and ints(r) == []
+    assert empty.is_sqr().shape == (0,)
+    for v in (inv4, vals[9], 0):                    # a single element, taken out of the array: no axis left
+        one = F.array([v, 1])[0:1].reshape(())
+        assert one.shape == () and ints(one.sqrt()) == root([v]) and ints(np.sqrt(one)) == root([v])
+        assert [bool(x) for x in np.asarray(one.is_sqr()).reshape(-1)] == euler([v])
+        if v:
+            assert ints(one.sqrt(INV=True)) == [pow(root([v])[0], -1, p)]
+        else:
+            with pytest.raises(ZeroDivisionError):
+                one.sqrt(INV=True)
+
+
 def test_twelve_byte_field_through_the_mirror(api):
     """SecInt(64)'s field size (96-bit Blum-like prime 2^96 - 17 and the 80-bit 2^80 - 65): elements live in
     12 bytes on the device (3 x uint32); everything the mirror does with limb tensors must handle the

@@ -1,6 +1,6 @@
 """The three promises of include/ffgpu.h about the element-wise entry points -- inputs are never written, `out` may alias an
-input exactly, elements are canonical on return -- for add, sub, mul, neg, reduce, the scalar forms, muladd, pow, inv and
-beaver_combine, on every field policy: every alias pattern at every size at which a path changes, on aligned, one-element-in
+input exactly, elements are canonical on return -- for add, sub, mul, neg, reduce, the scalar forms, muladd, pow, inv,
+beaver_combine and (primes = 1 mod 4; second half of this file) sqrt_cl, on every field policy: every alias pattern at every size at which a path changes, on aligned, one-element-in
 and mixed views, with guards around every operand, twice in a row so that the second call reads the first one's output and
 stores under the kept-in-cache policy (handoff.hpp), with the hand-off switched off, on a capped grid, on the routes the
 launcher picks by size (k_inv_digits, k_inv_fast, k_inv_batch<., 10, 2>, the GF(2^8) table product, the bit-sliced GF(2^64)
@@ -66,10 +66,12 @@ def num_cu():
 def test_alias_patterns_at_every_edge_size(coracle, modulus, binary):
     drv = driver(coracle, default_ctx(modulus, binary), modulus, binary)
     drv.run_matrix()
-    assert len(drv.seen) == MATRIX_CASES and drv.steps == 2 * MATRIX_CASES
+    sq_pairs, sq_matrix, _ = ew.sqrt_cases_of(drv.q)       # sqrt_cl joins for the two Montgomery primes, which are = 1 mod 4
+    assert (sq_pairs == 2) == (modulus in (2**127 + 2**100 + 0x101, 2**192 - 2**40 + 341))
+    assert len(drv.seen) == MATRIX_CASES + sq_matrix and drv.steps == 2 * (MATRIX_CASES + sq_matrix)
     # every (entry point, pattern) pair at every size up to 129
     pairs = {(e[0], e[1], p) for e in drv.entries for p in drv.patterns_of(e)}
-    assert len(pairs) == 71
+    assert len(pairs) == 71 + sq_pairs
     assert all((name, label, pat, n, 'aligned') in drv.seen for name, label, pat in pairs for n in ew.SMALL_SIZES)
 
 
@@ -82,7 +84,8 @@ def test_alignment_classes(coracle, modulus, binary):
         return                          # every view of 16-byte elements is 16-byte aligned: no such class
     drv = driver(coracle, ctx, modulus, binary, 1)
     drv.run_alignment()
-    assert len(drv.seen) == ALIGN_CASES and drv.steps == 2 * ALIGN_CASES
+    sq_align = ew.sqrt_cases_of(drv.q)[2]
+    assert len(drv.seen) == ALIGN_CASES + sq_align and drv.steps == 2 * (ALIGN_CASES + sq_align)
     assert {k[4] for k in drv.seen} == {'one-in', 'mixed'}
 
 
@@ -242,3 +245,155 @@ def test_reduce_of_noncanonical_patterns(coracle, modulus, binary):
     assert planted == len(ew.noncanonical_values(modulus, binary, drv.eb)) >= 2
     assert (1 << W) - 1 in ew.noncanonical_values(modulus, binary, drv.eb)
     assert len(drv.seen) == 2
+
+
+# ---- sqrt_cl: Cipolla-Lehmer for p = 1 mod 4 (k_sqrt_cl) --------------------------------------------------------------------
+# The expectation is oracle.pyoracle.sqrt_prime on Python integers, value by value (tests/golden/sqrt.json pins it to the
+# reference's FiniteFieldArray.sqrt() on every modulus below): the root the reference returns, not the other one, and its
+# non-root for a non-residue.  The operands come from a pool of 1024 elements per field, so the reference runs once per value.
+SQRT_FIELDS = ew.sqrt_fields()
+SQRT_IDS = ['%s:%s' % (pol, hex(m)) for m, pol, _ in SQRT_FIELDS]
+SQRT_MATRIX = 2 * len(ew.SMALL_SIZES) + 2 * len(ew.LARGE_SIZES)
+sqrt_checked = {}                   # policy -> cases of sqrt_cl checked by test_sqrt_cl_alias_patterns_sizes_and_alignment
+
+
+def test_sqrt_field_list_on_the_device():
+    for modulus, policy, eb in SQRT_FIELDS:
+        ctx = default_ctx(modulus, False)
+        assert ctx.elem_bytes == eb and ctx.reduction == ew.REDUCTION_OF[policy[:2]], (hex(modulus), ctx.reduction, ctx.elem_bytes)
+    assert {pol for _, pol, _ in SQRT_FIELDS} == set(ew.SQRT_ROWS)
+
+
+@pytest.mark.parametrize('modulus,policy,eb', SQRT_FIELDS, ids=SQRT_IDS)
+def test_sqrt_cl_alias_patterns_sizes_and_alignment(coracle, modulus, policy, eb):
+    """fresh and in place at every size of SMALL_SIZES and LARGE_SIZES, then on aligned, one-element-in and mixed views at
+    ALIGN_SIZES; the chained second call takes the roots of the first, residues or not"""
+    drv = driver(coracle, default_ctx(modulus, False), modulus, False, 12)
+    e = drv.entry('sqrt_cl')
+    drv.run_matrix(entries=[e])
+    assert len(drv.seen) == SQRT_MATRIX and drv.steps == 2 * SQRT_MATRIX
+    drv.run_alignment(entries=[e], aligns=('aligned', 'one-in', 'mixed'))
+    # (the aligned cases at these sizes are cases of the matrix, run again on other draws)
+    assert drv.steps == 2 * (SQRT_MATRIX + 3 * 2 * len(ew.ALIGN_SIZES))
+    assert {k[4] for k in drv.seen} == {'aligned', 'one-in', 'mixed'} and {k[0] for k in drv.seen} == {'sqrt_cl'}
+    cases = drv.steps // 2
+    sqrt_checked[policy] = sqrt_checked.get(policy, 0) + cases
+    print('sqrt_cl: %d cases (%d calls) checked on %s %s' % (cases, drv.steps, policy, hex(modulus)))
+    assert cases > 0
+
+
+def test_sqrt_cl_cases_were_checked_on_every_policy(coracle):
+    """(after the test above in file order; on its own it runs the first field of every policy itself)"""
+    for policy in ew.SQRT_ROWS:
+        if policy not in sqrt_checked:
+            modulus = next(m for m, pol, _ in SQRT_FIELDS if pol == policy)
+            drv = driver(coracle, default_ctx(modulus, False), modulus, False, 13)
+            drv.run_matrix(small=(0, 1, 65), large=(), entries=[drv.entry('sqrt_cl')])
+            sqrt_checked[policy] = drv.steps // 2
+    print('sqrt_cl cases per policy: %r' % sqrt_checked)
+    assert all(sqrt_checked[policy] > 0 for policy in ew.SQRT_ROWS)
+
+
+@pytest.mark.parametrize('modulus,policy,eb', SQRT_FIELDS, ids=SQRT_IDS)
+def test_sqrt_cl_chains_without_handoff(coracle, monkeypatch, modulus, policy, eb):
+    drv = driver(coracle, env_ctx(monkeypatch, modulus, False, 'FFGPU_HANDOFF', '0'), modulus, False, 14)
+    drv.run_matrix(entries=[drv.entry('sqrt_cl')])
+    assert len(drv.seen) == SQRT_MATRIX and drv.steps == 2 * SQRT_MATRIX
+
+
+def mixed_depth_input(drv, n=5003):
+    """n operands laid out by wavefront of 64: all zero | zero and non-zero alternating | depth 1 only | deep only (64 of depth
+    >= 6, among them 8 of depth >= 8 and 2 of depth >= 11) | four waves that mix residues, non-residues, 0, 1, p - 1, 4^-1,
+    9 * 4^-1, b^2 * 4^-1 for b <= 8 and deep elements | random elements.  GF(13): every element, over and over."""
+    p, rng = drv.q, drv.rng
+    if p == 13:
+        return ew.ints_to_bytes([i % 13 for i in range(n)], drv.eb), {}
+    deep = ew.deep_elements(p)
+    assert [len(deep[lvl]) for lvl in (6, 8, 11)] == [64, 8, 2], 'the walk over the squares reached its bound for %s' % hex(p)
+    rand = ew.bytes_to_ints(drv.ref.random(rng, n + 512), drv.eb)
+    nonzero = [v for v in rand if v]
+    shallow = [v for v in nonzero[:400] if ew.sqrt_depth(p, v) == 1][:64]
+    assert len(shallow) == 64
+    deepest = deep[11] + [a for a in deep[8] if a not in deep[11]]
+    deep_wave = (deepest + [a for a in deep[6] if a not in deepest])[:64]
+    assert len(deep_wave) == 64 and set(deep[11]) | set(deep[8]) <= set(deep_wave)
+    inv4 = pow(4, -1, p)
+    spice = [0, 1, p - 1, inv4, 9 * inv4 % p] + [b * b * inv4 % p for b in range(1, 9)] + deep[11] + deep[8][:4]
+    mixed = []
+    for w in range(4):
+        wave = [int(v) for v in rand[400 + 64 * w:464 + 64 * w]]
+        for s, pos in zip(spice, rng.choice(64, size=len(spice), replace=False)):
+            wave[pos] = s
+        mixed += wave
+    vals = [0] * 64 + [0 if i % 2 == 0 else nonzero[i] for i in range(64)] + shallow + deep_wave + mixed
+    vals += rand[512 + len(vals):512 + n]
+    assert len(vals) == n
+    depth = {'deep wave': min(ew.sqrt_depth(p, a) for a in deep_wave), 'max': max(ew.sqrt_depth(p, a) for a in deep_wave)}
+    return ew.ints_to_bytes(vals, drv.eb), depth
+
+
+@pytest.mark.parametrize('modulus,policy,eb', SQRT_FIELDS, ids=SQRT_IDS)
+def test_sqrt_cl_waves_of_mixed_search_depth(coracle, modulus, policy, eb):
+    """lanes that skip the search (a = 0), lanes that leave it after one candidate next to lanes that need eleven or more, waves
+    of one kind only: every one of the 5003 elements equals the reference, with a fresh output and in place"""
+    drv = driver(coracle, default_ctx(modulus, False), modulus, False, 15)
+    img, depth = mixed_depth_input(drv)
+    if modulus != 13:
+        assert depth['deep wave'] >= 6 and depth['max'] >= 11
+    e = drv.entry('sqrt_cl')
+    for pat in ('fresh', 'o=a'):
+        drv.run(e, pat, 5003, inputs={'a': img}, chain=False)
+    assert len(drv.seen) == 2 and drv.steps == 2
+
+
+@pytest.mark.parametrize('modulus', [2**40 - 87, 2**80 - 143, 2**136 - 243], ids=hex)
+def test_sqrt_cl_capped_grid(coracle, monkeypatch, modulus):
+    """FFGPU_BLOCKS_PER_CU=1: G = CUs x 256 threads, n = 2 G + G / 3 + 7, so every thread takes two elements and a third of
+    them a third one.  The operands are drawn from the pool with the special and the deep elements, so the integer reference
+    is known for every one of them: ALL n elements are compared (the second and the partial pass, and the whole first one),
+    after each of the two chained calls, fresh and in place.  v * v = a is checked through the vectorised reference on every
+    residue."""
+    assert any(m == modulus for m, _, _ in SQRT_FIELDS)
+    ctx = env_ctx(monkeypatch, modulus, False, 'FFGPU_BLOCKS_PER_CU', '1')
+    drv = driver(coracle, ctx, modulus, False, 16)
+    ref, eb = drv.ref, drv.eb
+    G = num_cu() * 256
+    n = 2 * G + G // 3 + 7
+    deep = ew.deep_elements(modulus)
+    extra = np.stack([ref.const(v, 1) for v in ew.sqrt_specials(modulus) + deep[8] + deep[11]])
+    values = np.concatenate([drv.sqrt_pool(), extra])
+    a = values[drv.rng.integers(0, len(values), size=n)].reshape(-1)
+    e = drv.entry('sqrt_cl')
+    for pat in ('fresh', 'o=a'):
+        drv.run(e, pat, n, inputs={'a': a})
+    assert len(drv.seen) == 2 and drv.steps == 4
+    # the driver found the device's output equal to ref.sqrt_cl(a), byte for byte: square that
+    root = ref.sqrt_cl(a)
+    euler = {v: v == 0 or pow(v, (modulus - 1) >> 1, modulus) == 1 for v in ew.bytes_to_ints(values.reshape(-1), eb)}
+    residue = np.array([euler[v] for v in ew.bytes_to_ints(a, eb)])
+    assert 0.3 * n < residue.sum() < 0.7 * n
+    assert not (ref.mul(root, root).reshape(n, eb) != a.reshape(n, eb)).any(axis=1)[residue].any()
+    assert (ref.mul(root, root).reshape(n, eb) != a.reshape(n, eb)).any(axis=1)[~residue].all()
+
+
+@pytest.mark.parametrize('modulus,binary', [(0x11b, True), ((1 << 64) | 0x1b, True), (2**61 - 1, False), (2**136 - 113, False),
+                                            (2, False)], ids=['gf2:0x11b', 'gf2:2^64', '2^61-1', '2^136-113', '2'])
+def test_sqrt_cl_is_refused_elsewhere(coracle, modulus, binary):
+    """binary fields, p = 3 mod 4 and p = 2: not supported, and nothing is written -- the pre-filled output, the operand and the
+    guards are byte for byte what was uploaded"""
+    ctx = default_ctx(modulus, binary)
+    drv = driver(coracle, ctx, modulus, binary, 17)
+    assert not any(e[0] == 'sqrt_cl' for e in drv.entries)
+    eb = drv.eb
+    for n in (1, 65, 1025):
+        off, total = ew.layout(eb, n, ['a', 'o'], ())
+        img = np.full(total, ew.GUARD_BYTE, dtype=np.uint8)
+        img[off['a']:off['a'] + n * eb] = drv.draw(drv.entry('neg'), n)
+        img[off['o']:off['o'] + n * eb] = drv.rng.integers(0, 256, size=n * eb, dtype=np.uint8)
+        base = torch.from_numpy(img.copy()).to(ctx.torch_device)
+        a, o = drv._view(base, off['a'], n), drv._view(base, off['o'], n)
+        for out in (o, a):
+            with pytest.raises(NotImplementedError):
+                ctx.sqrt_cl(a, out=out)
+        torch.cuda.synchronize()
+        assert np.array_equal(base.cpu().numpy(), img), (hex(modulus), n)

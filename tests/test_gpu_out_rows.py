@@ -1,4 +1,5 @@
-"""The two operand conventions every engine wrapper shares, on the device, over one 8-byte and one 24-byte prime policy:
+"""The two operand conventions every engine wrapper shares, on the device, over one 8-byte and one 24-byte prime policy (the
+element-wise wrappers, sqrt_cl among them, also over an 8-byte and a 24-byte prime = 1 mod 4, the only ones sqrt_cl serves):
 
   out=   a caller's output comes back as THE SAME OBJECT (an empty one too: a DevArray of no elements is falsy, so `out or ...`
          would hand back a fresh allocation), and an output one element short is refused with ValueError before anything is
@@ -15,6 +16,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 FIELDS = {'pm64-mersenne': 2**61 - 1, 'pm192': 2**136 - 113}
+ONE_MOD_FOUR = {'pm64-k64-1mod4': 2**64 - 59, 'pm192-1mod4': 2**136 - 243}
 OTHER = 2**40 - 87                                   # rows "of another modulus" come from this field
 
 
@@ -22,7 +24,7 @@ OTHER = 2**40 - 87                                   # rows "of another modulus"
 def ctxs():
     assert torch.cuda.is_available()
     from mpyc_amd import engine
-    return {name: engine.FieldContext(p, device=0) for name, p in FIELDS.items()}, engine.FieldContext(OTHER, device=0)
+    return {name: engine.FieldContext(p, device=0) for name, p in {**FIELDS, **ONE_MOD_FOUR}.items()}, engine.FieldContext(OTHER, device=0)
 
 
 def ones(ctx, n):
@@ -31,9 +33,12 @@ def ones(ctx, n):
 
 # ---- out= ------------------------------------------------------------------------------------------------------------------------
 def elementwise(ctx, n):
-    """name -> (call(out), inputs) for the element-wise wrappers and recombine (w = 1) on n elements"""
+    """name -> (call(out), inputs) for the element-wise wrappers and recombine (w = 1) on n elements; sqrt_cl where the field
+    has it"""
     a, b, c, d, e = (ones(ctx, n) for _ in range(5))
+    sqrt = {'sqrt_cl': (lambda out: ctx.sqrt_cl(a, out=out), [a])} if ctx.modulus % 4 == 1 else {}
     return {
+        **sqrt,
         'add': (lambda out: ctx.add(a, b, out=out), [a, b]),
         'sub': (lambda out: ctx.sub(a, b, out=out), [a, b]),
         'mul': (lambda out: ctx.mul(a, b, out=out), [a, b]),
@@ -88,6 +93,8 @@ def structured(ctx):
 
 ELEMENTWISE = ['add', 'sub', 'mul', 'neg', 'reduce', 'add_scalar', 'mul_scalar', 'rsub_scalar', 'muladd', 'pow', 'inv', 'beaver_combine',
                'recombine']
+ELEMENTWISE_CASES = [(name, fn) for name in FIELDS for fn in ELEMENTWISE] + \
+                    [(name, fn) for name in ONE_MOD_FOUR for fn in ELEMENTWISE + ['sqrt_cl']]
 STRUCTURED = ['matmul', 'matmul_stack', 'convolve', 'scan', 'scan_with_initial', 'axis_reduce', 'sgn_mask', 'sgn_finish', 'cx_diff',
               'bits_mask', 'carry_prod', 'bits_finish', 'tour_diff', 'tour_select', 'tour_unit_prod', 'tour_unit_expand',
               'find_leaf_prod', 'find_leaf_apply', 'find_prod', 'trunc_mask_ar', 'trunc_mask_masked', 'trunc_finish', 'norm_prod',
@@ -111,8 +118,14 @@ def test_the_tables_name_every_case(ctxs, name):
     assert sorted(elementwise(ctx, 1)) == sorted(ELEMENTWISE) and sorted(structured(ctx)) == sorted(STRUCTURED)
 
 
-@pytest.mark.parametrize('fn', ELEMENTWISE)
-@pytest.mark.parametrize('name', list(FIELDS))
+@pytest.mark.parametrize('name', list(ONE_MOD_FOUR))
+def test_the_table_names_sqrt_cl_where_the_field_has_it(ctxs, name):
+    assert sorted(elementwise(ctxs[0][name], 1)) == sorted(ELEMENTWISE + ['sqrt_cl'])
+    assert sorted(fn for nm, fn in ELEMENTWISE_CASES if nm == name) == sorted(ELEMENTWISE + ['sqrt_cl'])
+    assert all(p % 4 == 1 for p in ONE_MOD_FOUR.values()) and all(p % 4 == 3 for p in FIELDS.values())
+
+
+@pytest.mark.parametrize('name,fn', ELEMENTWISE_CASES, ids=['%s-%s' % c for c in ELEMENTWISE_CASES])
 def test_elementwise_out_comes_back_and_a_short_one_is_refused(ctxs, name, fn):
     ctx = ctxs[0][name]
     call, inputs = elementwise(ctx, 1)[fn]
@@ -132,8 +145,9 @@ def test_structured_out_comes_back_and_a_short_one_is_refused(ctxs, name, fn):
 
 @pytest.mark.parametrize('name', list(FIELDS))
 def test_short_out_is_refused_where_the_entry_needs_more_than_this_file_sets_up(ctxs, name):
-    """sqrt_cl serves p = 1 mod 4 only (neither prime here), the PRSS entries need key material: their outputs go through the
-    same check, which comes before the entry is reached"""
+    """sqrt_cl on a prime = 3 mod 4, which the entry would refuse (on the primes = 1 mod 4 it is one of the element-wise cases
+    above), and the PRSS entries, which need key material: their outputs go through the same check, which comes before the
+    entry is reached"""
     ctx = ctxs[0][name]
     a = ones(ctx, 2)
     with pytest.raises(ValueError):

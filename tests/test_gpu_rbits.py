@@ -2,7 +2,8 @@
 against Python integers computed here from the maps include/ffgpu_math.h states, over every prime policy, at every edge of the
 launch plan (mpyc_amd/csrc/rbits_geom.hpp) and with 1, 3, 5 and 7 rows (and 10: past the fused rows); the zero counter (planted
 zeros, none, all, accumulated over two calls, absent); guard bytes around every output row and the counter; outputs on their
-inputs; status codes; protocols.random_bits on the draws the reference was fed (tests/golden/rbits/rbits.json);
+inputs; status codes; protocols.random_bits on the draws the reference was fed (tests/golden/rbits/rbits.json) and, composed
+from sqrt_cl, over three primes = 1 mod 4 of 12, 16 and 24 bytes;
 protocols.Randomness share for share against the Python-integer stand-in on the same key; compare_zero, fxp_multiply and
 is_zero on nothing but its draws; and open -> finish replayed from a captured HIP graph."""
 import os
@@ -14,8 +15,8 @@ import pytest
 from test_gpu_sgn import draw, same, view
 from test_gpu_fxp import up
 from test_gpu_iszero import FIELDS, nonresidue
-from test_rbits_host import (BALANCE_KEY, BALANCE_ONES, P61, P80, check_end_to_end, golden, gf, open_two_ways, run_end_to_end, run_golden,
-                             zero_test_prime)
+from test_rbits_host import (BALANCE_KEY, BALANCE_ONES, COMPOSED, ONE_MOD_FOUR, P61, P80, check_end_to_end, golden, gf, open_two_ways,
+                             run_end_to_end, run_golden, run_one_mod_four, zero_test_prime)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -374,6 +375,17 @@ def test_random_bits_on_the_recorded_draws(mods, m, t):
         ctx = engine.FieldContext(e['p'], device=0)
         for c in e['cases']:
             run_golden(ctx, protocols, gf(e['p']), e, c, m, t, seed=100 * m + t)
+
+
+@pytest.mark.parametrize('p', ONE_MOD_FOUR, ids=hex)
+def test_random_bits_over_primes_one_mod_four(mods, p):
+    """p = 1 mod 4 on 12-, 24- and 16-byte elements: the bits come from sqrt_cl, inv, mul and the scalar forms, and their
+    signs from WHICH root k_sqrt_cl returns; three zero squares planted, so the compaction runs (tests/test_rbits_host.py
+    runs the same on Python integers)"""
+    _ffi, engine, _, protocols = mods
+    ctx = engine.FieldContext(p, device=0)
+    for m, t, signed, f in COMPOSED:
+        run_one_mod_four(ctx, protocols, m, t, signed, f, seed=10 * m + f)
 
 
 @pytest.mark.parametrize('p', [P61, P80, 2**40 - 87])

@@ -169,6 +169,13 @@ def test_py_sqrt():
         F = po.Field(int(c['modulus'], 16), False)
         assert [po.sqrt_prime(F, int(v, 16)) for v in c['a']] == [int(v, 16) for v in c['sqrt']], name
         assert [po.inv(F, po.sqrt_prime(F, int(v, 16))) for v in c['sq']] == [int(v, 16) for v in c['inv_sqrt']]
+        p = F.modulus
+        assert [int(v, 16) == 0 or pow(int(v, 16), (p - 1) >> 1, p) == 1 for v in c['a']] == c['is_sqr'], name
+        inv4 = pow(4, -1, p)             # b^2 - 4a = 0 at b = 1 and b = 3: the last two values of both lists
+        assert [int(v, 16) for v in c['a'][-2:]] == [int(v, 16) for v in c['sq'][-2:]] == [inv4, 9 * inv4 % p], name
+    # the reference's outputs pin sqrt_prime on every modulus the element-wise contract takes its square roots on
+    import ew_contract as ew
+    assert {m for m, _, _ in ew.sqrt_fields()} <= {int(c['modulus'], 16) for c in g.values()}
 
 
 def test_py_aes128_fips197():

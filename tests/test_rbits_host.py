@@ -408,3 +408,45 @@ def test_a_wrong_step_is_caught(wrong, monkeypatch):
             assert open_two_ways(ctx, got, 1) == c['bits'][0]['values']
         else:
             run_golden(ctx, protocols, gf(p), e, c, 3, 1)
+
+
+# ---- p = 1 mod 4: the bits composed from sqrt_cl, inv, mul and the scalar forms -------------------------------------------------
+ONE_MOD_FOUR = [2**80 - 143, 2**136 - 243, 2**127 + 2**100 + 0x101]          # 12-, 24- and 16-byte (Montgomery) storage
+COMPOSED = [(m, t, signed, f) for m, t in ((3, 1), (5, 2)) for signed in (False, True) for f in (0, 2)]
+
+
+def run_one_mod_four(ctx, protocols, m, t, signed, f, count=257, seed=1):
+    """random_bits over a prime = 1 mod 4 on draws made here: uniform non-zero r, z a sharing of zero but for three entries
+    (the first, the last, one inside), where z = -r^2 makes the opened square 0, so that the entries are compacted and three
+    are drawn again.  The opened result is r (r^2)^(-1/2) with the root of oracle.pyoracle.sqrt_prime -- the root the reference
+    takes, which decides the sign of every bit -- mapped to a bit and scaled by 2^f."""
+    from oracle import pyoracle as po
+    p = ctx.modulus
+    assert p % 4 == 1
+    rng = random.Random(seed)
+    planted = [0, count // 3, count - 1]
+    r1 = [rng.randrange(1, p) for _ in range(count)]
+    z1 = [(-r1[h] * r1[h]) % p if h in planted else 0 for h in range(count)]
+    r2 = [rng.randrange(1, p) for _ in planted]
+    rounds = [{'r': r1, 'z': z1}, {'r': r2, 'z': [0] * len(r2)}]
+    draw = GoldenDraw(ctx, rounds, m, t, seed)
+    got = protocols.random_bits(ctx, gf(p), count, t, draw, signed=signed, f=f)
+    assert draw.at == 2 and len(got) == m and all(g.n == count for g in got)
+    r = [v for h, v in enumerate(r1) if h not in planted] + r2                   # the kept entries, then the last draw whole
+    F, want = po.Field(p, False), []
+    for v in r:
+        b = v * pow(po.sqrt_prime(F, v * v % p), -1, p) % p
+        assert b in (1, p - 1)
+        want.append(((b if signed else (b + 1) * ((p + 1) >> 1)) << f) % p)
+    assert open_two_ways(ctx, got, t) == want, (hex(p), m, t, signed, f)
+    assert len({w for w in want}) == 2, 'both bits occur'
+    for r0, z0, rs, zs in draw.handed:
+        assert [x.to_ints() for x in rs] == r0 and [x.to_ints() for x in zs] == z0, 'an input of random_bits was written'
+
+
+@pytest.mark.parametrize('m,t,signed,f', COMPOSED)
+@pytest.mark.parametrize('p', ONE_MOD_FOUR, ids=hex)
+def test_random_bits_over_primes_one_mod_four(p, m, t, signed, f):
+    from mpyc_amd import protocols
+    from rbits_cpuctx import RbitsCpuFieldContext
+    run_one_mod_four(RbitsCpuFieldContext(p), protocols, m, t, signed, f, seed=10 * m + f)
